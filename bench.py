@@ -66,7 +66,13 @@ def parse():
     ap.add_argument("--configs-gib", type=float, default=10.0,
                     help="N=1: size of the sub-shard of the resident buffer on which BASELINE configs 2 and 4 (the list "
                          "tags) are timed and checked element by element; 0 = skip")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned to its caller as DIR/<name>.npy "
+                         "(float64): counters.npy = the XSG_NUM_COUNTERS counter vector of xs::count (summed over ranks)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -713,6 +719,12 @@ def main():
         return elapsed
 
     elapsed = measure(shard, expected_total, args.steps, args.warmup)
+    if args.dump_outputs and rank == 0:
+        # the counter vector the last timed step wrote (uint64 counts < 2^53: exact in float64)
+        out_dir = Path(args.dump_outputs)
+        out_dir.mkdir(parents=True, exist_ok=True)
+        last = counters[(args.steps - 1) & 1].cpu().numpy().view(np.uint64)
+        np.save(out_dir / "counters.npy", last.astype(np.float64))
     total_bytes = shard_bytes * world
     gibs = total_bytes * args.steps / elapsed / 2**30
     ms_per_step = elapsed / args.steps * 1e3

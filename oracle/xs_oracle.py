@@ -30,11 +30,10 @@ def _stale() -> bool:
 
 
 def build(force: bool = False) -> None:
-    """Compile the oracle (and oracle/_ref when /root/reference is mounted).  Several processes may get here at
-    once (bench.py under torch.distributed.run starts one per GPU): the build runs under a file lock and the
-    others find the library up to date when they get the lock."""
-    need_ref = not _REF.exists() and Path("/root/reference/src/string_search/simd_search.cpp").exists()
-    if not (force or _stale() or need_ref):
+    """Compile the oracle (oracle/Makefile; its `ref` target builds oracle/_ref where the reference tree is
+    present).  Several processes may get here at once (bench.py under torch.distributed.run starts one per GPU):
+    the build runs under a file lock and the others find the library up to date when they get the lock."""
+    if not (force or _stale()):
         return
     import fcntl
     with open(HERE / ".build.lock", "w") as lock:
@@ -42,8 +41,6 @@ def build(force: bool = False) -> None:
         try:
             if force or _stale():
                 subprocess.check_call(["make", "-C", str(HERE), "--no-print-directory"], stdout=subprocess.DEVNULL)
-            elif not _REF.exists() and need_ref:
-                subprocess.check_call(["make", "-C", str(HERE), "--no-print-directory", "ref"], stdout=subprocess.DEVNULL)
         finally:
             fcntl.flock(lock, fcntl.LOCK_UN)
 

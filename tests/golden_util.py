@@ -56,3 +56,40 @@ def generated_icase_cases():
         assert hashlib.sha256(data.tobytes()).hexdigest() == c["sha256"], f"generator drift in {c['name']}"
         for e in c["expect"]:
             yield c["name"], data, e
+
+
+def ref_metafile(name: str, directory) -> Path:
+    """Rebuilds the reference's test/files/<name> (one of its four .meta fixtures) byte for byte under `directory`
+    from tests/golden/ref_metafiles.json + ref_metafile_mappings.xz (tests/golden/extract_ref_metafiles.py)."""
+    import lzma
+    doc = load("ref_metafiles.json")
+    f = doc["files"][name]
+    n = doc["n_mappings"]
+    blob = lzma.decompress((GOLDEN / doc["mappings"]).read_bytes())
+    assert len(blob) == 3 * n, "mapping table size"
+    d = np.stack([np.frombuffer(blob[:2 * n], "<u2"), np.frombuffer(blob[2 * n:], "u1")], axis=1).astype(np.uint64)
+    table = np.cumsum(d, axis=0, dtype=np.uint64).astype("<u8")
+    parts, at = [np.array([f["compression_type"]], "<i4").tobytes()], 0
+    for rec in f["records"]:
+        parts += [np.array(rec, "<u8").tobytes(), table[at:at + rec[4]].tobytes()]
+        at += rec[4]
+    assert at == n, "the chunk records cover the mapping table"
+    raw = b"".join(parts)
+    assert len(raw) == f["file_bytes"] and hashlib.sha256(raw).hexdigest() == f["sha256"], f"{name} not rebuilt exactly"
+    path = Path(directory) / name
+    path.write_bytes(raw)
+    return path
+
+
+def digest(answers) -> str:
+    """sha256 of a nest of lists / tuples of ints and bytes (numpy integers included): how tests/golden/ holds what the
+    reference build answered on a test's seeded inputs without holding every answer"""
+    def plain(x):
+        if isinstance(x, (bytes, bytearray)):
+            return {"b": bytes(x).hex()}
+        if isinstance(x, np.integer):
+            return int(x)
+        if isinstance(x, np.ndarray):
+            return x.tolist()
+        raise TypeError(type(x))
+    return hashlib.sha256(json.dumps(answers, default=plain, separators=(",", ":")).encode()).hexdigest()

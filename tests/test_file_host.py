@@ -1,7 +1,7 @@
 """Host-side file logic of the pipeline (no GPU): newline-aligned chunk plans,
 metafile reader/writer.  The metafile format is pinned by the reference's four
-.meta fixtures (test/files/): they are parsed in place when the
-reference tree is mounted and compared with tests/golden/ref_metafile_summary.json."""
+.meta fixtures (test/files/): they are rebuilt byte for byte from tests/golden/ref_metafiles.json
+(golden_util.ref_metafile), parsed and compared with tests/golden/ref_metafile_summary.json."""
 import hashlib
 import json
 import os
@@ -13,8 +13,6 @@ import pytest
 import corpus
 import golden_util as G
 import xsg
-
-REF_FILES = Path("/root/reference/test/files")
 
 
 @pytest.fixture(scope="module")
@@ -157,7 +155,7 @@ def _summary(path):
     }
 
 
-def test_reference_metafile_fixtures():
+def test_reference_metafile_fixtures(tmp_path):
     """The four fixtures the reference's tests use must parse to exactly EOF with
     the values recorded in tests/golden/ref_metafile_summary.json."""
     want = G.load("ref_metafile_summary.json")
@@ -166,15 +164,15 @@ def test_reference_metafile_fixtures():
     for v in want.values():
         assert sum(v["original_size"]) == 100_000_000 and v["file_bytes"] == 3_060_484
         assert v["last_mapping"] == [99_999_691, 3_447_129]
-    if not REF_FILES.exists():
-        pytest.skip("reference tree not mounted: summary checked, fixtures not re-parsed")
     for name, v in want.items():
-        assert _summary(REF_FILES / name) == v, name
+        assert _summary(G.ref_metafile(name, tmp_path)) == v, name
 
 
-if __name__ == "__main__":  # regenerate the summary (build container only)
-    out = {n: _summary(REF_FILES / n) for n in ("sample.meta", "sample.xslz4.meta", "sample.xslz4hc.meta",
-                                                  "sample.xszst.meta")}
+if __name__ == "__main__":  # regenerate the summary: test_file_host.py <reference>/test/files
+    import sys
+    src = Path(sys.argv[1])
+    out = {n: _summary(src / n) for n in ("sample.meta", "sample.xslz4.meta", "sample.xslz4hc.meta",
+                                            "sample.xszst.meta")}
     (G.GOLDEN / "ref_metafile_summary.json").write_text(json.dumps(out, indent=1))
     print(json.dumps(out, indent=1)[:600])
 

@@ -7,7 +7,6 @@ globalLineIndex) mapping, whose first entry is (0, 0) and whose entries are line
 of '\\n' before its first byte, 0-based, global over the file.  No GPU needed.
 """
 import re
-from pathlib import Path
 
 import numpy as np
 import pytest
@@ -17,7 +16,6 @@ import sample_standin as S
 import xsg
 from xs_oracle import Oracle
 
-REF_META = Path("/root/reference/test/files/sample.meta")
 VEC = G.load("ref_xsearchtest_vectors.json")
 MAP = G.load("ref_xsearchtest_mapping_brackets.json")
 FAMILIES = ("literal_case", "literal_icase", "regex_case", "regex_icase")
@@ -93,9 +91,9 @@ def test_line_indices_live_in_the_mappings_index_space():
             assert c[0]["first_line"] <= i and i - c[0]["first_line"] <= o - c[0]["original_offset"]
 
 
-@pytest.mark.skipif(not REF_META.exists(), reason="reference tree not mounted")
-def test_brackets_are_what_xsg_meta_read_finds_in_sample_meta():
-    comp, chunks, maps = xsg.meta_read(str(REF_META), with_mappings=True)
+def test_brackets_are_what_xsg_meta_read_finds_in_sample_meta(tmp_path):
+    meta = G.ref_metafile("sample.meta", tmp_path)  # the reference's test/files/sample.meta, rebuilt from tests/golden/
+    comp, chunks, maps = xsg.meta_read(str(meta), with_mappings=True)
     maps = np.asarray(maps, dtype=np.uint64).reshape(-1, 2)
     assert comp == xsg.COMPRESSION_NONE and [int(x) for x in maps[0]] == [0, 0]
     assert [int(x) for x in maps[-1]] == MAP["last_mapping"]

@@ -5,6 +5,7 @@ g++ -fsanitize=... against tests/cpp/device_double.cpp, an oracle-backed stand-i
 the product library has no CPU path), and run the concurrent-jobs / early-destroy / live-iteration cases of
 tests/cpp/pipeline_sanitize.cpp.  CPU box only: GPU sanitizers are not available on the pool."""
 import os
+import platform
 import subprocess
 from pathlib import Path
 
@@ -12,6 +13,17 @@ import pytest
 
 ROOT = Path(__file__).resolve().parents[1]
 BUILD = ROOT / "tests" / "cpp" / "build"
+
+
+def _no_aslr_prefix():
+    """gcc's ThreadSanitizer runtime refuses a PIE mapped where hosts with more mmap randomisation bits put it
+    ("unexpected memory mapping"): the TSan binary runs with randomisation off for its own process, where allowed"""
+    cmd = ["setarch", platform.machine(), "-R"]
+    try:
+        ok = subprocess.run(cmd + ["true"], capture_output=True, timeout=30).returncode == 0
+    except (OSError, subprocess.SubprocessError):
+        ok = False
+    return cmd if ok else []
 
 
 @pytest.fixture(scope="module")
@@ -33,7 +45,8 @@ def test_host_pipeline_under_the_sanitizer(built, tmp_path, name, env, lanes):
     e["XSG_LANE2_MIN_CHUNKS"] = "1" if lanes == "two lanes" else "1000000"
     e["XSG_READ_PIECE"] = "65536"  # several pieces per chunk: the readers share chunks
     e.pop("XS_DEVICES", None)
-    r = subprocess.run([str(built / name), str(tmp_path)], env=e, capture_output=True, text=True, timeout=600)
+    prefix = _no_aslr_prefix() if name == "pipeline_tsan" else []
+    r = subprocess.run(prefix + [str(built / name), str(tmp_path)], env=e, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
     assert "ThreadSanitizer" not in r.stderr and "AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-4000:]
     assert "pipeline under the sanitizer: ok" in r.stdout
