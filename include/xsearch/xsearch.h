@@ -29,7 +29,8 @@
 // regex here too IF it is a fixed-length sequence of byte classes (`She[r ]lock`, `[0-9]{4}-\d\d`: XSG_FLAG_REGEX
 // in xsg.h -- every regex the reference's tests use); any other regex makes extern_search throw
 // std::invalid_argument instead of being searched as text with different results (XS_FORCE_LITERAL=1 searches
-// it as plain text).  ignore_case folds ASCII letters only (what the reference's simd::toLower does).
+// it as plain text; XS_FORCE_REGEX=1 reads every pattern as a regex, e.g. the line-anchored `(?m)^ERROR`).
+// ignore_case folds ASCII letters only (what the reference's simd::toLower does).
 //
 // Environment: XS_DEVICE (HIP device index, default 0), XS_DEVICES ("0,1,2,3" or "all": one search fans its chunk
 // ranges out over several devices of the node, one job each, results in file order), XS_CHUNK_BYTES (target
@@ -157,7 +158,9 @@ inline uint64_t count_chunks(const std::string& file_path, const char* meta, uin
 // invalid regex counts as plain text).  Such a pattern goes to the GPU matchers -- the scan
 // kernel's class-sequence matcher, or the automaton route for expressions of variable length --
 // when one of them can decide it (xsg_regex_check) and is refused loudly otherwise, never
-// searched as a literal with different results.  XS_FORCE_LITERAL=1 overrides.
+// searched as a literal with different results.  XS_FORCE_LITERAL=1 overrides.  XS_FORCE_REGEX=1 sends every
+// pattern down the regex route (a line-anchored `(?m)^x` is no valid std::regex, so the reference -- and this routing
+// -- reads it as text); XS_FORCE_LITERAL wins if both are set.
 inline bool reference_routes_to_regex(const std::string& pattern) {
   try {
     return !std::regex_match(pattern, std::regex("^" + pattern + "$"));
@@ -170,7 +173,8 @@ inline bool reference_routes_to_regex(const std::string& pattern) {
 // regular expression the GPU matcher does not serve.
 inline uint32_t pattern_flags(const std::string& pattern, bool ignore_case) {
   uint32_t flags = ignore_case ? XSG_FLAG_IGNORE_CASE : 0u;  // ASCII, as simd::toLower (string_utils.cpp:11-33)
-  if (reference_routes_to_regex(pattern) && env_u64("XS_FORCE_LITERAL", 0) == 0) {
+  if (env_u64("XS_FORCE_LITERAL", 0) != 0) return flags;
+  if (env_u64("XS_FORCE_REGEX", 0) != 0 || reference_routes_to_regex(pattern)) {
     if (xsg_regex_check(pattern.data(), pattern.size(), flags, nullptr, nullptr) != XSG_OK)
       throw std::invalid_argument("xs::extern_search: '" + pattern +
                                   "' is a regular expression for the reference (utils/utils.h:17-25) that the GPU "

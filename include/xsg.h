@@ -108,7 +108,14 @@ enum xsg_mode {
  * [^,]*) can match across lines: it is walked chunk by chunk, one lane per chunk
  * (slow), and serves XSG_COUNT_MATCHES / XSG_MATCH_BYTE_OFFSETS only.  Refused on
  * this route (XSG_ENOTSUP from xsg_set_pattern, never approximated): expressions
- * that can match the empty string, automata over 16384 table entries.  Refused on both routes: anchors ^ $ \b \A \z, (?flags), \p, \C.
+ * that can match the empty string, automata over 16384 table entries.  Refused on both routes: anchors ^ $ \b \A \z, (?flags), \p, \C
+ * -- except LINE ANCHORS in RE2's multi-line form  (?m) [^] BODY [$] : `(?m)` as the first four bytes, `^` as the next
+ * token, `$` as the last, BODY any expression served above with no top-level `|` (write (?m)^(?:a|b)$), no set that
+ * accepts '\n' and no empty match.  `^` holds at a line start and at the walk's resume point (in the match tags
+ * (?m)^ab on "abab" matches at 0 and 2, as the reference computes), `$` at a line end; a chunk's edges are line edges
+ * and the bytes beyond them are never read.  Such an expression is searched by the automaton route's line walks, all
+ * six tags; xsg_regex_check / xsg_regex_info describe BODY.  (?m) with neither anchor is BODY's search.  Anchors or
+ * flags anywhere else, (?m:...), (?mi) and the plain ^ $ stay refused.
  * CAPTURE GROUPS: the reference's walk is RE2::PartialMatch(input, pattern, &match) (search_wrappers.h:71-75,
  * 254-257), where `match` receives capture group ONE; its tests hand over an expression that IS one group,
  * re2::RE2("(a[n|m]t)") (test/src/string_search/search_wrappersTest.cpp:78).  XSG_FLAG_REGEX(expr) is that call with

@@ -1,10 +1,15 @@
 // xsgrep -- the reference's example/grep.cpp (PATTERN FILE, -c, -i; lines 23-82)
 // on the MI355X engine, without boost::program_options.
 //
-//   xsgrep [-c] [-i] [-F] [-j THREADS] [-m METAFILE] PATTERN FILE|-
+//   xsgrep [-c] [-i] [-E|-F] [-x] [-j THREADS] [-m METAFILE] PATTERN FILE|-
 //
 // -c  print only a count of matching lines   (grep.cpp:45-46 -> xs::count_lines)
 // -i  ignore ASCII case                      (grep.cpp:47-48)
+// -E  read PATTERN as a regex (RE2 syntax) whatever the reference's routing says (XS_FORCE_REGEX)
+// -F  read PATTERN as plain text (XS_FORCE_LITERAL)
+// -x  whole lines only: searches the regex (?m)^(?:PATTERN)$ (with -F, PATTERN escaped into an RE2 literal first;
+//     otherwise a leading `^` and a trailing `$` of PATTERN are dropped, redundant under -x).  An empty PATTERN is
+//     refused (it would match empty lines only), as is a PATTERN with anchors elsewhere (`^a|^b`).
 // otherwise print the matching lines, live, as they are found (grep.cpp:74-79).
 #include <xsearch/tasks/gpu_searchers.h>
 #include <xsearch/xsearch.h>
@@ -15,8 +20,34 @@
 #include <iostream>
 #include <string>
 
+static const char kUsage[] =
+    "usage: %s [-c] [-i] [-E|-F] [-x] [-j THREADS] [-m METAFILE] PATTERN FILE|-\n"
+    "  -x searches (?m)^(?:PATTERN)$; PATTERN must not be empty\n";
+
+// PATTERN without a leading `^` and a trailing unescaped `$`: under -x they say what the wrap says already
+static std::string strip_edge_anchors(std::string p) {
+  if (!p.empty() && p[0] == '^') p.erase(0, 1);
+  if (!p.empty() && p.back() == '$') {
+    size_t bs = 0;
+    while (bs + 1 < p.size() && p[p.size() - 2 - bs] == '\\') ++bs;
+    if (bs % 2 == 0) p.pop_back();
+  }
+  return p;
+}
+
+// PATTERN as an RE2 expression that matches exactly its bytes: ASCII punctuation gets a backslash
+static std::string re2_literal(const std::string& p) {
+  std::string r;
+  for (unsigned char c : p) {
+    const bool alnum = (c >= '0' && c <= '9') || ((c | 0x20) >= 'a' && (c | 0x20) <= 'z');
+    if (c > 0x20 && c < 0x7f && !alnum) r += '\\';
+    r += (char)c;
+  }
+  return r;
+}
+
 int main(int argc, char** argv) {
-  bool count = false, icase = false;
+  bool count = false, icase = false, fixed = false, extended = false, whole_lines = false;
   int threads = 2;  // grep.cpp:21
   std::string meta, pattern, file;
   int pos = 0;
@@ -27,13 +58,17 @@ int main(int argc, char** argv) {
     } else if (a == "-i" || a == "--ignore-case") {
       icase = true;
     } else if (a == "-F" || a == "--fixed-strings") {
-      setenv("XS_FORCE_LITERAL", "1", 1);  // like grep -F: never read the pattern as a regex
+      fixed = true;  // like grep -F: never read the pattern as a regex
+    } else if (a == "-E" || a == "--extended-regexp") {
+      extended = true;
+    } else if (a == "-x" || a == "--line-regexp") {
+      whole_lines = true;
     } else if ((a == "-j" || a == "--threads") && i + 1 < argc) {
       threads = std::atoi(argv[++i]);
     } else if ((a == "-m" || a == "--meta") && i + 1 < argc) {
       meta = argv[++i];
     } else if (a == "-h" || a == "--help") {
-      std::printf("usage: %s [-c] [-i] [-j THREADS] [-m METAFILE] PATTERN FILE\n", argv[0]);
+      std::printf(kUsage, argv[0]);
       return 0;
     } else if (pos == 0) {
       pattern = a;
@@ -47,9 +82,28 @@ int main(int argc, char** argv) {
     }
   }
   if (pos != 2) {
-    std::fprintf(stderr, "usage: %s [-c] [-i] [-j THREADS] [-m METAFILE] PATTERN FILE\n", argv[0]);
+    std::fprintf(stderr, kUsage, argv[0]);
     return 2;
   }
+  if (fixed && extended) {
+    std::fprintf(stderr, "xsgrep: -E and -F exclude each other\n");
+    return 2;
+  }
+  if (whole_lines) {  // a line-anchored regex (xsg.h, XSG_FLAG_REGEX): the whole line is one match of PATTERN
+    const std::string body = fixed ? re2_literal(pattern) : strip_edge_anchors(pattern);
+    if (body.empty()) {
+      std::fprintf(stderr, "xsgrep: -x with an empty pattern (it matches empty lines only) is not supported\n");
+      return 2;
+    }
+    pattern = "(?m)^(?:" + body + ")$";
+    if (pattern.size() > XSG_MAX_REGEX) {
+      std::fprintf(stderr, "xsgrep: -x: the expression is longer than %u bytes\n", (unsigned)XSG_MAX_REGEX);
+      return 2;
+    }
+    extended = true, fixed = false;
+  }
+  if (fixed) setenv("XS_FORCE_LITERAL", "1", 1);
+  if (extended) setenv("XS_FORCE_REGEX", "1", 1);
   try {
     std::ios::sync_with_stdio(false);
     if (file == "-") {

@@ -356,7 +356,17 @@ static int set_dfa_pattern(xsg_ctx* c, const uint8_t* re, size_t n, uint32_t fla
   c->koff_cands.clear();
   c->bordered = false;  // the kernel walks every line as the reference does: what it reports is already non-overlapping
   c->overlap_words.clear();
-  const size_t rev_off = rx_rev_offset((uint32_t)dfa.fwd.size());
+  // The table the line walks step (k_rx_scan / k_rx_count): the anchored automaton for the line-anchor form (`^` walks
+  // it; `$` alone walks the reverse automaton and ships `anc` only for its start row), else the forward one.
+  const bool anchored = dfa.anchor_begin || dfa.anchor_end;
+  const std::vector<uint16_t>& walk = anchored ? dfa.anc : dfa.fwd;
+  // a TRIGGER can begin a match: it moves the unanchored automaton out of its start state, or equally takes the
+  // anchored one to a live state.  (Anchored walks do not skip, but a span without a trigger still holds no match start.)
+  auto trigger = [&](uint32_t b) {
+    return anchored ? dfa.anc[(size_t)dfa.anc_start * dfa.ncls + dfa.class_of[b]] != 0
+                    : dfa.fwd[(size_t)dfa.fwd_start * dfa.ncls + dfa.class_of[b]] != dfa.fwd_start * dfa.ncls;
+  };
+  const size_t rev_off = rx_rev_offset((uint32_t)walk.size());
   const size_t anc_off = (rev_off + 2 * dfa.rev.size() + 15) & ~(size_t)15;
   const size_t bytes = anc_off + 2 * dfa.anc.size() + 16;
   std::vector<uint8_t> blob(bytes, 0);
@@ -370,14 +380,13 @@ static int set_dfa_pattern(xsg_ctx* c, const uint8_t* re, size_t n, uint32_t fla
     // skipping pays when triggers are rare in the data; an expression that can begin with most letters (`\\w+ing`)
     // triggers at every word and the jumps cost more than the steps they replace (measured: 156 against 201 GB/s)
     uint32_t common = 0;
-    for (uint32_t b = 'a'; b <= 'z'; ++b)
-      common += dfa.fwd[(size_t)dfa.fwd_start * dfa.ncls + dfa.class_of[b]] != dfa.fwd_start * dfa.ncls;
+    for (uint32_t b = 'a'; b <= 'z'; ++b) common += trigger(b);
     if (common >= 9) skip = false;
   }
   if (skip)
     for (uint32_t b = 0; b < 256; ++b)
-      if (b == '\n' || dfa.fwd[(size_t)dfa.fwd_start * dfa.ncls + dfa.class_of[b]] != dfa.fwd_start * dfa.ncls) blob[b] |= 0x80u;
-  memcpy(blob.data() + 256, dfa.fwd.data(), 2 * dfa.fwd.size());
+      if (b == '\n' || trigger(b)) blob[b] |= 0x80u;
+  memcpy(blob.data() + 256, walk.data(), 2 * walk.size());
   memcpy(blob.data() + rev_off, dfa.rev.data(), 2 * dfa.rev.size());
   XSG_TRY(c->d_pat.ensure(std::max<size_t>(bytes, XSG_MAX_REGEX + 16)));
   HIP_TRY(hipMemcpyAsync(c->d_pat.p, blob.data(), bytes, hipMemcpyHostToDevice, c->stream));
@@ -393,10 +402,12 @@ static int set_dfa_pattern(xsg_ctx* c, const uint8_t* re, size_t n, uint32_t fla
   P.has_newline = dfa.multiline ? 1u : 0u;  // a match may span lines: the line tags are refused, as for a literal with '\n'
   P.rx_multiline = dfa.multiline ? 1u : 0u;
   P.rx_ncls = dfa.ncls;
-  P.rx_fwd_n = (uint32_t)dfa.fwd.size();
+  P.rx_fwd_n = (uint32_t)walk.size();
   P.rx_rev_n = (uint32_t)dfa.rev.size();
-  P.rx_fwd_start = dfa.fwd_start * dfa.ncls;
-  P.rx_fwd_acc = dfa.fwd_first_acc * dfa.ncls;
+  P.rx_fwd_start = (anchored ? dfa.anc_start : dfa.fwd_start) * dfa.ncls;
+  P.rx_fwd_acc = (anchored ? dfa.anc_first_acc : dfa.fwd_first_acc) * dfa.ncls;
+  P.rx_bol = dfa.anchor_begin ? 1u : 0u;
+  P.rx_eol = dfa.anchor_end ? 1u : 0u;
   P.rx_rev_start = dfa.rev_start * dfa.ncls;
   P.rx_rev_acc = dfa.rev_first_acc * dfa.ncls;
   P.rx_skip = skip ? 1u : 0u;
@@ -457,6 +468,8 @@ static int set_class_pattern(xsg_ctx* c, const uint8_t* re, size_t n, uint32_t f
   std::string err;
   const bool icase = (flags & XSG_FLAG_IGNORE_CASE) != 0;
   if (!xsg::compile_class_expr(re, n, icase, &ex, &err)) return set_dfa_pattern(c, re, n, flags, err);
+  // (?m)^BODY$ with a fixed-length BODY: the anchors are decided by the line walks of the automaton route
+  if (ex.anchor_begin || ex.anchor_end) return set_dfa_pattern(c, re, n, flags, "line anchors");
   const size_t plen = ex.npos;
   const std::vector<xsg::ByteSet> seq = xsg::union_sets(ex);  // what the filter, the overlap and '\n' tests look at
   bool literal = ex.alts.size() == 1;
@@ -558,6 +571,8 @@ extern "C" int xsg_regex_check(const void* expr, size_t n, uint32_t flags, uint3
     if (positions) *positions = 0;  // variable length: no position-wise sets; such an expression never accepts '\n'
     return XSG_OK;
   }
+  if (ex.anchor_begin || ex.anchor_end)  // searched by the automaton route (set_class_pattern): it must serve it
+    XSG_TRY(dfa_route_serves(expr, n, flags, "line anchors", nullptr));
   const std::vector<xsg::ByteSet> seq = xsg::union_sets(ex);
   if (positions) *positions = (uint32_t)seq.size();
   if (sets) memcpy(sets, seq.data(), seq.size() * sizeof(xsg::ByteSet));
@@ -578,6 +593,7 @@ extern "C" int xsg_regex_info(const void* expr, size_t n, uint32_t flags, uint32
     if (ascii_only) *ascii_only = dfa.ascii_only ? 1u : 0u;
     return XSG_OK;
   }
+  if (ex.anchor_begin || ex.anchor_end) XSG_TRY(dfa_route_serves(expr, n, flags, "line anchors", nullptr));
   if (positions) *positions = ex.npos;
   if (alternatives) *alternatives = (uint32_t)ex.alts.size();
   if (ascii_only) *ascii_only = ex.ascii_only ? 1u : 0u;

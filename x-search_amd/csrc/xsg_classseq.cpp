@@ -16,6 +16,8 @@
 //            "(a[n|m]t)", the integration tests `She[r ]lock`)
 //   a|b      alternation at any depth, as long as every alternative of the whole expression ends up with the
 //            same length (then leftmost-first has nothing to choose: see xsg_classseq.h)
+//   (?m)^BODY$  the line-anchor form (xsg_rxlex.h: strip_line_anchors): BODY is parsed as above and the anchors are
+//            noted on the ClassExpr; a set of BODY that accepts '\n' is refused then
 // Refused HERE (the caller then tries the automaton route, xsg_regex.cpp, which serves the variable-length operators):
 //   * + ? {n,m} {n,} ^ $ (?flags) (?P<..>) \b \B \A \z \p \P \Q \C, backslash + letter/digit otherwise,
 //   class members >= 0x80, alternatives of different lengths, more than kMaxClassSeq positions, more than
@@ -221,11 +223,22 @@ bool class_expr_from_alternatives(std::vector<std::vector<ByteSet>> alts, ClassE
 
 bool compile_class_expr(const uint8_t* re, size_t n, bool ignore_case, ClassExpr* out, std::string* err) {
   *out = ClassExpr{};
+  const uint8_t* body = nullptr;
+  size_t body_n = 0;
+  bool multi_line = false, bol = false, eol = false;
+  if (!strip_line_anchors(re, n, &body, &body_n, &multi_line, &bol, &eol, err)) return false;
   Parser p;
-  p.re = re, p.n = n, p.err = err;
+  p.re = body, p.n = body_n, p.err = err;
   p.icase = ignore_case;
   Parser::SeqSet alts;
   if (!p.run(&alts)) return false;
+  if (multi_line)
+    for (const auto& a : alts)
+      for (const ByteSet& st : a)
+        if (set_has(st, '\n')) {
+          *err = "a set that accepts '\\n' under (?m) (a body that spans lines) is not supported";
+          return false;
+        }
   const size_t len = alts[0].size();
   for (const auto& a : alts)
     if (a.size() != len) {
@@ -246,6 +259,7 @@ bool compile_class_expr(const uint8_t* re, size_t n, bool ignore_case, ClassExpr
   out->npos = (uint32_t)len;
   out->alts = std::move(alts);
   out->ascii_only = p.ascii_only;
+  out->anchor_begin = bol, out->anchor_end = eol;
   return true;
 }
 
@@ -262,7 +276,7 @@ bool compile_class_sequence(const uint8_t* re, size_t n, std::vector<ByteSet>* s
   seq->clear();
   ClassExpr e;
   if (!compile_class_expr(re, n, false, &e, err)) return false;
-  if (e.alts.size() != 1 || e.ascii_only) {
+  if (e.alts.size() != 1 || e.ascii_only || e.anchor_begin || e.anchor_end) {
     *err = "not a single class sequence";
     return false;
   }

@@ -10,7 +10,8 @@
 // position-wise decision as a literal, so it runs in k_scan.  Expressions of
 // variable length (repetition operators, alternatives of different lengths) are
 // not this family: xsg_regex.h compiles them to automata for a second kernel.
-// Anchors and flags are refused by both, never approximated.
+// Anchors and flags are refused by both, never approximated -- except the line-anchor form (?m)^BODY$, whose
+// `^` means "at a line start or at the resume point" and `$` "at a line end" ("Line anchors").
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -50,6 +51,9 @@ struct ClassExpr {
   uint32_t npos = 0;
   std::vector<std::vector<ByteSet>> alts;  // each npos long
   bool ascii_only = false;
+  // the line-anchor form (?m)^BODY$: the expression was BODY with `^` / `$` at its edges.  Such an
+  // expression is searched by the automaton route (xsg_regex.h), which walks lines; the sets describe BODY.
+  bool anchor_begin = false, anchor_end = false;
 };
 // ignore_case: the sets come back folded (every 'A'..'Z' member replaced by its lower-case letter: the kernel lowers
 // the data), negated classes having been closed under case BEFORE the complement, as RE2's (?i) does.

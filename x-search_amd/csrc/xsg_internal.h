@@ -82,6 +82,10 @@ struct PatternDev {
                                    // the tile for them on the 16-byte loads and leaves a tile that holds none without staging it
   uint32_t rx_skip;                // bit 7 of every class_of[] entry flags a TRIGGER byte: one that moves the forward automaton
                                    // out of its start state, or '\n' (needs ncls <= 128; XSG_RX_SKIP=0 switches it off)
+  uint32_t rx_bol, rx_eol;         // the line-anchor form (?m)^BODY$ (xsg_regex.h): rx_bol -- the forward table is the
+                                   // ANCHORED automaton, walked from each line start (and each match end), never skipping;
+                                   // rx_eol -- it runs over BODY '\n', a '\n' is stepped at the chunk's end, at most one
+                                   // match per line, ending one byte before the last accepting position
 };
 
 // Per-tile line summaries (XSG_COUNT_LINES): see xsg_linesum.h.

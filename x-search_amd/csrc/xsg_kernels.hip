@@ -1168,8 +1168,10 @@ void describe_scan(const ScanArgs& a, bool want_nl, bool want_lines, bool emit, 
       snprintf(name, sizeof name, "xsg::k_rx_scan<%s, %s>", b[emit], b[emit ? 0 : want_lines]);
     else
       snprintf(name, sizeof name, "xsg::k_rx_count<%s>", b[want_lines]);
-    snprintf(out, cap, "%s states=%u classes=%u%s", name, a.pat.rx_ncls ? a.pat.rx_fwd_n / a.pat.rx_ncls : 0u, a.pat.rx_ncls,
-             a.tile_mask ? " (tiles marked by the factor prefilter only)" : "");
+    // the line-anchor form names its anchors: `anchored=^` walks the anchored automaton, `anchored=$` steps a '\n' at the end
+    const char* anc = a.pat.rx_bol ? (a.pat.rx_eol ? " anchored=^$" : " anchored=^") : (a.pat.rx_eol ? " anchored=$" : "");
+    snprintf(out, cap, "%s states=%u classes=%u%s%s", name, a.pat.rx_ncls ? a.pat.rx_fwd_n / a.pat.rx_ncls : 0u, a.pat.rx_ncls,
+             anc, a.tile_mask ? " (tiles marked by the factor prefilter only)" : "");
     return;
   }
   ScanArgs r = a;

@@ -14,6 +14,12 @@ namespace {
 
 constexpr uint32_t kInf = 0xffffffffu;
 
+ByteSet single_nl() {
+  ByteSet s{};
+  set_add(s, '\n');
+  return s;
+}
+
 struct Node {
   enum Kind { kSet, kCat, kAlt, kRep } kind = kSet;
   ByteSet set{};
@@ -558,8 +564,12 @@ void find_factor(const std::vector<Node>& pool, int root, ClassExpr* out) {
 
 bool compile_regex_dfa(const uint8_t* re, size_t n, bool ignore_case, RegexDfa* out, std::string* err) {
   *out = RegexDfa{};
+  const uint8_t* body = nullptr;
+  size_t body_n = 0;
+  bool multi_line = false;
+  if (!strip_line_anchors(re, n, &body, &body_n, &multi_line, &out->anchor_begin, &out->anchor_end, err)) return false;
   TreeParser p;
-  p.re = re, p.n = n, p.err = err;
+  p.re = body, p.n = body_n, p.err = err;
   p.icase = ignore_case;
   int root = -1;
   if (!p.run(&root)) return false;
@@ -576,11 +586,19 @@ bool compile_regex_dfa(const uint8_t* re, size_t n, bool ignore_case, RegexDfa* 
   // not the line (k_rx_chunk), and the line tags do not apply -- as for a literal that contains '\n'.
   for (const Node& nd : p.pool)
     if (nd.kind == Node::kSet && set_has(nd.set, '\n')) out->multiline = true;
+  if (multi_line && out->multiline) {
+    *err = "a set that accepts '\\n' under (?m) (a body that spans lines) is not supported";
+    return false;
+  }
+  const bool anchored = out->anchor_begin || out->anchor_end;
 
   // forward: any-byte loop of lowest priority in front of the expression (RE2's unanchored search)
   Nfa f;
   const int fmatch = f.add(Inst::kMatch, -1, -1, -1);
-  const int fentry = emit(p.pool, root, fmatch, false, &f);
+  // `$`: the forward automata run over BODY '\n' (the walk presents a '\n' at the chunk's end); the match ends in
+  // front of that '\n', and the reverse automaton, over BODY alone, runs back from there
+  const int fnl = out->anchor_end ? f.add(Inst::kSet, f.set_id(single_nl()), fmatch, -1) : fmatch;
+  const int fentry = emit(p.pool, root, fnl, false, &f);
   ByteSet any{};
   for (uint32_t b = 0; b < 256; ++b)
     if (b != '\n' || out->multiline) set_add(any, b);
@@ -612,13 +630,18 @@ bool compile_regex_dfa(const uint8_t* re, size_t n, bool ignore_case, RegexDfa* 
   out->ncls = (uint32_t)rep.size();
 
   Dfa fd, rd, ad;
-  if (!determinise(f, fstart, rep, true, &fd, err)) return false;
+  // The line-anchor form never walks the unanchored automaton (`^`: `anc`; `$` alone: `rev` back from each line's end,
+  // xsg_regex.h), and it is the one that can blow up (`a[ab]{12}` in front of an any-byte loop: 2^13 states): not built.
+  if (!anchored && !determinise(f, fstart, rep, true, &fd, err)) return false;
   if (!determinise(r, rentry, rep, false, &rd, err)) return false;
   if (!determinise(f, fentry, rep, true, &ad, err)) return false;  // anchored: the expression without the loop in front
-  if (!flatten(fd, out->ncls, &out->fwd, &out->fwd_states, &out->fwd_start, &out->fwd_first_acc, err)) return false;
+  if (!anchored && !flatten(fd, out->ncls, &out->fwd, &out->fwd_states, &out->fwd_start, &out->fwd_first_acc, err))
+    return false;
   if (!flatten(rd, out->ncls, &out->rev, &out->rev_states, &out->rev_start, &out->rev_first_acc, err)) return false;
   if (!flatten(ad, out->ncls, &out->anc, &out->anc_states, &out->anc_start, &out->anc_first_acc, err)) return false;
-  find_prefix(ad, rep, out->class_of, (uint32_t)std::min<uint64_t>(p.pool[root].minlen, 8), &out->prefix);
+  // The prefilter's candidate walk (k_rx_heads) knows nothing of line starts and ends: off for the anchored form.  The
+  // factor stays valid -- every match of (?m)^BODY$ is a match of BODY and contains BODY's factor.
+  if (!anchored) find_prefix(ad, rep, out->class_of, (uint32_t)std::min<uint64_t>(p.pool[root].minlen, 8), &out->prefix);
   if (out->prefix.npos == 0 && !out->multiline) find_factor(p.pool, root, &out->factor);
   out->minlen = (uint32_t)std::min<uint64_t>(p.pool[root].minlen, 0xffffffffu);
   out->ascii_only = p.ascii_only;

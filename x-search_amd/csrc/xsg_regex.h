@@ -26,7 +26,17 @@
 //     kernel hands to its lanes (a line is walked sequentially, as the reference walks a chunk; lines are
 //     independent).  An expression with a set that accepts '\n' (\s+, [^,]*) is `multiline`: its unit of sequential
 //     work is the chunk (k_rx_chunk: one lane per chunk), and only the match tags apply to it;
-//   * ^ $ \b \B \A \z (they read the context of a re-sliced input in the reference), (?flags), \p, \C, back-refs;
+//   * ^ $ \b \B \A \z (they read the context of a re-sliced input in the reference), (?flags), \p, \C, back-refs --
+//     except the LINE-ANCHOR form  (?m) [^] BODY [$]  (xsg_rxlex.h: strip_line_anchors): `(?m)` as the
+//     first four bytes, `^` right behind it, `$` as the last token, BODY any expression of this family without a
+//     top-level `|` and without a set that accepts '\n'.  On one chunk d[0, n) walked from a resume point r (0, then
+//     the end of the last match for the match tags, the start of the next line for the line tags), `^` holds at p iff
+//     p == r or d[p-1] == '\n', `$` iff p == n or d[p] == '\n': chunk edges are line edges, and in the match tags
+//     `(?m)^ab` on "abab" matches at 0 and 2 (the reference's resume-point quirk, replayed).  `^` makes the walk
+//     anchored (`anc`, from each line start and from each match end); `$` with `^` lives inside `anc` (BODY '\n');
+//     `$` alone makes the match [s, e) for the line's end e and the smallest s at or behind the resume point with
+//     [s, e) in BODY, which is what the reverse automaton (longest match) finds walking back from e.  A line then has
+//     at most one match.  The unanchored forward automaton is not built for this form;
 //   * automata over kRxMaxEntries table entries.
 #pragma once
 #include <stdint.h>
@@ -68,6 +78,11 @@ struct RegexDfa {
   ClassExpr factor;
   bool ascii_only = false;   // as ClassExpr::ascii_only: a search refuses data with a byte >= 0x80
   bool multiline = false;    // some set accepts '\n': matches may span lines ('\n' is then an ordinary byte for the automata)
+  // The line-anchor form (?m)^BODY$ (see the header comment): `fwd` is empty, no prefix.  anchor_begin: the walk uses
+  // `anc` from every line start and, in the match tags, from every match end; with anchor_end `anc` runs over BODY '\n'
+  // (the walk steps a '\n' at the chunk's end; the match ends one byte before the accepting position).  anchor_end
+  // alone: `rev` (over BODY) from each line's end back to the resume point, its last accepting position the start.
+  bool anchor_begin = false, anchor_end = false;
 };
 
 // ignore_case: every set is closed under ASCII case (the data is NOT folded on this route).

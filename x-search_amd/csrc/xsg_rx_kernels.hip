@@ -49,6 +49,7 @@ struct RxCtx {
   uint32_t tile_bytes = kRxTile;  // bytes staged at `tilew` (k_rx_scan: the 16 KiB tile; k_rx_count: a wave's 4 KiB span)
   uint32_t nseg = kBlock;         // ... = this many 64-byte segments (trigger words)
   const uint8_t* la = nullptr;    // LDS: the (up to) 64 RAW bytes behind the staged bytes, '\n' beyond the chunk (k_rx_count)
+  uint32_t bol = 0, eol = 0;      // PatternDev::rx_bol / rx_eol: the line-anchor form
 };
 
 // class code of the byte at q (< L), wherever it lives
@@ -68,6 +69,32 @@ __device__ __forceinline__ uint32_t rx_class(const RxCtx& X, uint64_t q) {
 template <bool EMITTING, bool LINES>
 __device__ __forceinline__ uint32_t rx_walk_line(const RxCtx& X, uint64_t cur, const ScanArgs& A, uint32_t chunk,
                                                  uint64_t& rank) {
+  if (X.eol && !X.bol) {
+    // `$` alone (xsg_regex.h): the line's one match is [s, e) for its end e and the smallest s >= cur with [s, e) in
+    // BODY -- the reverse automaton's longest match, walked back from e (bytes at or beyond L read as '\n' in the tile;
+    // the search for '\n' stops at L behind it).  The unanchored forward automaton, which can be exponentially larger
+    // for a fixed-length BODY, is never needed.
+    const uint32_t nlc = X.cls[0x0a] & X.cmask;
+    uint64_t e = cur;
+    while (e < X.L && rx_class(X, e) != nlc) ++e;
+    uint32_t rs = X.rev_start;
+    uint64_t r = e, start = e;
+    while (r > cur) {
+      rs = X.rev[rs + rx_class(X, r - 1)];
+      if (rs == 0) break;
+      --r;
+      if (rs >= X.rev_acc) start = r;
+    }
+    if (start == e) return 0u;  // (a match is never empty)
+    if (EMITTING) {
+      if (A.m_cap == 0 || rank < A.m_cap) {
+        A.m_pos[rank] = start;
+        A.m_chunk[rank] = chunk;
+      }
+      ++rank;
+    }
+    return 1u;
+  }
   uint32_t n = 0;
   for (;;) {
     uint32_t st = X.fwd_start;
@@ -81,7 +108,7 @@ __device__ __forceinline__ uint32_t rx_walk_line(const RxCtx& X, uint64_t cur, c
         // In its start state the automaton only waits for a byte that can begin a match: every other byte leaves it
         // where it is.  Those bytes (and '\n') are the tile's TRIGGERS, flagged for all 16 KiB at once in the staging
         // phase; the walk jumps from one to the next on the bit masks instead of stepping through the text.
-        if (X.skip && st == X.fwd_start) {
+        if (X.skip && !X.bol && st == X.fwd_start) {  // (anchored: the start state is left or dead on the first byte)
           uint32_t w = rel >> 6;
           unsigned long long m = X.trig[w] & (~0ull << (rel & 63u));
           while (!m && ++w < X.nseg) m = X.trig[w];
@@ -116,9 +143,11 @@ __device__ __forceinline__ uint32_t rx_walk_line(const RxCtx& X, uint64_t cur, c
       q = X.toff + rel;
       if (last_rel) last_end = X.toff + last_rel;
     }
-    while (!stop && q < X.L) {  // behind the tile
+    // behind the tile; `$` (eol) also steps the '\n' that the chunk's end stands for (inside the tile, bytes at or
+    // beyond L already read as '\n')
+    while (!stop && (q < X.L || (X.eol && q == X.L))) {
       const uint64_t bq = q - (X.toff + X.tile_bytes);  // the first 64 of those bytes may be at hand in LDS
-      const uint32_t byte = (X.la && bq < 64u) ? X.la[bq] : X.cbase[q];
+      const uint32_t byte = q == X.L ? 0x0au : (X.la && bq < 64u) ? X.la[bq] : X.cbase[q];
       st = X.fwd[st + (X.cls[byte] & X.cmask)];
       if (st == 0) break;
       ++q;
@@ -130,6 +159,7 @@ __device__ __forceinline__ uint32_t rx_walk_line(const RxCtx& X, uint64_t cur, c
     if (!last_end) break;  // no (further) match in this line
     ++n;
     if (LINES) break;
+    if (X.eol) --last_end;  // the '\n' behind BODY is not part of the match
     if (EMITTING) {
       uint32_t rs = X.rev_start;
       uint64_t r = last_end, start = last_end;
@@ -145,6 +175,7 @@ __device__ __forceinline__ uint32_t rx_walk_line(const RxCtx& X, uint64_t cur, c
       }
       ++rank;
     }
+    if (X.eol) break;  // a match that ends at the line's end is its last
     cur = last_end;
   }
   return n;
@@ -280,7 +311,8 @@ __global__ __launch_bounds__(kBlock) void k_rx_scan(const ScanArgs A, const uint
       // is no '\n', and it holds a line start: a '\n' somewhere, or its first byte opens the chunk / follows a '\n'.
       if (tid == 0) {
         const uint64_t tend = toff + kRxTile;
-        if (tend < L && !(tf & 4u) && (tf & (2u | 8u))) {
+        // (`^`: that line's start is no trigger, so the anchored walk dies on it at once)
+        if (tend < L && !(tf & 4u) && (tf & (2u | 8u)) && !P.rx_bol) {
           // Inside the tile the line holds no trigger: the automaton reaches the tile's end in its start state.  Nearly
           // always the line ends within the next few dozen bytes without a trigger either -- decided on the 64 bytes
           // fetched with the tile, a few LDS reads; stepping the automaton through global memory byte by byte, one
@@ -305,9 +337,10 @@ __global__ __launch_bounds__(kBlock) void k_rx_scan(const ScanArgs A, const uint
             RxCtx X;
             X.tilew = nullptr, X.cls = P.d_pat, X.fwd = reinterpret_cast<const uint16_t*>(P.d_pat + 256);
             X.trig = nullptr, X.skip = P.rx_skip, X.cmask = 0x7fu;
-            X.rev = nullptr;
+            X.rev = reinterpret_cast<const uint16_t*>(P.d_pat + ((256u + 2u * (size_t)P.rx_fwd_n + 15u) & ~(size_t)15u));
             X.cbase = cbase, X.toff = toff, X.L = L;
             X.fwd_start = P.rx_fwd_start, X.fwd_acc = P.rx_fwd_acc, X.rev_start = P.rx_rev_start, X.rev_acc = P.rx_rev_acc;
+            X.bol = P.rx_bol, X.eol = P.rx_eol;
             uint64_t rank = 0;
             const uint32_t n = rx_walk_line<false, LINES>(X, tend, A, c, rank);
             if (n) atomicAdd(A.tile_cnt + tile, n);
@@ -384,6 +417,7 @@ __global__ __launch_bounds__(kBlock) void k_rx_scan(const ScanArgs A, const uint
   X.rev = reinterpret_cast<const uint16_t*>(P.d_pat + ((256u + 2u * (size_t)P.rx_fwd_n + 15u) & ~(size_t)15u));
   X.cbase = cbase, X.toff = toff, X.L = L;
   X.fwd_start = P.rx_fwd_start, X.fwd_acc = P.rx_fwd_acc, X.rev_start = P.rx_rev_start, X.rev_acc = P.rx_rev_acc;
+  X.bol = P.rx_bol, X.eol = P.rx_eol;
 
   uint32_t cnt = 0;
   uint64_t rank = 0;
@@ -550,7 +584,7 @@ __global__ __launch_bounds__(kBlock) void k_rx_count(const ScanArgs A, const uin
     // last byte is no '\n', and it holds a line start: a '\n' somewhere, or its first byte opens the chunk / follows one.
     const bool last_is_nl = __ballot(lane == 63u && (dd[3][3] >> 24) == 0x0au) != 0;
     const bool has_start = __ballot((any_nl & 0x80808080u) != 0) != 0 || __ballot(lane == 0u && prev_byte == 0x0au) != 0;
-    if (send >= L || last_is_nl || !has_start) return;
+    if (send >= L || last_is_nl || !has_start || P.rx_bol) return;  // (`^`: that line's start is no trigger)
     // Inside the span the line holds no trigger: the automaton reaches the span's end in its start state.  Nearly always
     // the line ends within the next few dozen bytes without a trigger either: every lane holds a dword of the 256 bytes
     // behind the span; the first lane with a '\n' settles it -- no trigger in the lanes below, none below the '\n' in its
@@ -575,9 +609,10 @@ __global__ __launch_bounds__(kBlock) void k_rx_count(const ScanArgs A, const uin
       RxCtx X;
       X.tilew = nullptr, X.cls = P.d_pat, X.fwd = reinterpret_cast<const uint16_t*>(P.d_pat + 256);
       X.trig = nullptr, X.skip = P.rx_skip, X.cmask = 0x7fu;
-      X.rev = nullptr;
+      X.rev = reinterpret_cast<const uint16_t*>(P.d_pat + ((256u + 2u * (size_t)P.rx_fwd_n + 15u) & ~(size_t)15u));
       X.cbase = cbase, X.toff = soff, X.L = L;
       X.fwd_start = P.rx_fwd_start, X.fwd_acc = P.rx_fwd_acc, X.rev_start = P.rx_rev_start, X.rev_acc = P.rx_rev_acc;
+      X.bol = P.rx_bol, X.eol = P.rx_eol;
       X.tile_bytes = kRxSpan, X.nseg = 64u;
       uint64_t rank = 0;
       const uint32_t n = rx_walk_line<false, LINES>(X, send, A, c, rank);
@@ -651,9 +686,10 @@ __global__ __launch_bounds__(kBlock) void k_rx_count(const ScanArgs A, const uin
   RxCtx X;
   X.tilew = reinterpret_cast<const uint32_t*>(sp), X.cls = s_cls, X.fwd = reinterpret_cast<const uint16_t*>(s_dyn);
   X.trig = s_trig + wave * 64u, X.skip = P.rx_skip, X.cmask = P.rx_skip ? 0x7fu : 0xffu;
-  X.rev = nullptr;
+  X.rev = reinterpret_cast<const uint16_t*>(P.d_pat + ((256u + 2u * (size_t)P.rx_fwd_n + 15u) & ~(size_t)15u));
   X.cbase = cbase, X.toff = soff, X.L = L;
   X.fwd_start = P.rx_fwd_start, X.fwd_acc = P.rx_fwd_acc, X.rev_start = P.rx_rev_start, X.rev_acc = P.rx_rev_acc;
+  X.bol = P.rx_bol, X.eol = P.rx_eol;
   X.tile_bytes = kRxSpan, X.nseg = 64u;
   X.la = reinterpret_cast<const uint8_t*>(law);
 

@@ -1,11 +1,68 @@
 // xsg_rxlex.h -- the atom level of the RE2 syntax the GPU matchers read: escapes, bracket classes, POSIX classes,
 // shared by the class-sequence parser (xsg_classseq.cpp) and the automaton compiler (xsg_regex.cpp).  Internal.
 #pragma once
+#include <string.h>
+
 #include <string>
 
 #include "xsg_classseq.h"
 
 namespace xsg {
+
+// The line-anchor form  (?m) [^] BODY [$]  ("Line anchors"): `(?m)` as the first four bytes, `^` as the
+// next token, `$` as the last one.  On success [*body, *body + *body_n) is BODY, with the anchors noted; an expression
+// without a leading `(?m)` is its own BODY (and keeps every refusal it had).  Refused here: a BODY with a top-level
+// `|` (`(?m)^a|b` would anchor one alternative only) and an empty BODY (`(?m)^$`).  Anchors or flags anywhere else
+// reach the parsers, which refuse them.
+inline bool strip_line_anchors(const uint8_t* re, size_t n, const uint8_t** body, size_t* body_n, bool* multi_line,
+                               bool* bol, bool* eol, std::string* err) {
+  *body = re, *body_n = n, *multi_line = *bol = *eol = false;
+  if (n < 4 || memcmp(re, "(?m)", 4) != 0) return true;
+  size_t b = 4, e = n;
+  *multi_line = true;
+  if (b < e && re[b] == '^') *bol = true, ++b;
+  if (e > b && re[e - 1] == '$') {
+    size_t bs = 0;  // `\$` is a literal dollar
+    while (e - 1 - bs > b && re[e - 2 - bs] == '\\') ++bs;
+    if (bs % 2 == 0) *eol = true, --e;
+  }
+  if (e == b) {
+    *err = "(?m) with an empty body (it matches the empty string): not supported";
+    return false;
+  }
+  int depth = 0;
+  for (size_t k = b; k < e; ++k) {
+    const uint8_t c = re[k];
+    if (c == '\\') {
+      ++k;
+    } else if (c == '[') {  // a class: up to its closing ']' (a leading ']' or '^]' is a member)
+      size_t j = k + 1;
+      if (j < e && re[j] == '^') ++j;
+      if (j < e && re[j] == ']') ++j;
+      while (j < e && re[j] != ']') {
+        if (re[j] == '\\') {
+          j += 2;
+        } else if (re[j] == '[' && j + 1 < e && re[j + 1] == ':') {  // [:name:]
+          j += 2;
+          while (j + 1 < e && !(re[j] == ':' && re[j + 1] == ']')) ++j;
+          j += 2;
+        } else {
+          ++j;
+        }
+      }
+      k = j;
+    } else if (c == '(') {
+      ++depth;
+    } else if (c == ')') {
+      --depth;
+    } else if (c == '|' && depth == 0) {
+      *err = "a top-level '|' under (?m) is not supported (write (?m)^(?:a|b)$)";
+      return false;
+    }
+  }
+  *body = re + b, *body_n = e - b;
+  return true;
+}
 
 struct AtomLexer {
   const uint8_t* re = nullptr;
