@@ -9,10 +9,14 @@ kernel over every chunk, the finish kernel (per-tile sums + the reference's
 end-of-chunk walk) and -- for N > 1 -- one RCCL all-reduce (sum) of the four
 uint64 counters.  Inputs are resident in HBM when the timed region starts.
 
-Two forms are measured in every run:
+A plain run measures the headline alone: set-up, --warmup untimed and --steps timed steps of the weak form, the
+--dump-outputs arrays, one JSON line.  --full measures two forms:
   weak   : every rank owns --gib-per-gpu GiB (default 50)  -> `value`, "scaling": "weak"
   strong : --gib-per-gpu GiB IN TOTAL, the first 1/N of every rank's chunks       -> `strong`
            (50 GiB over 8 GPUs = 400 chunks of 16 MiB per GPU)
+and adds to the same line everything else the benchmark measures or checks: the all-reduce alone, the roofline of
+the scan kernel, the end-to-end leg; at N = 1 the `cli` block, the untuned first call, the regex and configs legs and
+the CPU baseline; at N > 1 the steps through the library's own communicator.
 
 Corpus: synthetic (no network).  T distinct '\\n'-terminated template chunks of
 16 MiB (+ a few bytes, like the reference's .meta fixtures) are generated on the
@@ -53,6 +57,9 @@ def parse():
     ap.add_argument("--templates", type=int, default=32)
     ap.add_argument("--pattern", type=str, default="Sherlock")
     ap.add_argument("--seed", type=int, default=0x5EED)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, measure and check everything else: the strong form, the all-reduce alone, "
+                         "the roofline, the legs and baselines (a plain run ignores the options that shape them)")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="budget of the CPU baseline leg (rank 0, N=1)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--kernel-iters", type=int, default=10)
@@ -516,7 +523,7 @@ def main():
     # `time grep Sherlock FILE` against `time my_grep Sherlock FILE` (README.md:44-62): fresh processes, wall time, outputs
     # compared byte for byte.  Never `value`.
     cli = None
-    if int(os.environ.get("WORLD_SIZE", "1")) == 1 and args.gpus == 1 and os.environ.get("XSG_BENCH_CLI", "1") != "0":
+    if args.full and int(os.environ.get("WORLD_SIZE", "1")) == 1 and args.gpus == 1 and os.environ.get("XSG_BENCH_CLI", "1") != "0":
         sys.path.insert(0, str(ROOT / "scripts"))
         try:
             from cli_clock import cli_block
@@ -594,9 +601,11 @@ def main():
     ctx = xsg.Context(dev_index)
     ctx.set_pattern(pattern)
     shard = xsg.Shard(ctx, shard_t.data_ptr(), cap, chunks)
-    # strong form: the same --gib-per-gpu GiB IN TOTAL, i.e. the first 1/world of this rank's chunks
+    # strong form (--full): the same --gib-per-gpu GiB IN TOTAL, i.e. the first 1/world of this rank's chunks; a binding
+    # of its own only at N > 1
     n_strong = max(1, nchunks // world)
-    shard_strong = shard if world == 1 else xsg.Shard(ctx, shard_t.data_ptr(), cap, chunks[:n_strong])
+    strong_own = args.full and world > 1
+    shard_strong = xsg.Shard(ctx, shard_t.data_ptr(), cap, chunks[:n_strong]) if strong_own else shard
     strong_bytes = int(ln[:n_strong].sum())
     expected_strong_local = int(tcount[plan[:n_strong]].sum())
     counters = torch.zeros((2, xsg.NUM_COUNTERS), dtype=torch.int64, device=dev)  # double-buffered, see step()
@@ -608,7 +617,7 @@ def main():
     # What a caller WITHOUT xsg_shard_tune gets, first call included (N=1; never `value`): a fresh binding, the
     # synchronous xsg_count -- the first call also runs the library's hot-filter probe.
     untuned = None
-    if world == 1:
+    if args.full and world == 1:
         su = xsg.Shard(ctx, shard_t.data_ptr(), cap, chunks)
         t0 = time.perf_counter()
         got = int(su.count(xsg.COUNT_MATCHES)[xsg.CTR_MATCHES])
@@ -627,7 +636,7 @@ def main():
         su.close()
     # the wave stagger of the bulk kernel: measured on this shard (a few launches), not a constant
     stagger = None if args.no_tune else shard.tune(xsg.COUNT_MATCHES)
-    stagger_strong = stagger if (world == 1 or args.no_tune) else shard_strong.tune(xsg.COUNT_MATCHES)
+    stagger_strong = shard_strong.tune(xsg.COUNT_MATCHES) if (strong_own and not args.no_tune) else stagger
     # one untimed launch per shard in any case: the library's first pass on a (binding, pattern) measures which hot
     # filter suits the data (a few short launches and a sync) -- set-up, not a step
     shard.time_scan_kernel(xsg.COUNT_MATCHES, 1)
@@ -729,6 +738,45 @@ def main():
     gibs = total_bytes * args.steps / elapsed / 2**30
     ms_per_step = elapsed / args.steps * 1e3
 
+    line = None
+    if rank == 0:
+        line = {
+            "metric": "GiB/s scanned, xs::count literal on plain text resident in HBM",
+            "value": round(gibs, 2),
+            "unit": "GiB/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": round(ms_per_step, 4),
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "u8",
+            "data": "synthetic",
+            "matches_per_s": round(expected_total * args.steps / elapsed, 1),
+            "matches_per_step": expected_total,
+            "parity": "count of every timed step == oracle-derived expected count (the counter buffer is poisoned on the "
+                      "scan's stream before every step)",
+            "config": {
+                "workload": f"xs::count literal '{args.pattern}' on {args.gib_per_gpu:g} GiB plain text per GPU "
+                            f"({nchunks} newline-aligned {args.chunk_mib} MiB chunks), device-resident",
+                "pattern": args.pattern,
+                "bytes_per_gpu": shard_bytes,
+                "chunks_per_gpu": nchunks,
+                "distinct_template_chunks": args.templates,
+                "sharding": "one process per GPU, contiguous chunk range per rank, no data-path collective; "
+                            "one RCCL all_reduce(sum) of 4 uint64 counters per step, on its own stream under the next scan" if world > 1 else
+                            "single GPU",
+                "setup_s": round(setup_s, 1),
+            },
+            "rccl_ranks": (world if (dist is not None and backend == "nccl") else 0),
+            "collective_backend": (backend if dist is not None else None),
+            "collective_through": None if dist is None else "torch.distributed",
+        }
+    if not args.full:
+        finish(line, rank, dist)
+        return
+
     if world == 1:
         elapsed_s, strong_total = elapsed, total_bytes
     else:
@@ -789,41 +837,9 @@ def main():
     if world == 1 and args.configs_gib > 0:
         configs = configs_leg(xsg, ctx, orc, shard_t, cap, chunks, plan, blocks, ln, pattern, args.configs_gib)
 
-    line = None
     if rank == 0:
-        line = {
-            "metric": "GiB/s scanned, xs::count literal on plain text resident in HBM",
-            "value": round(gibs, 2),
-            "unit": "GiB/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 4),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "u8",
-            "data": "synthetic",
-            "matches_per_s": round(expected_total * args.steps / elapsed, 1),
-            "matches_per_step": expected_total,
-            "parity": "count of every timed step == oracle-derived expected count (the counter buffer is poisoned on the "
-                      "scan's stream before every step)",
-            "config": {
-                "workload": f"xs::count literal '{args.pattern}' on {args.gib_per_gpu:g} GiB plain text per GPU "
-                            f"({nchunks} newline-aligned {args.chunk_mib} MiB chunks), device-resident",
-                "pattern": args.pattern,
-                "bytes_per_gpu": shard_bytes,
-                "chunks_per_gpu": nchunks,
-                "distinct_template_chunks": args.templates,
-                "sharding": "one process per GPU, contiguous chunk range per rank, no data-path collective; "
-                            "one RCCL all_reduce(sum) of 4 uint64 counters per step, on its own stream under the next scan" if world > 1 else
-                            "single GPU",
-                "setup_s": round(setup_s, 1),
-            },
+        line.update({
             "strong": strong,
-            "rccl_ranks": (world if (dist is not None and backend == "nccl") else 0),
-            "collective_backend": (backend if dist is not None else None),
-            "collective_through": None if dist is None else "torch.distributed",
             "allreduce_us": None if allreduce_us is None else round(allreduce_us, 1),
             # N > 1: the same strong-form steps with the per-step all-reduce on the LIBRARY's RCCL communicator
             # (xsg_comm_create_rank + xsg_reduce_counts_async); null when a rank has no librccl or the leg did not finish
@@ -842,7 +858,7 @@ def main():
                 "kernel_ms": round(kernel_ms, 4),
                 "algorithmic_bytes_per_launch": shard_bytes,
             },
-        }
+        })
         if cli is not None:
             line["cli"] = cli
         if untuned is not None:
@@ -936,6 +952,11 @@ def main():
         finally:
             dog.cancel()
 
+    finish(line, rank, dist)
+
+
+def finish(line, rank, dist):
+    """rank 0 prints the one JSON line; every rank leaves the process group"""
     if rank == 0:
         print(json.dumps(line), flush=True)
     if dist is not None:

@@ -26,9 +26,9 @@ case $WHAT in
 esac
 case $WHAT in
   all|bench)
-    step bench_50g 900 python bench.py || exit 1
+    step bench_50g 900 python bench.py --full || exit 1
     grep '^{' $OUT/bench_50g.log > $OUT/BENCH_r02_local.json
-    XSG_BENCH_BACKEND=gloo step bench_n2_gloo 900 python bench.py --gpus 2 --gib-per-gpu 8 --steps 10 --warmup 2 --e2e-gib 1 || exit 1
+    XSG_BENCH_BACKEND=gloo step bench_n2_gloo 900 python bench.py --full --gpus 2 --gib-per-gpu 8 --steps 10 --warmup 2 --e2e-gib 1 || exit 1
     ;;
 esac
 exit 0

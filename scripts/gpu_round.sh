@@ -27,6 +27,6 @@ SHFL_RC=$?
 if [ $DPP_RC -ne 0 ] && [ $SHFL_RC -ne 0 ]; then echo "both variants fail parity: no bench" | tee -a $OUT/round.log; exit 1; fi
 if [ $DPP_RC -ne 0 ]; then export XSG_LIB=$PWD/x-search_amd/lib/libxsg_shfl.so; echo "using shfl variant" | tee -a $OUT/round.log; fi
 step smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
-step bench_4g 600 python bench.py --gib-per-gpu 4 --steps 10 --warmup 2 --cpu-seconds 6
-step bench_50g 900 python bench.py
+step bench_4g 600 python bench.py --full --gib-per-gpu 4 --steps 10 --warmup 2 --cpu-seconds 6
+step bench_50g 900 python bench.py --full
 exit 0
