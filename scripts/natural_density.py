@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Where does the byte-parallel route of the 4..8-byte kinds start to pay?  (note_density, xsg_api.cpp.)
+"""Where does the byte-parallel route of the 4..8-byte kinds start to pay?  (note_density, xsg_count.cpp.)
 
 Words of the natural-text corpus (scripts/natural_variants.py) between one occurrence per 2 KiB and one per 100 KiB, each
 counted with the route pinned either way (XSG_DENSE_PER, a test hook): the scan kernel's own time for count and

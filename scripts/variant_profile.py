@@ -101,7 +101,7 @@ def main():
         ctx.set_pattern(pat.encode(), flags)
         st = sh.tune(modes[mode]) if a.tune else None
         # the count first: the timed launches are then what every call after the first one launches (a needle the first
-        # count found dense runs with a smaller wave stagger, x-search_amd/csrc/xsg_api.cpp: density_serial)
+        # count found dense runs with a smaller wave stagger, x-search_amd/csrc/xsg_count.cpp: density_serial)
         cm = int(sh.count(modes[mode])[xsg.CTR_LINES if mode == "count_lines" else xsg.CTR_MATCHES])
         if a.warm > 0:
             sh.time_scan_kernel(modes[mode], a.warm)

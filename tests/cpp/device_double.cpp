@@ -6,7 +6,7 @@
 // box without a GPU (the reference keeps such builds: Makefile:30-38).  It provides
 //   * the handful of HIP runtime entry points xsg_file.cpp calls, over plain host memory ("device" = malloc,
 //     hipMemcpyAsync = memcpy, streams are synchronous), and
-//   * the chunk-level C ABI of xsg_api.cpp (xsg_ctx_*, xsg_shard_*, xsg_count*, xsg_search, xsg_result_*), answered by
+//   * the chunk-level C ABI of xsg_ctx / xsg_pattern / xsg_shard / xsg_count / xsg_list.cpp (xsg_ctx_*, xsg_shard_*, xsg_count*, xsg_search, xsg_result_*), answered by
 //     the CPU oracle (oracle/xs_oracle.c, linked from tests/ only).
 // Nothing here is a CPU search path of the product: the product library has none, and this file is compiled only
 // into tests/cpp/build/pipeline_{tsan,asan}.
@@ -33,7 +33,7 @@ uint64_t xso_line_indices(const char* data, size_t len, const char* pat, size_t 
                           uint64_t cap);
 }
 
-// ---- errors (xsg_api.cpp's) -------------------------------------------------------------------------------------
+// ---- errors (xsg_ctx.cpp's) --------------------------------------------------------------------------------------
 static thread_local char g_err[512] = "";
 namespace xsg {
 int fail(int code, const char* fmt, ...) {
@@ -125,7 +125,7 @@ struct DoubleResult {
   std::vector<uint64_t> line_begin, line_len;
   std::vector<char> line_bytes;
 };
-static DoubleResult* res_of(xsg_shard* s) { return static_cast<DoubleResult*>(s->h_result); }
+static DoubleResult* res_of(xsg_shard* s) { return static_cast<DoubleResult*>(s->h_result.p); }
 
 static int bind(xsg_shard* s, const void* base, uint64_t cap, const xsg_chunk* chunks, uint64_t n) {
   s->base = static_cast<const uint8_t*>(base);
@@ -143,7 +143,7 @@ extern "C" int xsg_shard_create(xsg_ctx* c, const void* base, uint64_t cap, cons
   if (!c || !out) return fail(XSG_EINVAL, "null");
   xsg_shard* s = new xsg_shard();
   s->ctx = c;
-  s->h_result = new DoubleResult();
+  s->h_result.p = new DoubleResult();
   const int r = bind(s, base, cap, chunks, n);
   if (r != XSG_OK) {
     delete res_of(s);
@@ -160,7 +160,7 @@ extern "C" int xsg_shard_rebind(xsg_shard* s, const void* base, uint64_t cap, co
 extern "C" void xsg_shard_destroy(xsg_shard* s) {
   if (!s) return;
   delete res_of(s);
-  s->h_result = nullptr;
+  s->h_result.p = nullptr;
   delete s;
 }
 

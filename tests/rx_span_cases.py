@@ -249,7 +249,7 @@ def cases(family):
 
 def triggers(info, fwd):
     """the trigger byte values of an expression from xsg.regex_dfa's (info, fwd): a byte that moves the forward
-    automaton out of its start state (set_dfa_pattern's lambda, xsg_api.cpp), '\\n' left out as the kernel's
+    automaton out of its start state (set_dfa_pattern's lambda, xsg_pattern.cpp), '\\n' left out as the kernel's
     rx_trig4 leaves it out"""
     start = int(info.fwd_start)
     row = start * int(info.ncls)

@@ -1,4 +1,4 @@
-"""The list tags have two routes behind xsg_search (x-search_amd/csrc/xsg_api.cpp): the one-sync route (capacities,
+"""The list tags have two routes behind xsg_search (x-search_amd/csrc/xsg_list.cpp): the one-sync route (capacities,
 counts on the device, results mirrored into pinned memory; run_list_fast) and the exact route (every array sized
 from a fetched count; also the fallback when a capacity is exceeded).  Both must give the oracle's lists:
 search_wrappers.h:136-154,187-207 + the line-index definition of SURVEY 8a row a13."""

@@ -434,7 +434,7 @@ def test_one_huge_line_with_many_matches(gs, oracle):
 
 def test_long_patterns_with_a_shifted_filter_window(gs, oracle):
     """Long patterns are filtered on their rarest 8-byte window, not their first 8 bytes
-    (xsg_api.cpp pick_filter_window): a match is then found where its WINDOW lies.  Plant
+    (xsg_pattern.cpp pick_filter_window): a match is then found where its WINDOW lies.  Plant
     matches so that start and window fall into different units / wave-loads / tiles,
     at the very start of a chunk, closer to it than the window offset, and around the
     tail zone; add decoys that hold the window but not the rest."""

@@ -2,7 +2,7 @@
 // metafiles, reader/feeder threads, ordered result store.  C++ on the host (the
 // reference's pipeline is C++: include/xsearch/Searcher.h, tasks/readers.h,
 // ResultTypes.h); the scan itself always runs on the GPU through the shard API
-// of xsg_api.cpp -- there is no CPU search path in here.
+// of xsg_count.cpp / xsg_list.cpp -- there is no CPU search path in here.
 #include <ctype.h>
 #include <dlfcn.h>
 #include <fcntl.h>

@@ -1,0 +1,50 @@
+// xsg_host.h -- what the host files of the C ABI share besides the objects of xsg_objects.h: xsg_ctx.cpp (errors,
+// trace, contexts), xsg_pattern.cpp (compilation and upload), xsg_shard.cpp (bindings), xsg_count.cpp (count passes,
+// probe, tuner) and xsg_list.cpp (both list routes and the result accessors).  Everything else in those files is
+// static.  Not installed.
+#pragma once
+#include "xsg_objects.h"
+
+namespace xsg {
+
+// ---- xsg_pattern.cpp ---------------------------------------------------------------------------------------------
+uint32_t pick_filter_window(const uint8_t* p, size_t plen);
+// the window-dependent fields of a literal pattern: the 8 bytes at p[koff..] as compare dwords and masks
+void window_fields(const uint8_t* p, size_t plen, uint32_t koff, PatternDev* P);
+
+// ---- xsg_count.cpp -----------------------------------------------------------------------------------------------
+int check_ready(xsg_shard* s);
+uint32_t scan_variant(bool want_nl, bool want_lines);
+// `variant`: which k_scan instantiation the arguments are for (scan_variant): it selects the measured hot filter
+ScanArgs scan_args(xsg_shard* s, uint32_t variant = 0);
+int prepare_tiles(xsg_shard* s, bool want_lines, hipStream_t st);
+int ensure_tile_nl(xsg_shard* s);
+int choose_hot_filter(xsg_shard* s, hipStream_t st, bool want_nl = false, bool want_lines = false);
+int ensure_overlap_check(xsg_shard* s);
+bool overlap_free_known(const xsg_shard* s);
+
+inline const char* const kNonAsciiMsg =
+    "the expression uses '.', a negated class or \\D \\W \\S, which match whole code points in RE2; the data holds "
+    "bytes >= 0x80, where one byte per position is not the same thing: refused, not approximated";
+inline const char* const kNewlineExprMsg = "line modes do not accept an expression that can match '\\n'";
+
+// ---- xsg_list.cpp ------------------------------------------------------------------------------------------------
+// A LITERAL that contains '\n': its line tags are a chain of occurrences (k_nlpat_links), resolved on the exact list
+// route.  (An EXPRESSION that can match '\n' keeps being refused by the line tags: RE2's walk over a re-sliced input is
+// not restated for it.)
+bool newline_literal(const xsg_ctx* c);
+int ensure_factor_mask(xsg_shard* s);
+// `pre_off`: the caller must not take the prefilter route (run_list: its candidates were dense or outran their budget)
+bool use_prefilter(const xsg_shard* s, bool pre_off);
+// The tail zone of every chunk: its buffers sized for this binding and pattern, *tail_cap = entries per chunk.
+int ensure_tail_buffers(xsg_shard* s, uint32_t* tail_cap);
+// What every list kernel's arguments share: the shard, the scan's emitted list (a.m_pos / a.m_chunk / a.tile_off) and
+// the tail-zone buffers.  `pat`, M / M_dev, keep / m_ls / keep_pre and the mode are the caller's.
+ListArgs list_args(const xsg_shard* s, const ScanArgs& a);
+constexpr int kDenseCandidates = 1;  // run_list(outputs = false) on the prefilter route: too many candidates, count by k_rx_scan
+// The exact list route behind xsg_search and the counts that need the ordered list (the one-sync route first where it
+// serves).  `want_nl_total`: also leave the shard's newline total in last_newlines (xsg_count on the prefilter route);
+// `pre_off`: as for use_prefilter, set by run_list itself when it starts over
+int run_list(xsg_shard* s, uint32_t mode, bool outputs, bool want_nl_total = false, bool pre_off = false);
+
+}  // namespace xsg

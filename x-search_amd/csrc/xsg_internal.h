@@ -1,5 +1,6 @@
-// xsg_internal.h -- shared between the HIP kernels (xsg_kernels.hip) and the
-// C-ABI host code (xsg_api.cpp).  Not part of the public boundary.
+// xsg_internal.h -- shared between the HIP kernels (xsg_kernels.hip, xsg_list_kernels.hip, xsg_rx_kernels.hip) and the
+// C-ABI host code (through xsg_objects.h: xsg_ctx / xsg_pattern / xsg_shard / xsg_count / xsg_list.cpp, xsg_file.cpp).
+// Not part of the public boundary.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -115,7 +116,7 @@ struct ScanArgs {
                                        // tile_last altogether)
   uint32_t* flags;                     // one word per shard, zero at rest: bit 0 = "non-ASCII byte under an ascii_only expression"
   const uint32_t* tile_mask;           // k_rx_scan: if set, only tiles with a non-zero word can hold the start of a line with a
-                                       // match (the factor prefilter, xsg_api.cpp: ensure_factor_mask); null: every tile
+                                       // match (the factor prefilter, xsg_list.cpp: ensure_factor_mask); null: every tile
   // inputs/outputs of the emit pass
   uint64_t m_cap;            // entries m_pos / m_chunk can hold (ranks beyond are dropped; 0 = as many as there are)
   const uint64_t* tile_off;  // exclusive prefix of tile_cnt
@@ -199,7 +200,7 @@ uint64_t scan_tmp_elems(uint64_t n);
 hipError_t launch_exclusive_scan_u32(const uint32_t* in, uint64_t* out, uint64_t n, uint64_t* tmp, hipStream_t s);
 hipError_t launch_exclusive_scan_u64(const uint64_t* in, uint64_t* out, uint64_t n, uint64_t* tmp, hipStream_t s);
 
-// ---- the one-sync list route (xsg_api.cpp: run_list_fast) ---------------------------------------------------
+// ---- the one-sync list route (xsg_list.cpp: run_list_fast) ---------------------------------------------------
 // Every size the host used to fetch between the stages of a list search (raw occurrences, kept ones, tail matches,
 // line bytes) stays on the device: arrays have CAPACITIES, kernels read the counts they need from this block of
 // device words and bound themselves by the capacities, and the kernels that produce a count also store it in a

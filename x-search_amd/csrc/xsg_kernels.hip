@@ -139,7 +139,7 @@ __device__ __forceinline__ uint32_t match_mask16_from(uint32_t m, const uint32_t
     // windows live: 69-87 VGPRs), and, in round 2, comparing from the lane's 32-byte view parked in LDS as the
     // class sequences do -- 60 VGPRs / 100 SGPRs instead of 47 / 74 cost the memory-bound long patterns an eighth
     // of their rate (`Sherlock Holmes` 7.0 -> 6.1 TB/s) and bought `detective street` nothing: its cost is how
-    // often its window occurs (xsg_api.cpp picks the window by measurement now), not how a candidate is verified.
+    // often its window occurs (choose_hot_filter picks the window by measurement now), not how a candidate is verified.
     uint32_t c = m;
     while (c) {
       const uint32_t b = (uint32_t)__ffs((int)c) - 1u;
@@ -617,7 +617,7 @@ __device__ __forceinline__ uint32_t scan_load(const uint4 cur, const uint4 nx, b
     // compares; 4 of the 8 window bytes for three of the four alignments) straight in front of the exact slow
     // path -- half the VALU work of the window filter, the right choice whenever the window's 4-byte pieces are
     // rare in the text.  Otherwise the window filter proper (20 unaligned windows x 2 compares).  Which one runs
-    // is decided per shard and pattern by measurement (xsg_api.cpp: choose_hot_filter); running both as a cascade
+    // is decided per shard and pattern by measurement (xsg_count.cpp: choose_hot_filter); running both as a cascade
     // was measured slower than either (the straight-line body outgrows the instruction cache).
     constexpr bool kTrigger = ALIGNED && (KIND == kTwo || KIND == kLong || KIND == kClass);  // (kClassFast: never ALIGNED)
     // The window filter's 16 compare results are kept (as lane masks on the scalar side) and become the candidate

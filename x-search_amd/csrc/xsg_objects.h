@@ -1,5 +1,6 @@
-// xsg_objects.h -- private object definitions shared by xsg_api.cpp (device-
-// resident searches) and xsg_file.cpp (the file pipeline).  Not installed.
+// xsg_objects.h -- private object definitions shared by the host files of the C ABI (device-resident searches:
+// xsg_ctx / xsg_pattern / xsg_shard / xsg_count / xsg_list.cpp, through xsg_host.h) and xsg_file.cpp (the file
+// pipeline; tests/cpp/device_double.cpp stands in for the former under it).  Not installed.
 #pragma once
 #include <algorithm>
 #include <cstdarg>
@@ -83,6 +84,40 @@ struct DevBuf {
 };
 
 // ---------------------------------------------------------------------------
+// pinned host buffers (grow-only, exact size: page-locked memory is not over-allocated).  Like DevBuf without a
+// destructor: xsg_shard::release_all is the one place that frees.
+// ---------------------------------------------------------------------------
+struct PinBuf {
+  void* p = nullptr;
+  size_t cap = 0;  // bytes
+  // on failure the old buffer is gone too
+  int ensure(size_t bytes) {
+    if (p && cap >= bytes) return XSG_OK;
+    release();
+    hipError_t e = hipHostMalloc(&p, std::max<size_t>(bytes, 8), hipHostMallocDefault);
+    if (e != hipSuccess) {
+      p = nullptr;
+      return xsg::fail(XSG_ENOMEM, "hipHostMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
+    }
+    cap = bytes;
+    return XSG_OK;
+  }
+  void release() {
+    if (p) (void)hipHostFree(p);
+    p = nullptr;
+    cap = 0;
+  }
+  // a large buffer of which the next result needs less than a sixteenth is given back (xsg_list.cpp: trim_pinned)
+  void trim(size_t need_bytes) {
+    if (p && cap > (64u << 20) && need_bytes < cap / 16) release();
+  }
+  template <typename T>
+  T* as() const {
+    return static_cast<T*>(p);
+  }
+};
+
+// ---------------------------------------------------------------------------
 // context
 // ---------------------------------------------------------------------------
 struct xsg_ctx {
@@ -93,7 +128,7 @@ struct xsg_ctx {
   bool bordered = false;  // the pattern can overlap itself
   // ... a literal one, in these ways: for every border b the word P[0 .. plen - b) + P, the text of two occurrences
   // plen - b apart.  No such word in the data <=> no two occurrences overlap <=> the greedy walk keeps every occurrence
-  // (xsg_api.cpp: ensure_overlap_check).  Empty: not checkable (a regex, more than three borders, words too long).
+  // (xsg_count.cpp: ensure_overlap_check).  Empty: not checkable (a regex, more than three borders, words too long).
   std::vector<std::vector<uint8_t>> overlap_words;
   DevBuf d_aux_pat;  // device copies of the overlap words of the pattern (ensure_overlap_check), side by side
   uint64_t aux_serial = 0;  // ... of which pattern_serial
@@ -192,23 +227,20 @@ struct xsg_shard {
   void* h_stage = nullptr;  // pinned
   hipEvent_t table_ev = nullptr;
   bool table_pending = false;  // an upload has been enqueued on the ctx stream since the last sync
-  void* h_result = nullptr;  // pinned: xsg_result_u64_view
-  size_t h_result_cap = 0;
+  PinBuf h_result;  // uint64 list results: the one-sync route's mirror, xsg_result_u64_view, xs::lines offsets
   uint64_t* h_counters = nullptr;  // pinned mirror of the four counters (xsg_count reads it after the stream sync)
   bool begin_sync_result = false;  // xsg_count_begin had to run synchronously: _end hands out begin_counters
   uint64_t begin_counters[XSG_NUM_COUNTERS] = {0, 0, 0, 0};
 
-  // The one-sync list route (xsg_api.cpp: run_list_fast): capacities instead of fetched sizes, totals and results
+  // The one-sync list route (xsg_list.cpp: run_list_fast): capacities instead of fetched sizes, totals and results
   // mirrored in pinned host memory by the kernels, one stream sync per search.
   DevBuf d_tot;                    // FastTot words, then u32 ticket words
   DevBuf d_hit;                    // tiles that hold a match, in order
   DevBuf d_scan2;                  // scratch of the two-launch scans
   DevBuf d_wmask;                  // ScanArgs::tile_wmask
   uint64_t* h_tot = nullptr;       // pinned mirror of the FastTot words (+ one word for the scan flags)
-  uint64_t* hp_line_len = nullptr; // pinned: xs::lines lengths (UINT64_MAX = dropped)
-  size_t hp_line_len_cap = 0;      // entries
-  uint8_t* hp_line_bytes = nullptr;
-  size_t hp_line_bytes_cap = 0;
+  PinBuf hp_line_len;              // xs::lines lengths, uint64 (UINT64_MAX = dropped)
+  PinBuf hp_line_bytes;            // xs::lines packed bytes
   uint64_t fast_dense_serial = 0;  // ctx->pattern_serial whose result did not fit the route's capacity on this binding (0: none)
   bool fast_result = false;        // the pending result lives in the pinned mirrors (h_result, hp_line_*)
   bool line_len_on_device = false; // xs::lines on the exact route: the lengths have not been copied to hp_line_len yet (fetch_line_lengths)
@@ -217,8 +249,6 @@ struct xsg_shard {
   uint64_t nl_total = 0;           // '\n' in the shard, valid while nl_off_cached
 
   uint64_t pre_dense_serial = 0;  // the ctx->pattern_serial whose prefilter candidates were found dense on this binding (0: none)
-  bool pre_off = false;        // run_list: this call must not take the prefilter route (its verification budget ran out)
-  bool want_nl_total = false;  // run_list: also leave the shard's newline total in last_newlines (xsg_count on the prefilter route)
   int last_mode = -1;
   uint64_t last_raw_matches = 0;  // raw occurrences of the last list pass (capacity hint for xsg_count_async, bordered patterns)
   uint64_t total = 0;       // elements of the last list search
@@ -234,16 +264,9 @@ struct xsg_shard {
     for (DevBuf* b : all) b->release();
     if (h_stage) (void)hipHostFree(h_stage);
     if (h_counters) (void)hipHostFree(h_counters);
-    if (h_result) (void)hipHostFree(h_result);
-    h_result = nullptr;
-    h_result_cap = 0;
     if (h_tot) (void)hipHostFree(h_tot);
-    if (hp_line_len) (void)hipHostFree(hp_line_len);
-    if (hp_line_bytes) (void)hipHostFree(hp_line_bytes);
     h_tot = nullptr;
-    hp_line_len = nullptr;
-    hp_line_bytes = nullptr;
-    hp_line_len_cap = hp_line_bytes_cap = 0;
+    for (PinBuf* b : {&h_result, &hp_line_len, &hp_line_bytes}) b->release();
     if (table_ev) (void)hipEventDestroy(table_ev);
     h_stage = nullptr;
     h_counters = nullptr;

@@ -73,7 +73,7 @@ struct RegexDfa {
   ClassExpr prefix;
   // FACTOR: a class sequence that every match CONTAINS somewhere (`\\w+ing` -> `\\wing`), for expressions without a
   // selective start (prefix.npos == 0) that cannot match across lines.  A line without the factor has no match, so
-  // k_rx_scan only needs the tiles in which a line with a factor occurrence starts (csrc/xsg_api.cpp:
+  // k_rx_scan only needs the tiles in which a line with a factor occurrence starts (csrc/xsg_list.cpp:
   // ensure_factor_mask).  npos == 0: none found.
   ClassExpr factor;
   bool ascii_only = false;   // as ClassExpr::ascii_only: a search refuses data with a byte >= 0x80

@@ -18,7 +18,7 @@
 // tile, nothing stored when there are none; tile_nl on request; emission at tile_off ranks), so the finish kernel
 // and the whole list pipeline behind it are shared.  The automata are tables of pre-multiplied uint16 row offsets
 // in LDS: next = fwd[state + class_of[byte]]; all of it is byte/integer work, bound by instruction issue and LDS latency, no MFMA.
-// With a factor prefilter (xsg_api.cpp: ensure_factor_mask) the kernel returns at once from tiles in which no line with
+// With a factor prefilter (xsg_list.cpp: ensure_factor_mask) the kernel returns at once from tiles in which no line with
 // an occurrence of the factor starts.
 // The staged tile is translated to class codes in place (one table read per byte, off every dependency chain), the
 // walks read four codes at a time, and a walk in the start state skips from trigger byte to trigger byte.
@@ -401,7 +401,7 @@ __global__ __launch_bounds__(kBlock) void k_rx_scan(const ScanArgs A, const uint
     }
   }
   s_lastnl[tid] = (uint8_t)(nlm >> 63);
-  s_trig[tid] = tgm;  // '\n' is a trigger by construction (xsg_api.cpp); all zero without `skip`, never read then
+  s_trig[tid] = tgm;  // '\n' is a trigger by construction (xsg_pattern.cpp: set_dfa_pattern); all zero without `skip`, never read then
   __syncthreads();
   const uint64_t seg_off = toff + seg;
   const uint32_t nvalid = seg_off >= L ? 0u : (L - seg_off >= kRxSeg ? kRxSeg : (uint32_t)(L - seg_off));
@@ -809,7 +809,7 @@ __global__ __launch_bounds__(kBlock) void k_rx_newlines(const ScanArgs A) {
 // ---------------------------------------------------------------------------
 // The prefilter route (xsg_regex.h: RegexDfa::prefix).  Every match starts with one of a few class sequences, so the
 // scan kernel's class-sequence matcher finds the CANDIDATE positions at streaming speed (k_scan<kClass>, count +
-// emit, xsg_api.cpp: rx_pre_matches) and the automaton only looks at those:
+// emit, xsg_list.cpp: prefilter_candidates) and the automaton only looks at those:
 //   k_rx_verify   one lane per candidate: the ANCHORED forward automaton from the candidate -> the length of the
 //                 leftmost-first match that starts exactly there, or 0.  (No reverse automaton: the start is known.)
 //   k_rx_heads /  the reference's walk over the occurrences of a chunk (shift = match + match.size(),
