@@ -170,12 +170,14 @@ inline bool reference_routes_to_regex(const std::string& pattern) {
 }
 
 // XSG_FLAG_* for a pattern, routed as the reference routes it; throws std::invalid_argument for a
-// regular expression the GPU matcher does not serve.
+// regular expression the GPU matcher does not serve.  XS_INVERT_MATCH=1 adds XSG_FLAG_INVERT (the lines WITHOUT a
+// match, grep -v): the line tags only, see require_line_tag.
 inline uint32_t pattern_flags(const std::string& pattern, bool ignore_case) {
   uint32_t flags = ignore_case ? XSG_FLAG_IGNORE_CASE : 0u;  // ASCII, as simd::toLower (string_utils.cpp:11-33)
+  if (env_u64("XS_INVERT_MATCH", 0) != 0) flags |= XSG_FLAG_INVERT;
   if (env_u64("XS_FORCE_LITERAL", 0) != 0) return flags;
   if (env_u64("XS_FORCE_REGEX", 0) != 0 || reference_routes_to_regex(pattern)) {
-    if (xsg_regex_check(pattern.data(), pattern.size(), flags, nullptr, nullptr) != XSG_OK)
+    if (xsg_regex_check(pattern.data(), pattern.size(), flags & XSG_FLAG_IGNORE_CASE, nullptr, nullptr) != XSG_OK)
       throw std::invalid_argument("xs::extern_search: '" + pattern +
                                   "' is a regular expression for the reference (utils/utils.h:17-25) that the GPU "
                                   "matcher does not serve: " + xsg_last_error() +
@@ -183,6 +185,13 @@ inline uint32_t pattern_flags(const std::string& pattern, bool ignore_case) {
     flags |= XSG_FLAG_REGEX;
   }
   return flags;
+}
+
+// an inverted search has no match tags: a non-match has no offset (xsg.h, XSG_FLAG_INVERT)
+inline void require_line_tag(uint32_t flags, uint32_t mode) {
+  if ((flags & XSG_FLAG_INVERT) && (mode == XSG_COUNT_MATCHES || mode == XSG_MATCH_BYTE_OFFSETS))
+    throw std::invalid_argument("xs::extern_search: XS_INVERT_MATCH (invert) serves the line tags only: count_lines, "
+                                "line_byte_offsets, line_indices, lines");
 }
 
 template <class T>
@@ -404,6 +413,7 @@ class ExternSearcher {
     xsg_job_opts_init(&o);
     o.pattern_flags = detail::pattern_flags(pattern, ignore_case);
     o.mode = detail::traits<Tag>::mode;
+    detail::require_line_tag(o.pattern_flags, o.mode);
     o.num_threads = num_threads < 1 ? 1 : num_threads;
     o.num_max_readers = num_max_readers < 1 ? 1 : num_max_readers;
     o.chunk_bytes = detail::env_u64("XS_CHUNK_BYTES", 16u << 20);

@@ -127,6 +127,25 @@ enum xsg_mode {
  * the data and in every class, as for literals (automaton route: the classes are
  * closed under case instead, the same thing). */
 #define XSG_FLAG_REGEX 0x4u
+/* Inverted line search (grep -v): the line tags report the lines WITHOUT a match.  May be combined with any flag above.
+ * The lines of a chunk of `len` bytes start at offset 0 (if len > 0) and at p + 1 for every '\n' at p with p + 1 < len:
+ * "a\nb" has two lines, "a\n" one, "a\n\n" two (the second is empty), "" none; the last line is TERMINATED if the
+ * chunk ends in '\n'.  Let R be the line starts XSG_LINE_BYTE_OFFSETS reports for the same pattern and the same other
+ * flags without this one -- the default lossy end-of-chunk behaviour included: a line whose only occurrence the
+ * reference loses there counts as not matching unless XSG_FLAG_EXACT_TAIL is set.  The inverted set is
+ * I = lines(chunk) \ R, in file order, and with the flag set
+ *   XSG_COUNT_LINES        counts |I| over the chunks into XSG_CTR_LINES (every count entry point; XSG_CTR_NEWLINES,
+ *                          XSG_CTR_BYTES, the status word and the UINT64_MAX refusal are as without the flag),
+ *   XSG_LINE_BYTE_OFFSETS  lists global_offset + start of every line of I,
+ *   XSG_LINE_INDICES       lists their line indices (line bases and xsg_result_newlines as without the flag),
+ *   XSG_LINES              hands out the lines of I that are terminated, without their '\n' (the reference never hands
+ *                          out a last line that lacks its newline); a rare needle's inverted result is the whole text,
+ *   XSG_COUNT_MATCHES, XSG_MATCH_BYTE_OFFSETS  are refused (XSG_ENOTSUP): a non-match has no offset.
+ * A pattern that can match '\n' (a literal that contains one, an expression whose sets accept one) is refused with
+ * XSG_ENOTSUP by xsg_set_pattern -- the context then holds no pattern -- never approximated.  The complement is taken on
+ * the device from the assembled list of matching lines (csrc/xsg_list_kernels.hip: k_invert_tile); the scan kernels
+ * are the ones of the plain search. */
+#define XSG_FLAG_INVERT 0x8u
 
 /* A literal may be up to 32 KiB long (the reference's walk takes any std::string; what bounds it here is one 16-bit
  * field: the end of a tile's last match, relative to the tile, must stay below 2^16).  The scan kernel keeps the first

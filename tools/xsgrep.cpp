@@ -1,7 +1,7 @@
 // xsgrep -- the reference's example/grep.cpp (PATTERN FILE, -c, -i; lines 23-82)
 // on the MI355X engine, without boost::program_options.
 //
-//   xsgrep [-c] [-i] [-E|-F] [-x] [-j THREADS] [-m METAFILE] PATTERN FILE|-
+//   xsgrep [-c] [-i] [-v] [-E|-F] [-x] [-j THREADS] [-m METAFILE] PATTERN FILE|-
 //
 // -c  print only a count of matching lines   (grep.cpp:45-46 -> xs::count_lines)
 // -i  ignore ASCII case                      (grep.cpp:47-48)
@@ -10,6 +10,9 @@
 // -x  whole lines only: searches the regex (?m)^(?:PATTERN)$ (with -F, PATTERN escaped into an RE2 literal first;
 //     otherwise a leading `^` and a trailing `$` of PATTERN are dropped, redundant under -x).  An empty PATTERN is
 //     refused (it would match empty lines only), as is a PATTERN with anchors elsewhere (`^a|^b`).
+// -v  the lines WITHOUT a match (XS_INVERT_MATCH -> XSG_FLAG_INVERT); with -c their number.  Like the reference's
+//     xs::lines, a last line that lacks its newline is not printed.
+// The one-letter options without an argument may be bundled (-vc, -ci).
 // otherwise print the matching lines, live, as they are found (grep.cpp:74-79).
 #include <xsearch/tasks/gpu_searchers.h>
 #include <xsearch/xsearch.h>
@@ -19,9 +22,11 @@
 #include <cstring>
 #include <iostream>
 #include <string>
+#include <vector>
 
 static const char kUsage[] =
-    "usage: %s [-c] [-i] [-E|-F] [-x] [-j THREADS] [-m METAFILE] PATTERN FILE|-\n"
+    "usage: %s [-c] [-i] [-v] [-E|-F] [-x] [-j THREADS] [-m METAFILE] PATTERN FILE|-\n"
+    "  -v, --invert-match selects the lines WITHOUT a match (with -c: counts them)\n"
     "  -x searches (?m)^(?:PATTERN)$; PATTERN must not be empty\n";
 
 // PATTERN without a leading `^` and a trailing unescaped `$`: under -x they say what the wrap says already
@@ -47,13 +52,25 @@ static std::string re2_literal(const std::string& p) {
 }
 
 int main(int argc, char** argv) {
-  bool count = false, icase = false, fixed = false, extended = false, whole_lines = false;
+  bool count = false, icase = false, fixed = false, extended = false, whole_lines = false, invert = false;
   int threads = 2;  // grep.cpp:21
   std::string meta, pattern, file;
   int pos = 0;
-  for (int i = 1; i < argc; ++i) {
+  std::vector<std::string> args;
+  for (int i = 1; i < argc; ++i) {  // -vc -> -v -c (only letters that take no argument; anything else stays one word)
     const std::string a = argv[i];
-    if (a == "-c" || a == "--count") {
+    if (a.size() > 2 && a[0] == '-' && a[1] != '-' && a.find_first_not_of("ciEFxv", 1) == std::string::npos) {
+      for (size_t k = 1; k < a.size(); ++k) args.push_back(std::string("-") + a[k]);
+    } else {
+      args.push_back(a);
+    }
+  }
+  const int nargs = (int)args.size();
+  for (int i = 0; i < nargs; ++i) {
+    const std::string a = args[i];
+    if (a == "-v" || a == "--invert-match") {
+      invert = true;
+    } else if (a == "-c" || a == "--count") {
       count = true;
     } else if (a == "-i" || a == "--ignore-case") {
       icase = true;
@@ -63,10 +80,10 @@ int main(int argc, char** argv) {
       extended = true;
     } else if (a == "-x" || a == "--line-regexp") {
       whole_lines = true;
-    } else if ((a == "-j" || a == "--threads") && i + 1 < argc) {
-      threads = std::atoi(argv[++i]);
-    } else if ((a == "-m" || a == "--meta") && i + 1 < argc) {
-      meta = argv[++i];
+    } else if ((a == "-j" || a == "--threads") && i + 1 < nargs) {
+      threads = std::atoi(args[++i].c_str());
+    } else if ((a == "-m" || a == "--meta") && i + 1 < nargs) {
+      meta = args[++i];
     } else if (a == "-h" || a == "--help") {
       std::printf(kUsage, argv[0]);
       return 0;
@@ -104,6 +121,7 @@ int main(int argc, char** argv) {
   }
   if (fixed) setenv("XS_FORCE_LITERAL", "1", 1);
   if (extended) setenv("XS_FORCE_REGEX", "1", 1);
+  if (invert) setenv("XS_INVERT_MATCH", "1", 1);
   try {
     std::ios::sync_with_stdio(false);
     if (file == "-") {

@@ -426,6 +426,26 @@ static int enqueue_count_bordered(xsg_shard* s, hipStream_t st, uint64_t* d_coun
   return XSG_OK;
 }
 
+// XSG_FLAG_INVERT, XSG_COUNT_LINES: the lines WITHOUT a match = all lines of the chunks - the matching ones.  The count
+// pass ahead ran with newline counts; one small kernel behind it on the same stream turns XSG_CTR_LINES round.
+static bool inverted(const xsg_ctx* c) { return (c->flags & XSG_FLAG_INVERT) != 0; }
+static int enqueue_invert_lines(xsg_shard* s, hipStream_t st, uint64_t* d_counters, uint64_t* host_counters, uint64_t* d_status,
+                                bool keep_nl) {
+  HIP_TRY(launch_invert_count_lines(s->base, s->d_chunks.as<ChunkDev>(), s->chunks.size(), d_counters, host_counters, d_status,
+                                    keep_nl ? 1u : 0u, st));
+  return XSG_OK;
+}
+// ... for counters a list route left on the host (xsg_count on the prefilter route)
+static int invert_lines_sync(xsg_shard* s, uint64_t counters[XSG_NUM_COUNTERS], bool keep_nl) {
+  hipStream_t st = s->ctx->stream;
+  uint64_t* d = s->d_counters.as<uint64_t>();
+  HIP_TRY(hipMemcpyAsync(d, counters, 8 * XSG_NUM_COUNTERS, hipMemcpyHostToDevice, st));
+  XSG_TRY(enqueue_invert_lines(s, st, d, nullptr, nullptr, keep_nl));
+  HIP_TRY(hipMemcpyAsync(counters, d, 8 * XSG_NUM_COUNTERS, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return XSG_OK;
+}
+
 static int refuse_if_poisoned(const uint64_t counters[XSG_NUM_COUNTERS]) {
   if (counters[XSG_CTR_BYTES] == UINT64_MAX) return fail(XSG_ENOTSUP, "%s", kNonAsciiMsg);
   return XSG_OK;
@@ -450,6 +470,7 @@ static int count_async_impl(xsg_shard* s, uint32_t mode, void* stream, uint64_t*
   xsg_ctx* c = s->ctx;
   HIP_TRY(hipSetDevice(c->device));
   hipStream_t st = stream ? static_cast<hipStream_t>(stream) : c->stream;
+  if (m == XSG_COUNT_MATCHES && inverted(c)) return fail(XSG_ENOTSUP, "%s", kInvertMatchMsg);
   if (m == XSG_COUNT_MATCHES) {
     if (c->bordered && !overlap_free_known(s)) {  // (known from an earlier synchronous call: this entry point may not wait)
       if (want_nl)
@@ -462,7 +483,9 @@ static int count_async_impl(xsg_shard* s, uint32_t mode, void* stream, uint64_t*
     if (c->pat.has_newline)
       return fail(XSG_ENOTSUP, "count_lines of a pattern that contains '\\n' walks a chain of occurrences: the stream-ordered entry "
                                "point does not serve it, xsg_count() does");
-    return enqueue_count(s, false, true, want_nl, st, d_counters, nullptr, nullptr, d_status);
+    if (!inverted(c)) return enqueue_count(s, false, true, want_nl, st, d_counters, nullptr, nullptr, d_status);
+    XSG_TRY(enqueue_count(s, false, true, true, st, d_counters, nullptr, nullptr, d_status));
+    return enqueue_invert_lines(s, st, d_counters, nullptr, d_status, want_nl);
   }
   return fail(XSG_EINVAL, "xsg_count_async: mode %u is not a count mode", m);
 }
@@ -499,19 +522,22 @@ extern "C" int xsg_count(xsg_shard* s, uint32_t mode, uint64_t counters[XSG_NUM_
   uint32_t m = 0;
   bool want_nl = false;
   XSG_TRY(parse_count_mode(mode, &m, &want_nl));
+  if (m == XSG_COUNT_MATCHES && inverted(c)) return fail(XSG_ENOTSUP, "%s", kInvertMatchMsg);
+  const bool inv = inverted(c);  // (XSG_COUNT_LINES from here on: the pass below also counts newlines)
   XSG_TRY(ensure_factor_mask(s));
   if (use_prefilter(s, false) && s->pre_dense_serial != c->pattern_serial) {  // (not again where the candidates were found dense)
     // the prefilter route of the automaton family: candidates, verification and the walk produce the list; its
     // length is the count (the newline total, if asked for, comes from the cached per-tile counts)
     if (m == XSG_COUNT_LINES && c->pat.has_newline) return fail(XSG_ENOTSUP, "%s", kNewlineExprMsg);
-    const int r = run_list(s, m == XSG_COUNT_MATCHES ? XSG_MATCH_BYTE_OFFSETS : XSG_LINE_BYTE_OFFSETS, false, want_nl);
+    const int r = run_list(s, m == XSG_COUNT_MATCHES ? XSG_MATCH_BYTE_OFFSETS : XSG_LINE_BYTE_OFFSETS, false, want_nl || inv);
     if (r != kDenseCandidates) {
       XSG_TRY(r);
       memset(counters, 0, 8 * XSG_NUM_COUNTERS);
       counters[m == XSG_COUNT_MATCHES ? XSG_CTR_MATCHES : XSG_CTR_LINES] = s->total;
       counters[XSG_CTR_BYTES] = s->total_bytes;
-      if (want_nl) counters[XSG_CTR_NEWLINES] = s->last_newlines;
+      if (want_nl || inv) counters[XSG_CTR_NEWLINES] = s->last_newlines;
       s->last_mode = -1;
+      if (inv) XSG_TRY(invert_lines_sync(s, counters, want_nl));
       return XSG_OK;
     }
     // too many candidates for the list route to pay: the count passes below walk every line (k_rx_scan)
@@ -536,12 +562,13 @@ extern "C" int xsg_count(xsg_shard* s, uint32_t mode, uint64_t counters[XSG_NUM_
   }
   if (m == XSG_COUNT_LINES && c->pat.has_newline) return fail(XSG_ENOTSUP, "%s", kNewlineExprMsg);
   // the finish kernel writes the four values straight into pinned host memory: no copy, one sync
-  XSG_TRY(enqueue_count(s, m == XSG_COUNT_MATCHES, m == XSG_COUNT_LINES, want_nl, c->stream,
+  XSG_TRY(enqueue_count(s, m == XSG_COUNT_MATCHES, m == XSG_COUNT_LINES, want_nl || inv, c->stream,
                         s->d_counters.as<uint64_t>(), s->h_counters));
+  if (inv) XSG_TRY(enqueue_invert_lines(s, c->stream, s->d_counters.as<uint64_t>(), s->h_counters, nullptr, want_nl));
   HIP_TRY(hipStreamSynchronize(c->stream));
   s->table_pending = false;
   memcpy(counters, s->h_counters, 8 * XSG_NUM_COUNTERS);
-  note_density(s, counters[m == XSG_COUNT_MATCHES ? XSG_CTR_MATCHES : XSG_CTR_LINES]);
+  if (!inv) note_density(s, counters[m == XSG_COUNT_MATCHES ? XSG_CTR_MATCHES : XSG_CTR_LINES]);  // (of the needle, not of its complement)
   return refuse_if_poisoned(counters);
 }
 
@@ -555,6 +582,8 @@ extern "C" int xsg_count_begin(xsg_shard* s, uint32_t mode) {
   uint32_t m = 0;
   bool want_nl = false;
   XSG_TRY(parse_count_mode(mode, &m, &want_nl));
+  if (m == XSG_COUNT_MATCHES && inverted(c)) return fail(XSG_ENOTSUP, "%s", kInvertMatchMsg);
+  const bool inv = inverted(c);
   s->begin_sync_result = false;
   XSG_TRY(ensure_factor_mask(s));
   if (m == XSG_COUNT_MATCHES && c->bordered) XSG_TRY(ensure_overlap_check(s));
@@ -565,8 +594,9 @@ extern "C" int xsg_count_begin(xsg_shard* s, uint32_t mode) {
     return XSG_OK;
   }
   if (m == XSG_COUNT_LINES && c->pat.has_newline) return fail(XSG_ENOTSUP, "%s", kNewlineExprMsg);
-  XSG_TRY(enqueue_count(s, m == XSG_COUNT_MATCHES, m == XSG_COUNT_LINES, want_nl, c->stream,
+  XSG_TRY(enqueue_count(s, m == XSG_COUNT_MATCHES, m == XSG_COUNT_LINES, want_nl || inv, c->stream,
                         s->d_counters.as<uint64_t>(), s->h_counters));
+  if (inv) XSG_TRY(enqueue_invert_lines(s, c->stream, s->d_counters.as<uint64_t>(), s->h_counters, nullptr, want_nl));
   HIP_TRY(hipEventRecord(s->table_ev, c->stream));  // doubles as "pass done": it covers the table upload too
   s->table_pending = true;
   return XSG_OK;
@@ -623,9 +653,13 @@ extern "C" int xsg_scan_kernel_name(xsg_shard* s, uint32_t mode, char* out, size
     char inner[160];
     describe_scan(a, want_nl, false, false, inner, sizeof inner);
     snprintf(out, cap, "%s + xsg::k_rx_verify (prefilter route; xsg_count_async: k_rx_scan)", inner);
-    return XSG_OK;
+  } else {
+    describe_scan(a, want_nl, !list && m == XSG_COUNT_LINES, false, out, cap);
   }
-  describe_scan(a, want_nl, !list && m == XSG_COUNT_LINES, false, out, cap);
+  if (inverted(s->ctx)) {  // the inverted form: the same scan, then the complement (of the list, or of the line count)
+    const size_t n = strlen(out);
+    snprintf(out + n, cap - n, "%s", list ? " + xsg::k_invert_tile (inverted)" : " + xsg::k_invert_count_lines (inverted)");
+  }
   return XSG_OK;
 }
 

@@ -1155,6 +1155,11 @@ static int job_start_impl(const void* pattern, size_t plen, const char* file_pat
   if (opts->mode > XSG_LINES) return fail(XSG_EINVAL, "bad mode %u", opts->mode);
   if (opts->num_threads < 1 || opts->num_max_readers < 1) return fail(XSG_EINVAL, "num_threads/num_max_readers < 1");
   const bool line_mode = opts->mode != XSG_COUNT_MATCHES && opts->mode != XSG_MATCH_BYTE_OFFSETS;
+  if (opts->pattern_flags & XSG_FLAG_INVERT) {  // (xsg.h: the line tags only, and no pattern that can match '\n')
+    if (!line_mode) return fail(XSG_ENOTSUP, "XSG_FLAG_INVERT: an inverted search reports lines without a match; the match tags have no inverted form");
+    if (!(opts->pattern_flags & XSG_FLAG_REGEX) && memchr(pattern, '\n', plen))
+      return fail(XSG_ENOTSUP, "XSG_FLAG_INVERT: an inverted search does not accept a pattern that can match '\\n'");
+  }
   if (opts->pattern_flags & XSG_FLAG_REGEX) {  // refuse an expression the kernel cannot decide here, not in a worker
     uint32_t npos = 0;
     std::vector<uint32_t> sets(32 * 8, 0);

@@ -26,6 +26,8 @@ bool overlap_free_known(const xsg_shard* s);
 inline const char* const kNonAsciiMsg =
     "the expression uses '.', a negated class or \\D \\W \\S, which match whole code points in RE2; the data holds "
     "bytes >= 0x80, where one byte per position is not the same thing: refused, not approximated";
+inline const char* const kInvertMatchMsg =
+    "XSG_FLAG_INVERT: an inverted search reports lines without a match; the match tags have no inverted form";
 inline const char* const kNewlineExprMsg = "line modes do not accept an expression that can match '\\n'";
 
 // ---- xsg_list.cpp ------------------------------------------------------------------------------------------------

@@ -336,12 +336,44 @@ struct LineOutArgs {
   uint32_t* dropped;         // k_line_lengths: incremented per line without a terminating newline (may be null)
   uint64_t slice_begin, slice_end;  // k_line_gather: only the entries [slice_begin, slice_end) (slice_end == 0: all of them)
   uint32_t* edge_units;      // k_line_gather_span into a pinned mirror: 4 zeroed words per workgroup boundary (total / kBlock + 2), or null
+  uint32_t invert;           // XSG_FLAG_INVERT: the entries are lines WITHOUT a match (f_match is not meaningful): k_line_lengths
+                             // looks for the line's end from its start, not from behind a match
 };
 hipError_t launch_globalize(const LineOutArgs& a, hipStream_t s);
 hipError_t launch_line_nl_delta(const LineOutArgs& a, hipStream_t s);
 hipError_t launch_line_indices(const LineOutArgs& a, hipStream_t s);
 hipError_t launch_line_lengths(const LineOutArgs& a, hipStream_t s);
 hipError_t launch_line_gather(const LineOutArgs& a, hipStream_t s);
+
+// ---- XSG_FLAG_INVERT: the complement stage (xsg_list.cpp: invert_list) ---------------------------------------------
+// The assembled list of a line tag (r_pos / r_chunk: the chunk-relative starts of the lines the walk reports, ascending
+// inside a chunk, in chunk order) is replaced by the list of all OTHER line starts of the chunks.  Two passes over the
+// text, one workgroup per tile, around one prefix sum over the tiles; both passes decide a line start the same way (the
+// tile's slice of the reported list as a bitmap in LDS), so the emit pass stores exactly what the count pass counted.
+struct InvertArgs {
+  const uint8_t* base;
+  const ChunkDev* chunks;
+  const uint32_t* tile_chunk;   // tile -> chunk (null when the shard has one chunk)
+  const uint64_t* chunk_tile0;
+  uint64_t ntiles;
+  uint32_t tile_bytes;
+  uint64_t total;               // entries of the reported list
+  const uint64_t* r_pos;
+  const uint32_t* r_chunk;
+  uint64_t* tile_lo;            // ntiles + 1: the first reported entry at or behind the tile's first byte ([ntiles] = total)
+  uint32_t* tile_cnt;           // line starts in the tile that are not reported
+  const uint64_t* tile_off;     // exclusive prefix of tile_cnt (emit pass)
+  uint64_t inv_total;           // its total = entries of i_pos / i_chunk
+  uint64_t* i_pos;
+  uint32_t* i_chunk;
+};
+hipError_t launch_invert_count(const InvertArgs& a, hipStream_t s);  // tile_lo, tile_cnt
+hipError_t launch_invert_emit(const InvertArgs& a, hipStream_t s);   // i_pos, i_chunk
+// XSG_COUNT_LINES: counters[XSG_CTR_LINES] = newlines + chunks whose last line lacks its '\n' - counters[XSG_CTR_LINES], behind
+// a count pass that also counted newlines, on the same stream; a refusal (status word set, or poisoned counters) passes
+// through.  keep_nl == 0: the caller did not ask for XSG_CTR_NEWLINES, it is zeroed again.  host_counters, status: optional
+hipError_t launch_invert_count_lines(const uint8_t* base, const ChunkDev* chunks, uint64_t nchunks, uint64_t* counters,
+                                     uint64_t* host_counters, const uint64_t* status, uint32_t keep_nl, hipStream_t s);
 // one empty launch per kernel file (code object): see xsg_kernels.hip
 hipError_t warm_scan_kernels(hipStream_t s);
 hipError_t warm_list_kernels(hipStream_t s);

@@ -164,6 +164,7 @@ static bool fast_route_serves(const xsg_shard* s, uint32_t mode, bool outputs, b
   const xsg_ctx* c = s->ctx;
   const char* e = XSG_TOGGLE("XSG_LIST_FAST");  // 0: every list search takes the exact route (tests, A/B)
   if ((e && *e == '0') || !outputs || s->ntiles == 0 || want_nl_total) return false;
+  if (c->flags & XSG_FLAG_INVERT) return false;                         // the complement stage sits on the exact route
   if (c->pat.kind == kDfa) return false;                                // k_rx_scan / the prefilter route: exact route
   if (mode != XSG_MATCH_BYTE_OFFSETS && c->pat.has_newline) return false;  // the line walk of a literal with '\n': a chain, exact route
   if (mode == XSG_MATCH_BYTE_OFFSETS && c->bordered && !overlap_free_known(s)) return false;  // greedy keep: exact route
@@ -647,6 +648,49 @@ static int out_lines(xsg_shard* s, LineOutArgs& o) {
   return XSG_OK;
 }
 
+// XSG_FLAG_INVERT: the assembled list (the starts of the lines the walk reports) is replaced by its complement among
+// the line starts of the chunks, l.f_* and *total with it; every output kernel then runs on the new list unchanged.
+// Count per tile, ranks, one more size from the device, emit (xsg_list_kernels.hip: k_invert_tile).
+static int invert_list(xsg_shard* s, const ScanArgs& a, ListArgs& l, uint64_t* total) {
+  xsg_ctx* c = s->ctx;
+  hipStream_t st = c->stream;
+  const uint64_t ntiles = s->ntiles;
+  XSG_TRY(s->d_inv_lo.ensure(8 * (ntiles + 1)));
+  XSG_TRY(s->d_inv_cnt.ensure(4 * std::max<uint64_t>(ntiles, 1)));
+  XSG_TRY(s->d_inv_off.ensure(8 * (ntiles + 1)));
+  XSG_TRY(s->d_scan_tmp.ensure(8 * scan_tmp_elems(ntiles + 1)));
+  InvertArgs v{};
+  v.base = s->base;
+  v.chunks = a.chunks;
+  v.tile_chunk = a.tile_chunk;
+  v.chunk_tile0 = a.chunk_tile0;
+  v.ntiles = ntiles;
+  v.tile_bytes = s->tile_bytes;
+  v.total = *total;
+  v.r_pos = l.f_pos;
+  v.r_chunk = l.f_chunk;
+  v.tile_lo = s->d_inv_lo.as<uint64_t>();
+  v.tile_cnt = s->d_inv_cnt.as<uint32_t>();
+  HIP_TRY(launch_invert_count(v, st));
+  HIP_TRY(launch_exclusive_scan_u32(v.tile_cnt, s->d_inv_off.as<uint64_t>(), ntiles, s->d_scan_tmp.as<uint64_t>(), st));
+  uint64_t n = 0;
+  XSG_TRY(d2h_u64(c, s->d_inv_off.as<uint64_t>() + ntiles, &n));
+  XSG_TRY(s->d_inv_pos.ensure(8 * std::max<uint64_t>(n, 1)));
+  XSG_TRY(s->d_inv_chunk.ensure(4 * std::max<uint64_t>(n, 1)));
+  XSG_TRY(s->d_out_u64.ensure(8 * std::max<uint64_t>(n, 1)));
+  v.tile_off = s->d_inv_off.as<uint64_t>();
+  v.inv_total = n;
+  v.i_pos = s->d_inv_pos.as<uint64_t>();
+  v.i_chunk = s->d_inv_chunk.as<uint32_t>();
+  HIP_TRY(launch_invert_emit(v, st));
+  l.f_pos = v.i_pos;
+  l.f_match = v.i_pos;  // (no match in such a line: LineOutArgs::invert keeps the output kernels away from it)
+  l.f_chunk = v.i_chunk;
+  l.total = n;
+  *total = s->total = n;
+  return XSG_OK;
+}
+
 // 6. the final list of `total` entries, in file order, in the form the tag asks for
 static int list_outputs(xsg_shard* s, uint32_t mode, const ScanArgs& a, ListArgs& l, uint64_t total) {
   hipStream_t st = s->ctx->stream;
@@ -659,7 +703,10 @@ static int list_outputs(xsg_shard* s, uint32_t mode, const ScanArgs& a, ListArgs
   l.f_chunk = s->d_f_chunk.as<uint32_t>();
   l.total = total;
   HIP_TRY(launch_assemble(l, st));
+  const bool invert = (s->ctx->flags & XSG_FLAG_INVERT) != 0;
+  if (invert) XSG_TRY(invert_list(s, a, l, &total));
   LineOutArgs o = line_out_args(s, a, l, total);
+  o.invert = invert ? 1u : 0u;
   if (mode == XSG_MATCH_BYTE_OFFSETS || mode == XSG_LINE_BYTE_OFFSETS)
     HIP_TRY(launch_globalize(o, st));
   else if (mode == XSG_LINE_INDICES)
@@ -775,6 +822,7 @@ extern "C" int xsg_search(xsg_shard* s, uint32_t mode, uint64_t* n_results) {
   if (mode != XSG_MATCH_BYTE_OFFSETS && mode != XSG_LINE_BYTE_OFFSETS && mode != XSG_LINE_INDICES &&
       mode != XSG_LINES)
     return fail(XSG_EINVAL, "xsg_search: mode %u is not a list mode", mode);
+  if (mode == XSG_MATCH_BYTE_OFFSETS && (s->ctx->flags & XSG_FLAG_INVERT)) return fail(XSG_ENOTSUP, "%s", kInvertMatchMsg);
   HIP_TRY(hipSetDevice(s->ctx->device));
   XSG_TRY(run_list(s, mode, true));
   if (!s->fast_result) trim_pinned(s, 8 * (size_t)s->total, 8 * (size_t)s->total, (size_t)s->line_bytes);  // (an exact-route result is still on the device)

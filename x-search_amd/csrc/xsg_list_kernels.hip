@@ -963,7 +963,9 @@ __global__ __launch_bounds__(kBlock) void k_line_lengths(const LineOutArgs A) {
     const bool live = i < total;  // no early exit of a lane: see newline_query
     const ChunkDev ch = A.chunks[live ? A.f_chunk[i] : 0u];
     const uint8_t* d = A.base + ch.offset;
-    const int64_t e = newline_query<true>(live, d, live ? A.f_match[i] + A.pat.plen : 0, ch.length, threadIdx.x & 63u);
+    // (an inverted entry has no match: its line's end is looked for from its start)
+    const uint64_t from = !live ? 0 : A.invert ? A.f_pos[i] : A.f_match[i] + A.pat.plen;
+    const int64_t e = newline_query<true>(live, d, from, ch.length, threadIdx.x & 63u);
     if (!live) continue;
     const uint64_t len = e < 0 ? UINT64_MAX : (uint64_t)e - A.f_pos[i];
     const uint64_t g = ch.global_offset + A.f_pos[i];
@@ -1182,6 +1184,165 @@ hipError_t launch_line_gather(const LineOutArgs& a, hipStream_t s) {
     return hipGetLastError();
   }
   hipLaunchKernelGGL(k_line_gather, a.tot_dev ? grid_capped(n) : grid_for(n), dim3(kBlock), 0, s, a);
+  return hipGetLastError();
+}
+
+
+// ---------------------------------------------------------------------------
+// XSG_FLAG_INVERT: the complement of an assembled line list (InvertArgs, xsg_internal.h)
+// ---------------------------------------------------------------------------
+// The lines of a chunk of `len` bytes start at 0 (len > 0) and at p + 1 for every '\n' at p with p + 1 < len.  A start
+// belongs to the tile that holds it, so a tile [begin, end) owns `begin` itself (the chunk's first byte, or the byte
+// behind a '\n' that closes the previous tile) and p + 1 for the newlines at p in [begin, end - 1).
+constexpr uint32_t kInvMaxTile = 32768;                               // the largest tile k_scan is built for
+constexpr int kInvMaxSteps = (int)(kInvMaxTile / kWaves / kWaveLoad);  // wave-loads of one wave's span of the tile
+
+// tile_lo[t] = the first entry of the reported list that lies at or behind tile t's first byte (entries are ordered by
+// chunk, then offset; tiles likewise), one thread per tile
+__global__ void k_invert_bounds(const InvertArgs A) {
+  const uint64_t t = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (t > A.ntiles) return;
+  uint64_t lo = 0, hi = A.total;
+  if (t == A.ntiles) {
+    lo = hi;
+  } else {
+    const uint32_t c = A.tile_chunk ? A.tile_chunk[t] : 0u;
+    const uint64_t begin = (t - A.chunk_tile0[c]) * A.tile_bytes;
+    while (lo < hi) {
+      const uint64_t mid = (lo + hi) >> 1;
+      const uint32_t mc = A.r_chunk[mid];
+      if (mc < c || (mc == c && A.r_pos[mid] < begin)) lo = mid + 1; else hi = mid;
+    }
+  }
+  A.tile_lo[t] = lo;
+}
+
+// One workgroup per tile.  The tile's slice of the reported list becomes a bitmap in LDS (bit = offset in the tile);
+// every wave reads its quarter of the tile in coalesced 16-byte loads, a lane turns the newlines of its unit into the
+// starts behind them, drops the ones the bitmap holds, and the survivors are ranked by popcounts: per wave-load by a
+// DPP prefix over the lanes, per wave through LDS.  EMIT = false: the tile's count; true: the starts at their ranks.
+template <bool EMIT>
+__global__ __launch_bounds__(kBlock) void k_invert_tile(const InvertArgs A) {
+  __shared__ uint32_t s_bm[kInvMaxTile / 32 + 1];
+  __shared__ uint32_t s_wave[kWaves];
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const uint32_t tb = A.tile_bytes;
+  const uint32_t span = tb / kWaves;
+  const int steps = (int)(span / kWaveLoad);
+  for (uint64_t t = blockIdx.x; t < A.ntiles; t += gridDim.x) {  // (workgroup-uniform)
+    const uint32_t c = A.tile_chunk ? A.tile_chunk[t] : 0u;
+    const ChunkDev ch = A.chunks[c];
+    const uint8_t* d = A.base + ch.offset;
+    const uint64_t begin = (t - A.chunk_tile0[c]) * tb;
+    const uint64_t end = begin >= ch.length ? begin : (begin + tb < ch.length ? begin + tb : ch.length);
+    for (uint32_t w = threadIdx.x; w < tb / 32u + 1u; w += kBlock) s_bm[w] = 0u;
+    __syncthreads();
+    const uint64_t r0 = A.tile_lo[t], r1 = A.tile_lo[t + 1];
+    for (uint64_t i = r0 + threadIdx.x; i < r1; i += kBlock) {
+      const uint64_t r = A.r_pos[i] - begin;
+      if (r < tb) atomicOr(&s_bm[r >> 5], 1u << (r & 31u));
+    }
+    __syncthreads();
+    const bool first = begin < end && (begin == 0 || d[begin - 1] == '\n') && !(s_bm[0] & 1u);
+    uint32_t m[kInvMaxSteps], ex[kInvMaxSteps];
+    uint32_t wtot = 0;
+#pragma unroll
+    for (int k = 0; k < kInvMaxSteps; ++k) {
+      m[k] = 0u;
+      ex[k] = 0u;
+      if (k < steps) {  // (wave-uniform)
+        const uint64_t u = begin + (uint64_t)wave * span + (uint64_t)k * kWaveLoad + (uint64_t)lane * kUnit;
+        if (u < end) {  // the unit lies inside the chunk's padded length
+          const uint4 v = *reinterpret_cast<const uint4*>(d + u);
+          const uint32_t dw[8] = {v.x, v.y, v.z, v.w, 0u, 0u, 0u, 0u};
+          uint32_t nl = nl_mask16(dw);
+          const uint64_t room = end - u - 1u;  // a '\n' at byte b opens a line of this tile iff u + b + 1 < end
+          if (room < 16u) nl &= (1u << room) - 1u;
+          const uint32_t off = (uint32_t)(u - begin) + 1u;  // bitmap position of the start behind byte 0 of the unit
+          const uint64_t rep = ((uint64_t)s_bm[off >> 5] | ((uint64_t)s_bm[(off >> 5) + 1u] << 32)) >> (off & 31u);
+          m[k] = nl & ~(uint32_t)rep & 0xffffu;
+        }
+        const uint32_t p = (uint32_t)__popc(m[k]);
+        const uint32_t incl = wave_incl_scan_u32(p, lane);
+        ex[k] = wtot + incl - p;
+        wtot += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+      }
+    }
+    if (lane == 0) s_wave[wave] = wtot;
+    __syncthreads();
+    uint32_t wbase = first ? 1u : 0u, total = first ? 1u : 0u;
+#pragma unroll
+    for (int w = 0; w < kWaves; ++w) {
+      if ((uint32_t)w < wave) wbase += s_wave[w];
+      total += s_wave[w];
+    }
+    if (!EMIT) {
+      if (threadIdx.x == 0) A.tile_cnt[t] = total;
+    } else {
+      const uint64_t base = A.tile_off[t];
+      if (first && threadIdx.x == 0 && base < A.inv_total) {
+        A.i_pos[base] = begin;
+        A.i_chunk[base] = c;
+      }
+#pragma unroll
+      for (int k = 0; k < kInvMaxSteps; ++k) {
+        if (k < steps) {
+          const uint64_t u = begin + (uint64_t)wave * span + (uint64_t)k * kWaveLoad + (uint64_t)lane * kUnit;
+          uint64_t r = base + wbase + ex[k];
+          for (uint32_t mm = m[k]; mm; mm &= mm - 1u, ++r) {
+            if (r < A.inv_total) {  // (by construction; the arrays hold inv_total entries)
+              A.i_pos[r] = u + (uint32_t)__builtin_ctz(mm) + 1u;
+              A.i_chunk[r] = c;
+            }
+          }
+        }
+      }
+    }
+    __syncthreads();  // (the next round re-uses the bitmap and the wave totals)
+  }
+}
+
+static inline dim3 invert_grid(uint64_t ntiles) { return dim3((unsigned)std::min<uint64_t>(std::max<uint64_t>(ntiles, 1), 1u << 22)); }
+
+hipError_t launch_invert_count(const InvertArgs& a, hipStream_t s) {
+  if (a.tile_bytes > kInvMaxTile || a.tile_bytes % (kWaves * kWaveLoad)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_invert_bounds, grid_for(a.ntiles + 1), dim3(kBlock), 0, s, a);
+  if (a.ntiles) hipLaunchKernelGGL(k_invert_tile<false>, invert_grid(a.ntiles), dim3(kBlock), 0, s, a);
+  return hipGetLastError();
+}
+hipError_t launch_invert_emit(const InvertArgs& a, hipStream_t s) {
+  if (a.tile_bytes > kInvMaxTile || a.tile_bytes % (kWaves * kWaveLoad)) return hipErrorInvalidValue;
+  if (!a.ntiles || !a.inv_total) return hipSuccess;
+  hipLaunchKernelGGL(k_invert_tile<true>, invert_grid(a.ntiles), dim3(kBlock), 0, s, a);
+  return hipGetLastError();
+}
+
+// the inverted XSG_COUNT_LINES behind a count pass with newline counts (one workgroup; see xsg_internal.h)
+__global__ __launch_bounds__(kBlock) void k_invert_count_lines(const uint8_t* base, const ChunkDev* chunks, uint64_t nchunks,
+                                                               uint64_t* counters, uint64_t* host_counters,
+                                                               const uint64_t* status, uint32_t keep_nl) {
+  __shared__ uint64_t sh[kWaves];
+  uint64_t open = 0;  // chunks whose last line lacks its '\n'
+  for (uint64_t c = threadIdx.x; c < nchunks; c += kBlock) {
+    const ChunkDev ch = chunks[c];
+    open += ch.length != 0 && base[ch.offset + ch.length - 1] != '\n';
+  }
+  open = block_sum_u64(open, sh);
+  if (threadIdx.x != 0) return;
+  if ((status && *status) || counters[XSG_CTR_BYTES] == UINT64_MAX) return;  // a refusal passes through
+  const uint64_t lines = counters[XSG_CTR_NEWLINES] + open - counters[XSG_CTR_LINES];
+  const uint64_t nl = keep_nl ? counters[XSG_CTR_NEWLINES] : 0ull;
+  counters[XSG_CTR_LINES] = lines;
+  counters[XSG_CTR_NEWLINES] = nl;
+  if (host_counters) {
+    host_counters[XSG_CTR_LINES] = lines;
+    host_counters[XSG_CTR_NEWLINES] = nl;
+  }
+}
+hipError_t launch_invert_count_lines(const uint8_t* base, const ChunkDev* chunks, uint64_t nchunks, uint64_t* counters,
+                                     uint64_t* host_counters, const uint64_t* status, uint32_t keep_nl, hipStream_t s) {
+  hipLaunchKernelGGL(k_invert_count_lines, dim3(1), dim3(kBlock), 0, s, base, chunks, nchunks, counters, host_counters, status, keep_nl);
   return hipGetLastError();
 }
 

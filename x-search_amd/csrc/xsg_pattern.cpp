@@ -13,6 +13,8 @@
 
 using namespace xsg;
 
+static int set_pattern_plain(xsg_ctx* c, const void* pattern, size_t plen, uint32_t flags);  // xsg_set_pattern without XSG_FLAG_INVERT
+
 static uint32_t le32(const uint8_t* p, size_t n) {
   uint32_t v = 0;
   for (size_t i = 0; i < 4 && i < n; ++i) v |= (uint32_t)p[i] << (8 * i);
@@ -325,7 +327,7 @@ static int set_class_pattern(xsg_ctx* c, const uint8_t* re, size_t n, uint32_t f
     lit[k] = (uint8_t)(b >= 0 ? b : 0);
   }
   if (literal)  // e.g. `a\.b`: an ordinary literal, minus the reference's scalar-tail quirk (RE2 has none)
-    return xsg_set_pattern(c, lit.data(), plen, (flags & XSG_FLAG_IGNORE_CASE) | XSG_FLAG_EXACT_TAIL);
+    return set_pattern_plain(c, lit.data(), plen, (flags & XSG_FLAG_IGNORE_CASE) | XSG_FLAG_EXACT_TAIL);
 
   HIP_TRY(hipSetDevice(c->device));
   c->pattern.assign(re, re + n);
@@ -444,7 +446,23 @@ extern "C" int xsg_regex_info(const void* expr, size_t n, uint32_t flags, uint32
   return XSG_OK;
 }
 
+// XSG_FLAG_INVERT is not a property of the compiled pattern (PatternDev and the scan kernels never see it): the pattern
+// is set without it, refused if it can match '\n' (the line such a match belongs to is not a line of the chunk), and
+// the flag is kept on the context, where the list and count routes read it.
 extern "C" int xsg_set_pattern(xsg_ctx* c, const void* pattern, size_t plen, uint32_t flags) {
+  if (!(flags & XSG_FLAG_INVERT) || !c) return set_pattern_plain(c, pattern, plen, flags);
+  if (flags & ~(XSG_FLAG_EXACT_TAIL | XSG_FLAG_IGNORE_CASE | XSG_FLAG_REGEX | XSG_FLAG_INVERT))
+    return fail(XSG_EINVAL, "unknown pattern flags 0x%x", flags);
+  XSG_TRY(set_pattern_plain(c, pattern, plen, flags & ~XSG_FLAG_INVERT));
+  if (c->pat.has_newline) {
+    c->pattern.clear();  // no pattern is set: a search now says so instead of running the plain form
+    return fail(XSG_ENOTSUP, "XSG_FLAG_INVERT: an inverted search does not accept a pattern that can match '\\n'");
+  }
+  c->flags |= XSG_FLAG_INVERT;
+  return XSG_OK;
+}
+
+static int set_pattern_plain(xsg_ctx* c, const void* pattern, size_t plen, uint32_t flags) {
   if (!c) return fail(XSG_EINVAL, "ctx is null");
   if (!pattern || plen == 0) return fail(XSG_EINVAL, "empty pattern");
   if (plen > XSG_MAX_PATTERN) return fail(XSG_EINVAL, "pattern longer than %u bytes", XSG_MAX_PATTERN);

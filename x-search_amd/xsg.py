@@ -23,6 +23,7 @@ COUNT_MATCHES, COUNT_LINES, MATCH_BYTE_OFFSETS, LINE_BYTE_OFFSETS, LINE_INDICES,
 FLAG_EXACT_TAIL = 0x1
 FLAG_IGNORE_CASE = 0x2
 FLAG_REGEX = 0x4
+FLAG_INVERT = 0x8  # the line tags report the lines WITHOUT a match (grep -v); the match tags are refused
 WITH_NEWLINES = 0x100
 CTR_MATCHES, CTR_LINES, CTR_NEWLINES, CTR_BYTES = range(4)
 NUM_COUNTERS = 4
