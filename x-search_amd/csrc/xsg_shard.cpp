@@ -151,3 +151,39 @@ extern "C" int xsg_shard_set_line_base(xsg_shard* s, uint64_t line_base) {
   s->shard_line_base = line_base;
   return XSG_OK;
 }
+
+// XSG_TEST_HOOKS=1 only (not part of include/xsg.h): the host-side bookkeeping of a binding, for tests that must show
+// which state a call order met (tests/test_gpu_call_sequences.py).  Waits for the context's stream unless n <= 18.
+extern "C" int xsg_test_shard_state(xsg_shard* s, uint64_t* out, size_t n) {
+  if (!s || !out) return fail(XSG_EINVAL, "null argument");
+  if (!test_hooks()) return fail(XSG_ENOTSUP, "xsg_test_shard_state needs XSG_TEST_HOOKS=1");
+  const xsg_ctx* c = s->ctx;
+  const uint64_t serial = c->pattern_serial;
+  uint32_t word = 0;
+  if (n > 18) {  // the first tile's tile_last word
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (s->d_tile_last.p) HIP_TRY(hipMemcpy(&word, s->d_tile_last.p, 4, hipMemcpyDeviceToHost));
+  }
+  const uint64_t v[] = {s->epoch,
+                        s->cnt_clean,
+                        s->sum_clean,
+                        s->last_valid,
+                        s->nl_cached,
+                        s->table_pending,
+                        s->fast_result,
+                        (uint64_t)(s->fast_dense_serial == serial || c->fast_dense_serial == serial),
+                        (uint64_t)(s->overlap_serial == serial),
+                        (uint64_t)(s->overlap_serial == serial && s->overlap_free),
+                        s->last_raw_matches,
+                        (uint64_t)(s->mask_serial != 0 && s->mask_serial == serial),
+                        s->density_serial == serial ? s->dense : 0u,
+                        s->tune,
+                        (uint64_t)(s->tune_serial == serial),
+                        s->d_tile_cnt.cap,
+                        s->d_tile_sum.cap,
+                        (uint64_t)(uintptr_t)c->stream,
+                        word};
+  for (size_t i = 0; i < n && i < sizeof v / sizeof v[0]; ++i) out[i] = v[i];
+  return XSG_OK;
+}
