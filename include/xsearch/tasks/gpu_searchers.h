@@ -59,6 +59,27 @@ std::optional<std::vector<uint64_t>> offsets(const Handle& h, uint32_t mode, con
   return std::make_optional(std::move(v));
 }
 
+// xsg_host_lines / xsg_host_matches: n strings as lengths + packed bytes
+template <class T>
+std::optional<std::vector<std::string>> strings(const Handle& h, decltype(&xsg_host_lines) call, const T& data) {
+  uint64_t* lens = nullptr;
+  char* bytes = nullptr;
+  uint64_t n = 0, nb = 0;
+  const int r = call(h.hs, data.data(), data.size(), &lens, &bytes, &n, &nb);
+  if (r != XSG_OK) raise(r);
+  std::vector<std::string> v;
+  v.reserve(n);
+  uint64_t at = 0;
+  for (uint64_t i = 0; i < n; ++i) {
+    v.emplace_back(bytes + at, lens[i]);
+    at += lens[i];
+  }
+  xsg_free(lens);
+  xsg_free(bytes);
+  if (v.empty()) return {};
+  return v;
+}
+
 }  // namespace gpu_detail
 
 // replaces IndexSearcher (searchers.h:38-59): search::byte_offsets_match(data, pattern, false)
@@ -96,22 +117,21 @@ class GpuLineSearcher {
   explicit GpuLineSearcher(std::string pattern, int device = 0, int max_concurrent = 8, uint32_t flags = 0)
       : _h(std::make_shared<gpu_detail::Handle>(pattern, device, max_concurrent, flags)) {}
   std::optional<std::vector<std::string>> operator()(const T& data) const {
-    uint64_t* lens = nullptr;
-    char* bytes = nullptr;
-    uint64_t n = 0, nb = 0;
-    const int r = xsg_host_lines(_h->hs, data.data(), data.size(), &lens, &bytes, &n, &nb);
-    if (r != XSG_OK) gpu_detail::raise(r);
-    std::vector<std::string> v;
-    v.reserve(n);
-    uint64_t at = 0;
-    for (uint64_t i = 0; i < n; ++i) {
-      v.emplace_back(bytes + at, lens[i]);
-      at += lens[i];
-    }
-    xsg_free(lens);
-    xsg_free(bytes);
-    if (v.empty()) return {};
-    return v;
+    return gpu_detail::strings(*_h, xsg_host_lines, data);
+  }
+
+ private:
+  std::shared_ptr<gpu_detail::Handle> _h;
+};
+
+// the matched text of every match IndexSearcher reports (grep -o; no reference adapter exists for it): XSG_MATCHES
+template <class T = std::vector<char>>
+class GpuMatchSearcher {
+ public:
+  explicit GpuMatchSearcher(std::string pattern, int device = 0, int max_concurrent = 8, uint32_t flags = 0)
+      : _h(std::make_shared<gpu_detail::Handle>(pattern, device, max_concurrent, flags)) {}
+  std::optional<std::vector<std::string>> operator()(const T& data) const {
+    return gpu_detail::strings(*_h, xsg_host_matches, data);
   }
 
  private:

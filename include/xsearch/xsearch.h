@@ -11,13 +11,14 @@
 //   for (auto r : *res->getResult()) { ... }     // live, blocks per element          test/src/xsearchTest.cpp:735-739,888-890
 //
 // Tags: xs::count (== xs::count_matches), xs::count_lines, xs::match_byte_offsets,
-// xs::line_byte_offsets, xs::line_indices, xs::lines (README.md:77-81).
+// xs::line_byte_offsets, xs::line_indices, xs::lines (README.md:77-81), and xs::matches: the matched text of every
+// match xs::match_byte_offsets reports (grep -o; the reference has no such tag).
 //
 // Semantics (include/xsearch/string_search/search_wrappers.h, bit-exact):
 //   count tags   getResult()->size() is the count; live iteration yields the
 //                running total after every chunk (last value == total)
 //   vector tags  flat elements: global byte offsets / 0-based line indices /
-//                lines without the trailing '\n'; published in file order
+//                lines without the trailing '\n' / matched strings; published in file order
 //   the searcher's threads are joined on destruction (README.md:91; Searcher.h:41)
 //
 // Errors (the reference defines none; a bad path spins there, readers.h:40-47):
@@ -59,6 +60,7 @@ struct match_byte_offsets {};
 struct line_byte_offsets {};
 struct line_indices {};
 struct lines {};
+struct matches {};  // XSG_MATCHES: what matched, one string per match, in the order of match_byte_offsets
 
 namespace detail {
 
@@ -98,6 +100,12 @@ template <>
 struct traits<lines> {
   using value_type = std::string;
   static constexpr uint32_t mode = XSG_LINES;
+  static constexpr bool is_count = false;
+};
+template <>
+struct traits<matches> {
+  using value_type = std::string;
+  static constexpr uint32_t mode = XSG_MATCHES;
   static constexpr bool is_count = false;
 };
 
@@ -189,7 +197,7 @@ inline uint32_t pattern_flags(const std::string& pattern, bool ignore_case) {
 
 // an inverted search has no match tags: a non-match has no offset (xsg.h, XSG_FLAG_INVERT)
 inline void require_line_tag(uint32_t flags, uint32_t mode) {
-  if ((flags & XSG_FLAG_INVERT) && (mode == XSG_COUNT_MATCHES || mode == XSG_MATCH_BYTE_OFFSETS))
+  if ((flags & XSG_FLAG_INVERT) && (mode == XSG_COUNT_MATCHES || mode == XSG_MATCH_BYTE_OFFSETS || mode == XSG_MATCHES))
     throw std::invalid_argument("xs::extern_search: XS_INVERT_MATCH (invert) serves the line tags only: count_lines, "
                                 "line_byte_offsets, line_indices, lines");
 }

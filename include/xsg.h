@@ -59,8 +59,26 @@ enum xsg_mode {
   XSG_MATCH_BYTE_OFFSETS = 2, /* xs::match_byte_offsets       -> search::byte_offsets_match      (:136-139) */
   XSG_LINE_BYTE_OFFSETS = 3,  /* xs::line_byte_offsets        -> search::byte_offsets_line       (:149-154) */
   XSG_LINE_INDICES = 4,       /* xs::line_indices             -> (no reference impl)     */
-  XSG_LINES = 5               /* xs::lines                    -> search::line                    (:187-207) */
+  XSG_LINES = 5,              /* xs::lines                    -> search::line                    (:187-207) */
+  XSG_MATCHES = 6             /* xs::matches                  -> the matched text (grep -o); no reference impl, see below */
 };
+/* XSG_MATCHES: what matched, not only where.  Let M be the list XSG_MATCH_BYTE_OFFSETS reports for the same binding,
+ * pattern and flags -- the default lossy end-of-chunk behaviour included, lifted by XSG_FLAG_EXACT_TAIL.  XSG_MATCHES
+ * reports, for every element of M and in the same order, the bytes [start, start + len) of the chunk, where len is
+ *   the pattern length                      for a literal,
+ *   the number of positions                 for a fixed-length class sequence (XSG_FLAG_REGEX),
+ *   the length of the leftmost-first match  on the automaton route
+ * -- the same len the walk uses as its resume point; under the (?m)...$ form the '\n' is not part of the match.  The
+ * bytes are the ORIGINAL ones: under XSG_FLAG_IGNORE_CASE the text keeps its case, as for XSG_LINES.  A literal or an
+ * expression that can match '\n' is served (the match tags serve it); the strings then contain newlines, which is why
+ * lengths are reported.  Nothing is dropped: |M| strings come out, a match at a chunk's end that no '\n' follows
+ * included (a match always has a length; UINT64_MAX never appears among the lengths).  A match is shorter than 4 GiB:
+ * an expression whose matches vary in length is refused (XSG_ENOTSUP) on a binding with a chunk of 4 GiB or more.
+ * XSG_FLAG_INVERT refuses this tag as it refuses the other two match tags (XSG_ENOTSUP); the non-ASCII refusal of '.'
+ * and negated classes is unchanged; the count entry points do not take it (XSG_EINVAL, as for any list mode).
+ * Results: xsg_search sets *n_results = |M|; xsg_result_lines_size / xsg_result_lines / xsg_result_lines_view hand
+ * out the lengths, the packed bytes and, in `offsets`, global_offset + start of every match.  Every other accessor
+ * behaves after an XSG_MATCHES search as after an XSG_LINES search. */
 
 /* ---- pattern flags ------------------------------------------------------- */
 /* Default (0): reproduce the reference exactly, including the lossy scalar
@@ -329,7 +347,8 @@ int xsg_result_u64(xsg_shard* shard, uint64_t* out, uint64_t cap);
  * valid until the next search on it (a dense needle returns hundreds of MB: D2H into pageable memory runs at a
  * sixth of the pinned rate). */
 int xsg_result_u64_view(xsg_shard* shard, const uint64_t** out, uint64_t* n);
-/* After an XSG_LINES search: total number of line bytes (no '\n's). */
+/* After an XSG_LINES search: total number of line bytes (no '\n's).  After an XSG_MATCHES search here and in the two
+ * calls below: "line" reads "match" (n_lines = |M|, lengths / bytes / offsets of the matched text). */
 int xsg_result_lines_size(xsg_shard* shard, uint64_t* n_lines, uint64_t* total_bytes);
 /* line i = bytes[ starts[i] .. starts[i] + lengths[i] ), in file order;
  * `offsets` (optional) receives the global byte offset of each line start. */
@@ -409,7 +428,7 @@ int xsg_job_wait(xsg_job* job, uint64_t index, uint64_t* available, int* finishe
 /* Non-blocking form of xsg_job_wait. */
 int xsg_job_poll(xsg_job* job, uint64_t* available, int* finished);
 int xsg_job_get_u64(xsg_job* job, uint64_t first, uint64_t n, uint64_t* out);
-/* XSG_LINES: line `index`; *data stays valid until xsg_job_destroy. */
+/* XSG_LINES: line `index`, XSG_MATCHES: match `index`; *data stays valid until xsg_job_destroy. */
 int xsg_job_get_line(xsg_job* job, uint64_t index, const char** data, uint64_t* len);
 int xsg_job_stats_get(xsg_job* job, xsg_job_stats* stats);
 
@@ -437,6 +456,9 @@ int xsg_host_offsets(xsg_host_searcher* hs, uint32_t mode, const void* data, uin
 /* search::line (:187-207): n lines, lengths[i] bytes each, packed in *bytes; both malloc'ed (xsg_free) */
 int xsg_host_lines(xsg_host_searcher* hs, const void* data, uint64_t len, uint64_t** lengths, char** bytes,
                    uint64_t* n, uint64_t* nbytes);
+/* XSG_MATCHES of the chunk: n matches, lengths[i] bytes each, packed in *bytes; both malloc'ed (xsg_free) */
+int xsg_host_matches(xsg_host_searcher* hs, const void* data, uint64_t len, uint64_t** lengths, char** bytes,
+                     uint64_t* n, uint64_t* nbytes);
 
 /* ---- chunk plans and metafiles (host only: usable without a GPU) ------------- */
 /* One record of the reference's metafile (decoded from test/files/ *.meta,

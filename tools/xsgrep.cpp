@@ -1,7 +1,7 @@
 // xsgrep -- the reference's example/grep.cpp (PATTERN FILE, -c, -i; lines 23-82)
 // on the MI355X engine, without boost::program_options.
 //
-//   xsgrep [-c] [-i] [-v] [-E|-F] [-x] [-j THREADS] [-m METAFILE] PATTERN FILE|-
+//   xsgrep [-c] [-i] [-o] [-v] [-E|-F] [-x] [-j THREADS] [-m METAFILE] PATTERN FILE|-
 //
 // -c  print only a count of matching lines   (grep.cpp:45-46 -> xs::count_lines)
 // -i  ignore ASCII case                      (grep.cpp:47-48)
@@ -12,7 +12,9 @@
 //     refused (it would match empty lines only), as is a PATTERN with anchors elsewhere (`^a|^b`).
 // -v  the lines WITHOUT a match (XS_INVERT_MATCH -> XSG_FLAG_INVERT); with -c their number.  Like the reference's
 //     xs::lines, a last line that lacks its newline is not printed.
-// The one-letter options without an argument may be bundled (-vc, -ci).
+// -o  print only the matched text, every match on its own line (xs::matches -> XSG_MATCHES).  With -c the count stays
+//     the count of matching lines, as in grep.  Not with -v: a line without a match has no matched text.
+// The one-letter options without an argument may be bundled (-vc, -ci, -oi).
 // otherwise print the matching lines, live, as they are found (grep.cpp:74-79).
 #include <xsearch/tasks/gpu_searchers.h>
 #include <xsearch/xsearch.h>
@@ -25,7 +27,8 @@
 #include <vector>
 
 static const char kUsage[] =
-    "usage: %s [-c] [-i] [-v] [-E|-F] [-x] [-j THREADS] [-m METAFILE] PATTERN FILE|-\n"
+    "usage: %s [-c] [-i] [-o] [-v] [-E|-F] [-x] [-j THREADS] [-m METAFILE] PATTERN FILE|-\n"
+    "  -o, --only-matching prints only the matched text, every match on its own line (not with -v)\n"
     "  -v, --invert-match selects the lines WITHOUT a match (with -c: counts them)\n"
     "  -x searches (?m)^(?:PATTERN)$; PATTERN must not be empty\n";
 
@@ -52,14 +55,14 @@ static std::string re2_literal(const std::string& p) {
 }
 
 int main(int argc, char** argv) {
-  bool count = false, icase = false, fixed = false, extended = false, whole_lines = false, invert = false;
+  bool count = false, icase = false, fixed = false, extended = false, whole_lines = false, invert = false, only = false;
   int threads = 2;  // grep.cpp:21
   std::string meta, pattern, file;
   int pos = 0;
   std::vector<std::string> args;
   for (int i = 1; i < argc; ++i) {  // -vc -> -v -c (only letters that take no argument; anything else stays one word)
     const std::string a = argv[i];
-    if (a.size() > 2 && a[0] == '-' && a[1] != '-' && a.find_first_not_of("ciEFxv", 1) == std::string::npos) {
+    if (a.size() > 2 && a[0] == '-' && a[1] != '-' && a.find_first_not_of("ciEFxvo", 1) == std::string::npos) {
       for (size_t k = 1; k < a.size(); ++k) args.push_back(std::string("-") + a[k]);
     } else {
       args.push_back(a);
@@ -70,6 +73,8 @@ int main(int argc, char** argv) {
     const std::string a = args[i];
     if (a == "-v" || a == "--invert-match") {
       invert = true;
+    } else if (a == "-o" || a == "--only-matching") {
+      only = true;
     } else if (a == "-c" || a == "--count") {
       count = true;
     } else if (a == "-i" || a == "--ignore-case") {
@@ -106,6 +111,10 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "xsgrep: -E and -F exclude each other\n");
     return 2;
   }
+  if (only && invert) {
+    std::fprintf(stderr, "xsgrep: -o and -v exclude each other (a line without a match has no matched text)\n");
+    return 2;
+  }
   if (whole_lines) {  // a line-anchored regex (xsg.h, XSG_FLAG_REGEX): the whole line is one match of PATTERN
     const std::string body = fixed ? re2_literal(pattern) : strip_edge_anchors(pattern);
     if (body.empty()) {
@@ -130,6 +139,7 @@ int main(int argc, char** argv) {
       // (include/xsearch/tasks/gpu_searchers.h), like Searcher::run_thread does with a reader.
       const uint32_t flags = xs::detail::pattern_flags(pattern, icase);
       xs::GpuLineSearcher<std::vector<char>> lines(pattern, 0, 1, flags);
+      xs::GpuMatchSearcher<std::vector<char>> matches(pattern, 0, 1, flags);
       xs::GpuCountSearcher<std::vector<char>> counter(pattern, true, 0, 1, flags);
       const size_t target = 16u << 20;
       std::vector<char> buf;  // bytes read and not searched yet
@@ -158,6 +168,9 @@ int main(int argc, char** argv) {
         want = target;
         if (count) {
           if (auto c = counter(chunk)) total += *c;
+        } else if (only) {
+          if (auto ms = matches(chunk))
+            for (const auto& m : *ms) std::cout << m << '\n';
         } else if (auto ls = lines(chunk)) {
           for (const auto& l : *ls) std::cout << l << '\n';
         }
@@ -170,6 +183,12 @@ int main(int argc, char** argv) {
                                    : xs::extern_search<xs::count_lines>(pattern, file, meta, icase, threads, threads);
       searcher->join();
       std::cout << searcher->getResult()->size() << std::endl;
+    } else if (only) {
+      auto searcher = meta.empty() ? xs::extern_search<xs::matches>(pattern, file, icase, threads)
+                                   : xs::extern_search<xs::matches>(pattern, file, meta, icase, threads, threads);
+      for (auto const& match : *searcher->getResult()) {
+        std::cout << match << '\n';
+      }
     } else {
       auto searcher = meta.empty() ? xs::extern_search<xs::lines>(pattern, file, icase, threads)
                                    : xs::extern_search<xs::lines>(pattern, file, meta, icase, threads, threads);

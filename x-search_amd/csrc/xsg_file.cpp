@@ -461,6 +461,7 @@ struct Partial {
 
 static std::atomic<uint64_t> g_job_serial{0};
 
+static bool is_string_mode(uint32_t mode) { return mode == XSG_LINES || mode == XSG_MATCHES; }  // results are strings
 struct xsg_job {
   const uint64_t serial = ++g_job_serial;
   xsg_job_opts opts{};
@@ -498,7 +499,7 @@ struct xsg_job {
   std::map<uint64_t, Partial> pending;
   uint64_t next_publish = 0;
   std::vector<uint64_t> values;   // count tags: running totals; u64 tags: elements
-  std::deque<std::string> lines;  // XSG_LINES
+  std::deque<std::string> lines;  // XSG_LINES, XSG_MATCHES
   uint64_t total = 0;             // count so far / elements so far
   uint64_t nl_running = 0;        // '\n' in all published chunks
   bool finished = false;
@@ -531,7 +532,7 @@ static void publish(xsg_job* j, uint64_t index, Partial&& p) {
     if (mode == XSG_COUNT_MATCHES || mode == XSG_COUNT_LINES) {
       j->total += q.count;
       j->values.push_back(j->total);
-    } else if (mode == XSG_LINES) {
+    } else if (is_string_mode(mode)) {
       for (std::string& s : q.lines) j->lines.push_back(std::move(s));
       j->total = j->lines.size();
     } else {
@@ -954,7 +955,7 @@ static int list_collect(xsg_job* j, Lane& l, const HostBuf& hb) {
   const xsg_file_chunk& fc = j->plan[hb.index];
   const uint32_t mode = j->opts.mode;
   Partial p;
-  if (mode == XSG_LINES) {
+  if (is_string_mode(mode)) {
     uint64_t n = 0, nl = 0, nb = 0;
     const uint64_t* lens = nullptr;
     const char* bytes = nullptr;
@@ -1152,9 +1153,9 @@ static int job_start_impl(const void* pattern, size_t plen, const char* file_pat
   if (!pattern || plen == 0 || plen > XSG_MAX_PATTERN) return fail(XSG_EINVAL, "pattern must be 1..%u bytes",
                                                                   XSG_MAX_PATTERN);
   if ((opts->pattern_flags & XSG_FLAG_REGEX) && plen > XSG_MAX_REGEX) return fail(XSG_EINVAL, "expression longer than %u bytes", XSG_MAX_REGEX);
-  if (opts->mode > XSG_LINES) return fail(XSG_EINVAL, "bad mode %u", opts->mode);
+  if (opts->mode > XSG_MATCHES) return fail(XSG_EINVAL, "bad mode %u", opts->mode);
   if (opts->num_threads < 1 || opts->num_max_readers < 1) return fail(XSG_EINVAL, "num_threads/num_max_readers < 1");
-  const bool line_mode = opts->mode != XSG_COUNT_MATCHES && opts->mode != XSG_MATCH_BYTE_OFFSETS;
+  const bool line_mode = opts->mode != XSG_COUNT_MATCHES && opts->mode != XSG_MATCH_BYTE_OFFSETS && opts->mode != XSG_MATCHES;
   if (opts->pattern_flags & XSG_FLAG_INVERT) {  // (xsg.h: the line tags only, and no pattern that can match '\n')
     if (!line_mode) return fail(XSG_ENOTSUP, "XSG_FLAG_INVERT: an inverted search reports lines without a match; the match tags have no inverted form");
     if (!(opts->pattern_flags & XSG_FLAG_REGEX) && memchr(pattern, '\n', plen))
@@ -1296,7 +1297,7 @@ extern "C" int xsg_job_total(xsg_job* j, uint64_t* total) {
 extern "C" int xsg_job_wait(xsg_job* j, uint64_t index, uint64_t* available, int* finished) {
   if (!j) return fail(XSG_EINVAL, "job is null");
   std::unique_lock<std::mutex> lk(j->mu);
-  const bool is_lines = j->opts.mode == XSG_LINES;
+  const bool is_lines = is_string_mode(j->opts.mode);
   auto avail = [&] { return is_lines ? (uint64_t)j->lines.size() : (uint64_t)j->values.size(); };
   j->cv.wait(lk, [&] { return avail() > index || j->finished; });
   if (available) *available = avail();
@@ -1308,14 +1309,14 @@ extern "C" int xsg_job_wait(xsg_job* j, uint64_t index, uint64_t* available, int
 extern "C" int xsg_job_poll(xsg_job* j, uint64_t* available, int* finished) {
   if (!j) return fail(XSG_EINVAL, "job is null");
   std::lock_guard<std::mutex> g(j->mu);
-  if (available) *available = j->opts.mode == XSG_LINES ? (uint64_t)j->lines.size() : (uint64_t)j->values.size();
+  if (available) *available = is_string_mode(j->opts.mode) ? (uint64_t)j->lines.size() : (uint64_t)j->values.size();
   if (finished) *finished = j->finished ? 1 : 0;
   return XSG_OK;
 }
 
 extern "C" int xsg_job_get_u64(xsg_job* j, uint64_t first, uint64_t n, uint64_t* out) {
   if (!j || (!out && n)) return fail(XSG_EINVAL, "null argument");
-  if (j->opts.mode == XSG_LINES) return fail(XSG_ESTATE, "XSG_LINES results are strings: use xsg_job_get_line");
+  if (is_string_mode(j->opts.mode)) return fail(XSG_ESTATE, "XSG_LINES / XSG_MATCHES results are strings: use xsg_job_get_line");
   std::lock_guard<std::mutex> g(j->mu);
   if (first + n > j->values.size()) return fail(XSG_EINVAL, "range beyond the available results");
   if (n) memcpy(out, j->values.data() + first, 8 * n);
@@ -1324,7 +1325,7 @@ extern "C" int xsg_job_get_u64(xsg_job* j, uint64_t first, uint64_t n, uint64_t*
 
 extern "C" int xsg_job_get_line(xsg_job* j, uint64_t index, const char** data, uint64_t* len) {
   if (!j || !data || !len) return fail(XSG_EINVAL, "null argument");
-  if (j->opts.mode != XSG_LINES) return fail(XSG_ESTATE, "not an XSG_LINES job");
+  if (!is_string_mode(j->opts.mode)) return fail(XSG_ESTATE, "not an XSG_LINES or XSG_MATCHES job");
   std::lock_guard<std::mutex> g(j->mu);
   if (index >= j->lines.size()) return fail(XSG_EINVAL, "index beyond the available results");
   const std::string& s = j->lines[index];  // deque: references stay valid while the job lives
@@ -1602,8 +1603,8 @@ extern "C" int xsg_host_offsets(xsg_host_searcher* hs, uint32_t mode, const void
   return XSG_OK;
 }
 
-extern "C" int xsg_host_lines(xsg_host_searcher* hs, const void* data, uint64_t len, uint64_t** lengths, char** bytes,
-                              uint64_t* n, uint64_t* nbytes) {
+static int host_strings(xsg_host_searcher* hs, uint32_t mode, const void* data, uint64_t len, uint64_t** lengths, char** bytes,
+                        uint64_t* n, uint64_t* nbytes) {
   if (!hs || !lengths || !bytes || !n || !nbytes || (!data && len)) return fail(XSG_EINVAL, "null argument");
   SlotLease l(hs);
   XSG_TRY(host_slot_acquire(hs, &l.s));
@@ -1611,7 +1612,7 @@ extern "C" int xsg_host_lines(xsg_host_searcher* hs, const void* data, uint64_t 
   uint64_t cnt = 0, nl = 0, nb = 0;
   const uint64_t* vlens = nullptr;
   const char* vbytes = nullptr;
-  XSG_TRY(xsg_search(l.s->shard, XSG_LINES, &cnt));
+  XSG_TRY(xsg_search(l.s->shard, mode, &cnt));
   // out of the shard's pinned buffers (a large result arrives there by pinned copies, not by a pageable D2H)
   XSG_TRY(xsg_result_lines_view(l.s->shard, &vlens, &vbytes, nullptr, &nl, &nb));
   uint64_t* lens = static_cast<uint64_t*>(malloc(8 * std::max<uint64_t>(nl, 1)));
@@ -1628,4 +1629,14 @@ extern "C" int xsg_host_lines(xsg_host_searcher* hs, const void* data, uint64_t 
   *n = nl;
   *nbytes = nb;
   return XSG_OK;
+}
+
+extern "C" int xsg_host_lines(xsg_host_searcher* hs, const void* data, uint64_t len, uint64_t** lengths, char** bytes,
+                              uint64_t* n, uint64_t* nbytes) {
+  return host_strings(hs, XSG_LINES, data, len, lengths, bytes, n, nbytes);
+}
+
+extern "C" int xsg_host_matches(xsg_host_searcher* hs, const void* data, uint64_t len, uint64_t** lengths, char** bytes,
+                                uint64_t* n, uint64_t* nbytes) {
+  return host_strings(hs, XSG_MATCHES, data, len, lengths, bytes, n, nbytes);
 }

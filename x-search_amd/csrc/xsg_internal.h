@@ -122,6 +122,8 @@ struct ScanArgs {
   const uint64_t* tile_off;  // exclusive prefix of tile_cnt
   uint64_t* m_pos;           // chunk-local offset of every match, ascending
   uint32_t* m_chunk;         // its chunk
+  uint32_t* m_len;           // kDfa, XSG_MATCHES: its length (the walk's resume point minus its start); null for every other
+                             // tag -- the test is uniform per launch, and a launch without it stores what it always stored
   // emit pass over the tiles that hold a match only (the one-sync list route): the ordered list of those tiles and
   // where its length lives; null: one workgroup per tile of the shard, each leaving at once if its count is 0
   const uint32_t* hit_tiles;
@@ -188,6 +190,7 @@ struct RxPreArgs {
   const uint64_t* c_pre;     // exclusive prefix of c_keep
   uint64_t* m_pos;           // the reported ones, packed
   uint32_t* m_chunk;
+  uint32_t* m_len;           // XSG_MATCHES: their c_len, packed with them (null otherwise)
 };
 hipError_t launch_rx_verify_keep(const RxPreArgs& a, hipStream_t s);
 hipError_t launch_rx_compact(const RxPreArgs& a, hipStream_t s);
@@ -254,6 +257,7 @@ struct ListArgs {
                              // arrays and the kernels work on min(*M_dev, M) entries (xsg_count_async, bordered patterns)
   const uint64_t* m_pos;     // chunk-local offsets
   const uint32_t* m_chunk;
+  const uint32_t* m_len;     // kDfa, XSG_MATCHES: length of every raw match (ScanArgs::m_len); null otherwise
   const uint64_t* tile_off;  // -> first raw index of each chunk = tile_off[chunk_tile0[c]]
   uint64_t* m_ls;            // line start per raw match (line modes)
   uint32_t* keep;            // 1 = survives the walk (greedy / first in line)
@@ -268,6 +272,7 @@ struct ListArgs {
   uint64_t* f_pos;    // chunk-local: match offset (match mode) or line start (line modes)
   uint64_t* f_match;  // chunk-local offset of the (first) match of that line
   uint32_t* f_chunk;
+  uint32_t* f_len;    // k_assemble, XSG_MATCHES on the automaton routes: m_len of the entry (null otherwise)
   uint64_t total;
   // one-sync route
   uint32_t keep_all;         // every raw occurrence is reported (no keep[] / keep_pre[]: entry i stays entry i)
@@ -318,6 +323,7 @@ struct LineOutArgs {
   const uint64_t* f_pos;
   const uint64_t* f_match;
   const uint32_t* f_chunk;
+  const uint32_t* f_len;  // k_match_spans: length of every entry's match; null: pat.plen (a literal, a class sequence)
   uint64_t* out_u64;  // global offsets or line indices
   // line indices
   const uint64_t* tile_nl_off;  // exclusive prefix of tile_nl over all tiles of the shard
@@ -343,7 +349,11 @@ hipError_t launch_globalize(const LineOutArgs& a, hipStream_t s);
 hipError_t launch_line_nl_delta(const LineOutArgs& a, hipStream_t s);
 hipError_t launch_line_indices(const LineOutArgs& a, hipStream_t s);
 hipError_t launch_line_lengths(const LineOutArgs& a, hipStream_t s);
-hipError_t launch_line_gather(const LineOutArgs& a, hipStream_t s);
+hipError_t launch_line_gather(const LineOutArgs& a, hipStream_t s, bool short_strings = false);
+// XSG_MATCHES: the matched text of every entry of a list assembled in match mode (f_pos = where the match starts).
+// spans: line_len (never UINT64_MAX: a match always has a length), out_u64 and their pinned mirrors; the gather is
+// launch_line_gather(.., short_strings = true)
+hipError_t launch_match_spans(const LineOutArgs& a, hipStream_t s);
 
 // ---- XSG_FLAG_INVERT: the complement stage (xsg_list.cpp: invert_list) ---------------------------------------------
 // The assembled list of a line tag (r_pos / r_chunk: the chunk-relative starts of the lines the walk reports, ascending

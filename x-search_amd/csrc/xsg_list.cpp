@@ -41,6 +41,7 @@ ListArgs xsg::list_args(const xsg_shard* s, const ScanArgs& a) {
   l.nchunks = s->chunks.size();
   l.m_pos = a.m_pos;
   l.m_chunk = a.m_chunk;
+  l.m_len = a.m_len;
   l.tile_off = a.tile_off;
   l.chunk_shift0 = s->d_chunk_shift0.as<uint64_t>();
   l.tail_cnt = s->d_tail_cnt.as<uint32_t>();
@@ -63,6 +64,7 @@ static LineOutArgs line_out_args(const xsg_shard* s, const ScanArgs& a, const Li
   o.f_pos = l.f_pos;
   o.f_match = l.f_match;
   o.f_chunk = l.f_chunk;
+  o.f_len = l.f_len;
   o.out_u64 = s->d_out_u64.as<uint64_t>();
   o.shard_line_base = s->shard_line_base;
   o.tile_bytes = s->tile_bytes;
@@ -164,6 +166,7 @@ static bool fast_route_serves(const xsg_shard* s, uint32_t mode, bool outputs, b
   const xsg_ctx* c = s->ctx;
   const char* e = XSG_TOGGLE("XSG_LIST_FAST");  // 0: every list search takes the exact route (tests, A/B)
   if ((e && *e == '0') || !outputs || s->ntiles == 0 || want_nl_total) return false;
+  if (mode == XSG_MATCHES) return false;                                // the span and gather stages sit on the exact route
   if (c->flags & XSG_FLAG_INVERT) return false;                         // the complement stage sits on the exact route
   if (c->pat.kind == kDfa) return false;                                // k_rx_scan / the prefilter route: exact route
   if (mode != XSG_MATCH_BYTE_OFFSETS && c->pat.has_newline) return false;  // the line walk of a literal with '\n': a chain, exact route
@@ -414,7 +417,7 @@ constexpr int kRedoUnfiltered = 3;  // prefilter_candidates: the prefilter does 
 
 // 3 on the prefilter route.  *M candidates of the class-sequence scan in, *M matches out, listed in a.m_pos / a.m_chunk
 // as the emit pass of k_rx_scan would have written them.
-static int prefilter_candidates(xsg_shard* s, bool outputs, ScanArgs& a, uint64_t* M) {
+static int prefilter_candidates(xsg_shard* s, bool outputs, bool want_len, ScanArgs& a, uint64_t* M) {
   xsg_ctx* c = s->ctx;
   hipStream_t st = c->stream;
   const uint64_t nchunks = s->chunks.size(), ntiles = s->ntiles;
@@ -470,9 +473,14 @@ static int prefilter_candidates(xsg_shard* s, bool outputs, ScanArgs& a, uint64_
   XSG_TRY(s->d_m_chunk.ensure(4 * std::max<uint64_t>(*M, 1)));
   r.m_pos = s->d_m_pos.as<uint64_t>();
   r.m_chunk = s->d_m_chunk.as<uint32_t>();
+  if (want_len) {  // XSG_MATCHES: the lengths k_rx_verify measured travel with the reported candidates
+    XSG_TRY(s->d_m_len.ensure(4 * std::max<uint64_t>(*M, 1)));
+    r.m_len = s->d_m_len.as<uint32_t>();
+  }
   HIP_TRY(launch_rx_compact(r, st));
   a.m_pos = r.m_pos;
   a.m_chunk = r.m_chunk;
+  a.m_len = r.m_len;
   return XSG_OK;
 }
 
@@ -589,8 +597,10 @@ static int out_line_indices(xsg_shard* s, const ScanArgs& a, LineOutArgs& o) {
   return XSG_OK;
 }
 
-// 6, XSG_LINES: lengths, global offsets and the packed bytes of every entry's line
-static int out_lines(xsg_shard* s, LineOutArgs& o) {
+// 6, XSG_LINES: lengths, global offsets and the packed bytes of every entry's line.
+// XSG_MATCHES (`matches`): the same of every entry's match -- k_match_spans instead of k_line_lengths (no newline query,
+// nothing to drop) and the short-string gather; the buffers, the pinned mirrors and the one fetched size are shared.
+static int out_lines(xsg_shard* s, LineOutArgs& o, bool matches) {
   xsg_ctx* c = s->ctx;
   hipStream_t st = c->stream;
   const uint64_t total = o.total;
@@ -598,9 +608,11 @@ static int out_lines(xsg_shard* s, LineOutArgs& o) {
   XSG_TRY(s->d_line_off.ensure(8 * (total + 1)));
   XSG_TRY(s->d_scan_tmp.ensure(8 * scan_tmp_elems(total + 1)));
   o.line_len = s->d_line_len.as<uint64_t>();
-  XSG_TRY(s->d_dropped.ensure(16));
-  o.dropped = s->d_dropped.as<uint32_t>();
-  HIP_TRY(hipMemsetAsync(o.dropped, 0, 4, st));
+  if (!matches) {
+    XSG_TRY(s->d_dropped.ensure(16));
+    o.dropped = s->d_dropped.as<uint32_t>();
+    HIP_TRY(hipMemsetAsync(o.dropped, 0, 4, st));
+  }
   // The result leaves for the shard's pinned mirrors AS IT IS PRODUCED (what xsg_result_lines_view hands out;
   // xsg_result_lines copies from there): k_line_lengths stores lengths and global offsets there as well as on the device,
   // and the gather writes the packed bytes straight into pinned memory -- the kernels are the copies.  A needle in most
@@ -618,16 +630,19 @@ static int out_lines(xsg_shard* s, LineOutArgs& o) {
     o.line_len_host = s->hp_line_len.as<uint64_t>();
     o.out_host = s->h_result.as<uint64_t>();
   }
-  HIP_TRY(launch_line_lengths(o, st));
+  HIP_TRY(matches ? launch_match_spans(o, st) : launch_line_lengths(o, st));
   HIP_TRY(launch_exclusive_scan_u64(o.line_len, s->d_line_off.as<uint64_t>(), total, s->d_scan_tmp.as<uint64_t>(), st));
   uint64_t nbytes = 0;
-  HIP_TRY(hipMemcpyAsync(&s->h_dropped, o.dropped, 4, hipMemcpyDeviceToHost, st));  // (rides on the sync below)
+  if (matches)
+    s->h_dropped = 0;
+  else
+    HIP_TRY(hipMemcpyAsync(&s->h_dropped, o.dropped, 4, hipMemcpyDeviceToHost, st));  // (rides on the sync below)
   XSG_TRY(d2h_u64(c, s->d_line_off.as<uint64_t>() + total, &nbytes));
   o.line_out_off = s->d_line_off.as<uint64_t>();
   if (!eager) {
     XSG_TRY(s->d_line_bytes.ensure(std::max<uint64_t>(nbytes, 1)));
     o.line_bytes = s->d_line_bytes.as<uint8_t>();
-    HIP_TRY(launch_line_gather(o, st));
+    HIP_TRY(launch_line_gather(o, st, matches));
     // the lengths stay on the device until a result accessor asks (fetch_line_lengths): how many lines lack their
     // newline -- all the search itself needs to know -- was counted by the kernel
     s->line_len_on_device = true;
@@ -640,7 +655,7 @@ static int out_lines(xsg_shard* s, LineOutArgs& o) {
     o.edge_units = s->d_scan_tmp.as<uint32_t>();
     o.line_bytes = nullptr;  // no device copy of the packed bytes: nothing reads one when the mirrors hold the result
     o.line_bytes_host = s->hp_line_bytes.as<uint8_t>();
-    HIP_TRY(launch_line_gather(o, st));
+    HIP_TRY(launch_line_gather(o, st, matches));
     s->fast_result = true;  // the result lives in the pinned mirrors: the accessors read it there
   }
   s->line_bytes = nbytes;
@@ -701,6 +716,10 @@ static int list_outputs(xsg_shard* s, uint32_t mode, const ScanArgs& a, ListArgs
   l.f_pos = s->d_f_pos.as<uint64_t>();
   l.f_match = s->d_f_match.as<uint64_t>();
   l.f_chunk = s->d_f_chunk.as<uint32_t>();
+  if (l.m_len) {  // XSG_MATCHES on the automaton routes
+    XSG_TRY(s->d_f_len.ensure(4 * std::max<uint64_t>(total, 1)));
+    l.f_len = s->d_f_len.as<uint32_t>();
+  }
   l.total = total;
   HIP_TRY(launch_assemble(l, st));
   const bool invert = (s->ctx->flags & XSG_FLAG_INVERT) != 0;
@@ -712,7 +731,7 @@ static int list_outputs(xsg_shard* s, uint32_t mode, const ScanArgs& a, ListArgs
   else if (mode == XSG_LINE_INDICES)
     XSG_TRY(out_line_indices(s, a, o));
   else
-    XSG_TRY(out_lines(s, o));
+    XSG_TRY(out_lines(s, o, mode == XSG_MATCHES));
   HIP_TRY(hipStreamSynchronize(st));
   if (mode == XSG_LINE_INDICES) s->nl_total = s->last_newlines;
   if (mode == XSG_LINES) s->total = total - s->h_dropped;  // lines without a terminating '\n' are not reported (search_wrappers.h:199-202)
@@ -723,10 +742,16 @@ static int list_outputs(xsg_shard* s, uint32_t mode, const ScanArgs& a, ListArgs
 int xsg::run_list(xsg_shard* s, uint32_t mode, bool outputs, bool want_nl_total, bool pre_off) {
   xsg_ctx* c = s->ctx;
   hipStream_t st = c->stream;
-  const bool line_mode = mode != XSG_MATCH_BYTE_OFFSETS;
+  // XSG_MATCHES is the walk of XSG_MATCH_BYTE_OFFSETS up to the assembled list; only what leaves it differs
+  const bool match_mode = mode == XSG_MATCH_BYTE_OFFSETS || mode == XSG_MATCHES;
+  const bool line_mode = !match_mode;
+  const bool want_len = mode == XSG_MATCHES && c->pat.kind == kDfa;  // a length per emitted match (ScanArgs::m_len)
   const bool want_nl = mode == XSG_LINE_INDICES || want_nl_total;
   const uint64_t nchunks = s->chunks.size();
   const uint64_t ntiles = s->ntiles;
+  if (want_len)  // the lengths travel as uint32: no match may reach 4 GiB (a literal's or a class sequence's cannot)
+    for (const xsg_chunk& ch : s->chunks)
+      if (ch.length >= (1ull << 32)) return fail(XSG_ENOTSUP, "XSG_MATCHES with an expression of variable length needs chunks shorter than 4 GiB");
   if (line_mode && c->pat.has_newline && !newline_literal(c)) return fail(XSG_ENOTSUP, "%s", kNewlineExprMsg);
   const bool chain_lines = line_mode && newline_literal(c);
 
@@ -737,7 +762,7 @@ int xsg::run_list(xsg_shard* s, uint32_t mode, bool outputs, bool want_nl_total,
   s->line_len_on_device = false;
   XSG_TRY(ensure_factor_mask(s));
 
-  if (mode == XSG_MATCH_BYTE_OFFSETS && c->bordered) XSG_TRY(ensure_overlap_check(s));
+  if (match_mode && c->bordered) XSG_TRY(ensure_overlap_check(s));
   // 0. a result that fits the one-sync route's capacities is done there (one stream sync, a third of the launches)
   bool counts_ready = false;
   if (fast_route_serves(s, mode, outputs, want_nl_total)) {
@@ -787,9 +812,13 @@ int xsg::run_list(xsg_shard* s, uint32_t mode, bool outputs, bool want_nl_total,
     XSG_TRY(s->d_m_chunk.ensure(4 * std::max<uint64_t>(M, 1)));
     a.m_pos = s->d_m_pos.as<uint64_t>();
     a.m_chunk = s->d_m_chunk.as<uint32_t>();
+    if (want_len) {
+      XSG_TRY(s->d_m_len.ensure(4 * std::max<uint64_t>(M, 1)));
+      a.m_len = s->d_m_len.as<uint32_t>();
+    }
     if (M) HIP_TRY(launch_scan_emit(a, st));
   } else {
-    const int pr = prefilter_candidates(s, outputs, a, &M);
+    const int pr = prefilter_candidates(s, outputs, want_len, a, &M);
     if (pr == kRedoUnfiltered) return run_list(s, mode, outputs, want_nl_total, true);
     if (pr != XSG_OK) return pr;  // (kDenseCandidates among them)
   }
@@ -820,9 +849,9 @@ int xsg::run_list(xsg_shard* s, uint32_t mode, bool outputs, bool want_nl_total,
 extern "C" int xsg_search(xsg_shard* s, uint32_t mode, uint64_t* n_results) {
   XSG_TRY(check_ready(s));
   if (mode != XSG_MATCH_BYTE_OFFSETS && mode != XSG_LINE_BYTE_OFFSETS && mode != XSG_LINE_INDICES &&
-      mode != XSG_LINES)
+      mode != XSG_LINES && mode != XSG_MATCHES)
     return fail(XSG_EINVAL, "xsg_search: mode %u is not a list mode", mode);
-  if (mode == XSG_MATCH_BYTE_OFFSETS && (s->ctx->flags & XSG_FLAG_INVERT)) return fail(XSG_ENOTSUP, "%s", kInvertMatchMsg);
+  if ((mode == XSG_MATCH_BYTE_OFFSETS || mode == XSG_MATCHES) && (s->ctx->flags & XSG_FLAG_INVERT)) return fail(XSG_ENOTSUP, "%s", kInvertMatchMsg);
   HIP_TRY(hipSetDevice(s->ctx->device));
   XSG_TRY(run_list(s, mode, true));
   if (!s->fast_result) trim_pinned(s, 8 * (size_t)s->total, 8 * (size_t)s->total, (size_t)s->line_bytes);  // (an exact-route result is still on the device)
@@ -901,7 +930,8 @@ static int fetch_line_lengths(xsg_shard* s) {
 
 static int check_lines_result(const xsg_shard* s) {
   if (!s) return fail(XSG_EINVAL, "shard is null");
-  if (s->last_mode != XSG_LINES) return fail(XSG_ESTATE, "no XSG_LINES result is pending on this shard");
+  if (s->last_mode != XSG_LINES && s->last_mode != XSG_MATCHES)
+    return fail(XSG_ESTATE, "no XSG_LINES or XSG_MATCHES result is pending on this shard");
   return XSG_OK;
 }
 
@@ -925,6 +955,17 @@ static uint64_t squeeze_dropped(const uint64_t* len, const uint64_t* off, uint64
   return k;
 }
 
+// ... for the caller of xsg_result_lines.  An XSG_MATCHES result never drops an entry: two copies, no loop over matches.
+static void copy_entries(const xsg_shard* s, const uint64_t* len, const uint64_t* off, uint64_t raw, uint64_t* len_out,
+                         uint64_t* off_out) {
+  if (s->last_mode != XSG_MATCHES) {
+    squeeze_dropped(len, off, raw, len_out, off_out);
+    return;
+  }
+  if (len_out && raw) memcpy(len_out, len, 8 * raw);
+  if (off_out && raw) memcpy(off_out, off, 8 * raw);
+}
+
 extern "C" int xsg_result_lines(xsg_shard* s, uint64_t* lengths, char* bytes, uint64_t bytes_cap, uint64_t* offsets) {
   XSG_TRY(check_lines_result(s));
   if (bytes_cap < s->line_bytes) return fail(XSG_EINVAL, "bytes_cap too small");
@@ -933,7 +974,7 @@ extern "C" int xsg_result_lines(xsg_shard* s, uint64_t* lengths, char* bytes, ui
       if (!bytes) return fail(XSG_EINVAL, "bytes is null");
       memcpy(bytes, s->hp_line_bytes.p, s->line_bytes);
     }
-    squeeze_dropped(s->hp_line_len.as<uint64_t>(), s->h_result.as<uint64_t>(), s->fast_raw_lines, lengths, offsets);
+    copy_entries(s, s->hp_line_len.as<uint64_t>(), s->h_result.as<uint64_t>(), s->fast_raw_lines, lengths, offsets);
     return XSG_OK;
   }
   xsg_ctx* c = s->ctx;
@@ -950,7 +991,7 @@ extern "C" int xsg_result_lines(xsg_shard* s, uint64_t* lengths, char* bytes, ui
     HIP_TRY(hipMemcpyAsync(bytes, s->d_line_bytes.p, s->line_bytes, hipMemcpyDeviceToHost, c->stream));
   }
   HIP_TRY(hipStreamSynchronize(c->stream));
-  squeeze_dropped(s->hp_line_len.as<uint64_t>(), goff.data(), raw, lengths, goff.empty() ? nullptr : offsets);
+  copy_entries(s, s->hp_line_len.as<uint64_t>(), goff.data(), raw, lengths, goff.empty() ? nullptr : offsets);
   return XSG_OK;
 }
 

@@ -713,6 +713,7 @@ __global__ void k_assemble(const ListArgs A) {
     A.f_pos[dst] = A.line_mode ? A.m_ls[i] : A.m_pos[i];
     A.f_match[dst] = A.m_pos[i];
     A.f_chunk[dst] = c;
+    if (A.f_len) A.f_len[dst] = A.m_len[i];  // (XSG_MATCHES on the automaton routes)
   }
   // the tail walk's matches, one thread per chunk; their line starts may lie a whole huge line back, so the
   // loop runs wave-uniformly (up to the largest count in the wave) and the wave shares long scans
@@ -977,6 +978,20 @@ __global__ __launch_bounds__(kBlock) void k_line_lengths(const LineOutArgs A) {
   }
 }
 
+// XSG_MATCHES: the span of every entry of a list assembled in match mode -- its length (what the automaton routes
+// carried along in f_len, the constant of the pattern otherwise), its global offset, and both in their pinned mirrors,
+// as k_line_lengths leaves them for a line.  No newline is looked for and nothing is ever dropped.
+__global__ __launch_bounds__(kBlock) void k_match_spans(const LineOutArgs A) {
+  const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= A.total) return;
+  const uint64_t len = A.f_len ? (uint64_t)A.f_len[i] : (uint64_t)A.pat.plen;
+  const uint64_t g = A.chunks[A.f_chunk[i]].global_offset + A.f_pos[i];
+  A.line_len[i] = len;
+  A.out_u64[i] = g;
+  if (A.line_len_host) __builtin_nontemporal_store(len, A.line_len_host + i);
+  if (A.out_host) __builtin_nontemporal_store(g, A.out_host + i);
+}
+
 // xs::lines: the bytes of every reported line, packed.  One THREAD per line: a line of text is a few dozen bytes,
 // which a lane moves with one or two 16-byte loads and stores (unaligned global accesses are native on gfx950) --
 // a wave per line, the first version, kept 64 lanes busy with 30 bytes (19 ms for the 66 M lines that contain
@@ -1171,11 +1186,15 @@ __global__ __launch_bounds__(kBlock) void k_line_gather_edges(const LineOutArgs 
   *reinterpret_cast<uint4*>(A.line_bytes_host + U) = make_uint4(w[0], w[1], w[2], w[3]);  // (the mirror holds 16 bytes beyond the result)
 }
 
-hipError_t launch_line_gather(const LineOutArgs& a, hipStream_t s) {
+// short_strings (XSG_MATCHES): always the output-centric k_line_gather_span.  Such a list was assembled in match mode,
+// so the source the kernel reads (f_pos) is where the match starts, and strings of 3-20 bytes are what its units suit:
+// the thread-per-entry k_line_gather would move nearly every one of them in its byte tail.  A match of kilobytes is a
+// run of units like any other and is filled by the whole workgroup.
+hipError_t launch_line_gather(const LineOutArgs& a, hipStream_t s, bool short_strings) {
   if (!a.total) return hipSuccess;
   const uint64_t n = a.slice_end ? a.slice_end - a.slice_begin : a.total;
   if (!n) return hipSuccess;
-  if (!a.tot_dev && (n >= (1u << 16) || !a.line_bytes)) {  // the exact route with a result worth the set-up (or only a pinned destination)
+  if (!a.tot_dev && (short_strings || n >= (1u << 16) || !a.line_bytes)) {  // the exact route with a result worth the set-up (or only a pinned destination)
     const uint64_t nwg = (n + kBlock - 1) / kBlock;
     const uint64_t blocks = std::min<uint64_t>(nwg, 1u << 20);
     hipLaunchKernelGGL(k_line_gather_span, dim3((unsigned)blocks), dim3(kBlock), 0, s, a);
@@ -1186,7 +1205,11 @@ hipError_t launch_line_gather(const LineOutArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(k_line_gather, a.tot_dev ? grid_capped(n) : grid_for(n), dim3(kBlock), 0, s, a);
   return hipGetLastError();
 }
-
+hipError_t launch_match_spans(const LineOutArgs& a, hipStream_t s) {
+  if (!a.total) return hipSuccess;
+  hipLaunchKernelGGL(k_match_spans, grid_for(a.total), dim3(kBlock), 0, s, a);
+  return hipGetLastError();
+}
 
 // ---------------------------------------------------------------------------
 // XSG_FLAG_INVERT: the complement of an assembled line list (InvertArgs, xsg_internal.h)

@@ -206,6 +206,7 @@ struct xsg_shard {
   DevBuf d_finish;  // k_count_finish scratch: 3 x kFinishBlocks partial sums, then the ticket word
   DevBuf d_tile_off, d_tile_nl_off, d_scan_tmp;
   DevBuf d_m_pos, d_m_chunk, d_m_ls, d_keep, d_keep_pre;
+  DevBuf d_m_len, d_f_len;  // XSG_MATCHES on the automaton routes: a length per emitted match / per entry of the final list
   DevBuf d_chunk_shift0, d_tail_cnt, d_tail_pos, d_tail_pre;
   DevBuf d_f_pos, d_f_match, d_f_chunk, d_out_u64, d_line_len, d_line_off, d_line_bytes, d_dropped;
   DevBuf d_inv_lo, d_inv_cnt, d_inv_off, d_inv_pos, d_inv_chunk;  // XSG_FLAG_INVERT: the complement stage (xsg_list.cpp: invert_list)
@@ -262,7 +263,7 @@ struct xsg_shard {
                      &d_keep, &d_keep_pre, &d_chunk_shift0, &d_tail_cnt, &d_tail_pos, &d_tail_pre, &d_f_pos, &d_f_match,
                      &d_f_chunk, &d_out_u64, &d_line_len, &d_line_off, &d_line_bytes, &d_dropped, &d_c_pos, &d_c_chunk, &d_c_len, &d_c_keep,
                      &d_c_pre, &d_tile_mask, &d_tot, &d_hit, &d_scan2, &d_wmask, &d_inv_lo, &d_inv_cnt,
-                     &d_inv_off, &d_inv_pos, &d_inv_chunk};
+                     &d_inv_off, &d_inv_pos, &d_inv_chunk, &d_m_len, &d_f_len};
     for (DevBuf* b : all) b->release();
     if (h_stage) (void)hipHostFree(h_stage);
     if (h_counters) (void)hipHostFree(h_counters);

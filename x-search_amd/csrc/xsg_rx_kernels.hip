@@ -90,6 +90,7 @@ __device__ __forceinline__ uint32_t rx_walk_line(const RxCtx& X, uint64_t cur, c
       if (A.m_cap == 0 || rank < A.m_cap) {
         A.m_pos[rank] = start;
         A.m_chunk[rank] = chunk;
+        if (A.m_len) A.m_len[rank] = (uint32_t)(e - start);  // (XSG_MATCHES; uniform per launch)
       }
       ++rank;
     }
@@ -172,6 +173,7 @@ __device__ __forceinline__ uint32_t rx_walk_line(const RxCtx& X, uint64_t cur, c
       if (A.m_cap == 0 || rank < A.m_cap) {  // bounded emission, as k_scan
         A.m_pos[rank] = start;
         A.m_chunk[rank] = chunk;
+        if (A.m_len) A.m_len[rank] = (uint32_t)(last_end - start);  // (XSG_MATCHES; uniform per launch)
       }
       ++rank;
     }
@@ -762,6 +764,7 @@ __global__ __launch_bounds__(kBlock) void k_rx_chunk(const ScanArgs A, const uin
       if (A.m_cap == 0 || rank < A.m_cap) {
         A.m_pos[rank] = start;
         A.m_chunk[rank] = (uint32_t)c;
+        if (A.m_len) A.m_len[rank] = (uint32_t)(last_end - start);  // (XSG_MATCHES)
       }
       ++rank;
     }
@@ -982,6 +985,7 @@ __global__ void k_rx_compact(const RxPreArgs A) {
   const uint64_t dst = A.c_pre[i];
   A.m_pos[dst] = A.c_pos[i];
   A.m_chunk[dst] = A.c_chunk[i];
+  if (A.m_len) A.m_len[dst] = A.c_len[i];  // (XSG_MATCHES: what k_rx_verify measured)
 }
 
 hipError_t launch_rx_verify_keep(const RxPreArgs& a, hipStream_t s) {

@@ -19,7 +19,7 @@ HERE = Path(__file__).resolve().parent
 OK = 0
 EINVAL, ENODEV, EHIP, ENOMEM, ENOTSUP, EIO, ESTATE = -1, -2, -3, -4, -5, -6, -7
 
-COUNT_MATCHES, COUNT_LINES, MATCH_BYTE_OFFSETS, LINE_BYTE_OFFSETS, LINE_INDICES, LINES = range(6)
+COUNT_MATCHES, COUNT_LINES, MATCH_BYTE_OFFSETS, LINE_BYTE_OFFSETS, LINE_INDICES, LINES, MATCHES = range(7)
 FLAG_EXACT_TAIL = 0x1
 FLAG_IGNORE_CASE = 0x2
 FLAG_REGEX = 0x4
@@ -147,6 +147,7 @@ def load():
         "xsg_host_count": (ci, [vp, vp, u64, ci, _u64p]),
         "xsg_host_offsets": (ci, [vp, u32, vp, u64, C.POINTER(vp), _u64p]),
         "xsg_host_lines": (ci, [vp, vp, u64, C.POINTER(vp), C.POINTER(vp), _u64p, _u64p]),
+        "xsg_host_matches": (ci, [vp, vp, u64, C.POINTER(vp), C.POINTER(vp), _u64p, _u64p]),
         "xsg_plan_chunks": (ci, [C.c_char_p, u64, C.POINTER(vp), _u64p]),
         "xsg_meta_read": (ci, [C.c_char_p, C.POINTER(C.c_int32), C.POINTER(vp), _u64p, C.POINTER(vp), _u64p]),
         "xsg_meta_write": (ci, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32, u64, u64, ci]),
@@ -187,7 +188,8 @@ EXPORTS = ["xsg_abi_version", "xsg_strerror", "xsg_last_error", "xsg_device_coun
            "xsg_count_end", "xsg_comm_unique_id", "xsg_comm_create_rank", "xsg_comm_create_local", "xsg_comm_destroy",
            "xsg_comm_size", "xsg_comm_library", "xsg_reduce_counts_async", "xsg_reduce_counts", "xsg_allgather_u64",
            "xsg_jobs_reduce_total", "xsg_device_numa", "xsg_regex_info", "xsg_regex_dfa_info", "xsg_regex_prefix", "xsg_regex_factor",
-           "xsg_result_u64_view", "xsg_shard_invalidate", "xsg_result_lines_view", "xsg_count_async_status", "xsg_codec_name"]
+           "xsg_result_u64_view", "xsg_shard_invalidate", "xsg_result_lines_view", "xsg_count_async_status", "xsg_codec_name",
+           "xsg_host_matches"]
 
 
 def _check(rc):
@@ -393,10 +395,10 @@ class Shard:
             return np.zeros(0, dtype=np.uint64)
         return np.ctypeslib.as_array(ptr, shape=(cnt.value,))
 
-    def search_lines(self):
+    def search_lines(self, mode: int = LINES):
         """-> (list of bytes, global byte offset of every line start)"""
         n = C.c_uint64(0)
-        _check(self._lib.xsg_search(self.h, LINES, C.byref(n)))
+        _check(self._lib.xsg_search(self.h, mode, C.byref(n)))
         nl, nb = C.c_uint64(0), C.c_uint64(0)
         _check(self._lib.xsg_result_lines_size(self.h, C.byref(nl), C.byref(nb)))
         lens = np.empty(nl.value, dtype=np.uint64)
@@ -411,11 +413,19 @@ class Shard:
             pos += int(ln)
         return out, offs
 
-    def search_lines_view(self):
+    def search_matches(self):
+        """-> (list of bytes: the matched text, global byte offset of every match), the matches of MATCH_BYTE_OFFSETS"""
+        return self.search_lines(MATCHES)
+
+    def search_matches_view(self):
+        """-> (lengths, packed bytes, global offsets of the matches): numpy VIEWS, as search_lines_view"""
+        return self.search_lines_view(MATCHES)
+
+    def search_lines_view(self, mode: int = LINES):
         """-> (lengths, packed bytes, global offsets of the line starts): numpy VIEWS of the shard's pinned buffers, valid
         until the next search on it; no Python object per line"""
         n = C.c_uint64(0)
-        _check(self._lib.xsg_search(self.h, LINES, C.byref(n)))
+        _check(self._lib.xsg_search(self.h, mode, C.byref(n)))
         lens, offs, nl, nb = _u64p(), _u64p(), C.c_uint64(0), C.c_uint64(0)
         data = C.c_void_p()
         _check(self._lib.xsg_result_lines_view(self.h, C.byref(lens), C.cast(C.byref(data), C.POINTER(C.c_char_p)), C.byref(offs),
@@ -625,7 +635,7 @@ class Job:
                 i += 1
 
     def _get(self, i):
-        if self.mode == LINES:
+        if self.mode in (LINES, MATCHES):
             p, n = C.c_char_p(), C.c_uint64(0)
             _check(self._lib.xsg_job_get_line(self.h, i, C.byref(p), C.byref(n)))
             return C.string_at(p, n.value)
@@ -639,7 +649,7 @@ class Job:
         if self.mode in (COUNT_MATCHES, COUNT_LINES):
             return self.total()
         n = self.total()
-        if self.mode == LINES:
+        if self.mode in (LINES, MATCHES):
             return [self._get(i) for i in range(n)]
         out = np.empty(n, dtype=np.uint64)
         if n:
