@@ -11,6 +11,8 @@
 // (searchers.h:51-53), and one shared const instance may be called from many
 // threads at once (Searcher.h:110): each concurrent call uses its own pinned
 // staging buffer, device buffer and HIP stream inside libxsg.
+// Context lines (XSG_FLAG_CONTEXT in `flags`) are CHUNK-LOCAL like everything here: the context of the line functors is
+// clipped at the edges of the chunk handed in, and nothing joins consecutive calls (xs::extern_search does, xsg.h).
 //
 // DataT: anything with data() -> convertible to const char* and size()
 // (the reference's DefaultDataC, concepts.h:17-22; xs::strtype = std::vector<char>).

@@ -35,7 +35,9 @@
 //
 // Environment: XS_DEVICE (HIP device index, default 0), XS_DEVICES ("0,1,2,3" or "all": one search fans its chunk
 // ranges out over several devices of the node, one job each, results in file order), XS_CHUNK_BYTES (target
-// chunk size without a metafile, default 16 MiB).
+// chunk size without a metafile, default 16 MiB), XS_INVERT_MATCH (1: the lines WITHOUT a match), XS_CONTEXT_BEFORE /
+// XS_CONTEXT_AFTER (context lines of line_byte_offsets, line_indices and lines, grep -B / -A, at most 4095 each; the
+// other tags ignore them; not with several devices).
 #pragma once
 
 #include <xsg.h>
@@ -193,6 +195,17 @@ inline uint32_t pattern_flags(const std::string& pattern, bool ignore_case) {
     flags |= XSG_FLAG_REGEX;
   }
   return flags;
+}
+
+// XS_CONTEXT_BEFORE / XS_CONTEXT_AFTER: XSG_FLAG_CONTEXT for the tags whose list it widens (xsg.h); every other tag
+// ignores context, as grep -c -C and grep -o -C do
+inline uint32_t context_flags(uint32_t mode) {
+  if (mode != XSG_LINE_BYTE_OFFSETS && mode != XSG_LINE_INDICES && mode != XSG_LINES) return 0u;
+  const uint64_t before = env_u64("XS_CONTEXT_BEFORE", 0), after = env_u64("XS_CONTEXT_AFTER", 0);
+  if (before > XSG_CONTEXT_MAX || after > XSG_CONTEXT_MAX)
+    throw std::invalid_argument("xs::extern_search: XS_CONTEXT_BEFORE / XS_CONTEXT_AFTER take at most " +
+                                std::to_string(XSG_CONTEXT_MAX) + " lines");
+  return XSG_FLAG_CONTEXT(before, after);
 }
 
 // an inverted search has no match tags: a non-match has no offset (xsg.h, XSG_FLAG_INVERT)
@@ -422,6 +435,8 @@ class ExternSearcher {
     o.pattern_flags = detail::pattern_flags(pattern, ignore_case);
     o.mode = detail::traits<Tag>::mode;
     detail::require_line_tag(o.pattern_flags, o.mode);
+    const uint32_t context = detail::context_flags(o.mode);
+    o.pattern_flags |= context;
     o.num_threads = num_threads < 1 ? 1 : num_threads;
     o.num_max_readers = num_max_readers < 1 ? 1 : num_max_readers;
     o.chunk_bytes = detail::env_u64("XS_CHUNK_BYTES", 16u << 20);
@@ -429,6 +444,9 @@ class ExternSearcher {
     _set.is_count = detail::traits<Tag>::is_count;
     _set.add_newline_base = o.mode == XSG_LINE_INDICES && meta == nullptr;
     const std::vector<int> devices = detail::device_list();
+    if (context != 0 && devices.size() > 1)  // the seams between the devices' chunk ranges are not stitched
+      throw std::invalid_argument("xs::extern_search: XS_CONTEXT_BEFORE / XS_CONTEXT_AFTER (context lines) are served on one "
+                                  "device only: the ranges of XS_DEVICES are searched on their own");
     try {
       if (devices.size() == 1) {
         o.device = devices[0];

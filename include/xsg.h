@@ -37,7 +37,8 @@ extern "C" {
 #endif
 
 /* 3: xsg_shard_invalidate and xsg_result_lines_view joined (round 3); 4: xsg_count_async_status joined, XSG_MAX_PATTERN
- * grew and the line tags accept a literal that contains '\n' (round 4); nothing was removed or changed in meaning */
+ * grew and the line tags accept a literal that contains '\n' (round 4); still 4: XSG_FLAG_INVERT, XSG_MATCHES,
+ * XSG_FLAG_CONTEXT and xsg_result_context_edges joined; nothing was removed or changed in meaning */
 #define XSG_ABI_VERSION 4
 
 /* ---- status codes ------------------------------------------------------- */
@@ -164,6 +165,32 @@ enum xsg_mode {
  * the device from the assembled list of matching lines (csrc/xsg_list_kernels.hip: k_invert_tile); the scan kernels
  * are the ones of the plain search. */
 #define XSG_FLAG_INVERT 0x8u
+/* Context lines (grep -B before -A after): the line-LIST tags also report the lines around every reported line.  The
+ * two counts ride in the pattern flags (bits 8-19: before, bits 20-31: after; bits 4-7 stay unknown flags, XSG_EINVAL),
+ * so they pass through xsg_set_pattern, xsg_job_opts.pattern_flags and xsg_host_searcher_create.  The macro masks: a
+ * caller that takes the numbers from a user refuses values above XSG_CONTEXT_MAX itself.  XSG_FLAG_CONTEXT(0, 0) == 0 is
+ * the plain search.  May be combined with every flag above.
+ * The lines of a chunk and their indices are the ones defined under XSG_FLAG_INVERT (index 0 is the line at offset 0).
+ * Let R be the lines XSG_LINE_BYTE_OFFSETS reports for the same pattern and the same other flags -- XSG_FLAG_INVERT
+ * included if set (context around the NON-matching lines, grep -v -C), and the default lossy end-of-chunk behaviour
+ * included.  With B = XSG_CONTEXT_BEFORE(flags), A = XSG_CONTEXT_AFTER(flags) and n the chunk's line count
+ *   C = { q : 0 <= q < n and some r in R of the same chunk has r - B <= q <= r + A },
+ * every line of C once, in file order.  A chunk is searched on its own: context is cut at the chunk's edges.
+ *   XSG_LINE_BYTE_OFFSETS  lists global_offset + start of every line of C,
+ *   XSG_LINE_INDICES       lists their indices (line bases and xsg_result_newlines as without the bits),
+ *   XSG_LINES              hands out the lines of C that are terminated, without their '\n'; a line's end is looked for
+ *                          from its start, and an unterminated last line is dropped, as always,
+ *   everything else        ignores the bits (as grep -c -C and grep -o -C do): XSG_COUNT_MATCHES, XSG_COUNT_LINES, every
+ *                          count entry point, XSG_MATCH_BYTE_OFFSETS, XSG_MATCHES.
+ * A pattern that can match '\n' is refused with XSG_ENOTSUP by xsg_set_pattern when A or B is non-zero -- the context
+ * then holds no pattern -- exactly as under XSG_FLAG_INVERT.  The host-only inspection calls (xsg_regex_check,
+ * xsg_regex_info, xsg_regex_dfa_info, xsg_regex_prefix, xsg_regex_factor) accept and ignore the bits.  The list is
+ * widened on the device behind the assembled (and possibly inverted) list (csrc/xsg_list_kernels.hip: k_context_tile),
+ * on the exact list route; the scan kernels are the ones of the plain search. */
+#define XSG_CONTEXT_MAX 4095u
+#define XSG_FLAG_CONTEXT(before, after) ((((uint32_t)(before)) & 0xfffu) << 8 | (((uint32_t)(after)) & 0xfffu) << 20)
+#define XSG_CONTEXT_BEFORE(flags) (((flags) >> 8) & 0xfffu)
+#define XSG_CONTEXT_AFTER(flags) (((flags) >> 20) & 0xfffu)
 
 /* A literal may be up to 32 KiB long (the reference's walk takes any std::string; what bounds it here is one 16-bit
  * field: the end of a tile's last match, relative to the tile, must stay below 2^16).  The scan kernel keeps the first
@@ -366,6 +393,19 @@ int xsg_result_lines_view(xsg_shard* shard, const uint64_t** lengths, const char
  * caller chain line-index bases from chunk to chunk without a second pass). */
 int xsg_result_newlines(xsg_shard* shard, uint64_t* newlines);
 
+/* What the edges of every chunk cut off under XSG_FLAG_CONTEXT: what a pipeline needs to join the results of chunks
+ * that are consecutive pieces of one text (csrc/xsg_context.h holds the seam rule the file pipeline applies).  One
+ * entry per chunk of the binding, in chunk order.  Valid after an XSG_LINE_BYTE_OFFSETS / XSG_LINE_INDICES / XSG_LINES
+ * search with non-zero context; XSG_ESTATE otherwise, XSG_EINVAL if cap_chunks is below the number of chunks. */
+typedef struct xsg_context_edge {
+  uint64_t lines;       /* lines of the chunk */
+  uint64_t first, last; /* chunk-local index of the first / last line of C (before XSG_LINES drops an unterminated
+                           one); UINT64_MAX: C is empty */
+  uint32_t open_before; /* max(0, B - index of the first line of R); 0 if R is empty */
+  uint32_t open_after;  /* max(0, A - (lines - 1 - index of the last line of R)); 0 if R is empty */
+} xsg_context_edge;
+int xsg_result_context_edges(xsg_shard* shard, xsg_context_edge* out, uint64_t cap_chunks);
+
 /* ======================================================================== */
 /* File searches: the host pipeline behind xs::extern_search                 */
 /* ======================================================================== */
@@ -382,6 +422,14 @@ int xsg_result_newlines(xsg_shard* shard, uint64_t* newlines);
  *     than num_threads + 1 chunks);
  *   - partial results are published in chunk order; a consumer may read them
  *     while the search is still running (blocking cursor below).
+ *   - under XSG_FLAG_CONTEXT a line-list job reports the context of the WHOLE searched
+ *     range, however it was cut: every chunk is searched on its own, its worker keeps
+ *     the few lines a neighbour may still want, and the seams are joined when the
+ *     partial results are published (csrc/xsg_context.h).  Context crosses ONE seam
+ *     between chunks at most: if it would reach across a whole chunk that is not the
+ *     first or last of the range, the job fails with XSG_ENOTSUP from xsg_job_join
+ *     (search with a larger chunk_bytes), never approximated.  At the ends of the
+ *     range -- of [chunk_begin, chunk_end) -- context is clipped.
  * Errors: start fails for an unreadable file / bad metafile / no device; a
  * failure inside a worker stops the job and is returned by xsg_job_join. */
 typedef struct xsg_job xsg_job;
@@ -450,7 +498,9 @@ int xsg_host_searcher_create(int device, const void* pattern, size_t plen, uint3
 void xsg_host_searcher_destroy(xsg_host_searcher* hs);
 /* search::count(data, pattern, skip_to_nl)  (search_wrappers.h:163-185) */
 int xsg_host_count(xsg_host_searcher* hs, const void* data, uint64_t len, int skip_to_nl, uint64_t* count);
-/* mode = XSG_MATCH_BYTE_OFFSETS / XSG_LINE_BYTE_OFFSETS / XSG_LINE_INDICES; *out is malloc'ed (xsg_free) */
+/* mode = XSG_MATCH_BYTE_OFFSETS / XSG_LINE_BYTE_OFFSETS / XSG_LINE_INDICES; *out is malloc'ed (xsg_free).
+ * Under XSG_FLAG_CONTEXT this seam stays chunk-local like everything it returns: the context of xsg_host_offsets and
+ * xsg_host_lines is clipped at the edges of the chunk handed in, and nothing joins consecutive calls. */
 int xsg_host_offsets(xsg_host_searcher* hs, uint32_t mode, const void* data, uint64_t len, uint64_t** out,
                      uint64_t* n);
 /* search::line (:187-207): n lines, lengths[i] bytes each, packed in *bytes; both malloc'ed (xsg_free) */

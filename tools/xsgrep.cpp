@@ -1,7 +1,7 @@
 // xsgrep -- the reference's example/grep.cpp (PATTERN FILE, -c, -i; lines 23-82)
 // on the MI355X engine, without boost::program_options.
 //
-//   xsgrep [-c] [-i] [-o] [-v] [-E|-F] [-x] [-j THREADS] [-m METAFILE] PATTERN FILE|-
+//   xsgrep [-c] [-i] [-o] [-v] [-E|-F] [-x] [-A N] [-B N] [-C N] [-j THREADS] [-m METAFILE] PATTERN FILE|-
 //
 // -c  print only a count of matching lines   (grep.cpp:45-46 -> xs::count_lines)
 // -i  ignore ASCII case                      (grep.cpp:47-48)
@@ -14,6 +14,10 @@
 //     xs::lines, a last line that lacks its newline is not printed.
 // -o  print only the matched text, every match on its own line (xs::matches -> XSG_MATCHES).  With -c the count stays
 //     the count of matching lines, as in grep.  Not with -v: a line without a match has no matched text.
+// -A N, -B N, -C N  also print N lines after / before / around every selected line (XS_CONTEXT_AFTER / XS_CONTEXT_BEFORE ->
+//     XSG_FLAG_CONTEXT), every line once, in file order, as GNU grep does with --no-group-separator: no `--` lines.
+//     N is at most 4095.  With -c or -o the numbers are accepted and change nothing, as in grep.  Not with `-` (stdin):
+//     the chunks read from a pipe are searched on their own.  (-m is the METAFILE here, not grep's --max-count.)
 // The one-letter options without an argument may be bundled (-vc, -ci, -oi).
 // otherwise print the matching lines, live, as they are found (grep.cpp:74-79).
 #include <xsearch/tasks/gpu_searchers.h>
@@ -27,7 +31,9 @@
 #include <vector>
 
 static const char kUsage[] =
-    "usage: %s [-c] [-i] [-o] [-v] [-E|-F] [-x] [-j THREADS] [-m METAFILE] PATTERN FILE|-\n"
+    "usage: %s [-c] [-i] [-o] [-v] [-E|-F] [-x] [-A N] [-B N] [-C N] [-j THREADS] [-m METAFILE] PATTERN FILE|-\n"
+    "  -A N, -B N, -C N also print N lines after / before / around every selected line (N <= 4095), each line once and\n"
+    "     without group separators; nothing changes under -c and -o; not with FILE = -\n"
     "  -o, --only-matching prints only the matched text, every match on its own line (not with -v)\n"
     "  -v, --invert-match selects the lines WITHOUT a match (with -c: counts them)\n"
     "  -x searches (?m)^(?:PATTERN)$; PATTERN must not be empty\n";
@@ -54,9 +60,17 @@ static std::string re2_literal(const std::string& p) {
   return r;
 }
 
+// N of -A / -B / -C: digits only, at most XSG_CONTEXT_MAX
+static bool context_number(const std::string& text, long* out) {
+  if (text.empty() || text.size() > 9 || text.find_first_not_of("0123456789") != std::string::npos) return false;
+  *out = std::atol(text.c_str());
+  return *out <= (long)XSG_CONTEXT_MAX;
+}
+
 int main(int argc, char** argv) {
   bool count = false, icase = false, fixed = false, extended = false, whole_lines = false, invert = false, only = false;
   int threads = 2;  // grep.cpp:21
+  long before = 0, after = 0;
   std::string meta, pattern, file;
   int pos = 0;
   std::vector<std::string> args;
@@ -85,6 +99,14 @@ int main(int argc, char** argv) {
       extended = true;
     } else if (a == "-x" || a == "--line-regexp") {
       whole_lines = true;
+    } else if ((a == "-A" || a == "-B" || a == "-C") && i + 1 < nargs) {
+      long n = 0;
+      if (!context_number(args[++i], &n)) {
+        std::fprintf(stderr, "xsgrep: %s takes a number of lines from 0 to %u, not '%s'\n", a.c_str(), (unsigned)XSG_CONTEXT_MAX, args[i].c_str());
+        return 2;
+      }
+      if (a != "-A") before = n;
+      if (a != "-B") after = n;
     } else if ((a == "-j" || a == "--threads") && i + 1 < nargs) {
       threads = std::atoi(args[++i].c_str());
     } else if ((a == "-m" || a == "--meta") && i + 1 < nargs) {
@@ -115,6 +137,11 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "xsgrep: -o and -v exclude each other (a line without a match has no matched text)\n");
     return 2;
   }
+  const bool context = (before != 0 || after != 0) && !count && !only;  // (grep -c -C and grep -o -C ignore the numbers)
+  if (context && file == "-") {
+    std::fprintf(stderr, "xsgrep: -A, -B and -C are not served on stdin: the chunks of a pipe are searched on their own\n");
+    return 2;
+  }
   if (whole_lines) {  // a line-anchored regex (xsg.h, XSG_FLAG_REGEX): the whole line is one match of PATTERN
     const std::string body = fixed ? re2_literal(pattern) : strip_edge_anchors(pattern);
     if (body.empty()) {
@@ -131,6 +158,8 @@ int main(int argc, char** argv) {
   if (fixed) setenv("XS_FORCE_LITERAL", "1", 1);
   if (extended) setenv("XS_FORCE_REGEX", "1", 1);
   if (invert) setenv("XS_INVERT_MATCH", "1", 1);
+  setenv("XS_CONTEXT_BEFORE", context ? std::to_string(before).c_str() : "0", 1);
+  setenv("XS_CONTEXT_AFTER", context ? std::to_string(after).c_str() : "0", 1);
   try {
     std::ios::sync_with_stdio(false);
     if (file == "-") {

@@ -645,7 +645,9 @@ extern "C" int xsg_scan_kernel_name(xsg_shard* s, uint32_t mode, char* out, size
   const uint32_t m = mode & 0xffu;
   const bool list = m >= XSG_MATCH_BYTE_OFFSETS;
   // what the FIRST pass of this mode launches on this shard right now (newline counts already cached -> plain kernel)
-  const bool want_nl = ((mode & XSG_WITH_NEWLINES) != 0 || m == XSG_LINE_INDICES) && !s->nl_cached;
+  const bool context = (m == XSG_LINE_BYTE_OFFSETS || m == XSG_LINE_INDICES || m == XSG_LINES) &&
+                       (XSG_CONTEXT_BEFORE(s->ctx->flags) != 0 || XSG_CONTEXT_AFTER(s->ctx->flags) != 0);
+  const bool want_nl = ((mode & XSG_WITH_NEWLINES) != 0 || m == XSG_LINE_INDICES || context) && !s->nl_cached;
   ScanArgs a = scan_args(s, scan_variant(want_nl, !list && m == XSG_COUNT_LINES));
   if (use_prefilter(s, false)) {  // what xsg_count / xsg_search launch: the candidate scan, then the automaton at candidates
     a.pat = s->ctx->pre_pat;
@@ -659,6 +661,10 @@ extern "C" int xsg_scan_kernel_name(xsg_shard* s, uint32_t mode, char* out, size
   if (inverted(s->ctx)) {  // the inverted form: the same scan, then the complement (of the list, or of the line count)
     const size_t n = strlen(out);
     snprintf(out + n, cap - n, "%s", list ? " + xsg::k_invert_tile (inverted)" : " + xsg::k_invert_count_lines (inverted)");
+  }
+  if (context) {  // the widening stage behind the assembled (or inverted) list
+    const size_t n = strlen(out);
+    snprintf(out + n, cap - n, " + xsg::k_context_tile (context)");
   }
   return XSG_OK;
 }

@@ -21,6 +21,7 @@
 #include <new>
 #include <thread>
 
+#include "xsg_context.h"
 #include "xsg_lz4.h"
 #include "xsg_objects.h"
 
@@ -457,7 +458,21 @@ struct Partial {
   bool indices_local = false;
   std::vector<uint64_t> u64;
   std::vector<std::string> lines;
+  // XSG_FLAG_CONTEXT on a line-list tag: what the chunk's edges cut off, and the lines a neighbouring chunk may still
+  // want, in the job's result form (xsg_context.h)
+  bool context = false;
+  xsg_context_edge edge{};
+  std::vector<xsg_context::Extra<uint64_t>> head_u64, tail_u64;
+  std::vector<xsg_context::Extra<std::string>> head_lines, tail_lines;
 };
+
+// The device side of XSG_FLAG_CONTEXT, reached through a weak reference: this file is also linked without the device
+// library (tests/cpp: the sanitizer binaries, against a stand-in that knows nothing of context), and a context job is
+// then refused at its start.
+extern "C" int xsg_result_context_edges(xsg_shard* shard, xsg_context_edge* out, uint64_t cap_chunks) __attribute__((weak));
+static bool context_flags(uint32_t flags) { return XSG_CONTEXT_BEFORE(flags) != 0 || XSG_CONTEXT_AFTER(flags) != 0; }
+// the tags whose list context widens (every other tag ignores the bits)
+static bool context_mode(uint32_t mode) { return mode == XSG_LINE_BYTE_OFFSETS || mode == XSG_LINE_INDICES || mode == XSG_LINES; }
 
 static std::atomic<uint64_t> g_job_serial{0};
 
@@ -502,6 +517,10 @@ struct xsg_job {
   std::deque<std::string> lines;  // XSG_LINES, XSG_MATCHES
   uint64_t total = 0;             // count so far / elements so far
   uint64_t nl_running = 0;        // '\n' in all published chunks
+  // XSG_FLAG_CONTEXT: the seams between the published chunks (xsg_context.h); spent after a refusal
+  xsg_context::Stitcher<uint64_t> stitch_u64;
+  xsg_context::Stitcher<std::string> stitch_lines;
+  bool seam_refused = false;
   bool finished = false;
   int error = XSG_OK;
   std::string errmsg;
@@ -523,13 +542,51 @@ static void job_fail(xsg_job* j, int code) {
   j->q_cv_ready.notify_all();
 }
 
-static void publish(xsg_job* j, uint64_t index, Partial&& p) {
+// A chunk's result under XSG_FLAG_CONTEXT joins the job's through the seam stitcher: the lines its neighbour's edge left
+// open come first.  The one-neighbour rule (xsg_context.h) refuses, never approximates.
+template <typename T, typename Out>
+static int publish_context(xsg_job* j, xsg_context::Stitcher<T>& st, uint64_t index, const xsg_context_edge& edge, std::vector<T>&& own,
+                           std::vector<xsg_context::Extra<T>>&& head, std::vector<xsg_context::Extra<T>>&& tail, Out* out) {
+  if (j->seam_refused) return XSG_OK;  // (the job has failed already)
+  xsg_context::Part<T> part;
+  part.edge = edge;
+  part.own = std::move(own);
+  part.head = std::move(head);
+  part.tail = std::move(tail);
+  const xsg_context::SeamVerdict v = st.add(std::move(part), index == 0, index + 1 == j->plan.size(), out);
+  if (v == xsg_context::kSeamOk) return XSG_OK;
+  j->seam_refused = true;
+  const bool before = v == xsg_context::kSeamBeforeTooFar;
+  return fail(XSG_ENOTSUP,
+              "XSG_FLAG_CONTEXT: the lines %s a match in chunk %llu reach across the whole of chunk %llu; context crosses one "
+              "seam between chunks at most: search with a larger chunk_bytes (now %llu)",
+              before ? "before" : "after", (unsigned long long)(before ? index : index - 1),
+              (unsigned long long)(before ? index - 1 : index), (unsigned long long)j->opts.chunk_bytes);
+}
+
+static int publish(xsg_job* j, uint64_t index, Partial&& p) {
   std::lock_guard<std::mutex> g(j->mu);
   j->pending.emplace(index, std::move(p));
   const uint32_t mode = j->opts.mode;
+  int rc = XSG_OK;
   for (auto it = j->pending.find(j->next_publish); it != j->pending.end(); it = j->pending.find(j->next_publish)) {
     Partial& q = it->second;
-    if (mode == XSG_COUNT_MATCHES || mode == XSG_COUNT_LINES) {
+    if (q.context) {
+      int r = XSG_OK;
+      if (is_string_mode(mode)) {
+        r = publish_context(j, j->stitch_lines, it->first, q.edge, std::move(q.lines), std::move(q.head_lines), std::move(q.tail_lines), &j->lines);
+        j->total = j->lines.size();
+      } else {
+        if (q.indices_local) {
+          for (uint64_t& v : q.u64) v += j->nl_running;
+          for (auto& e : q.head_u64) e.value += j->nl_running;
+          for (auto& e : q.tail_u64) e.value += j->nl_running;
+        }
+        r = publish_context(j, j->stitch_u64, it->first, q.edge, std::move(q.u64), std::move(q.head_u64), std::move(q.tail_u64), &j->values);
+        j->total = j->values.size();
+      }
+      if (rc == XSG_OK) rc = r;
+    } else if (mode == XSG_COUNT_MATCHES || mode == XSG_COUNT_LINES) {
       j->total += q.count;
       j->values.push_back(j->total);
     } else if (is_string_mode(mode)) {
@@ -546,6 +603,7 @@ static void publish(xsg_job* j, uint64_t index, Partial&& p) {
     ++j->next_publish;
   }
   j->cv.notify_all();
+  return rc;
 }
 
 // A pinned host buffer travelling between the two stages.
@@ -950,6 +1008,32 @@ static int bind_chunk(xsg_job* j, Lane& l, const HostBuf& hb) {
   return xsg_shard_rebind(l.shard, l.dev, l.cap, &ch, 1);
 }
 
+// XSG_FLAG_CONTEXT: the chunk's edge from the device, and from its text in the pinned buffer the lines a neighbouring
+// chunk may still want -- its first `after` lines ahead of its first reported line, its last `before` lines behind its
+// last one -- in the job's result form (xsg_context.h)
+static int context_extras(xsg_job* j, Lane& l, const HostBuf& hb, Partial& p) {
+  const xsg_file_chunk& fc = j->plan[hb.index];
+  const uint32_t mode = j->opts.mode;
+  if (!xsg_result_context_edges) return fail(XSG_ENOTSUP, "XSG_FLAG_CONTEXT: this build holds no device side for context lines");
+  XSG_TRY(xsg_result_context_edges(l.shard, &p.edge, 1));
+  p.context = true;
+  const uint8_t* d = static_cast<const uint8_t*>(hb.pinned);
+  const uint64_t len = fc.original_size;
+  const uint64_t after = XSG_CONTEXT_AFTER(j->opts.pattern_flags), before = XSG_CONTEXT_BEFORE(j->opts.pattern_flags);
+  const std::vector<xsg_context::Line> head = xsg_context::first_lines(d, len, std::min(after, xsg_context::lines_ahead(p.edge)));
+  const std::vector<xsg_context::Line> tail = xsg_context::last_lines(d, len, p.edge.lines, std::min(before, xsg_context::lines_behind(p.edge)));
+  const uint64_t index_base = fc.first_line == XSG_LINE_BASE_AUTO ? 0 : fc.first_line;  // (AUTO: the running base joins at publish)
+  for (int side = 0; side < 2; ++side) {
+    for (const xsg_context::Line& ln : side ? tail : head) {
+      if (mode == XSG_LINES)
+        (side ? p.tail_lines : p.head_lines).push_back({ln.index, std::string(reinterpret_cast<const char*>(d) + ln.start, ln.end - ln.start), ln.terminated});
+      else
+        (side ? p.tail_u64 : p.head_u64).push_back({ln.index, mode == XSG_LINE_INDICES ? index_base + ln.index : fc.original_offset + ln.start, true});
+    }
+  }
+  return XSG_OK;
+}
+
 // list tags, second half: the search on the lane whose copy was queued one chunk earlier, then publish
 static int list_collect(xsg_job* j, Lane& l, const HostBuf& hb) {
   const xsg_file_chunk& fc = j->plan[hb.index];
@@ -980,9 +1064,9 @@ static int list_collect(xsg_job* j, Lane& l, const HostBuf& hb) {
       XSG_TRY(xsg_result_newlines(l.shard, &p.newlines));
     }
   }
+  if (context_flags(j->opts.pattern_flags) && context_mode(mode)) XSG_TRY(context_extras(j, l, hb, p));
   // the search synchronised the lane's stream: its pinned buffer is free again
-  publish(j, hb.index, std::move(p));
-  return XSG_OK;
+  return publish(j, hb.index, std::move(p));
 }
 
 // count tags, first half: copy + scan of the chunk go into lane k's queue; nothing is waited for
@@ -996,8 +1080,7 @@ static int count_collect(xsg_job* j, Slot& s, int k, uint64_t index) {
   XSG_TRY(xsg_count_end(s.lane[k].shard, ctr));
   Partial p;
   p.count = ctr[j->opts.mode == XSG_COUNT_MATCHES ? XSG_CTR_MATCHES : XSG_CTR_LINES];
-  publish(j, index, std::move(p));
-  return XSG_OK;
+  return publish(j, index, std::move(p));
 }
 
 static void give_back(xsg_job* j, HostBuf* b) {
@@ -1161,16 +1244,25 @@ static int job_start_impl(const void* pattern, size_t plen, const char* file_pat
     if (!(opts->pattern_flags & XSG_FLAG_REGEX) && memchr(pattern, '\n', plen))
       return fail(XSG_ENOTSUP, "XSG_FLAG_INVERT: an inverted search does not accept a pattern that can match '\\n'");
   }
+  const bool context = context_flags(opts->pattern_flags);
+  static const char kContextNlMsg[] = "XSG_FLAG_CONTEXT: a search with context lines does not accept a pattern that can match '\\n'";
+  if (context) {  // (xsg.h: xsg_set_pattern refuses such a pattern whatever the tag; here, not in a worker)
+    if (!(opts->pattern_flags & XSG_FLAG_REGEX) && memchr(pattern, '\n', plen)) return fail(XSG_ENOTSUP, "%s", kContextNlMsg);
+    if (context_mode(opts->mode) && !xsg_result_context_edges)
+      return fail(XSG_ENOTSUP, "XSG_FLAG_CONTEXT: this build holds no device side for context lines");
+  }
   if (opts->pattern_flags & XSG_FLAG_REGEX) {  // refuse an expression the kernel cannot decide here, not in a worker
     uint32_t npos = 0;
     std::vector<uint32_t> sets(32 * 8, 0);
     XSG_TRY(xsg_regex_check(pattern, plen, opts->pattern_flags & XSG_FLAG_IGNORE_CASE, &npos, sets.data()));
-    for (uint32_t k = 0; line_mode && k < npos; ++k)
-      if (sets[8 * k] & (1u << '\n')) return fail(XSG_ENOTSUP, "line modes do not accept a pattern that can match '\\n'");
-    if (line_mode && npos == 0) {  // the automaton route: does a set of the expression accept '\n'?
+    for (uint32_t k = 0; (line_mode || context) && k < npos; ++k)
+      if (sets[8 * k] & (1u << '\n'))
+        return line_mode ? fail(XSG_ENOTSUP, "line modes do not accept a pattern that can match '\\n'") : fail(XSG_ENOTSUP, "%s", kContextNlMsg);
+    if ((line_mode || context) && npos == 0) {  // the automaton route: does a set of the expression accept '\n'?
       xsg_regex_dfa info;
       XSG_TRY(xsg_regex_dfa_info(pattern, plen, opts->pattern_flags & XSG_FLAG_IGNORE_CASE, &info, nullptr, nullptr, 0));
-      if (info.multiline) return fail(XSG_ENOTSUP, "line modes do not accept a pattern that can match '\\n'");
+      if (info.multiline)
+        return line_mode ? fail(XSG_ENOTSUP, "line modes do not accept a pattern that can match '\\n'") : fail(XSG_ENOTSUP, "%s", kContextNlMsg);
     }
   }  // (a LITERAL that contains '\n' is served by every tag since round 4: xsg.h, xsg_set_pattern)
   std::unique_ptr<xsg_job> j(new (std::nothrow) xsg_job());

@@ -384,6 +384,39 @@ hipError_t launch_invert_emit(const InvertArgs& a, hipStream_t s);   // i_pos, i
 // through.  keep_nl == 0: the caller did not ask for XSG_CTR_NEWLINES, it is zeroed again.  host_counters, status: optional
 hipError_t launch_invert_count_lines(const uint8_t* base, const ChunkDev* chunks, uint64_t nchunks, uint64_t* counters,
                                      uint64_t* host_counters, const uint64_t* status, uint32_t keep_nl, hipStream_t s);
+// ---- XSG_FLAG_CONTEXT: the widening stage (xsg_list.cpp: context_list) ----------------------------------------------
+// The assembled (and possibly inverted) list of a line tag is replaced by the list of every line start whose index lies
+// within `before` lines ahead of or `after` lines behind a reported line of the same chunk, each once, in file order.
+// The line index (rank) of every entry comes from the newline prefix of the tiles plus the near/far count of the
+// line-index passes (nl_before); k_context_spans turns the ranks into disjoint rank spans [lo, hi] per entry -- hi is
+// monotone, so the previous entry's hi follows from its rank alone -- and one prefix sum over the span lengths gives
+// every span its slots.  k_context_tile then selects: one workgroup per tile, which knows its own rank range from the
+// newline prefix, finds the spans that touch it by binary search and leaves without a load if none does.
+struct ContextArgs {
+  const uint8_t* base;
+  const ChunkDev* chunks;
+  const uint32_t* tile_chunk;   // tile -> chunk (null when the shard has one chunk)
+  const uint64_t* chunk_tile0;  // nchunks + 1 entries
+  uint64_t nchunks;
+  uint64_t ntiles;
+  uint32_t tile_bytes;
+  uint32_t before, after;
+  const uint64_t* tile_nl_off;  // exclusive prefix of the newline counts of the tiles (ntiles + 1)
+  uint64_t total;               // entries of the reported list
+  const uint64_t* r_pos;
+  const uint32_t* r_chunk;
+  const uint64_t* nl_before;    // total + 1: [i + 1] = newlines of the shard before entry i's line start
+  uint64_t* lo;                 // per entry: its span of chunk-local line indices; empty where lo > hi
+  uint64_t* hi;
+  uint32_t* cnt;                // its length
+  const uint64_t* slot;         // exclusive prefix of cnt
+  xsg_context_edge* edges;      // nchunks
+  uint64_t out_total;           // slot[total] = entries of o_pos / o_chunk
+  uint64_t* o_pos;
+  uint32_t* o_chunk;
+};
+hipError_t launch_context_spans(const ContextArgs& a, hipStream_t s);  // edges, lo, hi, cnt
+hipError_t launch_context_emit(const ContextArgs& a, hipStream_t s);   // o_pos, o_chunk
 // one empty launch per kernel file (code object): see xsg_kernels.hip
 hipError_t warm_scan_kernels(hipStream_t s);
 hipError_t warm_list_kernels(hipStream_t s);

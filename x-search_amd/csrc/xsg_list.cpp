@@ -16,6 +16,9 @@ static int d2h_u64(xsg_ctx* c, const uint64_t* d, uint64_t* h) {
   return XSG_OK;
 }
 
+// XSG_FLAG_CONTEXT with a non-zero count (the line-list tags widen their list; every other tag ignores the bits)
+static bool context_on(const xsg_ctx* c) { return XSG_CONTEXT_BEFORE(c->flags) != 0 || XSG_CONTEXT_AFTER(c->flags) != 0; }
+
 bool xsg::newline_literal(const xsg_ctx* c) { return c->pat.has_newline && c->pat.kind != kClass && c->pat.kind != kDfa; }
 
 // ---------------------------------------------------------------------------
@@ -168,6 +171,7 @@ static bool fast_route_serves(const xsg_shard* s, uint32_t mode, bool outputs, b
   if ((e && *e == '0') || !outputs || s->ntiles == 0 || want_nl_total) return false;
   if (mode == XSG_MATCHES) return false;                                // the span and gather stages sit on the exact route
   if (c->flags & XSG_FLAG_INVERT) return false;                         // the complement stage sits on the exact route
+  if (context_on(c) && mode != XSG_MATCH_BYTE_OFFSETS) return false;    // the widening stage sits on the exact route
   if (c->pat.kind == kDfa) return false;                                // k_rx_scan / the prefilter route: exact route
   if (mode != XSG_MATCH_BYTE_OFFSETS && c->pat.has_newline) return false;  // the line walk of a literal with '\n': a chain, exact route
   if (mode == XSG_MATCH_BYTE_OFFSETS && c->bordered && !overlap_free_known(s)) return false;  // greedy keep: exact route
@@ -706,6 +710,90 @@ static int invert_list(xsg_shard* s, const ScanArgs& a, ListArgs& l, uint64_t* t
   return XSG_OK;
 }
 
+// the exclusive prefix of the per-tile newline counts (a.tile_nl: the caller's count pass ran with them), once per binding
+static int ensure_tile_nl_off(xsg_shard* s, const ScanArgs& a) {
+  hipStream_t st = s->ctx->stream;
+  const uint64_t ntiles = s->ntiles;
+  bool grew = false;
+  XSG_TRY(s->d_tile_nl_off.ensure(8 * (ntiles + 1), &grew));
+  if (grew) s->nl_off_cached = false;
+  if (s->nl_off_cached) return XSG_OK;
+  XSG_TRY(s->d_scan_tmp.ensure(8 * scan_tmp_elems(ntiles + 1)));
+  HIP_TRY(launch_exclusive_scan_u32(a.tile_nl, s->d_tile_nl_off.as<uint64_t>(), ntiles, s->d_scan_tmp.as<uint64_t>(), st));
+  s->nl_off_cached = true;
+  return XSG_OK;
+}
+
+// XSG_FLAG_CONTEXT: the assembled (or inverted) list is replaced by the starts of every line within `before` lines ahead
+// of or `after` lines behind one of its lines, in the same chunk, each once; l.f_* and *total with it, and the output
+// kernels run on the new list unchanged.  Ranks of the entries (the passes of XSG_LINE_INDICES: near entries count their
+// gap, far ones their tile), spans and edges, one prefix sum, one more size from the device, then the select pass over
+// the tiles (xsg_list_kernels.hip: k_context_spans, k_context_tile).  The edges of the chunks stay on the shard for
+// xsg_result_context_edges.
+static int context_list(xsg_shard* s, const ScanArgs& a, ListArgs& l, uint64_t* total) {
+  xsg_ctx* c = s->ctx;
+  hipStream_t st = c->stream;
+  const uint64_t n_in = *total, nchunks = s->chunks.size();
+  XSG_TRY(ensure_tile_nl_off(s, a));
+  XSG_TRY(s->d_line_len.ensure(8 * std::max<uint64_t>(n_in, 1)));
+  XSG_TRY(s->d_line_off.ensure(8 * (n_in + 1)));
+  XSG_TRY(s->d_scan_tmp.ensure(8 * scan_tmp_elems(n_in + 1)));
+  XSG_TRY(s->d_cx_lo.ensure(8 * std::max<uint64_t>(n_in, 1)));
+  XSG_TRY(s->d_cx_hi.ensure(8 * std::max<uint64_t>(n_in, 1)));
+  XSG_TRY(s->d_cx_cnt.ensure(4 * std::max<uint64_t>(n_in, 1)));
+  XSG_TRY(s->d_cx_slot.ensure(8 * (n_in + 1)));
+  XSG_TRY(s->d_cx_edge.ensure(sizeof(xsg_context_edge) * std::max<uint64_t>(nchunks, 1)));
+  // 1. newlines of the shard before every entry: d_line_off[i + 1] (d_out_u64 and d_line_len are scratch here)
+  LineOutArgs o = line_out_args(s, a, l, n_in);
+  o.tile_nl_off = s->d_tile_nl_off.as<uint64_t>();
+  o.line_len = s->d_line_len.as<uint64_t>();
+  o.line_out_off = s->d_line_off.as<uint64_t>();
+  HIP_TRY(launch_line_nl_delta(o, st));
+  HIP_TRY(launch_exclusive_scan_u64(o.line_len, s->d_line_off.as<uint64_t>(), n_in, s->d_scan_tmp.as<uint64_t>(), st));
+  // 2. spans, edges, slots
+  ContextArgs x{};
+  x.base = s->base;
+  x.chunks = a.chunks;
+  x.tile_chunk = a.tile_chunk;
+  x.chunk_tile0 = a.chunk_tile0;
+  x.nchunks = nchunks;
+  x.ntiles = s->ntiles;
+  x.tile_bytes = s->tile_bytes;
+  x.before = XSG_CONTEXT_BEFORE(c->flags);
+  x.after = XSG_CONTEXT_AFTER(c->flags);
+  x.tile_nl_off = o.tile_nl_off;
+  x.total = n_in;
+  x.r_pos = l.f_pos;
+  x.r_chunk = l.f_chunk;
+  x.nl_before = s->d_line_off.as<uint64_t>();
+  x.lo = s->d_cx_lo.as<uint64_t>();
+  x.hi = s->d_cx_hi.as<uint64_t>();
+  x.cnt = s->d_cx_cnt.as<uint32_t>();
+  x.edges = s->d_cx_edge.as<xsg_context_edge>();
+  HIP_TRY(launch_context_spans(x, st));
+  HIP_TRY(launch_exclusive_scan_u32(x.cnt, s->d_cx_slot.as<uint64_t>(), n_in, s->d_scan_tmp.as<uint64_t>(), st));
+  s->context_edges.resize(nchunks);
+  if (nchunks)
+    HIP_TRY(hipMemcpyAsync(s->context_edges.data(), x.edges, sizeof(xsg_context_edge) * nchunks, hipMemcpyDeviceToHost, st));
+  uint64_t n = 0;
+  XSG_TRY(d2h_u64(c, s->d_cx_slot.as<uint64_t>() + n_in, &n));
+  // 3. the starts whose rank lies in a span, at their slots
+  XSG_TRY(s->d_cx_pos.ensure(8 * std::max<uint64_t>(n, 1)));
+  XSG_TRY(s->d_cx_chunk.ensure(4 * std::max<uint64_t>(n, 1)));
+  XSG_TRY(s->d_out_u64.ensure(8 * std::max<uint64_t>(n, 1)));
+  x.slot = s->d_cx_slot.as<uint64_t>();
+  x.out_total = n;
+  x.o_pos = s->d_cx_pos.as<uint64_t>();
+  x.o_chunk = s->d_cx_chunk.as<uint32_t>();
+  HIP_TRY(launch_context_emit(x, st));
+  l.f_pos = x.o_pos;
+  l.f_match = x.o_pos;  // (most of these lines hold no match: LineOutArgs::invert keeps the output kernels away from it)
+  l.f_chunk = x.o_chunk;
+  l.total = n;
+  *total = s->total = n;
+  return XSG_OK;
+}
+
 // 6. the final list of `total` entries, in file order, in the form the tag asks for
 static int list_outputs(xsg_shard* s, uint32_t mode, const ScanArgs& a, ListArgs& l, uint64_t total) {
   hipStream_t st = s->ctx->stream;
@@ -724,8 +812,10 @@ static int list_outputs(xsg_shard* s, uint32_t mode, const ScanArgs& a, ListArgs
   HIP_TRY(launch_assemble(l, st));
   const bool invert = (s->ctx->flags & XSG_FLAG_INVERT) != 0;
   if (invert) XSG_TRY(invert_list(s, a, l, &total));
+  const bool context = context_on(s->ctx) && mode != XSG_MATCH_BYTE_OFFSETS && mode != XSG_MATCHES;
+  if (context) XSG_TRY(context_list(s, a, l, &total));
   LineOutArgs o = line_out_args(s, a, l, total);
-  o.invert = invert ? 1u : 0u;
+  o.invert = invert || context ? 1u : 0u;
   if (mode == XSG_MATCH_BYTE_OFFSETS || mode == XSG_LINE_BYTE_OFFSETS)
     HIP_TRY(launch_globalize(o, st));
   else if (mode == XSG_LINE_INDICES)
@@ -736,6 +826,7 @@ static int list_outputs(xsg_shard* s, uint32_t mode, const ScanArgs& a, ListArgs
   if (mode == XSG_LINE_INDICES) s->nl_total = s->last_newlines;
   if (mode == XSG_LINES) s->total = total - s->h_dropped;  // lines without a terminating '\n' are not reported (search_wrappers.h:199-202)
   s->last_mode = (int)mode;
+  s->context_edges_valid = context;
   return XSG_OK;
 }
 
@@ -746,7 +837,8 @@ int xsg::run_list(xsg_shard* s, uint32_t mode, bool outputs, bool want_nl_total,
   const bool match_mode = mode == XSG_MATCH_BYTE_OFFSETS || mode == XSG_MATCHES;
   const bool line_mode = !match_mode;
   const bool want_len = mode == XSG_MATCHES && c->pat.kind == kDfa;  // a length per emitted match (ScanArgs::m_len)
-  const bool want_nl = mode == XSG_LINE_INDICES || want_nl_total;
+  // (the widening stage of XSG_FLAG_CONTEXT ranks lines by the per-tile newline counts)
+  const bool want_nl = mode == XSG_LINE_INDICES || want_nl_total || (outputs && line_mode && context_on(c));
   const uint64_t nchunks = s->chunks.size();
   const uint64_t ntiles = s->ntiles;
   if (want_len)  // the lengths travel as uint32: no match may reach 4 GiB (a literal's or a class sequence's cannot)
@@ -756,6 +848,7 @@ int xsg::run_list(xsg_shard* s, uint32_t mode, bool outputs, bool want_nl_total,
   const bool chain_lines = line_mode && newline_literal(c);
 
   s->last_mode = -1;
+  s->context_edges_valid = false;
   s->total = 0;
   s->line_bytes = 0;
   s->fast_result = false;
@@ -912,6 +1005,17 @@ extern "C" int xsg_result_newlines(xsg_shard* s, uint64_t* newlines) {
   if (!s || !newlines) return fail(XSG_EINVAL, "null argument");
   if (s->last_mode != XSG_LINE_INDICES) return fail(XSG_ESTATE, "no XSG_LINE_INDICES result is pending on this shard");
   *newlines = s->last_newlines;
+  return XSG_OK;
+}
+
+extern "C" int xsg_result_context_edges(xsg_shard* s, xsg_context_edge* out, uint64_t cap_chunks) {
+  if (!s) return fail(XSG_EINVAL, "shard is null");
+  if (!s->context_edges_valid || (s->last_mode != XSG_LINE_BYTE_OFFSETS && s->last_mode != XSG_LINE_INDICES && s->last_mode != XSG_LINES))
+    return fail(XSG_ESTATE, "no line-list result of a search with XSG_FLAG_CONTEXT is pending on this shard");
+  const uint64_t n = s->context_edges.size();
+  if (cap_chunks < n) return fail(XSG_EINVAL, "cap_chunks %llu < %llu chunks", (unsigned long long)cap_chunks, (unsigned long long)n);
+  if (n && !out) return fail(XSG_EINVAL, "out is null");
+  if (n) memcpy(out, s->context_edges.data(), sizeof(xsg_context_edge) * n);
   return XSG_OK;
 }
 

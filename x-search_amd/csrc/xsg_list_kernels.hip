@@ -1370,6 +1370,176 @@ hipError_t launch_invert_count_lines(const uint8_t* base, const ChunkDev* chunks
 }
 
 
+// ---------------------------------------------------------------------------
+// XSG_FLAG_CONTEXT: the lines around the reported ones (ContextArgs, xsg_internal.h)
+// ---------------------------------------------------------------------------
+// lines of chunk c: one at offset 0 if it has a byte, one behind every '\n' that is not its last byte
+__device__ __forceinline__ uint64_t context_chunk_lines(const ContextArgs& A, uint32_t c) {
+  const ChunkDev ch = A.chunks[c];
+  if (ch.length == 0) return 0;
+  const uint64_t nl = A.tile_nl_off[A.chunk_tile0[c + 1]] - A.tile_nl_off[A.chunk_tile0[c]];
+  return nl + 1u - (A.base[ch.offset + ch.length - 1] == '\n' ? 1u : 0u);
+}
+
+// one thread per chunk: the edge of a chunk in which nothing is reported (k_context_spans overwrites the others)
+__global__ void k_context_edges(const ContextArgs A) {
+  const uint64_t c = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (c >= A.nchunks) return;
+  xsg_context_edge e;
+  e.lines = context_chunk_lines(A, (uint32_t)c);
+  e.first = UINT64_MAX;
+  e.last = UINT64_MAX;
+  e.open_before = 0u;
+  e.open_after = 0u;
+  A.edges[c] = e;
+}
+
+// one thread per entry: its span of line indices, cut at the chunk's edges and behind the previous entry's span
+__global__ void k_context_spans(const ContextArgs A) {
+  const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= A.total) return;
+  const uint32_t c = A.r_chunk[i];
+  const uint64_t off0 = A.tile_nl_off[A.chunk_tile0[c]];
+  const uint64_t n = context_chunk_lines(A, c);  // (>= 1: the chunk holds a reported line)
+  const uint64_t r = A.nl_before[i + 1] - off0;
+  const uint64_t hi = r + A.after < n - 1u ? r + A.after : n - 1u;
+  uint64_t lo = r > A.before ? r - A.before : 0u;
+  if (i > 0 && A.r_chunk[i - 1] == c) {
+    const uint64_t rp = A.nl_before[i] - off0;
+    const uint64_t hip = rp + A.after < n - 1u ? rp + A.after : n - 1u;
+    if (lo < hip + 1u) lo = hip + 1u;
+  } else {
+    A.edges[c].first = lo;
+    A.edges[c].open_before = A.before > r ? (uint32_t)(A.before - r) : 0u;
+  }
+  A.lo[i] = lo;
+  A.hi[i] = hi;
+  A.cnt[i] = hi >= lo ? (uint32_t)(hi - lo + 1u) : 0u;
+  if (i + 1 == A.total || A.r_chunk[i + 1] != c) {
+    const uint64_t behind = n - 1u - r;
+    A.edges[c].last = hi;
+    A.edges[c].open_after = A.after > behind ? (uint32_t)(A.after - behind) : 0u;
+  }
+}
+
+// the last span of [j0, j1) whose lo is at most q (j0 if there is none): the only one that can hold rank q
+__device__ __forceinline__ uint64_t context_span_of(const ContextArgs& A, uint64_t j0, uint64_t j1, uint64_t q) {
+  uint64_t a = j0, b = j1;  // invariant: lo[a] <= q or a == j0; lo[b] > q or b == j1
+  while (a + 1 < b) {
+    const uint64_t mid = (a + b) >> 1;
+    if (A.lo[mid] <= q) a = mid; else b = mid;
+  }
+  return a;
+}
+__device__ __forceinline__ void context_store(const ContextArgs& A, uint64_t j, uint64_t q, uint64_t pos, uint32_t c) {
+  const uint64_t lo = A.lo[j];
+  if (q < lo || q > A.hi[j]) return;
+  const uint64_t r = A.slot[j] + (q - lo);
+  if (r < A.out_total) {  // (by construction; the arrays hold out_total entries)
+    A.o_pos[r] = pos;
+    A.o_chunk[r] = c;
+  }
+}
+
+// One workgroup per tile.  The ranks of the line starts a tile owns (see the invert stage) follow from the newline prefix:
+// [n0, n1] = newlines of the chunk before the tile / before its end, less rank n0 if the tile's first byte opens no line
+// and rank n1 if its last byte is a '\n' (that line starts in the next tile, or nowhere).  The spans that meet this range
+// are a run [j0, j1) of the entries, found by two binary searches over the monotone hi / lo; an empty run leaves without
+// reading the tile.  Otherwise every wave reads its quarter of the tile once in coalesced 16-byte loads, the rank of the
+// start behind every '\n' is n0 + the popcount prefix (DPP per wave-load, LDS across waves), and a start whose rank lies
+// in a span goes to that span's slot -- the slots are known before the tile is read, so there is no count pass.
+__global__ __launch_bounds__(kBlock) void k_context_tile(const ContextArgs A) {
+  __shared__ uint32_t s_wave[kWaves];
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const uint32_t tb = A.tile_bytes;
+  const uint32_t span = tb / kWaves;
+  const int steps = (int)(span / kWaveLoad);
+  for (uint64_t t = blockIdx.x; t < A.ntiles; t += gridDim.x) {  // (workgroup-uniform, and so is every `continue`)
+    const uint32_t c = A.tile_chunk ? A.tile_chunk[t] : 0u;
+    const ChunkDev ch = A.chunks[c];
+    const uint8_t* d = A.base + ch.offset;
+    const uint64_t begin = (t - A.chunk_tile0[c]) * tb;
+    if (begin >= ch.length) continue;
+    const uint64_t end = begin + tb < ch.length ? begin + tb : ch.length;
+    const uint64_t off0 = A.tile_nl_off[A.chunk_tile0[c]];
+    const uint64_t n0 = A.tile_nl_off[t] - off0, n1 = A.tile_nl_off[t + 1] - off0;
+    const bool first = begin == 0 || d[begin - 1] == '\n';
+    const uint64_t rank_lo = n0 + (first ? 0u : 1u);
+    if (d[end - 1] == '\n' && n1 == 0) continue;  // (cannot be: that newline is counted)
+    const uint64_t rank_hi = n1 - (d[end - 1] == '\n' ? 1u : 0u);
+    if (rank_lo > rank_hi) continue;
+    uint64_t j0 = 0, j1 = A.total;
+    for (uint64_t b = A.total; j0 < b;) {  // the first entry of chunk c or behind whose hi reaches rank_lo
+      const uint64_t mid = (j0 + b) >> 1;
+      const uint32_t mc = A.r_chunk[mid];
+      if (mc < c || (mc == c && A.hi[mid] < rank_lo)) j0 = mid + 1; else b = mid;
+    }
+    for (uint64_t a = j0; a < j1;) {  // the first entry behind chunk c, or of it with lo behind rank_hi
+      const uint64_t mid = (a + j1) >> 1;
+      const uint32_t mc = A.r_chunk[mid];
+      if (mc < c || (mc == c && A.lo[mid] <= rank_hi)) a = mid + 1; else j1 = mid;
+    }
+    if (j0 >= j1) continue;  // no span meets the tile: nothing of it is read
+    uint32_t m[kInvMaxSteps], ex[kInvMaxSteps];
+    uint32_t wtot = 0;
+#pragma unroll
+    for (int k = 0; k < kInvMaxSteps; ++k) {
+      m[k] = 0u;
+      ex[k] = 0u;
+      if (k < steps) {  // (wave-uniform)
+        const uint64_t u = begin + (uint64_t)wave * span + (uint64_t)k * kWaveLoad + (uint64_t)lane * kUnit;
+        if (u < end) {  // the unit lies inside the chunk's padded length
+          const uint4 v = *reinterpret_cast<const uint4*>(d + u);
+          const uint32_t dw[8] = {v.x, v.y, v.z, v.w, 0u, 0u, 0u, 0u};
+          uint32_t nl = nl_mask16(dw) & 0xffffu;
+          const uint64_t room = end - u - 1u;  // a '\n' at byte b opens a line of this tile iff u + b + 1 < end
+          if (room < 16u) nl &= (1u << room) - 1u;
+          m[k] = nl;
+        }
+        const uint32_t p = (uint32_t)__popc(m[k]);
+        const uint32_t incl = wave_incl_scan_u32(p, lane);
+        ex[k] = wtot + incl - p;
+        wtot += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+      }
+    }
+    if (lane == 0) s_wave[wave] = wtot;
+    __syncthreads();
+    uint32_t wbase = 0;
+#pragma unroll
+    for (int w = 0; w < kWaves; ++w)
+      if ((uint32_t)w < wave) wbase += s_wave[w];
+    if (first && threadIdx.x == 0) context_store(A, context_span_of(A, j0, j1, n0), n0, begin, c);
+#pragma unroll
+    for (int k = 0; k < kInvMaxSteps; ++k) {
+      if (k < steps && m[k]) {
+        const uint64_t u = begin + (uint64_t)wave * span + (uint64_t)k * kWaveLoad + (uint64_t)lane * kUnit;
+        uint64_t q = n0 + wbase + ex[k];  // newlines of the chunk before this unit: the next start has rank q + 1
+        uint64_t j = context_span_of(A, j0, j1, q + 1u);
+        for (uint32_t mm = m[k]; mm; mm &= mm - 1u) {
+          ++q;
+          while (j + 1 < j1 && A.lo[j + 1] <= q) ++j;  // (ranks ascend inside a unit: the span only moves forward)
+          context_store(A, j, q, u + (uint32_t)__builtin_ctz(mm) + 1u, c);
+        }
+      }
+    }
+    __syncthreads();  // (the next round re-uses the wave totals)
+  }
+}
+
+hipError_t launch_context_spans(const ContextArgs& a, hipStream_t s) {
+  if (a.nchunks) hipLaunchKernelGGL(k_context_edges, grid_for(a.nchunks), dim3(kBlock), 0, s, a);
+  if (a.total) hipLaunchKernelGGL(k_context_spans, grid_for(a.total), dim3(kBlock), 0, s, a);
+  return hipGetLastError();
+}
+hipError_t launch_context_emit(const ContextArgs& a, hipStream_t s) {
+  if (a.tile_bytes > kInvMaxTile || a.tile_bytes % (kWaves * kWaveLoad)) return hipErrorInvalidValue;
+  if (!a.ntiles || !a.out_total) return hipSuccess;
+  hipLaunchKernelGGL(k_context_tile, invert_grid(a.ntiles), dim3(kBlock), 0, s, a);
+  return hipGetLastError();
+}
+
+
 // Loading a code object costs milliseconds the first time one of its kernels is launched: xsg_ctx_create launches this
 // empty kernel of every kernel file, so that the first search of a process does not pay for it (5.5 ms of the first
 // xsg_count, scripts/first_call.py).

@@ -210,6 +210,10 @@ struct xsg_shard {
   DevBuf d_chunk_shift0, d_tail_cnt, d_tail_pos, d_tail_pre;
   DevBuf d_f_pos, d_f_match, d_f_chunk, d_out_u64, d_line_len, d_line_off, d_line_bytes, d_dropped;
   DevBuf d_inv_lo, d_inv_cnt, d_inv_off, d_inv_pos, d_inv_chunk;  // XSG_FLAG_INVERT: the complement stage (xsg_list.cpp: invert_list)
+  // XSG_FLAG_CONTEXT: the widening stage (xsg_list.cpp: context_list)
+  DevBuf d_cx_lo, d_cx_hi, d_cx_cnt, d_cx_slot, d_cx_pos, d_cx_chunk, d_cx_edge;
+  std::vector<xsg_context_edge> context_edges;  // ... the edges of the last search with context, one per chunk
+  bool context_edges_valid = false;             // ... which was the last search on this shard (xsg_result_context_edges)
   DevBuf d_c_pos, d_c_chunk, d_c_len, d_c_keep, d_c_pre;  // prefilter route of kDfa: the candidates
   DevBuf d_tile_mask;             // factor prefilter of kDfa: tiles in which a line with a factor occurrence starts
   uint64_t mask_serial = 0;       // ... valid for this ctx->pattern_serial on this binding (0: not built)
@@ -263,7 +267,8 @@ struct xsg_shard {
                      &d_keep, &d_keep_pre, &d_chunk_shift0, &d_tail_cnt, &d_tail_pos, &d_tail_pre, &d_f_pos, &d_f_match,
                      &d_f_chunk, &d_out_u64, &d_line_len, &d_line_off, &d_line_bytes, &d_dropped, &d_c_pos, &d_c_chunk, &d_c_len, &d_c_keep,
                      &d_c_pre, &d_tile_mask, &d_tot, &d_hit, &d_scan2, &d_wmask, &d_inv_lo, &d_inv_cnt,
-                     &d_inv_off, &d_inv_pos, &d_inv_chunk, &d_m_len, &d_f_len};
+                     &d_inv_off, &d_inv_pos, &d_inv_chunk, &d_m_len, &d_f_len, &d_cx_lo, &d_cx_hi, &d_cx_cnt,
+                     &d_cx_slot, &d_cx_pos, &d_cx_chunk, &d_cx_edge};
     for (DevBuf* b : all) b->release();
     if (h_stage) (void)hipHostFree(h_stage);
     if (h_counters) (void)hipHostFree(h_counters);

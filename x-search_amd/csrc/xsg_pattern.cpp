@@ -13,7 +13,7 @@
 
 using namespace xsg;
 
-static int set_pattern_plain(xsg_ctx* c, const void* pattern, size_t plen, uint32_t flags);  // xsg_set_pattern without XSG_FLAG_INVERT
+static int set_pattern_plain(xsg_ctx* c, const void* pattern, size_t plen, uint32_t flags);  // xsg_set_pattern without XSG_FLAG_INVERT / XSG_FLAG_CONTEXT
 
 static uint32_t le32(const uint8_t* p, size_t n) {
   uint32_t v = 0;
@@ -446,19 +446,23 @@ extern "C" int xsg_regex_info(const void* expr, size_t n, uint32_t flags, uint32
   return XSG_OK;
 }
 
-// XSG_FLAG_INVERT is not a property of the compiled pattern (PatternDev and the scan kernels never see it): the pattern
-// is set without it, refused if it can match '\n' (the line such a match belongs to is not a line of the chunk), and
-// the flag is kept on the context, where the list and count routes read it.
+// XSG_FLAG_INVERT and the context counts of XSG_FLAG_CONTEXT are not properties of the compiled pattern (PatternDev and the
+// scan kernels never see them): the pattern is set without them, refused if it can match '\n' (the line such a match
+// belongs to is not a line of the chunk), and the bits are kept on the context, where the list and count routes read them.
+constexpr uint32_t kContextBits = 0xffffff00u;  // XSG_FLAG_CONTEXT(before, after): bits 8-19 and 20-31
 extern "C" int xsg_set_pattern(xsg_ctx* c, const void* pattern, size_t plen, uint32_t flags) {
-  if (!(flags & XSG_FLAG_INVERT) || !c) return set_pattern_plain(c, pattern, plen, flags);
-  if (flags & ~(XSG_FLAG_EXACT_TAIL | XSG_FLAG_IGNORE_CASE | XSG_FLAG_REGEX | XSG_FLAG_INVERT))
+  const uint32_t list_bits = flags & (XSG_FLAG_INVERT | kContextBits);
+  if (!list_bits || !c) return set_pattern_plain(c, pattern, plen, flags);
+  if (flags & ~(XSG_FLAG_EXACT_TAIL | XSG_FLAG_IGNORE_CASE | XSG_FLAG_REGEX | XSG_FLAG_INVERT | kContextBits))
     return fail(XSG_EINVAL, "unknown pattern flags 0x%x", flags);
-  XSG_TRY(set_pattern_plain(c, pattern, plen, flags & ~XSG_FLAG_INVERT));
+  XSG_TRY(set_pattern_plain(c, pattern, plen, flags & ~list_bits));
   if (c->pat.has_newline) {
     c->pattern.clear();  // no pattern is set: a search now says so instead of running the plain form
-    return fail(XSG_ENOTSUP, "XSG_FLAG_INVERT: an inverted search does not accept a pattern that can match '\\n'");
+    if (flags & XSG_FLAG_INVERT)
+      return fail(XSG_ENOTSUP, "XSG_FLAG_INVERT: an inverted search does not accept a pattern that can match '\\n'");
+    return fail(XSG_ENOTSUP, "XSG_FLAG_CONTEXT: a search with context lines does not accept a pattern that can match '\\n'");
   }
-  c->flags |= XSG_FLAG_INVERT;
+  c->flags |= list_bits;
   return XSG_OK;
 }
 

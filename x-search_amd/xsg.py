@@ -24,6 +24,7 @@ FLAG_EXACT_TAIL = 0x1
 FLAG_IGNORE_CASE = 0x2
 FLAG_REGEX = 0x4
 FLAG_INVERT = 0x8  # the line tags report the lines WITHOUT a match (grep -v); the match tags are refused
+CONTEXT_MAX = 4095  # XSG_CONTEXT_MAX: the largest number of context lines either way
 WITH_NEWLINES = 0x100
 CTR_MATCHES, CTR_LINES, CTR_NEWLINES, CTR_BYTES = range(4)
 NUM_COUNTERS = 4
@@ -34,6 +35,9 @@ STATUS_OK, STATUS_OVERFLOW, STATUS_NONASCII = 0, 1, 2
 TILE = 16384
 
 CHUNK_DTYPE = np.dtype([("offset", "<u8"), ("length", "<u8"), ("global_offset", "<u8"), ("line_base", "<u8")])
+
+# xsg_context_edge: what a chunk's edges cut off under flag_context (xsg.h)
+CONTEXT_EDGE_DTYPE = np.dtype([("lines", "<u8"), ("first", "<u8"), ("last", "<u8"), ("open_before", "<u4"), ("open_after", "<u4")])
 
 _u64p = C.POINTER(C.c_uint64)
 
@@ -132,6 +136,7 @@ def load():
         "xsg_result_lines": (ci, [vp, _u64p, vp, u64, _u64p]),
         "xsg_result_lines_view": (ci, [vp, C.POINTER(_u64p), C.POINTER(C.c_char_p), C.POINTER(_u64p), _u64p, _u64p]),
         "xsg_result_newlines": (ci, [vp, _u64p]),
+        "xsg_result_context_edges": (ci, [vp, vp, u64]),
         "xsg_job_opts_init": (None, [C.POINTER(JobOpts)]),
         "xsg_job_start": (ci, [C.c_char_p, sz, C.c_char_p, C.c_char_p, C.POINTER(JobOpts), C.POINTER(vp)]),
         "xsg_job_join": (ci, [vp]),
@@ -189,12 +194,28 @@ EXPORTS = ["xsg_abi_version", "xsg_strerror", "xsg_last_error", "xsg_device_coun
            "xsg_comm_size", "xsg_comm_library", "xsg_reduce_counts_async", "xsg_reduce_counts", "xsg_allgather_u64",
            "xsg_jobs_reduce_total", "xsg_device_numa", "xsg_regex_info", "xsg_regex_dfa_info", "xsg_regex_prefix", "xsg_regex_factor",
            "xsg_result_u64_view", "xsg_shard_invalidate", "xsg_result_lines_view", "xsg_count_async_status", "xsg_codec_name",
-           "xsg_host_matches"]
+           "xsg_host_matches", "xsg_result_context_edges"]
 
 
 def _check(rc):
     if rc != OK:
         raise XsgError(rc, load().xsg_last_error().decode("utf-8", "replace"))
+
+
+def flag_context(before: int, after: int) -> int:
+    """XSG_FLAG_CONTEXT(before, after): the pattern-flag bits that add `before` lines ahead of and `after` lines behind
+    every reported line to the line-list tags (grep -B / -A).  OR it into the other flags."""
+    if not (0 <= before <= CONTEXT_MAX and 0 <= after <= CONTEXT_MAX):
+        raise ValueError(f"context lines must be 0..{CONTEXT_MAX}, got ({before}, {after})")
+    return (before & 0xfff) << 8 | (after & 0xfff) << 20
+
+
+def context_before(flags: int) -> int:
+    return (flags >> 8) & 0xfff
+
+
+def context_after(flags: int) -> int:
+    return (flags >> 20) & 0xfff
 
 
 def regex_check(expr: bytes, flags: int = 0):
@@ -383,6 +404,12 @@ class Shard:
         _check(self._lib.xsg_search(self.h, mode, C.byref(n)))
         out = np.empty(n.value, dtype=np.uint64)
         _check(self._lib.xsg_result_u64(self.h, out.ctypes.data_as(_u64p), n.value))
+        return out
+
+    def context_edges(self) -> np.ndarray:
+        """after a line-list search with flag_context: one CONTEXT_EDGE_DTYPE record per chunk (xsg_result_context_edges)"""
+        out = np.zeros(self.nchunks, dtype=CONTEXT_EDGE_DTYPE)
+        _check(self._lib.xsg_result_context_edges(self.h, out.ctypes.data, self.nchunks))
         return out
 
     def search_u64_view(self, mode: int) -> np.ndarray:
