@@ -308,6 +308,23 @@ static int set_dfa_pattern(xsg_ctx* c, const uint8_t* re, size_t n, uint32_t fla
   return XSG_OK;
 }
 
+// Where set_class_pattern sends an expression the class-sequence compiler took (and what xsg_test_class_fields answers for):
+// (?m)^BODY$ with a fixed-length BODY goes to the automaton route, whose line walks decide the anchors; one alternative
+// of single bytes (`a\.b`) is an ordinary literal (*lit), minus the reference's scalar-tail quirk (RE2 has none); the rest
+// is class_fields'.
+enum ClassRoute { kRouteClass, kRouteAutomaton, kRouteLiteral };
+static ClassRoute class_route(const xsg::ClassExpr& ex, const std::vector<xsg::ByteSet>& seq, std::vector<uint8_t>* lit) {
+  if (ex.anchor_begin || ex.anchor_end) return kRouteAutomaton;
+  bool literal = ex.alts.size() == 1;
+  lit->assign(seq.size(), 0);
+  for (size_t k = 0; k < seq.size(); ++k) {
+    const int b = xsg::set_single(seq[k]);
+    literal &= b >= 0;
+    (*lit)[k] = (uint8_t)(b >= 0 ? b : 0);
+  }
+  return literal ? kRouteLiteral : kRouteClass;
+}
+
 // XSG_FLAG_REGEX: a fixed-length class sequence (xsg_classseq.h).  RE2 has no lossy tail, so the
 // matching is exact up to the end of the chunk (as with XSG_FLAG_EXACT_TAIL).
 static int set_class_pattern(xsg_ctx* c, const uint8_t* re, size_t n, uint32_t flags) {
@@ -315,19 +332,14 @@ static int set_class_pattern(xsg_ctx* c, const uint8_t* re, size_t n, uint32_t f
   std::string err;
   const bool icase = (flags & XSG_FLAG_IGNORE_CASE) != 0;
   if (!xsg::compile_class_expr(re, n, icase, &ex, &err)) return set_dfa_pattern(c, re, n, flags, err);
-  // (?m)^BODY$ with a fixed-length BODY: the anchors are decided by the line walks of the automaton route
-  if (ex.anchor_begin || ex.anchor_end) return set_dfa_pattern(c, re, n, flags, "line anchors");
   const size_t plen = ex.npos;
   const std::vector<xsg::ByteSet> seq = xsg::union_sets(ex);  // what the filter, the overlap and '\n' tests look at
-  bool literal = ex.alts.size() == 1;
-  std::vector<uint8_t> lit(plen);
-  for (size_t k = 0; k < plen; ++k) {
-    const int b = xsg::set_single(seq[k]);
-    literal &= b >= 0;
-    lit[k] = (uint8_t)(b >= 0 ? b : 0);
+  std::vector<uint8_t> lit;
+  switch (class_route(ex, seq, &lit)) {
+    case kRouteAutomaton: return set_dfa_pattern(c, re, n, flags, "line anchors");
+    case kRouteLiteral: return set_pattern_plain(c, lit.data(), plen, (flags & XSG_FLAG_IGNORE_CASE) | XSG_FLAG_EXACT_TAIL);
+    case kRouteClass: break;
   }
-  if (literal)  // e.g. `a\.b`: an ordinary literal, minus the reference's scalar-tail quirk (RE2 has none)
-    return set_pattern_plain(c, lit.data(), plen, (flags & XSG_FLAG_IGNORE_CASE) | XSG_FLAG_EXACT_TAIL);
 
   HIP_TRY(hipSetDevice(c->device));
   c->pattern.assign(re, re + n);
@@ -443,6 +455,34 @@ extern "C" int xsg_regex_info(const void* expr, size_t n, uint32_t flags, uint32
   if (sets)
     for (size_t a = 0; a < ex.alts.size(); ++a)
       memcpy(sets + a * ex.npos * 8, ex.alts[a].data(), ex.npos * sizeof(xsg::ByteSet));
+  return XSG_OK;
+}
+
+// XSG_TEST_HOOKS=1 only (not part of include/xsg.h): what class_fields decides for an expression -- the fields k_scan
+// picks its verification path from -- without a device: out[] = plen, nalt, koff, cls_fast, cls_inreg, cls_exact, cls_chk,
+// ascii_only, has_newline, m0, m1, p0, p1 (as many as `cap` holds).  XSG_ENOTSUP for an expression that set_class_pattern
+// does not hand to class_fields: the automaton route's, and a plain literal (which becomes an ordinary pattern).
+extern "C" int xsg_test_class_fields(const void* expr, size_t n, uint32_t flags, uint32_t* out, size_t cap) {
+  if (!test_hooks()) return fail(XSG_ENOTSUP, "xsg_test_class_fields needs XSG_TEST_HOOKS=1");
+  if (!out) return fail(XSG_EINVAL, "out is null");
+  XSG_TRY(check_expr(expr, n));
+  xsg::ClassExpr ex;
+  std::string err;
+  const bool icase = (flags & XSG_FLAG_IGNORE_CASE) != 0;
+  if (!xsg::compile_class_expr(static_cast<const uint8_t*>(expr), n, icase, &ex, &err))
+    return fail(XSG_ENOTSUP, "not a class sequence: %s", err.c_str());
+  std::vector<uint8_t> lit;
+  switch (class_route(ex, xsg::union_sets(ex), &lit)) {  // as set_class_pattern routes it
+    case kRouteAutomaton: return fail(XSG_ENOTSUP, "not a class sequence: line anchors");
+    case kRouteLiteral: return fail(XSG_ENOTSUP, "a literal: searched as an ordinary pattern");
+    case kRouteClass: break;
+  }
+  PatternDev P;
+  std::vector<uint8_t> blob;
+  class_fields(ex, icase, &P, &blob);
+  const uint32_t v[] = {P.plen, P.nalt, P.koff, P.cls_fast, P.cls_inreg, P.cls_exact, P.cls_chk,
+                        P.ascii_only, P.has_newline, P.m0, P.m1, P.p0, P.p1};
+  for (size_t i = 0; i < cap && i < sizeof v / sizeof v[0]; ++i) out[i] = v[i];
   return XSG_OK;
 }
 
