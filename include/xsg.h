@@ -296,9 +296,18 @@ int xsg_regex_factor(const void* expr, size_t n, uint32_t flags, uint32_t* posit
 /* ---- shards ---------------------------------------------------------------- */
 /* d_base/capacity: device memory owned by the caller (hipMalloc, a torch
  * tensor's data_ptr(), ...), must stay valid, and its BYTES ARE IMMUTABLE FOR THE LIFETIME OF THE BINDING: the library
- * keeps results derived from them per binding (newline counts per tile, the measured hot filter and filter window of
- * a pattern, the tile marks and density verdicts of the regex prefilters, whether a pattern's lists fit the one-sync
- * route) and every later pass -- the stream-ordered xsg_count_async included -- relies on them.  A caller that refills
+ * keeps results derived from them per binding (newline counts per tile, the 4-gram sketch of every tile and whether
+ * its gate pays for a pattern, the measured hot filter and filter window of a pattern, the tile marks and density
+ * verdicts of the regex prefilters, whether a pattern's lists fit the one-sync route) and every later pass -- the
+ * stream-ordered xsg_count_async included -- relies on them.
+ * The sketch is 512 bytes of device memory per 16 KiB tile (3.1 % of the text; a binding simply goes without if the
+ * allocation fails): one bit per hashed 4-gram that starts in the tile.  It does not depend on the pattern.  The plain
+ * count pass of a case-sensitive literal of 4 bytes and more -- xsg_count, xsg_count_begin, xsg_count_async, the count
+ * pass of xsg_search -- then leaves every tile whose sketch lacks one of the needle's grams without reading it; a needle
+ * whose grams are words of the text passes everywhere and keeps the full scan.  Bindings of 64 MiB and more get it from
+ * xsg_shard_tune, or from the second such pass of a synchronous entry point (the build is enqueued on the context's
+ * stream); xsg_count_async on a caller's stream never builds, it uses what is there.  XSG_SKETCH=0 switches the feature
+ * off, XSG_SKETCH=1 builds before the first pass.  A caller that refills
  * the buffer in place calls xsg_shard_rebind (same pointer and table are fine) or xsg_shard_invalidate before the
  * next search; searching rewritten bytes under an old binding can silently lose matches.
  * Requirements: d_base 16-byte aligned; for every chunk offset % 16 == 0 and
@@ -601,11 +610,15 @@ int xsg_ctx_info(xsg_ctx* ctx, char* arch, size_t arch_cap, int* compute_units, 
  * returns the average milliseconds per launch (bench.py's roofline figure). */
 int xsg_time_scan_kernel(xsg_shard* shard, uint32_t mode, int iters, float* avg_ms);
 /* Name of the bulk-kernel instantiation the next pass of `mode` launches on this shard with the current pattern
- * ("xsg::k_scan<KIND, WANT_NL, WANT_LINES, EMIT, LOADS, ICASE> stagger=N"): what a profile of that pass shows. */
+ * ("xsg::k_scan<KIND, WANT_NL, WANT_LINES, EMIT, LOADS, ICASE> stagger=N"): what a profile of that pass shows.
+ * " gated by xsg::k_sketch (512 B/tile)" follows when that pass would run behind the binding's sketch. */
 int xsg_scan_kernel_name(xsg_shard* shard, uint32_t mode, char* out, size_t cap);
 /* Measure and fix the bulk kernel's wave stagger for this shard, the current pattern and `mode` (a handful of
  * launches; replaces the per-variant default until the shard is destroyed or tuned again).  *chosen (optional)
- * receives the value, or UINT32_MAX when the default was kept (shard under 1 GiB, or XSG_TUNE set). */
+ * receives the value, or UINT32_MAX when the default was kept (shard under 1 GiB, or XSG_TUNE set).
+ * A caller that tunes is investing in the binding: for a plain count mode and a pattern the sketch serves, the
+ * binding's sketch is built first (bindings of 64 MiB and more: about two full scans' worth of time, once), and the
+ * sweep then times the kernel the later passes launch, gated where the gate pays. */
 int xsg_shard_tune(xsg_shard* shard, uint32_t mode, uint32_t* chosen);
 /* (The read-only HBM probes of round 1 -- xsg_time_read_ceiling and friends -- moved to libxsg_diag.so,
  * x-search_amd/csrc/diag/xsg_diag.hip: the product library holds search code only.) */

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "xsg_host.h"
+#include "xsg_sketch.h"
 
 using namespace xsg;
 
@@ -39,7 +40,103 @@ ScanArgs xsg::scan_args(xsg_shard* s, uint32_t variant) {
   a.flags = reinterpret_cast<uint32_t*>(s->d_finish.as<uint64_t>() + 3 * (size_t)kFinishBlocks) + 1;  // behind the ticket
   a.tile_mask = (a.pat.kind == kDfa && s->mask_serial != 0 && s->mask_serial == s->ctx->pattern_serial)
                     ? s->d_tile_mask.as<uint32_t>() : nullptr;
+  // the gate: the sketch of these bytes, unless a verdict for this pattern and window says it does not pay (a pass
+  // without a verdict -- xsg_count_async ahead of any synchronous call -- gates: a wrong guess costs the sketch's 3 %)
+  const bool verdict = s->gate_serial == s->ctx->pattern_serial && s->gate_koff == a.pat.koff;
+  if (sketch_ready(s) && (!verdict || s->gate_on)) sketch_fields(s, &a);
   return a;
+}
+
+// ---- the per-tile 4-gram sketch of a binding and the gate of the plain count pass (xsg_sketch.h) ------------------------
+static bool sketch_enabled() {
+  const char* e = XSG_TOGGLE("XSG_SKETCH");
+  return !(e && *e == '0');
+}
+// the context's pattern is one the gate serves: a case-sensitive literal of 4 bytes and more
+static bool sketch_pattern(const xsg_ctx* c) {
+  const uint32_t k = c->pat.kind;
+  return (k == kOne || k == kMask2 || k == kTwo || k == kLong) && !c->pat.icase && c->sketch_hashes.size() + 3 == c->pat.plen;
+}
+bool xsg::sketch_ready(const xsg_shard* s) {
+  return s->sketch_tiles != 0 && s->sketch_tiles == s->ntiles && s->d_sketch.p && sketch_enabled() && sketch_pattern(s->ctx);
+}
+// The pattern's bits as (word, mask) pairs, one per distinct word of a tile's sketch: the grams at the pattern offsets
+// koff .. min(plen - 4, koff + 28), koff = the filter window of `a->pat` -- k_scan counts an occurrence in the tile its
+// WINDOW starts in.
+void xsg::sketch_fields(const xsg_shard* s, ScanArgs* a) {
+  const xsg_ctx* c = s->ctx;
+  const uint32_t first = a->pat.koff, n = sketch_pattern_grams(a->pat.plen, first);
+  if (n == 0 || first + n > c->sketch_hashes.size()) return;
+  uint32_t used = 0;
+  for (uint32_t g = 0; g < n; ++g) {
+    const uint32_t h = c->sketch_hashes[first + g], w = h >> 5, bit = 1u << (h & 31u);
+    uint32_t k = 0;
+    while (k < used && a->sk_word[k] != w) ++k;
+    if (k == used) a->sk_word[used] = w, a->sk_mask[used] = 0u, ++used;
+    a->sk_mask[k] |= bit;
+  }
+  for (; used & 7u; ++used) a->sk_word[used] = a->sk_word[0], a->sk_mask[used] = 0u;  // groups of eight loads
+  a->sk_n = used;
+  a->sketch = s->d_sketch.as<uint32_t>();
+  a->sk_pat = a->pat.d_pat;
+  a->sk_koff = first;
+}
+
+static int build_sketch(xsg_shard* s) {
+  xsg_ctx* c = s->ctx;
+  if (s->sketch_refused || s->ntiles == 0 || s->tile_bytes != kSketchTileBytes) return XSG_OK;
+  if (s->d_sketch.ensure((size_t)s->ntiles * (kSketchBits / 8)) != XSG_OK) {
+    s->sketch_refused = true;  // no memory for it: this binding simply has no sketch
+    return XSG_OK;
+  }
+  SketchArgs b{};
+  b.base = s->base;
+  b.chunks = s->d_chunks.as<ChunkDev>();
+  b.tile_chunk = s->chunks.size() > 1 ? s->d_tile_chunk.as<uint32_t>() : nullptr;
+  b.chunk_tile0 = s->d_chunk_tile0.as<uint64_t>();
+  b.ntiles = s->ntiles;
+  b.sketch = s->d_sketch.as<uint32_t>();
+  HIP_TRY(launch_sketch_build(b, c->stream));
+  // a pass on a caller's stream must find it complete: the event that orders the chunk table orders the sketch as well
+  HIP_TRY(hipEventRecord(s->table_ev, c->stream));
+  s->table_pending = true;
+  s->sketch_tiles = s->ntiles;
+  s->gate_serial = 0;
+  return XSG_OK;
+}
+
+int xsg::sketch_before_pass(xsg_shard* s, hipStream_t st, bool plain, bool may_sync, bool counts) {
+  xsg_ctx* c = s->ctx;
+  if (!plain || !may_sync || st != c->stream || !sketch_enabled() || !sketch_pattern(c)) return XSG_OK;
+  if (s->sketch_tiles != s->ntiles && s->total_bytes >= c->sketch_min_bytes) {
+    // a synchronous entry point builds before its SECOND eligible pass over a binding (the file pipeline re-binds per
+    // chunk and must not pay); XSG_SKETCH=1: before the first; xsg_shard_tune: at once (counts == false, forced there)
+    const char* e = XSG_TOGGLE("XSG_SKETCH");
+    if (counts && (++s->sketch_passes >= 2u || (e && *e == '1'))) XSG_TRY(build_sketch(s));
+  }
+  if (!sketch_ready(s)) return XSG_OK;
+  if (s->gate_serial == c->pattern_serial && s->gate_koff == scan_args(s).pat.koff) return XSG_OK;
+  // The verdict for (binding, pattern, window): the pattern's bits against a strided sample of about 4096 tiles' sketches.
+  // A needle whose grams are words of the text passes nearly everywhere and the gate would only add its reads: it is
+  // used where fewer than a quarter of the sampled tiles pass.
+  ScanArgs a = scan_args(s);
+  s->gate_serial = c->pattern_serial;
+  s->gate_koff = a.pat.koff;
+  s->gate_on = false;
+  if (!a.sketch) sketch_fields(s, &a);
+  if (!a.sketch) return XSG_OK;
+  const uint64_t stride = std::max<uint64_t>(1, s->ntiles / 4096);
+  const uint32_t nsamp = (uint32_t)((s->ntiles + stride - 1) / stride);
+  uint32_t* word = reinterpret_cast<uint32_t*>(s->d_finish.as<uint64_t>() + 3 * (size_t)kFinishBlocks) + 2;  // behind ticket and flags
+  uint32_t passed = 0;
+  HIP_TRY(hipMemsetAsync(word, 0, 4, st));
+  HIP_TRY(launch_sketch_sample(a, stride, nsamp, word, st));
+  HIP_TRY(hipMemcpyAsync(&passed, word, 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  s->gate_on = (uint64_t)passed * 4u < nsamp;
+  static const bool probe_log = getenv("XSG_PROBE_LOG") != nullptr;
+  if (probe_log) fprintf(stderr, "[xsg] sketch gate: %u of %u sampled tiles pass -> %s\n", passed, nsamp, s->gate_on ? "on" : "off");
+  return XSG_OK;
 }
 
 int xsg::check_ready(xsg_shard* s) {
@@ -192,6 +289,7 @@ int xsg::choose_hot_filter(xsg_shard* s, hipStream_t st, bool want_nl, bool want
       window_fields(c->pattern.data(), c->pattern.size(), koff, &a.pat);
       a.pat.hot = 0;
       a.tune = 0;
+      a.sketch = nullptr;  // (the probes measure the filters on the text itself, not the gate in front of them)
       a.ntiles = std::min<uint64_t>(a.ntiles, 65536);
       float t = 0;
       const hipError_t e = time_scan(a, true, false, true, 1, st, ev, &t);  // warm-up, then one timed launch
@@ -216,6 +314,7 @@ int xsg::choose_hot_filter(xsg_shard* s, hipStream_t st, bool want_nl, bool want
     for (uint32_t hot = 0; hot < 2 && rc == XSG_OK; ++hot) {
       ScanArgs a = scan_args(s);
       a.pat.hot = hot;
+      a.sketch = nullptr;
       // (with the wave stagger the variant's real launches use: round 3 timed with the stagger off, which is how the
       // newline-counting variant runs anyway -- but count_lines runs with 16, and there the aligned trigger wins by 3.7 %
       // where it ties with the stagger off: profiles/r04_dense_variants.txt)
@@ -253,6 +352,7 @@ int xsg::choose_hot_filter(xsg_shard* s, hipStream_t st, bool want_nl, bool want
         ScanArgs a = scan_args(s);
         a.pat.hot = s->hot_v[v];
         a.tune = cand[k];
+        a.sketch = nullptr;
         a.ntiles = std::min<uint64_t>(a.ntiles, 131072);
         float t = 0;
         const hipError_t e = time_scan(a, false, false, round == 0, 1, st, ev, &t);
@@ -285,7 +385,7 @@ int xsg::choose_hot_filter(xsg_shard* s, hipStream_t st, bool want_nl, bool want
 
 static int enqueue_count(xsg_shard* s, bool want_matches, bool want_lines, bool want_nl, hipStream_t st,
                          uint64_t* d_counters, uint64_t* host_counters, const PatternDev* other_pattern = nullptr,
-                         uint64_t* d_status = nullptr) {
+                         uint64_t* d_status = nullptr, bool may_sync = true) {
   if (want_nl) XSG_TRY(ensure_tile_nl(s));
   const uint64_t nchunks = s->chunks.size();
   // kDfa: k_rx_scan counts matching lines directly into tile_cnt (a line is one lane's work): no line summaries
@@ -293,10 +393,12 @@ static int enqueue_count(xsg_shard* s, bool want_matches, bool want_lines, bool 
   if (rx_lines) want_lines = false;
   const bool scan_nl = want_nl && !s->nl_cached;  // the per-tile newline counts of this binding may already exist
   if (!other_pattern) XSG_TRY(choose_hot_filter(s, st, scan_nl, want_lines));  // measured for the variant this pass launches
+  if (!other_pattern) XSG_TRY(sketch_before_pass(s, st, !scan_nl && !want_lines, may_sync, true));
   XSG_TRY(prepare_tiles(s, want_lines, st));
   ScanArgs a = scan_args(s, scan_variant(scan_nl, want_lines));
   if (other_pattern) {  // (ensure_overlap_check: a word derived from the ctx's pattern, nothing measured or remembered for it)
     a.pat = *other_pattern;
+    a.sketch = nullptr;
     a.dense_hint = 0;
     if (s->tune_serial != 0) a.tune = kTuneAuto;
   }
@@ -392,7 +494,7 @@ int xsg::ensure_overlap_check(xsg_shard* s) {
 static int enqueue_count_bordered(xsg_shard* s, hipStream_t st, uint64_t* d_counters, uint64_t* d_status) {
   const uint64_t nchunks = s->chunks.size();
   const uint64_t ntiles = s->ntiles;
-  XSG_TRY(choose_hot_filter(s, st));
+  XSG_TRY(choose_hot_filter(s, st));  // (stream-ordered entry point: the sketch and the gate's verdict are used as they are)
   XSG_TRY(prepare_tiles(s, false, st));
   ScanArgs a = scan_args(s);
   s->cnt_clean = false;  // the tile counts stay for the emit pass
@@ -477,14 +579,14 @@ static int count_async_impl(xsg_shard* s, uint32_t mode, void* stream, uint64_t*
         return fail(XSG_ENOTSUP, "pattern can overlap itself: XSG_WITH_NEWLINES next to its match count needs xsg_count()");
       return enqueue_count_bordered(s, st, d_counters, d_status);
     }
-    return enqueue_count(s, true, false, want_nl, st, d_counters, nullptr, nullptr, d_status);
+    return enqueue_count(s, true, false, want_nl, st, d_counters, nullptr, nullptr, d_status, false);
   }
   if (m == XSG_COUNT_LINES) {
     if (c->pat.has_newline)
       return fail(XSG_ENOTSUP, "count_lines of a pattern that contains '\\n' walks a chain of occurrences: the stream-ordered entry "
                                "point does not serve it, xsg_count() does");
-    if (!inverted(c)) return enqueue_count(s, false, true, want_nl, st, d_counters, nullptr, nullptr, d_status);
-    XSG_TRY(enqueue_count(s, false, true, true, st, d_counters, nullptr, nullptr, d_status));
+    if (!inverted(c)) return enqueue_count(s, false, true, want_nl, st, d_counters, nullptr, nullptr, d_status, false);
+    XSG_TRY(enqueue_count(s, false, true, true, st, d_counters, nullptr, nullptr, d_status, false));
     return enqueue_invert_lines(s, st, d_counters, nullptr, d_status, want_nl);
   }
   return fail(XSG_EINVAL, "xsg_count_async: mode %u is not a count mode", m);
@@ -626,6 +728,7 @@ extern "C" int xsg_time_scan_kernel(xsg_shard* s, uint32_t mode, int iters, floa
   const bool want_lines = m == XSG_COUNT_LINES;
   if (want_nl) XSG_TRY(ensure_tile_nl(s));
   XSG_TRY(choose_hot_filter(s, c->stream, want_nl, want_lines));  // time what a real pass of this mode would launch
+  XSG_TRY(sketch_before_pass(s, c->stream, !want_nl && !want_lines, true, false));  // (its verdict; a timing loop builds none)
   XSG_TRY(prepare_tiles(s, want_lines, c->stream));
   ScanArgs a = scan_args(s, scan_variant(want_nl, want_lines));
   a.lines_only = want_lines;  // XSG_COUNT_LINES: what xsg_count launches for it (enqueue_count)
@@ -680,6 +783,13 @@ extern "C" int xsg_shard_tune(xsg_shard* s, uint32_t mode, uint32_t* chosen) {
   s->tune_serial = 0;  // (0: the candidate values set inside the loop below apply whatever the serial)
   s->tune_probe = false;
   if (chosen) *chosen = kTuneAuto;
+  // The caller is investing in this binding: its sketch is built now (bindings under the sketch's own size limit keep
+  // none), ahead of the sweep, which then times the kernel the real passes launch -- gated where the gate pays.
+  if (sketch_enabled() && sketch_pattern(c) && (mode & XSG_WITH_NEWLINES) == 0 && (mode & 0xffu) != XSG_COUNT_LINES &&
+      s->sketch_tiles != s->ntiles && s->total_bytes >= c->sketch_min_bytes) {
+    XSG_TRY(build_sketch(s));
+    XSG_TRY(sketch_before_pass(s, c->stream, true, true, false));
+  }
   if (c->tune != kTuneAuto || s->total_bytes < (1ull << 30)) return XSG_OK;  // XSG_TUNE wins; too small to measure
   if (c->pat.kind == kDfa) return XSG_OK;  // k_rx_scan has no stagger
   static const uint32_t cand[] = {0, 4, 8, 10, 12, 14, 16, 20};

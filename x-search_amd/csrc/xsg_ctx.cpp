@@ -115,6 +115,7 @@ extern "C" int xsg_ctx_create(int device, xsg_ctx** out) {
   if (const char* tn = getenv("XSG_TUNE")) c->tune = (uint32_t)strtoul(tn, nullptr, 0);
   if (const char* hf = getenv("XSG_HOT")) c->hot_env = (*hf == '0' || *hf == '1') ? *hf - '0' : -1;
   if (const char* pm = getenv("XSG_PROBE_MIN_BYTES")) c->probe_min_bytes = strtoull(pm, nullptr, 0);
+  if (const char* sm = getenv("XSG_SKETCH_MIN_BYTES")) c->sketch_min_bytes = strtoull(sm, nullptr, 0);
   if (const char* tk = getenv("XSG_TILE_KIB")) {
     const int v = atoi(tk);
     if (v == 16) c->tile_bytes = (uint32_t)v * 1024u;

@@ -20,6 +20,12 @@ ScanArgs scan_args(xsg_shard* s, uint32_t variant = 0);
 int prepare_tiles(xsg_shard* s, bool want_lines, hipStream_t st);
 int ensure_tile_nl(xsg_shard* s);
 int choose_hot_filter(xsg_shard* s, hipStream_t st, bool want_nl = false, bool want_lines = false);
+// Ahead of a pass with the context's own pattern, behind choose_hot_filter: builds the binding's sketch where it is due
+// (`counts`: the pass is one of a synchronous entry point, which builds before its second) and takes the gate's verdict
+// for (binding, pattern).  `may_sync` false (xsg_count_async): neither -- the pass uses what exists.
+int sketch_before_pass(xsg_shard* s, hipStream_t st, bool plain, bool may_sync, bool counts);
+bool sketch_ready(const xsg_shard* s);                  // the binding holds a sketch and the context's pattern has a gate
+void sketch_fields(const xsg_shard* s, ScanArgs* a);    // ScanArgs::sketch, sk_* for a->pat's filter window
 int ensure_overlap_check(xsg_shard* s);
 bool overlap_free_known(const xsg_shard* s);
 

@@ -133,7 +133,34 @@ struct ScanArgs {
   // followed by an emit pass over the hit list (null otherwise), read and cleared by that emit pass; a stale bit is
   // harmless (the wave reads its 4 KiB and finds nothing), so the array is only ever zeroed when it is (re)allocated
   uint32_t* tile_wmask;
+  // The gate of the plain count pass (k_scan<..., GATED>): the binding's per-tile 4-gram sketch (xsg_sketch.h; null: none, or
+  // not to be used for this pattern here) and the pattern's bits in it, one entry per distinct word of the tile's 128
+  // (sk_n entries, a multiple of 8, padded with mask 0).  A workgroup whose tile lacks one of the bits leaves before it
+  // loads any text.  sk_pat / sk_koff say which pattern and filter window the entries were computed for: launch_scan gates
+  // only a pass whose `pat` is still that one (callers put other patterns and windows into a copy of these arguments).
+  const uint32_t* sketch;
+  const uint8_t* sk_pat;
+  uint32_t sk_koff;
+  uint32_t sk_n;
+  uint32_t sk_word[32];
+  uint32_t sk_mask[32];
 };
+
+// k_sketch_build: one workgroup per tile, 512 B per tile (xsg_sketch.h)
+struct SketchArgs {
+  const uint8_t* base;
+  const ChunkDev* chunks;
+  const uint32_t* tile_chunk;   // tile -> chunk (null when the shard has one chunk)
+  const uint64_t* chunk_tile0;
+  uint64_t ntiles;
+  uint32_t* sketch;             // ntiles x kSketchWords
+};
+hipError_t launch_sketch_build(const SketchArgs& a, hipStream_t s);
+// k_sketch_sample: *passed += the number of tiles among 0, stride, 2 * stride, ... (nsamp of them, all < ntiles) whose
+// sketch holds every bit of a.sk_word / a.sk_mask -- what share of the tiles the gate of this pattern would let through
+hipError_t launch_sketch_sample(const ScanArgs& a, uint64_t stride, uint32_t nsamp, uint32_t* passed, hipStream_t s);
+// would launch_scan_count run the gated instantiation for these arguments?
+bool scan_gated(const ScanArgs& a, bool want_nl, bool want_lines);
 
 constexpr int kFinishBlocks = 2048;  // upper bound of k_count_finish's grid (size of FinishArgs::partials / 3)
 

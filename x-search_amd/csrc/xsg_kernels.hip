@@ -22,10 +22,12 @@
 // summaries) lives in a wave-uniform slow path.
 #include <algorithm>
 #include <cstdlib>
+#include <cstring>
 #include <type_traits>
 
 #include "xsg_devutil.h"
 #include "xsg_linesum.h"
+#include "xsg_sketch.h"
 #include "xsg_tail.h"
 
 namespace xsg {
@@ -756,7 +758,7 @@ __device__ __forceinline__ uint32_t scan_load(const uint4 cur, const uint4 nx, b
 // summaries.  EMIT=true: the same decisions, writing every match offset at its
 // rank (tile_off[tile] + rank inside the tile).
 // ---------------------------------------------------------------------------
-template <int KIND, bool WANT_NL, bool WANT_LINES, bool EMIT, int LOADS, bool ICASE, bool ALIGNED>
+template <int KIND, bool WANT_NL, bool WANT_LINES, bool EMIT, int LOADS, bool ICASE, bool ALIGNED, bool GATED = false>
 __device__ __forceinline__ void scan_tile(const ScanArgs& A, const uint64_t tile) {
   constexpr int kLoads = LOADS;                          // 16-byte units per lane
   constexpr uint32_t kWaveSpan = kWaveLoad * kLoads;     // contiguous bytes per wave
@@ -768,6 +770,24 @@ __device__ __forceinline__ void scan_tile(const ScanArgs& A, const uint64_t tile
   __shared__ __attribute__((aligned(16))) uint8_t s_view[is_cls(KIND) ? kBlock * 48 : 16];  // match_mask16<kClass>
 
   if (tile >= A.ntiles) return;
+  if (GATED) {
+    // The gate (xsg_sketch.h): an occurrence counted in this tile has the hash bit of each of its first grams in the
+    // tile's sketch.  The pattern's bits arrive as (word, mask) pairs, one per distinct word, padded to groups of eight
+    // whose loads are in flight together; everything here is wave-uniform and all four waves decide alike.  A tile that
+    // lacks a bit is left before the stagger and before any text is requested, and without a store: "nothing found" is
+    // the rest state of the per-tile arrays.
+    const uint32_t* sk = A.sketch + tile * kSketchWords;
+    uint32_t miss = 0;
+    for (uint32_t i = 0; i < A.sk_n; i += 8u) {
+      uint32_t v[8];
+#pragma unroll
+      for (uint32_t k = 0; k < 8u; ++k) v[k] = sk[A.sk_word[i + k]];
+      __builtin_amdgcn_sched_barrier(0);  // (eight scalar loads, one wait: left alone the scheduler pairs them off, a round trip per pair)
+#pragma unroll
+      for (uint32_t k = 0; k < 8u; ++k) miss |= ~v[k] & A.sk_mask[i + k];
+    }
+    if (miss != 0) return;
+  }
   // (a tile from the hit list holds a match by construction: no look at its count -- the emit pass over a sparse list
   // is a chain of dependent memory round trips per tile, 2048 tiles resident at a time, and this was one of them)
   if (EMIT && !A.hit_tiles && A.tile_cnt[tile] == 0) return;
@@ -1063,7 +1083,7 @@ __device__ __forceinline__ void scan_tile(const ScanArgs& A, const uint64_t tile
 // instead of 8; `amdgpu_waves_per_eu(8, 8)` brings them to 78 SGPRs and a dozen more spills.  Three builds, two
 // interleaved rounds on one box, 50 GiB: no gain for `She[r ]lock` (5.29 against 5.36 TB/s), a loss for `[Ss]herlock`
 // and `[0-9]{4}-[0-9]{2}` (6.50 against 6.88, 6.52 against 6.94): not adopted.  scripts/ab_waves.sh.)
-template <int KIND, bool WANT_NL, bool WANT_LINES, bool EMIT, int LOADS, bool ICASE, bool ALIGNED>
+template <int KIND, bool WANT_NL, bool WANT_LINES, bool EMIT, int LOADS, bool ICASE, bool ALIGNED, bool GATED = false>
 __global__ __launch_bounds__(kBlock) void k_scan(const ScanArgs A) {
   if (EMIT) {
     if (A.hit_tiles) {
@@ -1079,13 +1099,28 @@ __global__ __launch_bounds__(kBlock) void k_scan(const ScanArgs A) {
       return;
     }
   }
-  scan_tile<KIND, WANT_NL, WANT_LINES, EMIT, LOADS, ICASE, ALIGNED>(A, (uint64_t)blockIdx.x + (uint64_t)blockIdx.y * gridDim.x);
+  scan_tile<KIND, WANT_NL, WANT_LINES, EMIT, LOADS, ICASE, ALIGNED, GATED>(A, (uint64_t)blockIdx.x + (uint64_t)blockIdx.y * gridDim.x);
+}
+
+// The plain count pass may run gated by the binding's sketch: literals of 4 bytes and more, case-sensitive, no newline
+// counts and no line summaries (those passes have something to write for every tile), and only while the arguments still
+// hold the pattern and filter window the sketch entries were computed for (scan_args).
+static bool gate_kind(uint32_t kind) { return kind == kOne || kind == kMask2 || kind == kTwo || kind == kLong; }
+static bool gate_applies(const ScanArgs& a, bool want_nl, bool want_lines, bool emit) {
+  return a.sketch != nullptr && a.sk_n != 0 && !emit && !want_nl && !want_lines && gate_kind(a.pat.kind) && !a.pat.icase &&
+         a.sk_pat == a.pat.d_pat && a.sk_koff == a.pat.koff;
 }
 
 template <int KIND, bool ICASE, bool ALIGNED>
 static hipError_t launch_scan_kind(const ScanArgs& a, bool want_nl, bool want_lines, bool emit, dim3 grid,
                                    hipStream_t s) {
   constexpr int LOADS = 4;  // 16 KiB tiles (32 KiB measured 8 % slower)
+  if constexpr (!ICASE && (KIND == kOne || KIND == kMask2 || KIND == kTwo || KIND == kLong)) {
+    if (gate_applies(a, want_nl, want_lines, emit)) {
+      hipLaunchKernelGGL((k_scan<KIND, false, false, false, LOADS, ICASE, ALIGNED, true>), grid, dim3(kBlock), 0, s, a);
+      return hipGetLastError();
+    }
+  }
 #define KSCAN_LAUNCH(NL, LINES, EM) hipLaunchKernelGGL((k_scan<KIND, NL, LINES, EM, LOADS, ICASE, ALIGNED>), grid, dim3(kBlock), 0, s, a)
   if (emit) {
     KSCAN_LAUNCH(false, false, true);
@@ -1181,6 +1216,16 @@ void describe_scan(const ScanArgs& a, bool want_nl, bool want_lines, bool emit, 
   snprintf(out, cap, "xsg::k_scan<%d, %s, %s, %s, 4, %s, %s> stagger=%u%s", kind, b[emit ? 0 : want_nl],
            b[emit ? 0 : want_lines], b[emit], b[r.pat.icase ? 1 : 0], b[window && r.pat.hot ? 1 : 0],
            pick_stagger(r, want_nl, want_lines, emit), r.pat.kind != a.pat.kind ? " (dense: byte-parallel)" : "");
+  if (gate_applies(r, want_nl, want_lines, emit)) {
+    const size_t n = strlen(out);
+    snprintf(out + n, cap - n, " gated by xsg::k_sketch (512 B/tile)");
+  }
+}
+
+bool scan_gated(const ScanArgs& a, bool want_nl, bool want_lines) {
+  ScanArgs r = a;
+  if (dense_bytes_route(a, want_lines, false)) r.pat.kind = kMask1;
+  return gate_applies(r, want_nl, want_lines, false);
 }
 
 static hipError_t launch_scan(const ScanArgs& a_in, bool want_nl, bool want_lines, bool emit, hipStream_t s) {
@@ -1400,6 +1445,89 @@ hipError_t launch_count_finish(const FinishArgs& a, hipStream_t s) {
   return hipGetLastError();
 }
 
+
+// ---------------------------------------------------------------------------
+// k_sketch_build: the 4-gram sketch of every tile (xsg_sketch.h), once per binding.  One workgroup per tile of k_scan's
+// geometry; the tile's 1024 units go by in four rounds of 4 KiB (a 16-byte non-temporal load per lane), then the two
+// units behind the tile whose first 29 positions still belong to it.  A lane hashes the 16 grams that start in its unit
+// -- the three bytes behind the unit come from the next lane (DPP), the last lane's from memory -- and sets their bits in
+// a 128-word bitmap in LDS: tested first, OR-ed only where still clear (text repeats its grams: most are already there,
+// and atomics on one word serialise).  One coalesced 512-byte store per tile.
+// Reads stay inside the chunk's rounded length (a unit behind it re-reads the last one, as in k_scan).  Grams that
+// reach beyond `length`, and what a clamped neighbour contributes, may set bits: the sketch is a superset.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(kBlock) void k_sketch_build(const SketchArgs A) {
+  __shared__ uint32_t s_bits[kSketchWords];
+  const uint64_t tile = (uint64_t)blockIdx.x + (uint64_t)blockIdx.y * gridDim.x;
+  if (tile >= A.ntiles) return;
+  const uint32_t tid = threadIdx.x;
+  const uint32_t lane = tid & 63u;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  if (tid < kSketchWords) s_bits[tid] = 0u;
+  __syncthreads();
+  const uint32_t c = A.tile_chunk ? A.tile_chunk[tile] : 0u;
+  const ChunkDev ch = A.chunks[c];
+  const uint8_t* cbase = A.base + ch.offset;
+  const uint64_t Lr = (ch.length + 15u) & ~(uint64_t)15u;
+  const uint64_t last_unit = Lr - kUnit;  // length >= 1: a chunk of length 0 has no tiles
+  const uint64_t toff = (tile - A.chunk_tile0[c]) * (uint64_t)kSketchTileBytes;
+  constexpr uint32_t kRounds = kSketchTileBytes / (kBlock * kUnit);  // 4
+  for (uint32_t r = 0; r <= kRounds; ++r) {
+    if (r == kRounds && wave != 0) break;  // the two units behind the tile: lanes 0 and 1 of the first wave
+    const uint32_t u = r * kBlock + (r == kRounds ? (lane < 2u ? lane : 1u) : tid);
+    const uint64_t off = toff + (uint64_t)u * kUnit;
+    const uint64_t offc = off < last_unit ? off : last_unit;
+    const u32x4 t = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(cbase + offc));
+    // what follows the wave's 64 units (wave-uniform address)
+    uint64_t eoff = toff + ((uint64_t)r * kBlock + (uint64_t)(wave + 1u) * 64u) * kUnit;
+    eoff = eoff < last_unit ? eoff : last_unit;
+    const uint32_t e0 = *reinterpret_cast<const uint32_t*>(cbase + eoff);
+    const uint32_t d[5] = {t.x, t.y, t.z, t.w, from_next_lane(t.x, e0, lane)};
+    const bool own = off < Lr && (r < kRounds || lane < 2u);
+    const uint32_t npos = (r == kRounds && lane == 1u) ? kSketchReach + 1u - kUnit : kUnit;
+    if (own) {
+#pragma unroll
+      for (uint32_t b = 0; b < kUnit; ++b) {
+        if (b < npos) {
+          const uint32_t q = b >> 2, sh = b & 3u;
+          const uint32_t g = sh ? __builtin_amdgcn_alignbyte(d[q + 1], d[q], sh) : d[q];
+          const uint32_t h = sketch_hash(g);
+          const uint32_t bit = 1u << (h & 31u);
+          if (!(s_bits[h >> 5] & bit)) atomicOr(&s_bits[h >> 5], bit);
+        }
+      }
+    }
+  }
+  __syncthreads();
+  if (tid < kSketchWords) A.sketch[tile * kSketchWords + tid] = s_bits[tid];
+}
+
+hipError_t launch_sketch_build(const SketchArgs& a, hipStream_t s) {
+  if (a.ntiles == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_sketch_build, tile_grid(a.ntiles), dim3(kBlock), 0, s, a);
+  return hipGetLastError();
+}
+
+// What share of the tiles would the gate of this pattern let through?  One lane per sampled tile.
+__global__ __launch_bounds__(kBlock) void k_sketch_sample(const ScanArgs A, const uint64_t stride, const uint32_t nsamp,
+                                                          uint32_t* passed) {
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  bool pass = false;
+  if (i < nsamp && (uint64_t)i * stride < A.ntiles) {
+    const uint32_t* sk = A.sketch + (uint64_t)i * stride * kSketchWords;
+    uint32_t miss = 0;
+    for (uint32_t k = 0; k < A.sk_n; ++k) miss |= ~sk[A.sk_word[k]] & A.sk_mask[k];
+    pass = miss == 0;
+  }
+  const unsigned long long b = __ballot(pass);
+  if ((threadIdx.x & 63u) == 0 && b != 0) atomicAdd(passed, (uint32_t)__popcll(b));
+}
+
+hipError_t launch_sketch_sample(const ScanArgs& a, uint64_t stride, uint32_t nsamp, uint32_t* passed, hipStream_t s) {
+  if (nsamp == 0 || !a.sketch) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_sketch_sample, dim3((nsamp + kBlock - 1) / kBlock), dim3(kBlock), 0, s, a, stride, nsamp, passed);
+  return hipGetLastError();
+}
 
 // Loading a code object costs milliseconds the first time one of its kernels is launched: xsg_ctx_create launches this
 // empty kernel of every kernel file, so that the first search of a process does not pay for it (5.5 ms of the first

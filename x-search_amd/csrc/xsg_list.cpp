@@ -258,6 +258,7 @@ static int run_list_fast(xsg_shard* s, uint32_t mode) {
   // ---- 1. bulk count per tile (+ newlines per tile, once per binding)
   const bool scan_nl = want_nl && !s->nl_cached;
   XSG_TRY(choose_hot_filter(s, st, scan_nl, false));
+  XSG_TRY(sketch_before_pass(s, st, !scan_nl, true, true));
   XSG_TRY(prepare_tiles(s, false, st));
   ScanArgs a = scan_args(s, scan_variant(scan_nl, false));
   a.tile_wmask = s->d_wmask.as<uint32_t>();  // the count pass marks the waves that found something, the emit pass reads only those
@@ -871,6 +872,7 @@ int xsg::run_list(xsg_shard* s, uint32_t mode, bool outputs, bool want_nl_total,
   const bool scan_nl = want_nl && !s->nl_cached;  // newline counts per tile: once per binding, whatever the pattern
   if (!counts_ready) {
     XSG_TRY(choose_hot_filter(s, st, scan_nl, false));
+    if (!use_prefilter(s, pre_off)) XSG_TRY(sketch_before_pass(s, st, !scan_nl, true, true));
     XSG_TRY(prepare_tiles(s, false, st));
   }
   ScanArgs a = scan_args(s, scan_variant(scan_nl, false));
@@ -878,6 +880,7 @@ int xsg::run_list(xsg_shard* s, uint32_t mode, bool outputs, bool want_nl_total,
   if (pre) {
     a.pat = c->pre_pat;
     a.pat.hot = 0;
+    a.sketch = nullptr;
   }
   s->cnt_clean = false;  // the tile counts stay in place for the emit pass: the next pass re-zeroes them
   if (!counts_ready) HIP_TRY(launch_scan_count(a, scan_nl, false, st));

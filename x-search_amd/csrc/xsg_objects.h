@@ -154,6 +154,10 @@ struct xsg_ctx {
   // whole one-sync attempt first and then the exact route, chunk after chunk.  A choice, not a result.
   uint64_t fast_dense_serial = 0;
   std::vector<uint32_t> koff_cands;                // long literal patterns: filter windows worth measuring (first: the heuristic's)
+  // a literal of 4 bytes and more: sketch_hash of the gram at every pattern offset 0 .. plen - 4 (xsg_sketch.h), computed
+  // by xsg_set_pattern; scan_args picks the ones behind the filter window in use.  Empty: the pattern has no gate.
+  std::vector<uint16_t> sketch_hashes;
+  uint64_t sketch_min_bytes = 64ull << 20;         // bindings below this never build a sketch (XSG_SKETCH_MIN_BYTES; tests set 0)
   char arch[128] = "";
   int cus = 0;
   uint64_t hbm = 0;
@@ -215,6 +219,15 @@ struct xsg_shard {
   std::vector<xsg_context_edge> context_edges;  // ... the edges of the last search with context, one per chunk
   bool context_edges_valid = false;             // ... which was the last search on this shard (xsg_result_context_edges)
   DevBuf d_c_pos, d_c_chunk, d_c_len, d_c_keep, d_c_pre;  // prefilter route of kDfa: the candidates
+  // The 4-gram sketch of the bound bytes (xsg_sketch.h): 512 B per tile, pattern-independent, built once per binding by
+  // xsg_shard_tune or before the second eligible pass of a synchronous entry point (xsg_count.cpp: sketch_before_pass)
+  DevBuf d_sketch;
+  uint64_t sketch_tiles = 0;      // != 0: d_sketch holds the sketch of this binding's `ntiles` tiles
+  uint32_t sketch_passes = 0;     // eligible synchronous passes this binding has seen
+  bool sketch_refused = false;    // its allocation failed: the binding goes without
+  uint64_t gate_serial = 0;       // ctx->pattern_serial the verdict below was taken for (0: none)
+  uint32_t gate_koff = 0;         // ... with this filter window
+  bool gate_on = false;           // ... fewer than a quarter of the sampled tiles pass: the gate pays
   DevBuf d_tile_mask;             // factor prefilter of kDfa: tiles in which a line with a factor occurrence starts
   uint64_t mask_serial = 0;       // ... valid for this ctx->pattern_serial on this binding (0: not built)
   uint64_t mask_dense_serial = 0; // ... found useless for this pattern here (factor occurrences too dense)
@@ -268,7 +281,7 @@ struct xsg_shard {
                      &d_f_chunk, &d_out_u64, &d_line_len, &d_line_off, &d_line_bytes, &d_dropped, &d_c_pos, &d_c_chunk, &d_c_len, &d_c_keep,
                      &d_c_pre, &d_tile_mask, &d_tot, &d_hit, &d_scan2, &d_wmask, &d_inv_lo, &d_inv_cnt,
                      &d_inv_off, &d_inv_pos, &d_inv_chunk, &d_m_len, &d_f_len, &d_cx_lo, &d_cx_hi, &d_cx_cnt,
-                     &d_cx_slot, &d_cx_pos, &d_cx_chunk, &d_cx_edge};
+                     &d_cx_slot, &d_cx_pos, &d_cx_chunk, &d_cx_edge, &d_sketch};
     for (DevBuf* b : all) b->release();
     if (h_stage) (void)hipHostFree(h_stage);
     if (h_counters) (void)hipHostFree(h_counters);

@@ -10,6 +10,7 @@
 #include "xsg_classseq.h"
 #include "xsg_regex.h"
 #include "xsg_host.h"
+#include "xsg_sketch.h"
 
 using namespace xsg;
 
@@ -207,6 +208,7 @@ static int set_dfa_pattern(xsg_ctx* c, const uint8_t* re, size_t n, uint32_t fla
   c->flags = flags;
   ++c->pattern_serial;
   c->koff_cands.clear();
+  c->sketch_hashes.clear();
   c->bordered = false;  // the kernel walks every line as the reference does: what it reports is already non-overlapping
   c->overlap_words.clear();
   // The table the line walks step (k_rx_scan / k_rx_count): the anchored automaton for the line-anchor form (`^` walks
@@ -346,6 +348,7 @@ static int set_class_pattern(xsg_ctx* c, const uint8_t* re, size_t n, uint32_t f
   c->flags = flags;
   ++c->pattern_serial;
   c->koff_cands.clear();
+  c->sketch_hashes.clear();
   c->bordered = xsg::sequence_can_overlap(seq);
   c->overlap_words.clear();
   std::vector<uint8_t> blob;
@@ -555,6 +558,9 @@ static int set_pattern_plain(xsg_ctx* c, const void* pattern, size_t plen, uint3
   P.plen = (uint32_t)plen;
   window_fields(p, plen, pick_filter_window(p, plen), &P);  // koff 0 unless plen > 8
   c->koff_cands = window_candidates(p, plen);
+  c->sketch_hashes.clear();  // the gate of the plain count pass: case-sensitive literals of 4 bytes and more
+  if (plen >= 4 && !(flags & XSG_FLAG_IGNORE_CASE))
+    for (size_t k = 0; k + 4 <= plen; ++k) c->sketch_hashes.push_back((uint16_t)sketch_hash(sketch_gram(p + k)));
   c->rx_pre = false;
   c->rx_fac = false;
   P.kind = plen < 4 ? kMask1 : plen == 4 ? kOne : plen < 8 ? kMask2 : plen == 8 ? kTwo : kLong;

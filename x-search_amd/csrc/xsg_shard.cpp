@@ -19,6 +19,10 @@ static void forget_derived(xsg_shard* s) {
   s->line_len_on_device = false;
   s->density_serial = 0;                     // a pattern found dense in this data (scan_args: stagger)
   s->overlap_serial = 0;                     // a bordered pattern whose occurrences do not overlap in this data
+  s->sketch_tiles = 0;                       // the 4-gram sketch of the tiles and the gate's verdict on a pattern
+  s->sketch_passes = 0;
+  s->sketch_refused = false;
+  s->gate_serial = 0;
 }
 
 static int bind_shard(xsg_shard* s, const void* d_base, uint64_t capacity, const xsg_chunk* chunks, uint64_t nchunks) {
