@@ -3,7 +3,10 @@
 collected separately, one pair of passes per kernel instantiation): HBM bytes per k_scan launch, with the gfx950
 correction of MI355X_MICROARCH.md's HBM section (FETCH_SIZE counts a 128-byte request as 64 bytes -> read bytes =
 2 x FETCH_SIZE x 1024; WRITE_SIZE x 1024 is exact).
-Usage: pmc_traffic.py <BENCH json> <tag> <fetch csv> <write csv> [<fetch csv> <write csv> ...]"""
+Usage: pmc_traffic.py [--gated] <BENCH json> <tag> <fetch csv> <write csv> [<fetch csv> <write csv> ...]
+--gated: the timed pass is the sketch-gated one, two kernels per step -- k_sketch_select, then k_scan<..., GATED> on a
+bounded grid.  Only the GATED instantiation's launches are averaged (the same run also launches ungated k_scan at full
+size), k_sketch_select gets a row of its own and `per_step` adds the two."""
 import csv
 import json
 import sys
@@ -12,16 +15,24 @@ from pathlib import Path
 ROOT = Path(__file__).resolve().parents[1]
 
 
-def avg_counter(path, counter):
-    """average over the FULL-SHARD k_scan launches only (largest grid): the library's hot-filter probe also launches
+def is_gated(name):
+    """k_scan<KIND, NL, LINES, EMIT, LOADS, ICASE, ALIGNED, GATED>: the eighth template argument"""
+    args = name.split("k_scan<", 1)[1].split(">", 1)[0].split(",")
+    return len(args) == 8 and args[7].strip() == "true"
+
+
+def avg_counter(path, counter, kernel="k_scan<", gated=False):
+    """average over the FULL-SHARD launches of `kernel` only (largest grid): the library's hot-filter probe also launches
     k_scan, on a 2 GiB prefix of the shard"""
     rows = []
     with open(path, newline="") as f:
         for row in csv.DictReader(f):
-            if row["Counter_Name"] == counter and "k_scan<" in row["Kernel_Name"]:
+            if row["Counter_Name"] == counter and kernel in row["Kernel_Name"]:
+                if gated and not is_gated(row["Kernel_Name"]):
+                    continue
                 rows.append((int(row["Grid_Size"]), float(row["Counter_Value"]), row["Kernel_Name"]))
     if not rows:
-        raise SystemExit(f"no {counter} rows for k_scan in {path}")
+        raise SystemExit(f"no {counter} rows for {kernel} in {path}")
     full = max(g for g, _, _ in rows)
     vals = [v for g, v, _ in rows if g == full]
     names = sorted({n for g, _, n in rows if g == full})
@@ -29,14 +40,16 @@ def avg_counter(path, counter):
 
 
 def main():
-    bench_json, tag = sys.argv[1:3]
-    pairs = sys.argv[3:]
+    argv = [x for x in sys.argv[1:] if x != "--gated"]
+    gated = "--gated" in sys.argv[1:]
+    bench_json, tag = argv[0:2]
+    pairs = argv[2:]
     bench = json.loads(Path(bench_json).read_text().splitlines()[-1])
     alg = bench["roofline"]["algorithmic_bytes_per_launch"]
     by = {}
     for fetch_csv, write_csv in zip(pairs[0::2], pairs[1::2]):
-        fetch_kb, nf, names = avg_counter(fetch_csv, "FETCH_SIZE")
-        write_kb, nw, _ = avg_counter(write_csv, "WRITE_SIZE")
+        fetch_kb, nf, names = avg_counter(fetch_csv, "FETCH_SIZE", gated=gated)
+        write_kb, nw, _ = avg_counter(write_csv, "WRITE_SIZE", gated=gated)
         if len(names) != 1:
             raise SystemExit(f"{fetch_csv}: full-shard launches of more than one instantiation: {names}")
         rd, wr = 2.0 * fetch_kb * 1024.0, write_kb * 1024.0
@@ -44,6 +57,15 @@ def main():
         by[key] = {"FETCH_SIZE_KB_avg": fetch_kb, "WRITE_SIZE_KB_avg": write_kb, "launches_averaged": [nf, nw],
                    "hbm_read_bytes_per_launch": rd, "hbm_write_bytes_per_launch": wr, "hbm_bytes_per_launch": rd + wr,
                    "ratio_traffic_over_algorithmic": (rd + wr) / alg}
+        if gated:
+            sf, ns, _ = avg_counter(fetch_csv, "FETCH_SIZE", kernel="k_sketch_select")
+            sw, nsw, _ = avg_counter(write_csv, "WRITE_SIZE", kernel="k_sketch_select")
+            srd, swr = 2.0 * sf * 1024.0, sw * 1024.0
+            by["xsg::k_sketch_select"] = {"FETCH_SIZE_KB_avg": sf, "WRITE_SIZE_KB_avg": sw, "launches_averaged": [ns, nsw],
+                                          "hbm_read_bytes_per_launch": srd, "hbm_write_bytes_per_launch": swr,
+                                          "hbm_bytes_per_launch": srd + swr, "ratio_traffic_over_algorithmic": (srd + swr) / alg}
+            by[key]["per_step_with_select"] = {"hbm_read_bytes": rd + srd, "hbm_write_bytes": wr + swr,
+                                               "ratio_traffic_over_algorithmic": (rd + wr + srd + swr) / alg}
     out = {
         "timed_kernel": bench["roofline"]["kernel"],
         "pattern": bench["config"]["pattern"],
@@ -53,7 +75,11 @@ def main():
         "correction": "HBM read bytes = 2 x FETCH_SIZE x 1024 (gfx950 counts 128-B requests as 64 B, "
                       "MI355X_MICROARCH.md HBM section); WRITE_SIZE x 1024 exact",
         "by_kernel": by,
-        "collected": f"rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE in separate passes per instantiation, pinned with "
+        "collected": (f"rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE in separate passes of `XSG_HOT=0 python3 bench.py --full "
+                      f"--steps 2 --warmup 1 --kernel-iters 1 --no-cpu-baseline --e2e-gib 0 --configs-gib 0 --no-regex --cli-gib 0`; "
+                      f"only the GATED k_scan launches and k_sketch_select are averaged; written by this script, nothing "
+                      f"edited by hand") if gated else
+                     f"rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE in separate passes per instantiation, pinned with "
                      f"XSG_HOT / XSG_TUNE at the timed run's stagger (scripts/gpu_profiles.sh {tag}); written by this script, "
                      f"nothing edited by hand",
     }

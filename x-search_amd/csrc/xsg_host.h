@@ -25,7 +25,7 @@ int choose_hot_filter(xsg_shard* s, hipStream_t st, bool want_nl = false, bool w
 // for (binding, pattern).  `may_sync` false (xsg_count_async): neither -- the pass uses what exists.
 int sketch_before_pass(xsg_shard* s, hipStream_t st, bool plain, bool may_sync, bool counts);
 bool sketch_ready(const xsg_shard* s);                  // the binding holds a sketch and the context's pattern has a gate
-void sketch_fields(const xsg_shard* s, ScanArgs* a);    // ScanArgs::sketch, sk_* for a->pat's filter window
+void sketch_fields(const xsg_shard* s, ScanArgs* a);    // ScanArgs::sketch, cand_*, gate_grid, sk_* for a->pat's filter window
 int ensure_overlap_check(xsg_shard* s);
 bool overlap_free_known(const xsg_shard* s);
 

@@ -758,7 +758,7 @@ __device__ __forceinline__ uint32_t scan_load(const uint4 cur, const uint4 nx, b
 // summaries.  EMIT=true: the same decisions, writing every match offset at its
 // rank (tile_off[tile] + rank inside the tile).
 // ---------------------------------------------------------------------------
-template <int KIND, bool WANT_NL, bool WANT_LINES, bool EMIT, int LOADS, bool ICASE, bool ALIGNED, bool GATED = false>
+template <int KIND, bool WANT_NL, bool WANT_LINES, bool EMIT, int LOADS, bool ICASE, bool ALIGNED>
 __device__ __forceinline__ void scan_tile(const ScanArgs& A, const uint64_t tile) {
   constexpr int kLoads = LOADS;                          // 16-byte units per lane
   constexpr uint32_t kWaveSpan = kWaveLoad * kLoads;     // contiguous bytes per wave
@@ -770,24 +770,6 @@ __device__ __forceinline__ void scan_tile(const ScanArgs& A, const uint64_t tile
   __shared__ __attribute__((aligned(16))) uint8_t s_view[is_cls(KIND) ? kBlock * 48 : 16];  // match_mask16<kClass>
 
   if (tile >= A.ntiles) return;
-  if (GATED) {
-    // The gate (xsg_sketch.h): an occurrence counted in this tile has the hash bit of each of its first grams in the
-    // tile's sketch.  The pattern's bits arrive as (word, mask) pairs, one per distinct word, padded to groups of eight
-    // whose loads are in flight together; everything here is wave-uniform and all four waves decide alike.  A tile that
-    // lacks a bit is left before the stagger and before any text is requested, and without a store: "nothing found" is
-    // the rest state of the per-tile arrays.
-    const uint32_t* sk = A.sketch + tile * kSketchWords;
-    uint32_t miss = 0;
-    for (uint32_t i = 0; i < A.sk_n; i += 8u) {
-      uint32_t v[8];
-#pragma unroll
-      for (uint32_t k = 0; k < 8u; ++k) v[k] = sk[A.sk_word[i + k]];
-      __builtin_amdgcn_sched_barrier(0);  // (eight scalar loads, one wait: left alone the scheduler pairs them off, a round trip per pair)
-#pragma unroll
-      for (uint32_t k = 0; k < 8u; ++k) miss |= ~v[k] & A.sk_mask[i + k];
-    }
-    if (miss != 0) return;
-  }
   // (a tile from the hit list holds a match by construction: no look at its count -- the emit pass over a sparse list
   // is a chain of dependent memory round trips per tile, 2048 tiles resident at a time, and this was one of them)
   if (EMIT && !A.hit_tiles && A.tile_cnt[tile] == 0) return;
@@ -1099,7 +1081,25 @@ __global__ __launch_bounds__(kBlock) void k_scan(const ScanArgs A) {
       return;
     }
   }
-  scan_tile<KIND, WANT_NL, WANT_LINES, EMIT, LOADS, ICASE, ALIGNED, GATED>(A, (uint64_t)blockIdx.x + (uint64_t)blockIdx.y * gridDim.x);
+  if (GATED) {
+    // The gated count pass (xsg_sketch.h): k_sketch_select listed the tiles whose sketch holds every bit of the pattern's
+    // first grams, in no particular order -- everything this pass writes is per tile -- and a bounded grid strides over
+    // that list.  A tile that is not listed gets no store: "nothing found" is the rest state of the per-tile arrays.
+    // Every workgroup has read the count before it takes its ticket, so the last one to leave may put count and ticket
+    // back to zero for the next select (stream order): the steady state enqueues no memset.
+    uint64_t H = A.cand_words[0];
+    H = H < A.ntiles ? H : A.ntiles;
+    for (uint64_t h = blockIdx.x; h < H; h += gridDim.x) {
+      scan_tile<KIND, WANT_NL, WANT_LINES, EMIT, LOADS, ICASE, ALIGNED>(A, (uint64_t)A.cand_tiles[h]);
+      __syncthreads();  // the tile's LDS words are reused by the next one
+    }
+    if (threadIdx.x == 0 && atomicAdd(A.cand_words + 1, 1u) == gridDim.x - 1u) {
+      __hip_atomic_store(A.cand_words, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(A.cand_words + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    return;
+  }
+  scan_tile<KIND, WANT_NL, WANT_LINES, EMIT, LOADS, ICASE, ALIGNED>(A, (uint64_t)blockIdx.x + (uint64_t)blockIdx.y * gridDim.x);
 }
 
 // The plain count pass may run gated by the binding's sketch: literals of 4 bytes and more, case-sensitive, no newline
@@ -1107,8 +1107,15 @@ __global__ __launch_bounds__(kBlock) void k_scan(const ScanArgs A) {
 // hold the pattern and filter window the sketch entries were computed for (scan_args).
 static bool gate_kind(uint32_t kind) { return kind == kOne || kind == kMask2 || kind == kTwo || kind == kLong; }
 static bool gate_applies(const ScanArgs& a, bool want_nl, bool want_lines, bool emit) {
-  return a.sketch != nullptr && a.sk_n != 0 && !emit && !want_nl && !want_lines && gate_kind(a.pat.kind) && !a.pat.icase &&
-         a.sk_pat == a.pat.d_pat && a.sk_koff == a.pat.koff;
+  return a.sketch != nullptr && a.cand_tiles != nullptr && a.cand_words != nullptr && a.sk_n != 0 && !emit && !want_nl &&
+         !want_lines && gate_kind(a.pat.kind) && !a.pat.icase && a.sk_pat == a.pat.d_pat && a.sk_koff == a.pat.koff;
+}
+
+static hipError_t launch_sketch_select(const ScanArgs& a, hipStream_t s);
+// The grid of the gated pass: bounded, each workgroup strides over the candidate list (ScanArgs::gate_grid, 0: kGateGrid)
+static dim3 gate_grid(const ScanArgs& a) {
+  const uint64_t g = a.gate_grid ? a.gate_grid : kGateGrid;
+  return dim3((unsigned)std::min<uint64_t>(std::max<uint64_t>(a.ntiles, 1), g), 1, 1);
 }
 
 template <int KIND, bool ICASE, bool ALIGNED>
@@ -1117,7 +1124,10 @@ static hipError_t launch_scan_kind(const ScanArgs& a, bool want_nl, bool want_li
   constexpr int LOADS = 4;  // 16 KiB tiles (32 KiB measured 8 % slower)
   if constexpr (!ICASE && (KIND == kOne || KIND == kMask2 || KIND == kTwo || KIND == kLong)) {
     if (gate_applies(a, want_nl, want_lines, emit)) {
-      hipLaunchKernelGGL((k_scan<KIND, false, false, false, LOADS, ICASE, ALIGNED, true>), grid, dim3(kBlock), 0, s, a);
+      // select, then the strided pass over what it listed: stream-ordered, nothing for the host to wait for
+      const hipError_t e = launch_sketch_select(a, s);
+      if (e != hipSuccess) return e;
+      hipLaunchKernelGGL((k_scan<KIND, false, false, false, LOADS, ICASE, ALIGNED, true>), gate_grid(a), dim3(kBlock), 0, s, a);
       return hipGetLastError();
     }
   }
@@ -1452,15 +1462,23 @@ hipError_t launch_count_finish(const FinishArgs& a, hipStream_t s) {
 // units behind the tile whose first 29 positions still belong to it.  A lane hashes the 16 grams that start in its unit
 // -- the three bytes behind the unit come from the next lane (DPP), the last lane's from memory -- and sets their bits in
 // a 128-word bitmap in LDS: tested first, OR-ed only where still clear (text repeats its grams: most are already there,
-// and atomics on one word serialise).  One coalesced 512-byte store per tile.
+// and atomics on one word serialise).  The tile's 128 words go to their places in the group (sketch_index: a dword every
+// 256 bytes).
 // Reads stay inside the chunk's rounded length (a unit behind it re-reads the last one, as in k_scan).  Grams that
 // reach beyond `length`, and what a clamped neighbour contributes, may set bits: the sketch is a superset.
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(kBlock) void k_sketch_build(const SketchArgs A) {
   __shared__ uint32_t s_bits[kSketchWords];
-  const uint64_t tile = (uint64_t)blockIdx.x + (uint64_t)blockIdx.y * gridDim.x;
-  if (tile >= A.ntiles) return;
+  // Workgroups are dealt round-robin to the card's eight XCDs, each with an L2 of its own, and the words of a group of 64
+  // tiles interleave (sketch_index): the 64 workgroups of a group are made ones of the SAME XCD -- 512 consecutive
+  // workgroups build eight groups, one per residue of 8 -- so that one L2 collects a group's 32 KiB before it writes them.
+  const uint64_t wg = (uint64_t)blockIdx.x + (uint64_t)blockIdx.y * gridDim.x;
+  const uint64_t tile = ((wg >> 9) * 8u + (wg & 7u)) * kSketchGroup + ((wg >> 3) & 63u);
   const uint32_t tid = threadIdx.x;
+  if (tile >= A.ntiles) {  // behind the last tile: the rest of its group reads as "no bit set"
+    if (tile * kSketchWords < sketch_alloc_words(A.ntiles) && tid < kSketchWords) A.sketch[sketch_index(tile, tid)] = 0u;
+    return;
+  }
   const uint32_t lane = tid & 63u;
   const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   if (tid < kSketchWords) s_bits[tid] = 0u;
@@ -1499,12 +1517,12 @@ __global__ __launch_bounds__(kBlock) void k_sketch_build(const SketchArgs A) {
     }
   }
   __syncthreads();
-  if (tid < kSketchWords) A.sketch[tile * kSketchWords + tid] = s_bits[tid];
+  if (tid < kSketchWords) A.sketch[sketch_index(tile, tid)] = s_bits[tid];
 }
 
 hipError_t launch_sketch_build(const SketchArgs& a, hipStream_t s) {
   if (a.ntiles == 0) return hipSuccess;
-  hipLaunchKernelGGL(k_sketch_build, tile_grid(a.ntiles), dim3(kBlock), 0, s, a);
+  hipLaunchKernelGGL(k_sketch_build, tile_grid((a.ntiles + 511u) & ~(uint64_t)511u), dim3(kBlock), 0, s, a);
   return hipGetLastError();
 }
 
@@ -1514,9 +1532,8 @@ __global__ __launch_bounds__(kBlock) void k_sketch_sample(const ScanArgs A, cons
   const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
   bool pass = false;
   if (i < nsamp && (uint64_t)i * stride < A.ntiles) {
-    const uint32_t* sk = A.sketch + (uint64_t)i * stride * kSketchWords;
     uint32_t miss = 0;
-    for (uint32_t k = 0; k < A.sk_n; ++k) miss |= ~sk[A.sk_word[k]] & A.sk_mask[k];
+    for (uint32_t k = 0; k < A.sk_n; ++k) miss |= ~A.sketch[sketch_index((uint64_t)i * stride, A.sk_word[k])] & A.sk_mask[k];
     pass = miss == 0;
   }
   const unsigned long long b = __ballot(pass);
@@ -1526,6 +1543,72 @@ __global__ __launch_bounds__(kBlock) void k_sketch_sample(const ScanArgs A, cons
 hipError_t launch_sketch_sample(const ScanArgs& a, uint64_t stride, uint32_t nsamp, uint32_t* passed, hipStream_t s) {
   if (nsamp == 0 || !a.sketch) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_sketch_sample, dim3((nsamp + kBlock - 1) / kBlock), dim3(kBlock), 0, s, a, stride, nsamp, passed);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// k_sketch_select: the tiles the gated count pass has to read.  One lane per tile, kSelectRounds rounds of 256 tiles per
+// workgroup; a wave reads word w of its 64 tiles as one 256-byte load (sketch_index), the words of the pattern's entries
+// four at a time.  The tiles that hold every bit are appended to A.cand_tiles: a ballot and a prefix popcount per wave
+// and round, the sixteen wave counts combined in LDS, one atomicAdd per workgroup on the count word (none where nothing
+// passed).  The order of the list is whatever order the workgroups arrive in.
+// ---------------------------------------------------------------------------
+constexpr uint32_t kSelectRounds = 4;  // 1024 tiles per workgroup
+__global__ __launch_bounds__(kBlock) void k_sketch_select(const ScanArgs A) {
+  __shared__ uint32_t s_off[kSelectRounds * kWaves + 1];
+  const uint32_t tid = threadIdx.x;
+  const uint32_t lane = tid & 63u;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const uint64_t tile0 = (uint64_t)blockIdx.x * (kSelectRounds * kBlock);
+  const uint32_t n = A.sk_n;
+  unsigned long long bal[kSelectRounds];
+#pragma unroll
+  for (uint32_t r = 0; r < kSelectRounds; ++r) {
+    const uint64_t tile = tile0 + r * kBlock + tid;
+    bool pass = false;
+    if (tile < A.ntiles) {
+      const uint32_t* sk = A.sketch + sketch_index(tile, 0);
+      uint32_t miss = 0;
+      for (uint32_t i = 0; i < n; i += 4u) {
+        uint32_t v[4], m[4];
+#pragma unroll
+        for (uint32_t k = 0; k < 4u; ++k) {  // (an entry behind the last one repeats it)
+          const uint32_t e = i + k < n ? i + k : n - 1u;
+          v[k] = sk[A.sk_word[e] * kSketchGroup];
+          m[k] = A.sk_mask[e];
+        }
+#pragma unroll
+        for (uint32_t k = 0; k < 4u; ++k) miss |= ~v[k] & m[k];
+      }
+      pass = miss == 0;
+    }
+    bal[r] = __ballot(pass);
+    if (lane == 0) s_off[r * kWaves + wave] = (uint32_t)__popcll(bal[r]);
+  }
+  __syncthreads();
+  if (tid == 0) {
+    uint32_t total = 0;
+    for (uint32_t k = 0; k < kSelectRounds * kWaves; ++k) {
+      const uint32_t c = s_off[k];
+      s_off[k] = total;
+      total += c;
+    }
+    s_off[kSelectRounds * kWaves] = total ? atomicAdd(A.cand_words, total) : 0u;
+  }
+  __syncthreads();
+  const uint32_t base = s_off[kSelectRounds * kWaves];
+#pragma unroll
+  for (uint32_t r = 0; r < kSelectRounds; ++r) {
+    if ((bal[r] >> lane) & 1ull) {
+      const uint64_t at = (uint64_t)base + s_off[r * kWaves + wave] + (uint32_t)__popcll(bal[r] & ((1ull << lane) - 1ull));
+      if (at < A.ntiles) A.cand_tiles[at] = (uint32_t)(tile0 + r * kBlock + tid);  // (the list holds ntiles entries)
+    }
+  }
+}
+
+static hipError_t launch_sketch_select(const ScanArgs& a, hipStream_t s) {
+  const uint64_t per = (uint64_t)kSelectRounds * kBlock;
+  hipLaunchKernelGGL(k_sketch_select, dim3((unsigned)((a.ntiles + per - 1) / per)), dim3(kBlock), 0, s, a);
   return hipGetLastError();
 }
 

@@ -1,6 +1,7 @@
 // xsg_sketch.h -- the per-tile 4-gram sketch of a binding: what is shared by the kernel that builds it (k_sketch_build),
-// the host code that turns a pattern into the bits k_scan's gate tests (xsg_set_pattern, scan_args) and the CPU model of
-// the tests (tests/test_sketch_model.py compiles this header into a host helper).  Plain C++, host and device.
+// the kernels that test it (k_sketch_select, k_sketch_sample), the host code that turns a pattern into the bits they test
+// (xsg_set_pattern, scan_args) and the CPU models of the tests (tests/sketch_model.py and tests/test_sketch_layout.py
+// compile this header into host helpers).  Plain C++, host and device.
 //
 // Tile T of a chunk (16 KiB, k_scan's tile) owns kSketchBits bits.  Bit sketch_hash(g) is set for every 4-gram g -- four
 // consecutive bytes, read as a little-endian dword -- that STARTS at a chunk-relative position in
@@ -34,6 +35,17 @@ XSG_SKETCH_HD uint32_t sketch_hash(uint32_t g) {
   g *= 0x85EBCA77u;
   g ^= g >> 13;
   return g >> 20;
+}
+
+// Where the words live.  The sketch is stored word-major inside groups of kSketchGroup consecutive tiles: word w of the
+// 64 tiles of a group are 64 consecutive dwords, so a wave that holds one tile per lane (k_sketch_select) reads one word
+// of 64 tiles as one 256-byte load.  The allocation covers whole groups; the words of tiles behind the last one are zero.
+constexpr uint32_t kSketchGroup = 64;
+XSG_SKETCH_HD uint64_t sketch_alloc_words(uint64_t ntiles) {
+  return (ntiles + kSketchGroup - 1) / kSketchGroup * kSketchGroup * kSketchWords;
+}
+XSG_SKETCH_HD uint64_t sketch_index(uint64_t tile, uint32_t word) {
+  return tile / kSketchGroup * ((uint64_t)kSketchGroup * kSketchWords) + (uint64_t)word * kSketchGroup + tile % kSketchGroup;
 }
 
 // the grams of a pattern that the gate tests: pattern offsets [first, first + n)
