@@ -300,16 +300,16 @@ int xsg_regex_factor(const void* expr, size_t n, uint32_t flags, uint32_t* posit
  * its gate pays for a pattern, the measured hot filter and filter window of a pattern, the tile marks and density
  * verdicts of the regex prefilters, whether a pattern's lists fit the one-sync route) and every later pass -- the
  * stream-ordered xsg_count_async included -- relies on them.
- * The sketch is 512 bytes of device memory per 16 KiB tile, and 4 bytes more for a list of tiles (3.2 % of the text; a
+ * The sketch is 512 bytes of device memory per 16 KiB tile (3.1 % of the text; a
  * binding simply goes without if the allocation fails): one bit per hashed 4-gram that starts in the tile.  It does not
  * depend on the pattern.  The plain count pass of a case-sensitive literal of 4 bytes and more -- xsg_count,
- * xsg_count_begin, xsg_count_async, the count pass of xsg_search -- is then two stream-ordered launches: a select pass
- * lists the tiles whose sketch holds every one of the needle's first grams, and the scan strides over that list of
- * candidate tiles and reads no other text.  A needle whose grams are words of the text passes everywhere: the synchronous
+ * xsg_count_begin, xsg_count_async, the count pass of xsg_search -- is then one launch of a bounded grid: its workgroups
+ * test the sketches of 256 tiles at a time for the needle's first grams and scan the tiles that hold every one of them --
+ * the candidate tiles -- and read no other text.  A needle whose grams are words of the text passes everywhere: the synchronous
  * entry points find that out first (a sample of the sketch, once per binding and pattern) and keep the full scan.
- * xsg_count_async cannot -- it never waits for the device -- and uses the list whenever no synchronous call has judged
- * the pattern on this binding; for such a needle the list then holds every tile and the pass is SLOWER than the full
- * scan (measured 1.4 x on a 50 GiB binding): call a synchronous entry point once with the pattern,
+ * xsg_count_async cannot -- it never waits for the device -- and uses the gate whenever no synchronous call has judged
+ * the pattern on this binding; for such a needle every tile is then a candidate and the pass is SLOWER than the full
+ * scan (measured 1.07 x on a 50 GiB binding): call a synchronous entry point once with the pattern,
  * or set XSG_SKETCH=0, where that matters.  Bindings of 64 MiB and more get the sketch from
  * xsg_shard_tune, or from the second such pass of a synchronous entry point (the build is enqueued on the context's
  * stream); xsg_count_async on a caller's stream never builds, it uses what is there.  XSG_SKETCH=0 switches the feature
@@ -617,8 +617,8 @@ int xsg_ctx_info(xsg_ctx* ctx, char* arch, size_t arch_cap, int* compute_units, 
 int xsg_time_scan_kernel(xsg_shard* shard, uint32_t mode, int iters, float* avg_ms);
 /* Name of the bulk-kernel instantiation the next pass of `mode` launches on this shard with the current pattern
  * ("xsg::k_scan<KIND, WANT_NL, WANT_LINES, EMIT, LOADS, ICASE> stagger=N"): what a profile of that pass shows.
- * " gated by xsg::k_sketch (512 B/tile)" follows when that pass would run behind the binding's sketch: xsg::k_sketch_select,
- * then this instantiation on a bounded grid over the candidate tiles. */
+ * " gated by xsg::k_sketch (512 B/tile)" follows when that pass would run behind the binding's sketch: this
+ * instantiation on a bounded grid, which selects the candidate tiles and scans them. */
 int xsg_scan_kernel_name(xsg_shard* shard, uint32_t mode, char* out, size_t cap);
 /* Measure and fix the bulk kernel's wave stagger for this shard, the current pattern and `mode` (a handful of
  * launches; replaces the per-variant default until the shard is destroyed or tuned again).  *chosen (optional)

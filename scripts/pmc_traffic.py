@@ -4,9 +4,9 @@ collected separately, one pair of passes per kernel instantiation): HBM bytes pe
 correction of MI355X_MICROARCH.md's HBM section (FETCH_SIZE counts a 128-byte request as 64 bytes -> read bytes =
 2 x FETCH_SIZE x 1024; WRITE_SIZE x 1024 is exact).
 Usage: pmc_traffic.py [--gated] <BENCH json> <tag> <fetch csv> <write csv> [<fetch csv> <write csv> ...]
---gated: the timed pass is the sketch-gated one, two kernels per step -- k_sketch_select, then k_scan<..., GATED> on a
-bounded grid.  Only the GATED instantiation's launches are averaged (the same run also launches ungated k_scan at full
-size), k_sketch_select gets a row of its own and `per_step` adds the two."""
+--gated: the timed pass is the sketch-gated one, one kernel per step -- k_scan<..., GATED>, a bounded grid of persistent
+workgroups that selects and scans.  Only the GATED instantiation's launches are averaged (the same run also launches
+ungated k_scan at full size)."""
 import csv
 import json
 import sys
@@ -57,15 +57,6 @@ def main():
         by[key] = {"FETCH_SIZE_KB_avg": fetch_kb, "WRITE_SIZE_KB_avg": write_kb, "launches_averaged": [nf, nw],
                    "hbm_read_bytes_per_launch": rd, "hbm_write_bytes_per_launch": wr, "hbm_bytes_per_launch": rd + wr,
                    "ratio_traffic_over_algorithmic": (rd + wr) / alg}
-        if gated:
-            sf, ns, _ = avg_counter(fetch_csv, "FETCH_SIZE", kernel="k_sketch_select")
-            sw, nsw, _ = avg_counter(write_csv, "WRITE_SIZE", kernel="k_sketch_select")
-            srd, swr = 2.0 * sf * 1024.0, sw * 1024.0
-            by["xsg::k_sketch_select"] = {"FETCH_SIZE_KB_avg": sf, "WRITE_SIZE_KB_avg": sw, "launches_averaged": [ns, nsw],
-                                          "hbm_read_bytes_per_launch": srd, "hbm_write_bytes_per_launch": swr,
-                                          "hbm_bytes_per_launch": srd + swr, "ratio_traffic_over_algorithmic": (srd + swr) / alg}
-            by[key]["per_step_with_select"] = {"hbm_read_bytes": rd + srd, "hbm_write_bytes": wr + swr,
-                                               "ratio_traffic_over_algorithmic": (rd + wr + srd + swr) / alg}
     out = {
         "timed_kernel": bench["roofline"]["kernel"],
         "pattern": bench["config"]["pattern"],
@@ -77,7 +68,7 @@ def main():
         "by_kernel": by,
         "collected": (f"rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE in separate passes of `XSG_HOT=0 python3 bench.py --full "
                       f"--steps 2 --warmup 1 --kernel-iters 1 --no-cpu-baseline --e2e-gib 0 --configs-gib 0 --no-regex --cli-gib 0`; "
-                      f"only the GATED k_scan launches and k_sketch_select are averaged; written by this script, nothing "
+                      f"only the GATED k_scan launches are averaged; written by this script, nothing "
                       f"edited by hand") if gated else
                      f"rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE in separate passes per instantiation, pinned with "
                      f"XSG_HOT / XSG_TUNE at the timed run's stagger (scripts/gpu_profiles.sh {tag}); written by this script, "

@@ -77,8 +77,6 @@ void xsg::sketch_fields(const xsg_shard* s, ScanArgs* a) {
   }
   a->sk_n = used;
   a->sketch = s->d_sketch.as<uint32_t>();
-  a->cand_words = s->d_cand.as<uint32_t>();  // count and ticket, then the list (build_sketch)
-  a->cand_tiles = a->cand_words + kCandHead;
   const char* g = XSG_TOGGLE("XSG_GATE_GRID");
   a->gate_grid = g && atoll(g) > 0 ? (uint32_t)std::min<long long>(atoll(g), 1 << 30) : 0u;
   a->sk_pat = a->pat.d_pat;
@@ -88,14 +86,10 @@ void xsg::sketch_fields(const xsg_shard* s, ScanArgs* a) {
 static int build_sketch(xsg_shard* s) {
   xsg_ctx* c = s->ctx;
   if (s->sketch_refused || s->ntiles == 0 || s->tile_bytes != kSketchTileBytes) return XSG_OK;
-  if (s->ntiles >= 0xffffffffull) return XSG_OK;  // (the candidate list holds tile numbers as uint32)
-  // with it the list of candidate tiles that k_sketch_select fills per pass, behind its count and ticket words
-  if (s->d_sketch.ensure((size_t)sketch_alloc_words(s->ntiles) * 4) != XSG_OK ||
-      s->d_cand.ensure(4 * ((size_t)s->ntiles + kCandHead)) != XSG_OK) {
+  if (s->d_sketch.ensure((size_t)sketch_alloc_words(s->ntiles) * 4) != XSG_OK) {
     s->sketch_refused = true;  // no memory for it: this binding simply has no sketch
     return XSG_OK;
   }
-  HIP_TRY(hipMemsetAsync(s->d_cand.p, 0, 4 * kCandHead, c->stream));  // at rest; every gated pass leaves them so
   SketchArgs b{};
   b.base = s->base;
   b.chunks = s->d_chunks.as<ChunkDev>();

@@ -22,8 +22,7 @@ constexpr uint32_t kWaveLoad = 64 * kUnit;
 // kLoads KiB per wave x 4 waves = 16 KiB (kLoads 4) or 32 KiB (kLoads 8).
 constexpr uint32_t kDefaultTileBytes = 16384;
 constexpr uint32_t kDefaultStagger = 16;  // see k_scan / pick_stagger (round 2: xsg_shard_tune picked 16 in every 50 GiB run)
-constexpr uint32_t kCandHead = 64;        // words in front of ScanArgs::cand_tiles (a 256-byte line of their own): [0] count, [1] ticket
-constexpr uint32_t kGateGrid = 4096;      // workgroups of the gated count pass (k_scan<..., GATED>): DESIGN.md section 5, "Sketch gate"
+constexpr uint32_t kGateGrid = 8192;      // workgroups of the gated count pass (k_scan<..., GATED>): DESIGN.md section 5, "Sketch gate"
 constexpr uint32_t kTuneAuto = 0xffffffffu;  // ScanArgs::tune: let launch_scan pick the stagger per variant
 
 // Same layout as xsg_chunk (include/xsg.h).
@@ -135,16 +134,13 @@ struct ScanArgs {
   // followed by an emit pass over the hit list (null otherwise), read and cleared by that emit pass; a stale bit is
   // harmless (the wave reads its 4 KiB and finds nothing), so the array is only ever zeroed when it is (re)allocated
   uint32_t* tile_wmask;
-  // The gate of the plain count pass (k_sketch_select, then k_scan<..., GATED>): the binding's per-tile 4-gram sketch
+  // The gate of the plain count pass (k_scan<..., GATED>: gated_pass): the binding's per-tile 4-gram sketch
   // (xsg_sketch.h; null: none, or not to be used for this pattern here) and the pattern's bits in it, one entry per
-  // distinct word of the tile's 128 (sk_n entries).  k_sketch_select lists the tiles that hold every bit in cand_tiles
-  // (capacity ntiles, any order) and counts them in cand_words[0]; the gated k_scan is a bounded grid that strides over
-  // that list, and its last workgroup to leave (a ticket in cand_words[1]) puts both words back to zero, their rest
-  // state.  sk_pat / sk_koff say which pattern and filter window the entries were computed for: launch_scan gates only a
+  // distinct word of the tile's 128 (sk_n entries).  The gated k_scan is a bounded grid of persistent workgroups that
+  // stride over units of 256 tiles, test each tile's words and scan the tiles that hold every bit: no list, no counter,
+  // nothing to reset between passes.  sk_pat / sk_koff say which pattern and filter window the entries were computed for: launch_scan gates only a
   // pass whose `pat` is still that one (callers put other patterns and windows into a copy of these arguments).
   const uint32_t* sketch;
-  uint32_t* cand_tiles;
-  uint32_t* cand_words;
   const uint8_t* sk_pat;
   uint32_t sk_koff;
   uint32_t sk_n;

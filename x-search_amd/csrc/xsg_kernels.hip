@@ -758,8 +758,30 @@ __device__ __forceinline__ uint32_t scan_load(const uint4 cur, const uint4 nx, b
 // summaries.  EMIT=true: the same decisions, writing every match offset at its
 // rank (tile_off[tile] + rank inside the tile).
 // ---------------------------------------------------------------------------
-template <int KIND, bool WANT_NL, bool WANT_LINES, bool EMIT, int LOADS, bool ICASE, bool ALIGNED>
-__device__ __forceinline__ void scan_tile(const ScanArgs& A, const uint64_t tile) {
+// Where a tile lies: its chunk, the chunk's bytes and the chunk's first tile.  scan_tile looks them up itself (a chain
+// of three dependent loads in front of the tile's text); the fused gated pass (gated_pass) has them ready per candidate.
+struct TileGeom {
+  uint64_t offset;  // ChunkDev::offset
+  uint64_t length;  // ChunkDev::length
+  uint64_t tile0;   // chunk_tile0[c]
+  uint32_t c;
+};
+__device__ __forceinline__ TileGeom tile_geom(const ScanArgs& A, const uint64_t tile) {
+  TileGeom g;
+  g.c = A.tile_chunk ? A.tile_chunk[tile] : 0u;
+  const ChunkDev ch = A.chunks[g.c];
+  g.offset = ch.offset;
+  g.length = ch.length;
+  g.tile0 = A.chunk_tile0[g.c];
+  return g;
+}
+
+// One tile: its loads and what is decided on them, with the geometry look-up split off.  HAVE_GEOM: the caller passes
+// the geometry (and says whether the pattern still has to be staged: `stage`, workgroup-uniform); otherwise it is looked
+// up here, where it always was.  (The loads and their consumption are still one piece: a candidate's text is not
+// requested ahead of the previous candidate's compares.)
+template <int KIND, bool WANT_NL, bool WANT_LINES, bool EMIT, int LOADS, bool ICASE, bool ALIGNED, bool HAVE_GEOM>
+__device__ __forceinline__ void scan_tile_at(const ScanArgs& A, const uint64_t tile, const TileGeom& geom, const bool stage) {
   constexpr int kLoads = LOADS;                          // 16-byte units per lane
   constexpr uint32_t kWaveSpan = kWaveLoad * kLoads;     // contiguous bytes per wave
   constexpr uint32_t kTile = kWaveSpan * kWaves;         // bytes per workgroup
@@ -779,20 +801,20 @@ __device__ __forceinline__ void scan_tile(const ScanArgs& A, const uint64_t tile
   const uint32_t lane = tid & 63u;
   const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // wave-uniform: keeps wbase and the branches on it scalar
 
-  if (KIND == kLong) {  // the first KiB of the pattern; a candidate of a longer one is verified against the device copy beyond it
+  if (KIND == kLong && (!HAVE_GEOM || stage)) {  // the first KiB of the pattern; a candidate of a longer one is verified against the device copy beyond it
     for (uint32_t k = tid; k < P.plen && k < kLdsPattern; k += kBlock) s_pat[k] = P.d_pat[k];
     __syncthreads();
   }
 
-  const uint32_t c = A.tile_chunk ? A.tile_chunk[tile] : 0u;
-  const ChunkDev ch = A.chunks[c];
-  const uint8_t* cbase = A.base + ch.offset;
-  const uint64_t L = ch.length;
+  const TileGeom tg = HAVE_GEOM ? geom : tile_geom(A, tile);
+  const uint32_t c = tg.c;
+  const uint8_t* cbase = A.base + tg.offset;
+  const uint64_t L = tg.length;
   const uint64_t Lr = (L + 15u) & ~(uint64_t)15u;
   // positions o < limit are decided here; [limit, L) belongs to the tail walk
   const uint64_t limit =
       P.exact_tail ? (L >= P.plen ? L - P.plen + 1u : 0u) : tail_zone_begin(L, P.plen);
-  const uint64_t toff = (tile - A.chunk_tile0[c]) * (uint64_t)kTile;
+  const uint64_t toff = (tile - tg.tile0) * (uint64_t)kTile;
   const uint64_t wbase = toff + (uint64_t)wave * kWaveSpan;
 
   // ---- issue all loads of the wave span up front (kLoads KiB in flight per wave).
@@ -1060,6 +1082,133 @@ __device__ __forceinline__ void scan_tile(const ScanArgs& A, const uint64_t tile
   }
 }
 
+// the tile as one piece: every caller but the fused gated pass
+template <int KIND, bool WANT_NL, bool WANT_LINES, bool EMIT, int LOADS, bool ICASE, bool ALIGNED>
+__device__ __forceinline__ void scan_tile(const ScanArgs& A, const uint64_t tile) {
+  scan_tile_at<KIND, WANT_NL, WANT_LINES, EMIT, LOADS, ICASE, ALIGNED, false>(A, tile, TileGeom{}, true);
+}
+
+// ---------------------------------------------------------------------------
+// The gated count pass (xsg_sketch.h), select and scan in one persistent kernel.  A UNIT is 256 consecutive tiles: four
+// sketch groups, one per wave, one tile per lane.  Workgroup b of G takes the units b, b + G, b + 2 G, ... (a device
+// counter that hands units out measured slower at every grid: its atomics serialise), tests each
+// lane's tile against the pattern's sketch entries --
+// word w of a wave's 64 tiles is one 256-byte load (sketch_index) -- and scans the tiles that hold every bit.  The four
+// ballots are the unit's candidate list; all four waves walk their set bits in the same order.  A tile that is no
+// candidate gets no store: "nothing found" is the rest state of the per-tile arrays.
+//
+// Per unit: the lane's sk_n words and its tile's chunk number (tile_chunk) are requested, all before any is used; the
+// words are tested and the ballot taken; lanes that pass request their chunk's entry and first tile; ballots and the
+// passing lanes' geometry go to LDS; the candidates are scanned (scan_tile_at) with their geometry ready, so a
+// candidate's text waits behind nothing but the previous candidate's text -- no barrier between the tiles of a unit.
+// A variant that kept the sketch words of unit u + 2 and the geometry of unit u + 1 in flight under the scans of unit u
+// cost 10 VGPRs and a wave per SIMD and measured 4 % slower: the other workgroups of the compute
+// unit hide a unit's two round trips better than the workgroup itself.
+// Workgroups share nothing and never wait for one another; the pass leaves no word behind that a later one would have
+// to find at rest.
+// ---------------------------------------------------------------------------
+// a wave-uniform 64-bit value that the compiler holds in vector registers (an LDS read), moved to scalar ones; the halves
+// go through unsigned: readfirstlane returns int, and a low half with bit 31 set must not sign-extend into the high one
+__device__ __forceinline__ uint64_t uniform_u64(const uint64_t v) {
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32));
+  return ((uint64_t)hi << 32) | lo;
+}
+constexpr uint32_t kGateRegs = 6;  // sketch words a lane requests at once; entries beyond (long needles) follow in batches
+template <int KIND, int LOADS, bool ICASE, bool ALIGNED>
+__device__ __forceinline__ void gated_pass(const ScanArgs& A) {
+  __shared__ unsigned long long s_bal[kWaves];
+  __shared__ uint64_t s_goff[kBlock], s_glen[kBlock];
+  __shared__ uint32_t s_gt0[kBlock];  // the low half of the chunk's first tile: the tile's distance from it is below 2^32
+  const uint32_t tid = threadIdx.x;
+  const uint32_t lane = tid & 63u;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const uint64_t nunits = (A.ntiles + kBlock - 1) / kBlock;
+  const uint32_t n = A.sk_n;
+
+  // the loads of this lane's tile in unit u, all issued here; `miss` takes what does not fit kGateRegs
+  uint32_t w[kGateRegs], wc = 0, miss = 0;
+  auto sketch_stage = [&](const uint64_t u) {
+    const uint64_t tile = u * kBlock + tid;
+    miss = 1u;  // a tile at or beyond ntiles does not pass
+#pragma unroll
+    for (uint32_t k = 0; k < kGateRegs; ++k) w[k] = 0xffffffffu;
+    wc = 0;
+    if (u < nunits && tile < A.ntiles) {
+      const uint32_t* sk = A.sketch + sketch_index(tile, 0);
+      miss = 0;
+#pragma unroll
+      for (uint32_t k = 0; k < kGateRegs; ++k)
+        if (k < n) w[k] = sk[A.sk_word[k] * kSketchGroup];
+      if (A.tile_chunk) wc = A.tile_chunk[tile];
+      for (uint32_t i = kGateRegs; i < n; i += kGateRegs) {  // (more than kGateRegs distinct words: long needles only)
+        uint32_t x[kGateRegs];
+#pragma unroll
+        for (uint32_t k = 0; k < kGateRegs; ++k) x[k] = i + k < n ? sk[A.sk_word[i + k] * kSketchGroup] : 0xffffffffu;
+#pragma unroll
+        for (uint32_t k = 0; k < kGateRegs; ++k) miss |= i + k < n ? ~x[k] & A.sk_mask[i + k] : 0u;
+      }
+    }
+  };
+  // the verdict on those words; a passing lane requests its tile's geometry
+  unsigned long long bal = 0;
+  uint64_t g_off = 0, g_len = 0;
+  uint32_t g_t0 = 0;
+  auto pass_stage = [&]() {
+    uint32_t m = miss;
+#pragma unroll
+    for (uint32_t k = 0; k < kGateRegs; ++k)
+      if (k < n) m |= ~w[k] & A.sk_mask[k];
+    const bool pass = m == 0;
+    bal = __ballot(pass);
+    if (pass) {
+      const ChunkDev ch = A.chunks[wc];
+      g_off = ch.offset;
+      g_len = ch.length;
+      g_t0 = reinterpret_cast<const uint32_t*>(A.chunk_tile0 + wc)[0];
+    }
+  };
+
+  bool stage_pat = true;
+  for (uint64_t u1 = blockIdx.x; u1 < nunits; u1 += gridDim.x) {
+    sketch_stage(u1);
+    pass_stage();
+    if (lane == 0) s_bal[wave] = bal;
+    if ((bal >> lane) & 1ull) {
+      s_goff[tid] = g_off;
+      s_glen[tid] = g_len;
+      s_gt0[tid] = g_t0;
+    }
+    __syncthreads();
+#pragma unroll 1
+    for (uint32_t q = 0; q < (uint32_t)kWaves; ++q) {
+      const unsigned long long bq = s_bal[q];
+      uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)bq), hi = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(bq >> 32));
+      while (lo | hi) {
+        uint32_t l;
+        if (lo) {
+          l = (uint32_t)__builtin_ctz(lo);
+          lo &= lo - 1u;
+        } else {
+          l = 32u + (uint32_t)__builtin_ctz(hi);
+          hi &= hi - 1u;
+        }
+        const uint32_t at = q * 64u + l;
+        TileGeom tg;
+        const uint64_t o = s_goff[at], len = s_glen[at];
+        const uint64_t tile = u1 * kBlock + at;
+        tg.offset = uniform_u64(o);
+        tg.length = uniform_u64(len);
+        tg.tile0 = tile - (uint32_t)((uint32_t)tile - (uint32_t)__builtin_amdgcn_readfirstlane(s_gt0[at]));
+        tg.c = 0;  // (the emit pass names the chunk; a count pass does not)
+        scan_tile_at<KIND, false, false, false, LOADS, ICASE, ALIGNED, true>(A, tile, tg, stage_pat);
+        stage_pat = false;
+      }
+    }
+    __syncthreads();  // the unit's LDS words are rewritten for the next one
+  }
+}
+
 // The kernel proper.  (Round 2 also measured an occupancy request for the class-sequence kinds -- they keep sixteen
 // lane masks and the window dwords in scalar registers and take all 106 SGPRs the compiler may use, 7 waves per SIMD
 // instead of 8; `amdgpu_waves_per_eu(8, 8)` brings them to 78 SGPRs and a dozen more spills.  Three builds, two
@@ -1081,22 +1230,8 @@ __global__ __launch_bounds__(kBlock) void k_scan(const ScanArgs A) {
       return;
     }
   }
-  if (GATED) {
-    // The gated count pass (xsg_sketch.h): k_sketch_select listed the tiles whose sketch holds every bit of the pattern's
-    // first grams, in no particular order -- everything this pass writes is per tile -- and a bounded grid strides over
-    // that list.  A tile that is not listed gets no store: "nothing found" is the rest state of the per-tile arrays.
-    // Every workgroup has read the count before it takes its ticket, so the last one to leave may put count and ticket
-    // back to zero for the next select (stream order): the steady state enqueues no memset.
-    uint64_t H = A.cand_words[0];
-    H = H < A.ntiles ? H : A.ntiles;
-    for (uint64_t h = blockIdx.x; h < H; h += gridDim.x) {
-      scan_tile<KIND, WANT_NL, WANT_LINES, EMIT, LOADS, ICASE, ALIGNED>(A, (uint64_t)A.cand_tiles[h]);
-      __syncthreads();  // the tile's LDS words are reused by the next one
-    }
-    if (threadIdx.x == 0 && atomicAdd(A.cand_words + 1, 1u) == gridDim.x - 1u) {
-      __hip_atomic_store(A.cand_words, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(A.cand_words + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+  if constexpr (GATED) {
+    gated_pass<KIND, LOADS, ICASE, ALIGNED>(A);  // select and scan, a bounded grid of persistent workgroups
     return;
   }
   scan_tile<KIND, WANT_NL, WANT_LINES, EMIT, LOADS, ICASE, ALIGNED>(A, (uint64_t)blockIdx.x + (uint64_t)blockIdx.y * gridDim.x);
@@ -1107,15 +1242,15 @@ __global__ __launch_bounds__(kBlock) void k_scan(const ScanArgs A) {
 // hold the pattern and filter window the sketch entries were computed for (scan_args).
 static bool gate_kind(uint32_t kind) { return kind == kOne || kind == kMask2 || kind == kTwo || kind == kLong; }
 static bool gate_applies(const ScanArgs& a, bool want_nl, bool want_lines, bool emit) {
-  return a.sketch != nullptr && a.cand_tiles != nullptr && a.cand_words != nullptr && a.sk_n != 0 && !emit && !want_nl &&
+  return a.sketch != nullptr && a.sk_n != 0 && !emit && !want_nl &&
          !want_lines && gate_kind(a.pat.kind) && !a.pat.icase && a.sk_pat == a.pat.d_pat && a.sk_koff == a.pat.koff;
 }
 
-static hipError_t launch_sketch_select(const ScanArgs& a, hipStream_t s);
-// The grid of the gated pass: bounded, each workgroup strides over the candidate list (ScanArgs::gate_grid, 0: kGateGrid)
+// The grid of the gated pass: bounded, persistent workgroups that claim units of 256 tiles (ScanArgs::gate_grid, 0:
+// kGateGrid); never more workgroups than units
 static dim3 gate_grid(const ScanArgs& a) {
   const uint64_t g = a.gate_grid ? a.gate_grid : kGateGrid;
-  return dim3((unsigned)std::min<uint64_t>(std::max<uint64_t>(a.ntiles, 1), g), 1, 1);
+  return dim3((unsigned)std::min<uint64_t>(std::max<uint64_t>((a.ntiles + kBlock - 1) / kBlock, 1), g), 1, 1);
 }
 
 template <int KIND, bool ICASE, bool ALIGNED>
@@ -1124,9 +1259,7 @@ static hipError_t launch_scan_kind(const ScanArgs& a, bool want_nl, bool want_li
   constexpr int LOADS = 4;  // 16 KiB tiles (32 KiB measured 8 % slower)
   if constexpr (!ICASE && (KIND == kOne || KIND == kMask2 || KIND == kTwo || KIND == kLong)) {
     if (gate_applies(a, want_nl, want_lines, emit)) {
-      // select, then the strided pass over what it listed: stream-ordered, nothing for the host to wait for
-      const hipError_t e = launch_sketch_select(a, s);
-      if (e != hipSuccess) return e;
+      // one launch selects and scans (gated_pass): stream-ordered, nothing for the host to wait for
       hipLaunchKernelGGL((k_scan<KIND, false, false, false, LOADS, ICASE, ALIGNED, true>), gate_grid(a), dim3(kBlock), 0, s, a);
       return hipGetLastError();
     }
@@ -1543,72 +1676,6 @@ __global__ __launch_bounds__(kBlock) void k_sketch_sample(const ScanArgs A, cons
 hipError_t launch_sketch_sample(const ScanArgs& a, uint64_t stride, uint32_t nsamp, uint32_t* passed, hipStream_t s) {
   if (nsamp == 0 || !a.sketch) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_sketch_sample, dim3((nsamp + kBlock - 1) / kBlock), dim3(kBlock), 0, s, a, stride, nsamp, passed);
-  return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------
-// k_sketch_select: the tiles the gated count pass has to read.  One lane per tile, kSelectRounds rounds of 256 tiles per
-// workgroup; a wave reads word w of its 64 tiles as one 256-byte load (sketch_index), the words of the pattern's entries
-// four at a time.  The tiles that hold every bit are appended to A.cand_tiles: a ballot and a prefix popcount per wave
-// and round, the sixteen wave counts combined in LDS, one atomicAdd per workgroup on the count word (none where nothing
-// passed).  The order of the list is whatever order the workgroups arrive in.
-// ---------------------------------------------------------------------------
-constexpr uint32_t kSelectRounds = 4;  // 1024 tiles per workgroup
-__global__ __launch_bounds__(kBlock) void k_sketch_select(const ScanArgs A) {
-  __shared__ uint32_t s_off[kSelectRounds * kWaves + 1];
-  const uint32_t tid = threadIdx.x;
-  const uint32_t lane = tid & 63u;
-  const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const uint64_t tile0 = (uint64_t)blockIdx.x * (kSelectRounds * kBlock);
-  const uint32_t n = A.sk_n;
-  unsigned long long bal[kSelectRounds];
-#pragma unroll
-  for (uint32_t r = 0; r < kSelectRounds; ++r) {
-    const uint64_t tile = tile0 + r * kBlock + tid;
-    bool pass = false;
-    if (tile < A.ntiles) {
-      const uint32_t* sk = A.sketch + sketch_index(tile, 0);
-      uint32_t miss = 0;
-      for (uint32_t i = 0; i < n; i += 4u) {
-        uint32_t v[4], m[4];
-#pragma unroll
-        for (uint32_t k = 0; k < 4u; ++k) {  // (an entry behind the last one repeats it)
-          const uint32_t e = i + k < n ? i + k : n - 1u;
-          v[k] = sk[A.sk_word[e] * kSketchGroup];
-          m[k] = A.sk_mask[e];
-        }
-#pragma unroll
-        for (uint32_t k = 0; k < 4u; ++k) miss |= ~v[k] & m[k];
-      }
-      pass = miss == 0;
-    }
-    bal[r] = __ballot(pass);
-    if (lane == 0) s_off[r * kWaves + wave] = (uint32_t)__popcll(bal[r]);
-  }
-  __syncthreads();
-  if (tid == 0) {
-    uint32_t total = 0;
-    for (uint32_t k = 0; k < kSelectRounds * kWaves; ++k) {
-      const uint32_t c = s_off[k];
-      s_off[k] = total;
-      total += c;
-    }
-    s_off[kSelectRounds * kWaves] = total ? atomicAdd(A.cand_words, total) : 0u;
-  }
-  __syncthreads();
-  const uint32_t base = s_off[kSelectRounds * kWaves];
-#pragma unroll
-  for (uint32_t r = 0; r < kSelectRounds; ++r) {
-    if ((bal[r] >> lane) & 1ull) {
-      const uint64_t at = (uint64_t)base + s_off[r * kWaves + wave] + (uint32_t)__popcll(bal[r] & ((1ull << lane) - 1ull));
-      if (at < A.ntiles) A.cand_tiles[at] = (uint32_t)(tile0 + r * kBlock + tid);  // (the list holds ntiles entries)
-    }
-  }
-}
-
-static hipError_t launch_sketch_select(const ScanArgs& a, hipStream_t s) {
-  const uint64_t per = (uint64_t)kSelectRounds * kBlock;
-  hipLaunchKernelGGL(k_sketch_select, dim3((unsigned)((a.ntiles + per - 1) / per)), dim3(kBlock), 0, s, a);
   return hipGetLastError();
 }
 

@@ -222,8 +222,6 @@ struct xsg_shard {
   // The 4-gram sketch of the bound bytes (xsg_sketch.h): 512 B per tile, pattern-independent, built once per binding by
   // xsg_shard_tune or before the second eligible pass of a synchronous entry point (xsg_count.cpp: sketch_before_pass)
   DevBuf d_sketch;
-  DevBuf d_cand;                  // the gated count pass: kCandHead words (candidate count, ticket; zero at rest), then
-                                  // the candidate tiles of the pass in flight (ScanArgs::cand_tiles), allocated with the sketch
   uint64_t sketch_tiles = 0;      // != 0: d_sketch holds the sketch of this binding's `ntiles` tiles
   uint32_t sketch_passes = 0;     // eligible synchronous passes this binding has seen
   bool sketch_refused = false;    // its allocation failed: the binding goes without
@@ -283,7 +281,7 @@ struct xsg_shard {
                      &d_f_chunk, &d_out_u64, &d_line_len, &d_line_off, &d_line_bytes, &d_dropped, &d_c_pos, &d_c_chunk, &d_c_len, &d_c_keep,
                      &d_c_pre, &d_tile_mask, &d_tot, &d_hit, &d_scan2, &d_wmask, &d_inv_lo, &d_inv_cnt,
                      &d_inv_off, &d_inv_pos, &d_inv_chunk, &d_m_len, &d_f_len, &d_cx_lo, &d_cx_hi, &d_cx_cnt,
-                     &d_cx_slot, &d_cx_pos, &d_cx_chunk, &d_cx_edge, &d_sketch, &d_cand};
+                     &d_cx_slot, &d_cx_pos, &d_cx_chunk, &d_cx_edge, &d_sketch};
     for (DevBuf* b : all) b->release();
     if (h_stage) (void)hipHostFree(h_stage);
     if (h_counters) (void)hipHostFree(h_counters);

@@ -1,5 +1,5 @@
 // xsg_sketch.h -- the per-tile 4-gram sketch of a binding: what is shared by the kernel that builds it (k_sketch_build),
-// the kernels that test it (k_sketch_select, k_sketch_sample), the host code that turns a pattern into the bits they test
+// the kernels that test it (k_scan<..., GATED>: gated_pass, k_sketch_sample), the host code that turns a pattern into the bits they test
 // (xsg_set_pattern, scan_args) and the CPU models of the tests (tests/sketch_model.py and tests/test_sketch_layout.py
 // compile this header into host helpers).  Plain C++, host and device.
 //
@@ -38,7 +38,7 @@ XSG_SKETCH_HD uint32_t sketch_hash(uint32_t g) {
 }
 
 // Where the words live.  The sketch is stored word-major inside groups of kSketchGroup consecutive tiles: word w of the
-// 64 tiles of a group are 64 consecutive dwords, so a wave that holds one tile per lane (k_sketch_select) reads one word
+// 64 tiles of a group are 64 consecutive dwords, so a wave that holds one tile per lane (gated_pass) reads one word
 // of 64 tiles as one 256-byte load.  The allocation covers whole groups; the words of tiles behind the last one are zero.
 constexpr uint32_t kSketchGroup = 64;
 XSG_SKETCH_HD uint64_t sketch_alloc_words(uint64_t ntiles) {
