@@ -37,7 +37,8 @@
 // ranges out over several devices of the node, one job each, results in file order), XS_CHUNK_BYTES (target
 // chunk size without a metafile, default 16 MiB), XS_INVERT_MATCH (1: the lines WITHOUT a match), XS_CONTEXT_BEFORE /
 // XS_CONTEXT_AFTER (context lines of line_byte_offsets, line_indices and lines, grep -B / -A, at most 4095 each; the
-// other tags ignore them; not with several devices).
+// other tags ignore them; not with several devices), XS_PATTERN_LIST (1: the pattern is a LIST of literals separated by
+// '\n', searched leftmost-first in listing order -- xsg.h: xsg_set_literals; it implies the literal reading).
 #pragma once
 
 #include <xsg.h>
@@ -179,13 +180,16 @@ inline bool reference_routes_to_regex(const std::string& pattern) {
   }
 }
 
+// XS_PATTERN_LIST=1: the pattern is a list of literals separated by '\n' (xsg.h: xsg_set_literals)
+inline bool pattern_is_list() { return env_u64("XS_PATTERN_LIST", 0) != 0; }
+
 // XSG_FLAG_* for a pattern, routed as the reference routes it; throws std::invalid_argument for a
 // regular expression the GPU matcher does not serve.  XS_INVERT_MATCH=1 adds XSG_FLAG_INVERT (the lines WITHOUT a
 // match, grep -v): the line tags only, see require_line_tag.
 inline uint32_t pattern_flags(const std::string& pattern, bool ignore_case) {
   uint32_t flags = ignore_case ? XSG_FLAG_IGNORE_CASE : 0u;  // ASCII, as simd::toLower (string_utils.cpp:11-33)
   if (env_u64("XS_INVERT_MATCH", 0) != 0) flags |= XSG_FLAG_INVERT;
-  if (env_u64("XS_FORCE_LITERAL", 0) != 0) return flags;
+  if (env_u64("XS_FORCE_LITERAL", 0) != 0 || pattern_is_list()) return flags;  // (a list is literals: never a regex)
   if (env_u64("XS_FORCE_REGEX", 0) != 0 || reference_routes_to_regex(pattern)) {
     if (xsg_regex_check(pattern.data(), pattern.size(), flags & XSG_FLAG_IGNORE_CASE, nullptr, nullptr) != XSG_OK)
       throw std::invalid_argument("xs::extern_search: '" + pattern +
@@ -433,6 +437,7 @@ class ExternSearcher {
     xsg_job_opts o;
     xsg_job_opts_init(&o);
     o.pattern_flags = detail::pattern_flags(pattern, ignore_case);
+    o.pattern_is_list = detail::pattern_is_list() ? 1u : 0u;
     o.mode = detail::traits<Tag>::mode;
     detail::require_line_tag(o.pattern_flags, o.mode);
     const uint32_t context = detail::context_flags(o.mode);

@@ -38,7 +38,9 @@ extern "C" {
 
 /* 3: xsg_shard_invalidate and xsg_result_lines_view joined (round 3); 4: xsg_count_async_status joined, XSG_MAX_PATTERN
  * grew and the line tags accept a literal that contains '\n' (round 4); still 4: XSG_FLAG_INVERT, XSG_MATCHES,
- * XSG_FLAG_CONTEXT and xsg_result_context_edges joined; nothing was removed or changed in meaning */
+ * XSG_FLAG_CONTEXT and xsg_result_context_edges joined; xsg_set_literals, xsg_literals_info, xsg_host_searcher_create_list
+ * and xsg_job_opts.pattern_is_list joined (the structure grew: see there for what that asks of a program built before);
+ * no entry point was removed or changed in meaning */
 #define XSG_ABI_VERSION 4
 
 /* ---- status codes ------------------------------------------------------- */
@@ -198,6 +200,10 @@ enum xsg_mode {
  * expression (XSG_FLAG_REGEX) is at most XSG_MAX_REGEX bytes of text. */
 #define XSG_MAX_PATTERN 32768u
 #define XSG_MAX_REGEX 1024u
+/* A literal LIST (xsg_set_literals): at most XSG_MAX_PATTERN bytes in all, XSG_MAX_LITERALS literals, each of
+ * 1..XSG_MAX_LITERAL_BYTES bytes. */
+#define XSG_MAX_LITERALS 4096u
+#define XSG_MAX_LITERAL_BYTES 255u
 
 /* ---- counters written by the count entry points --------------------------- */
 #define XSG_CTR_MATCHES 0  /* XSG_COUNT_MATCHES result */
@@ -245,6 +251,42 @@ void xsg_ctx_destroy(xsg_ctx* ctx);
  * XSG_COUNT_LINES for such a pattern (XSG_ENOTSUP: use xsg_count).  A regular EXPRESSION that can match '\n' keeps
  * to XSG_COUNT_MATCHES / XSG_MATCH_BYTE_OFFSETS (the line modes return XSG_ENOTSUP for it). */
 int xsg_set_pattern(xsg_ctx* ctx, const void* pattern, size_t plen, uint32_t flags);
+/* A LIST of literals as the pattern (grep -F -e a -e b, grep -F -f words.txt): the counterpart of xsg_set_pattern, and
+ * like it a failed call leaves the context without a pattern.  `list` holds the literals l1 .. lk separated by '\n' --
+ * the format of a grep -f file; one final '\n' is allowed.  Limits (XSG_EINVAL, never approximated): 1..XSG_MAX_PATTERN
+ * bytes in all, 1..XSG_MAX_LITERALS literals, each 1..XSG_MAX_LITERAL_BYTES bytes of any value but '\n'; an EMPTY literal
+ * ("a\n\nb", a leading '\n') is refused: grep lets it match every line, and that is not served.  Duplicates are allowed.
+ * Under flags F the search is BY DEFINITION the one XSG_FLAG_REGEX | F performs for esc(l1)|esc(l2)|...|esc(lk), esc
+ * backslash-escaping ASCII punctuation -- for every tag and every other flag, without that route's size limits and
+ * without RE2's code-point reading (a literal is bytes).  That is:
+ *   leftmost-first  at the leftmost position where any literal occurs, the FIRST-LISTED literal that occurs there is the
+ *                   match (("ab","abc") on "abcd" matches "ab"; GNU grep -o would print the longest), and the walk
+ *                   resumes at its end; XSG_MATCHES reports that literal's bytes and length;
+ *   exact           up to the chunk's end, as the regex routes are: XSG_FLAG_EXACT_TAIL is accepted and changes nothing;
+ *   XSG_FLAG_IGNORE_CASE folds ASCII letters on both sides, reported bytes keep their case;
+ *   XSG_FLAG_INVERT, XSG_FLAG_CONTEXT work as for any pattern that cannot match '\n' (a list never can);
+ *   XSG_FLAG_REGEX  together with a list is XSG_EINVAL.
+ * Afterwards xsg_count, xsg_count_begin / _end (done synchronously inside _begin), xsg_search with every result accessor
+ * and xsg_result_context_edges serve the list on all seven tags.  xsg_count_async and xsg_count_async_status return
+ * XSG_ENOTSUP (the route fetches sizes from the device); a binding of 2^24 chunks or more is XSG_ENOTSUP.
+ * How: every position of the text is tested against a filter of 65 536 bits held in LDS -- one bit per hashed g-gram a
+ * literal starts with, g = min(shortest literal, 4) (k_set_scan) -- the candidates are verified against the literals in
+ * listing order (k_set_verify), and the walk and the list stages are the ones of every other pattern.  There is no
+ * density bail-out: a list that makes most positions candidates ("e", "th") is slow but exact. */
+int xsg_set_literals(xsg_ctx* ctx, const void* list, size_t n, uint32_t flags);
+/* Would xsg_set_literals accept this list, and what does it compile to?  Host only, needs no device (like
+ * xsg_regex_check).  XSG_OK or XSG_EINVAL with the reason in xsg_last_error().  `info` (optional) receives the numbers,
+ * `filter` (optional, XSG_LITERAL_FILTER_BYTES) the filter image: bit h of the little-endian uint32 words is set <=> some
+ * literal starts with a g-gram whose hash is h; the hash of a gram v (its g bytes, first byte lowest, folded under
+ * XSG_FLAG_IGNORE_CASE) is v for g <= 2 and (v * 0x9E3779B1 mod 2^32) >> 16 for g = 3, 4. */
+#define XSG_LITERAL_FILTER_BYTES 8192u
+typedef struct xsg_literal_list {
+  uint32_t count;            /* literals */
+  uint32_t min_len, max_len; /* shortest / longest, bytes */
+  uint32_t gram;             /* g = min(min_len, 4) */
+  uint32_t filter_bits_set;  /* of 65 536 */
+} xsg_literal_list;
+int xsg_literals_info(const void* list, size_t n, uint32_t flags, xsg_literal_list* info, uint8_t* filter);
 /* Would XSG_FLAG_REGEX accept this expression?  XSG_OK, or XSG_ENOTSUP with the
  * reason in xsg_last_error().  Needs no device (callers route on it the way the
  * reference routes on use_str_as_regex, utils/utils.h:17-25).  Optional outputs:
@@ -459,7 +501,13 @@ typedef struct xsg_job_opts {
   uint64_t chunk_bytes;     /* target chunk size without a metafile (default 16 MiB) */
   uint64_t chunk_begin;     /* search only chunks [chunk_begin, chunk_end) of the plan; 0,0 = all. */
   uint64_t chunk_end;       /* (how one rank of a multi-GPU job takes its contiguous range) */
+  uint32_t pattern_is_list; /* != 0: `pattern` of xsg_job_start is a literal list (xsg_set_literals).  Honoured only when
+                               struct_size covers it; xsg_job_opts_init zeroes it. */
 } xsg_job_opts;
+/* The structure grew by pattern_is_list (48 -> 56 bytes).  xsg_job_start still takes the 48-byte form from a caller that
+ * fills struct_size by hand.  xsg_job_opts_init cannot know its caller's size: it clears and stamps sizeof(xsg_job_opts)
+ * of the library it is in, so a program compiled against the 48-byte header that calls it must be rebuilt before it runs
+ * with this library. */
 
 typedef struct xsg_job_stats {
   uint64_t bytes_scanned;  /* uncompressed bytes handed to the GPU */
@@ -510,6 +558,9 @@ int xsg_job_stats_get(xsg_job* job, xsg_job_stats* stats);
 typedef struct xsg_host_searcher xsg_host_searcher;
 int xsg_host_searcher_create(int device, const void* pattern, size_t plen, uint32_t flags, int max_slots,
                              xsg_host_searcher** out);
+/* The same for a literal list (xsg_set_literals); every xsg_host_* call then works on it. */
+int xsg_host_searcher_create_list(int device, const void* list, size_t n, uint32_t flags, int max_slots,
+                                  xsg_host_searcher** out);
 void xsg_host_searcher_destroy(xsg_host_searcher* hs);
 /* search::count(data, pattern, skip_to_nl)  (search_wrappers.h:163-185) */
 int xsg_host_count(xsg_host_searcher* hs, const void* data, uint64_t len, int skip_to_nl, uint64_t* count);
@@ -614,15 +665,18 @@ int xsg_ctx_info(xsg_ctx* ctx, char* arch, size_t arch_cap, int* compute_units, 
 /* Time the dominant kernel alone: runs the bulk scan kernel of the given count
  * mode `iters` times back to back on the ctx stream between two HIP events and
  * returns the average milliseconds per launch (bench.py's roofline figure). */
+/* (A literal list: the candidate count pass, xsg::k_set_scan.) */
 int xsg_time_scan_kernel(xsg_shard* shard, uint32_t mode, int iters, float* avg_ms);
 /* Name of the bulk-kernel instantiation the next pass of `mode` launches on this shard with the current pattern
  * ("xsg::k_scan<KIND, WANT_NL, WANT_LINES, EMIT, LOADS, ICASE> stagger=N"): what a profile of that pass shows.
  * " gated by xsg::k_sketch (512 B/tile)" follows when that pass would run behind the binding's sketch: this
- * instantiation on a bounded grid, which selects the candidate tiles and scans them. */
+ * instantiation on a bounded grid, which selects the candidate tiles and scans them.  A literal list:
+ * "xsg::k_set_scan<EMIT, ICASE> g=N + xsg::k_set_verify". */
 int xsg_scan_kernel_name(xsg_shard* shard, uint32_t mode, char* out, size_t cap);
 /* Measure and fix the bulk kernel's wave stagger for this shard, the current pattern and `mode` (a handful of
  * launches; replaces the per-variant default until the shard is destroyed or tuned again).  *chosen (optional)
- * receives the value, or UINT32_MAX when the default was kept (shard under 1 GiB, or XSG_TUNE set).
+ * receives the value, or UINT32_MAX when the default was kept (shard under 1 GiB, XSG_TUNE set, an expression of
+ * variable length or a literal list: their kernels have no stagger).
  * A caller that tunes is investing in the binding: for a plain count mode and a pattern the sketch serves, the
  * binding's sketch is built first (bindings of 64 MiB and more: about two full scans' worth of time, once), and the
  * sweep then times the kernel the later passes launch, gated where the gate pays. */

@@ -2,6 +2,7 @@
 // on the MI355X engine, without boost::program_options.
 //
 //   xsgrep [-c] [-i] [-o] [-v] [-E|-F] [-x] [-A N] [-B N] [-C N] [-j THREADS] [-m METAFILE] PATTERN FILE|-
+//   xsgrep -F [-c] [-i] [-o] [-v] [-A N] [-B N] [-C N] [-j THREADS] [-m METAFILE] (-e PATTERN)... [-f FILE]... FILE|-
 //
 // -c  print only a count of matching lines   (grep.cpp:45-46 -> xs::count_lines)
 // -i  ignore ASCII case                      (grep.cpp:47-48)
@@ -18,6 +19,12 @@
 //     XSG_FLAG_CONTEXT), every line once, in file order, as GNU grep does with --no-group-separator: no `--` lines.
 //     N is at most 4095.  With -c or -o the numbers are accepted and change nothing, as in grep.  Not with `-` (stdin):
 //     the chunks read from a pipe are searched on their own.  (-m is the METAFILE here, not grep's --max-count.)
+// -e PATTERN (repeatable), -f FILE (one literal per line, repeatable)  search for ANY of several literals (XS_PATTERN_LIST ->
+//     xsg_set_literals).  They take PATTERN's place.  More than one pattern requires -F and excludes -x; a single -e equals
+//     the positional PATTERN.  They combine with -c -i -o -v -A/-B/-C and with stdin.  -o with several patterns is
+//     leftmost-FIRST in listing order: at a position where several literals occur the first-listed one is printed (-e ab
+//     -e abc prints `ab` for `abc`); GNU grep prints the longest.  An empty pattern among several is refused (grep lets
+//     it match every line).
 // The one-letter options without an argument may be bundled (-vc, -ci, -oi).
 // otherwise print the matching lines, live, as they are found (grep.cpp:74-79).
 #include <xsearch/tasks/gpu_searchers.h>
@@ -26,12 +33,17 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <fstream>
 #include <iostream>
+#include <sstream>
 #include <string>
 #include <vector>
 
 static const char kUsage[] =
     "usage: %s [-c] [-i] [-o] [-v] [-E|-F] [-x] [-A N] [-B N] [-C N] [-j THREADS] [-m METAFILE] PATTERN FILE|-\n"
+    "       %s -F [-c] [-i] [-o] [-v] [-A N] [-B N] [-C N] [-j THREADS] [-m METAFILE] (-e PATTERN)... [-f FILE]... FILE|-\n"
+    "  -e PATTERN, -f FILE (one literal per line) search for any of several literals; both may repeat, need -F and exclude -x\n"
+    "     when they give more than one pattern; -o then prints the FIRST-listed literal that occurs at a position (GNU grep: the longest)\n"
     "  -A N, -B N, -C N also print N lines after / before / around every selected line (N <= 4095), each line once and\n"
     "     without group separators; nothing changes under -c and -o; not with FILE = -\n"
     "  -o, --only-matching prints only the matched text, every match on its own line (not with -v)\n"
@@ -72,6 +84,8 @@ int main(int argc, char** argv) {
   int threads = 2;  // grep.cpp:21
   long before = 0, after = 0;
   std::string meta, pattern, file;
+  std::vector<std::string> patterns;  // -e / -f: they take PATTERN's place
+  bool have_patterns = false;
   int pos = 0;
   std::vector<std::string> args;
   for (int i = 1; i < argc; ++i) {  // -vc -> -v -c (only letters that take no argument; anything else stays one word)
@@ -111,23 +125,76 @@ int main(int argc, char** argv) {
       threads = std::atoi(args[++i].c_str());
     } else if ((a == "-m" || a == "--meta") && i + 1 < nargs) {
       meta = args[++i];
+    } else if ((a == "-e" || a == "--regexp") && i + 1 < nargs) {
+      patterns.push_back(args[++i]);
+      have_patterns = true;
+    } else if ((a == "-f" || a == "--file") && i + 1 < nargs) {
+      std::ifstream in(args[++i], std::ios::binary);
+      if (!in) {
+        std::fprintf(stderr, "xsgrep: cannot read the pattern file '%s'\n", args[i].c_str());
+        return 2;
+      }
+      std::stringstream all;
+      all << in.rdbuf();
+      std::string text = all.str();
+      if (!text.empty() && text.back() == '\n') text.pop_back();  // the last line's newline ends it, it opens no empty pattern
+      for (size_t at = 0;;) {  // (an empty file holds no pattern: grep -f /dev/null matches nothing)
+        if (text.empty()) break;
+        const size_t nl = text.find('\n', at);
+        patterns.push_back(text.substr(at, nl == std::string::npos ? std::string::npos : nl - at));
+        if (nl == std::string::npos) break;
+        at = nl + 1;
+      }
+      have_patterns = true;
     } else if (a == "-h" || a == "--help") {
-      std::printf(kUsage, argv[0]);
+      std::printf(kUsage, argv[0], argv[0]);
       return 0;
-    } else if (pos == 0) {
+    } else if (pos == 0 && !have_patterns) {
       pattern = a;
       ++pos;
-    } else if (pos == 1) {
+    } else if (pos <= 1 && file.empty()) {
       file = a;
-      ++pos;
+      pos = 2;
     } else {
       std::fprintf(stderr, "unexpected argument '%s'\n", a.c_str());
       return 2;
     }
   }
+  if (have_patterns && !pattern.empty()) {  // (PATTERN was read before the first -e / -f: it is the FILE)
+    if (!file.empty()) {
+      std::fprintf(stderr, "unexpected argument '%s'\n", file.c_str());
+      return 2;
+    }
+    file = pattern;
+    pattern.clear();
+    pos = 2;
+  }
   if (pos != 2) {
-    std::fprintf(stderr, kUsage, argv[0]);
+    std::fprintf(stderr, kUsage, argv[0], argv[0]);
     return 2;
+  }
+  bool list = false;
+  if (have_patterns) {
+    if (patterns.empty()) {
+      std::fprintf(stderr, "xsgrep: -f: the pattern file holds no pattern\n");
+      return 2;
+    }
+    if (patterns.size() == 1) {
+      pattern = patterns[0];  // a single -e equals the positional PATTERN
+    } else {
+      if (!fixed || whole_lines) {
+        std::fprintf(stderr, "xsgrep: more than one pattern (-e / -f) is served as a list of literals: it needs -F and excludes -x\n");
+        return 2;
+      }
+      for (const std::string& p : patterns) {
+        if (p.empty() || p.find('\n') != std::string::npos) {
+          std::fprintf(stderr, "xsgrep: an empty pattern (or one with a newline) among several is not served\n");
+          return 2;
+        }
+        pattern += (pattern.empty() ? "" : "\n") + p;
+      }
+      list = true;
+    }
   }
   if (fixed && extended) {
     std::fprintf(stderr, "xsgrep: -E and -F exclude each other\n");
@@ -155,6 +222,7 @@ int main(int argc, char** argv) {
     }
     extended = true, fixed = false;
   }
+  if (list) setenv("XS_PATTERN_LIST", "1", 1);
   if (fixed) setenv("XS_FORCE_LITERAL", "1", 1);
   if (extended) setenv("XS_FORCE_REGEX", "1", 1);
   if (invert) setenv("XS_INVERT_MATCH", "1", 1);
@@ -167,9 +235,9 @@ int main(int argc, char** argv) {
       // read newline-aligned chunks here and hand each to the reference-style searcher functors
       // (include/xsearch/tasks/gpu_searchers.h), like Searcher::run_thread does with a reader.
       const uint32_t flags = xs::detail::pattern_flags(pattern, icase);
-      xs::GpuLineSearcher<std::vector<char>> lines(pattern, 0, 1, flags);
-      xs::GpuMatchSearcher<std::vector<char>> matches(pattern, 0, 1, flags);
-      xs::GpuCountSearcher<std::vector<char>> counter(pattern, true, 0, 1, flags);
+      xs::GpuLineSearcher<std::vector<char>> lines(pattern, 0, 1, flags, list);
+      xs::GpuMatchSearcher<std::vector<char>> matches(pattern, 0, 1, flags, list);
+      xs::GpuCountSearcher<std::vector<char>> counter(pattern, true, 0, 1, flags, list);
       const size_t target = 16u << 20;
       std::vector<char> buf;  // bytes read and not searched yet
       size_t want = target;

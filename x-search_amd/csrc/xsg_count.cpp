@@ -53,6 +53,7 @@ static bool sketch_enabled() {
   return !(e && *e == '0');
 }
 // the context's pattern is one the gate serves: a case-sensitive literal of 4 bytes and more
+// (not kSet: a tile would have to lack the grams of EVERY literal, and the list route runs no k_scan to gate)
 static bool sketch_pattern(const xsg_ctx* c) {
   const uint32_t k = c->pat.kind;
   return (k == kOne || k == kMask2 || k == kTwo || k == kLong) && !c->pat.icase && c->sketch_hashes.size() + 3 == c->pat.plen;
@@ -223,6 +224,7 @@ static bool is_window_kind(uint32_t k) { return k == kTwo || k == kLong || k == 
 // take microseconds either way); XSG_HOT pins the choice.
 int xsg::choose_hot_filter(xsg_shard* s, hipStream_t st, bool want_nl, bool want_lines) {
   xsg_ctx* c = s->ctx;
+  // (kSet is no window kind: k_set_scan has one filter, the list's, and nothing to choose between)
   if (!is_window_kind(c->pat.kind) || c->hot_env >= 0) return XSG_OK;
   const uint32_t v = scan_variant(want_nl, want_lines);
   const bool first = s->hot_serial != c->pattern_serial;  // nothing measured for this pattern on this binding yet
@@ -573,6 +575,8 @@ static int count_async_impl(xsg_shard* s, uint32_t mode, void* stream, uint64_t*
   xsg_ctx* c = s->ctx;
   HIP_TRY(hipSetDevice(c->device));
   hipStream_t st = stream ? static_cast<hipStream_t>(stream) : c->stream;
+  if (c->pat.kind == kSet)  // (no sketch, no hot-filter probe, no one-pass count either: candidates are verified from a fetched size)
+    return fail(XSG_ENOTSUP, "a literal list fetches sizes from the device: the stream-ordered counts do not serve it, xsg_count() does");
   if (m == XSG_COUNT_MATCHES && inverted(c)) return fail(XSG_ENOTSUP, "%s", kInvertMatchMsg);
   if (m == XSG_COUNT_MATCHES) {
     if (c->bordered && !overlap_free_known(s)) {  // (known from an earlier synchronous call: this entry point may not wait)
@@ -726,7 +730,8 @@ extern "C" int xsg_time_scan_kernel(xsg_shard* s, uint32_t mode, int iters, floa
   HIP_TRY(hipSetDevice(c->device));
   const uint32_t m = mode & 0xffu;
   const bool want_nl = (mode & XSG_WITH_NEWLINES) != 0;
-  const bool want_lines = m == XSG_COUNT_LINES;
+  // (a literal list: the candidate count pass, which builds no line summaries)
+  const bool want_lines = m == XSG_COUNT_LINES && c->pat.kind != kSet;
   if (want_nl) XSG_TRY(ensure_tile_nl(s));
   XSG_TRY(choose_hot_filter(s, c->stream, want_nl, want_lines));  // time what a real pass of this mode would launch
   XSG_TRY(sketch_before_pass(s, c->stream, !want_nl && !want_lines, true, false));  // (its verdict; a timing loop builds none)
@@ -753,7 +758,9 @@ extern "C" int xsg_scan_kernel_name(xsg_shard* s, uint32_t mode, char* out, size
                        (XSG_CONTEXT_BEFORE(s->ctx->flags) != 0 || XSG_CONTEXT_AFTER(s->ctx->flags) != 0);
   const bool want_nl = ((mode & XSG_WITH_NEWLINES) != 0 || m == XSG_LINE_INDICES || context) && !s->nl_cached;
   ScanArgs a = scan_args(s, scan_variant(want_nl, !list && m == XSG_COUNT_LINES));
-  if (use_prefilter(s, false)) {  // what xsg_count / xsg_search launch: the candidate scan, then the automaton at candidates
+  if (s->ctx->pat.kind == kSet) {  // a literal list: the candidate scan and its verifier, for every mode
+    describe_scan(a, want_nl, false, false, out, cap);
+  } else if (use_prefilter(s, false)) {  // what xsg_count / xsg_search launch: the candidate scan, then the automaton at candidates
     a.pat = s->ctx->pre_pat;
     a.pat.hot = 0;
     char inner[160];
@@ -792,7 +799,7 @@ extern "C" int xsg_shard_tune(xsg_shard* s, uint32_t mode, uint32_t* chosen) {
     XSG_TRY(sketch_before_pass(s, c->stream, true, true, false));
   }
   if (c->tune != kTuneAuto || s->total_bytes < (1ull << 30)) return XSG_OK;  // XSG_TUNE wins; too small to measure
-  if (c->pat.kind == kDfa) return XSG_OK;  // k_rx_scan has no stagger
+  if (c->pat.kind == kDfa || c->pat.kind == kSet) return XSG_OK;  // k_rx_scan and k_set_scan have no stagger
   static const uint32_t cand[] = {0, 4, 8, 10, 12, 14, 16, 20};
   float best_ms = 0;
   uint32_t best = kTuneAuto, best_hot = 0;

@@ -136,6 +136,7 @@ extern "C" int xsg_ctx_create(int device, xsg_ctx** out) {
   if (warm_all) {
     if (e == hipSuccess) e = warm_list_kernels(c->stream);
     if (e == hipSuccess) e = warm_rx_kernels(c->stream);
+    if (e == hipSuccess) e = warm_set_kernels(c->stream);
   }
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
   XSG_TRACE("ctx_create: warm-up synchronised");

@@ -470,6 +470,16 @@ struct Partial {
 // library (tests/cpp: the sanitizer binaries, against a stand-in that knows nothing of context), and a context job is
 // then refused at its start.
 extern "C" int xsg_result_context_edges(xsg_shard* shard, xsg_context_edge* out, uint64_t cap_chunks) __attribute__((weak));
+// ... and of a literal list (xsg_job_opts.pattern_is_list, xsg_host_searcher_create_list), the same way
+extern "C" int xsg_set_literals(xsg_ctx* ctx, const void* list, size_t n, uint32_t flags) __attribute__((weak));
+extern "C" int xsg_literals_info(const void* list, size_t n, uint32_t flags, xsg_literal_list* info, uint8_t* filter) __attribute__((weak));
+static const char kNoListMsg[] = "this build holds no device side for literal lists";
+// the pattern of a worker or a slot: a literal list where the caller said so
+static int set_job_pattern(xsg_ctx* ctx, const std::vector<uint8_t>& pattern, uint32_t flags, bool is_list) {
+  if (!is_list) return xsg_set_pattern(ctx, pattern.data(), pattern.size(), flags);
+  if (!xsg_set_literals) return xsg::fail(XSG_ENOTSUP, "%s", kNoListMsg);
+  return xsg_set_literals(ctx, pattern.data(), pattern.size(), flags);
+}
 static bool context_flags(uint32_t flags) { return XSG_CONTEXT_BEFORE(flags) != 0 || XSG_CONTEXT_AFTER(flags) != 0; }
 // the tags whose list context widens (every other tag ignores the bits)
 static bool context_mode(uint32_t mode) { return mode == XSG_LINE_BYTE_OFFSETS || mode == XSG_LINE_INDICES || mode == XSG_LINES; }
@@ -694,7 +704,7 @@ static int lane_prepare(xsg_job* j, Slot& s, int k) {
     XSG_TRY(xsg_shard_create(l.ctx, nullptr, 0, nullptr, 0, &l.shard));
     XSG_TRACE("slot: lane %d ctx + shard created", k);
   }
-  XSG_TRY(xsg_set_pattern(l.ctx, j->pattern.data(), j->pattern.size(), j->opts.pattern_flags));
+  XSG_TRY(set_job_pattern(l.ctx, j->pattern, j->opts.pattern_flags, j->opts.pattern_is_list != 0));
   if (need > l.cap) {
     if (l.dev) (void)hipFree(l.dev);
     l.dev = nullptr;
@@ -1232,7 +1242,20 @@ static int job_start_impl(const void* pattern, size_t plen, const char* file_pat
   XSG_TRACE("job: start");
   if (!out) return fail(XSG_EINVAL, "out is null");
   *out = nullptr;
-  if (!opts || opts->struct_size != sizeof(xsg_job_opts)) return fail(XSG_EINVAL, "bad xsg_job_opts (struct_size)");
+  // the structure grew by pattern_is_list behind chunk_end: the older size is still taken from a caller that stamps
+  // struct_size itself (one that goes through xsg_job_opts_init gets this library's size and must be rebuilt: xsg.h)
+  constexpr uint32_t kOptsSizeV1 = offsetof(xsg_job_opts, chunk_end) + sizeof(uint64_t);
+  if (!opts || (opts->struct_size != sizeof(xsg_job_opts) && opts->struct_size != kOptsSizeV1))
+    return fail(XSG_EINVAL, "bad xsg_job_opts (struct_size)");
+  xsg_job_opts known;
+  memset(&known, 0, sizeof known);
+  memcpy(&known, opts, opts->struct_size);
+  opts = &known;
+  const bool is_list = known.pattern_is_list != 0;
+  if (is_list) {  // refuse a bad list here, not in a worker
+    if (!xsg_literals_info) return fail(XSG_ENOTSUP, "%s", kNoListMsg);
+    XSG_TRY(xsg_literals_info(pattern, plen, opts->pattern_flags, nullptr, nullptr));
+  }
   if (!pattern || plen == 0 || plen > XSG_MAX_PATTERN) return fail(XSG_EINVAL, "pattern must be 1..%u bytes",
                                                                   XSG_MAX_PATTERN);
   if ((opts->pattern_flags & XSG_FLAG_REGEX) && plen > XSG_MAX_REGEX) return fail(XSG_EINVAL, "expression longer than %u bytes", XSG_MAX_REGEX);
@@ -1241,13 +1264,13 @@ static int job_start_impl(const void* pattern, size_t plen, const char* file_pat
   const bool line_mode = opts->mode != XSG_COUNT_MATCHES && opts->mode != XSG_MATCH_BYTE_OFFSETS && opts->mode != XSG_MATCHES;
   if (opts->pattern_flags & XSG_FLAG_INVERT) {  // (xsg.h: the line tags only, and no pattern that can match '\n')
     if (!line_mode) return fail(XSG_ENOTSUP, "XSG_FLAG_INVERT: an inverted search reports lines without a match; the match tags have no inverted form");
-    if (!(opts->pattern_flags & XSG_FLAG_REGEX) && memchr(pattern, '\n', plen))
+    if (!is_list && !(opts->pattern_flags & XSG_FLAG_REGEX) && memchr(pattern, '\n', plen))
       return fail(XSG_ENOTSUP, "XSG_FLAG_INVERT: an inverted search does not accept a pattern that can match '\\n'");
   }
   const bool context = context_flags(opts->pattern_flags);
   static const char kContextNlMsg[] = "XSG_FLAG_CONTEXT: a search with context lines does not accept a pattern that can match '\\n'";
   if (context) {  // (xsg.h: xsg_set_pattern refuses such a pattern whatever the tag; here, not in a worker)
-    if (!(opts->pattern_flags & XSG_FLAG_REGEX) && memchr(pattern, '\n', plen)) return fail(XSG_ENOTSUP, "%s", kContextNlMsg);
+    if (!is_list && !(opts->pattern_flags & XSG_FLAG_REGEX) && memchr(pattern, '\n', plen)) return fail(XSG_ENOTSUP, "%s", kContextNlMsg);
     if (context_mode(opts->mode) && !xsg_result_context_edges)
       return fail(XSG_ENOTSUP, "XSG_FLAG_CONTEXT: this build holds no device side for context lines");
   }
@@ -1551,6 +1574,7 @@ struct xsg_host_searcher {
   int device = 0;
   std::vector<uint8_t> pattern;
   uint32_t flags = 0;
+  bool is_list = false;  // xsg_host_searcher_create_list
   int max_slots = 1;
   std::mutex mu;
   std::condition_variable cv;
@@ -1571,7 +1595,7 @@ static int host_slot_acquire(xsg_host_searcher* hs, HostSlot** out) {
       HostSlot* s = hs->all.back().get();
       lk.unlock();
       int r = xsg_ctx_create(hs->device, &s->ctx);
-      if (r == XSG_OK) r = xsg_set_pattern(s->ctx, hs->pattern.data(), hs->pattern.size(), hs->flags);
+      if (r == XSG_OK) r = set_job_pattern(s->ctx, hs->pattern, hs->flags, hs->is_list);
       if (r == XSG_OK) r = xsg_shard_create(s->ctx, nullptr, 0, nullptr, 0, &s->shard);
       if (r != XSG_OK) {
         // give the place back, or later callers would wait for a slot that never comes
@@ -1626,13 +1650,18 @@ static int host_stage(HostSlot* s, const void* data, uint64_t len) {
   return xsg_shard_rebind(s->shard, s->dev, s->cap, &ch, 1);
 }
 
-extern "C" int xsg_host_searcher_create(int device, const void* pattern, size_t plen, uint32_t flags, int max_slots,
-                                        xsg_host_searcher** out) {
+static int host_searcher_create(int device, const void* pattern, size_t plen, uint32_t flags, bool is_list, int max_slots,
+                                xsg_host_searcher** out) {
   if (!out) return fail(XSG_EINVAL, "out is null");
   *out = nullptr;
   if (!pattern || plen == 0 || plen > XSG_MAX_PATTERN) return fail(XSG_EINVAL, "pattern must be 1..%u bytes",
                                                                   XSG_MAX_PATTERN);
-  if (flags & XSG_FLAG_REGEX) XSG_TRY(xsg_regex_check(pattern, plen, flags & XSG_FLAG_IGNORE_CASE, nullptr, nullptr));
+  if (is_list) {
+    if (!xsg_literals_info) return fail(XSG_ENOTSUP, "%s", kNoListMsg);
+    XSG_TRY(xsg_literals_info(pattern, plen, flags, nullptr, nullptr));
+  } else if (flags & XSG_FLAG_REGEX) {
+    XSG_TRY(xsg_regex_check(pattern, plen, flags & XSG_FLAG_IGNORE_CASE, nullptr, nullptr));
+  }
   int ndev = 0;
   XSG_TRY(xsg_device_count(&ndev));
   if (device < 0 || device >= ndev) return fail(XSG_ENODEV, "device %d out of range", device);
@@ -1641,6 +1670,7 @@ extern "C" int xsg_host_searcher_create(int device, const void* pattern, size_t 
   hs->device = device;
   hs->pattern.assign((const uint8_t*)pattern, (const uint8_t*)pattern + plen);
   hs->flags = flags;
+  hs->is_list = is_list;
   hs->max_slots = max_slots < 1 ? 1 : max_slots;
   // build the first slot now so that a bad pattern / missing GPU fails here, not in the first search
   HostSlot* s = nullptr;
@@ -1648,6 +1678,16 @@ extern "C" int xsg_host_searcher_create(int device, const void* pattern, size_t 
   host_slot_release(hs.get(), s);
   *out = hs.release();
   return XSG_OK;
+}
+
+extern "C" int xsg_host_searcher_create(int device, const void* pattern, size_t plen, uint32_t flags, int max_slots,
+                                        xsg_host_searcher** out) {
+  return host_searcher_create(device, pattern, plen, flags, false, max_slots, out);
+}
+
+extern "C" int xsg_host_searcher_create_list(int device, const void* list, size_t n, uint32_t flags, int max_slots,
+                                             xsg_host_searcher** out) {
+  return host_searcher_create(device, list, n, flags, true, max_slots, out);
 }
 
 extern "C" void xsg_host_searcher_destroy(xsg_host_searcher* hs) { delete hs; }

@@ -44,6 +44,8 @@ bool newline_literal(const xsg_ctx* c);
 int ensure_factor_mask(xsg_shard* s);
 // `pre_off`: the caller must not take the prefilter route (run_list: its candidates were dense or outran their budget)
 bool use_prefilter(const xsg_shard* s, bool pre_off);
+// XSG_ENOTSUP where the candidate route cannot serve a literal list on this binding (2^24 chunks and more)
+int set_route_serves(const xsg_shard* s);
 // The tail zone of every chunk: its buffers sized for this binding and pattern, *tail_cap = entries per chunk.
 int ensure_tail_buffers(xsg_shard* s, uint32_t* tail_cap);
 // What every list kernel's arguments share: the shard, the scan's emitted list (a.m_pos / a.m_chunk / a.tile_off) and

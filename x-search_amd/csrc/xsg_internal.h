@@ -45,8 +45,10 @@ enum FilterKind : int {
                // then every position against its 256-bit set (d_pat holds the sets, 32 bytes per position)
   kClassFast = 7,  // instantiation only (PatternDev::kind stays kClass): a class sequence whose window takes the exact
                    // 16 + 32 bit compare (PatternDev::cls_fast), window filter
-  kDfa = 6     // variable-length expression (xsg_regex.h): k_rx_scan walks every line with a byte-class DFA; d_pat holds
+  kDfa = 6,    // variable-length expression (xsg_regex.h): k_rx_scan walks every line with a byte-class DFA; d_pat holds
                // class_of[256], the forward table, the reverse table (uint16 row offsets)
+  kSet = 8     // a list of literals (xsg_set.h): k_set_scan finds the positions whose g-gram is in the filter, k_set_verify
+               // decides them; d_pat holds the filter (8 KiB) and the verify table.  Always on the candidate route.
 };
 
 struct PatternDev {
@@ -88,6 +90,10 @@ struct PatternDev {
                                    // ANCHORED automaton, walked from each line start (and each match end), never skipping;
                                    // rx_eol -- it runs over BODY '\n', a '\n' is stepped at the chunk's end, at most one
                                    // match per line, ending one byte before the last accepting position
+  // kSet (plen = the shortest literal; exact_tail = 1; icase: the data is folded, the literals are folded on the host)
+  uint32_t set_g;                  // gram length, 1..4
+  uint32_t set_ngrams;             // distinct grams = entries of the sorted key array
+  uint32_t set_keys, set_first, set_ent, set_bytes;  // byte offsets of the verify table's arrays inside d_pat (xsg_set.h: SetTable)
 };
 
 // Per-tile line summaries (XSG_COUNT_LINES): see xsg_linesum.h.
@@ -224,6 +230,12 @@ struct RxPreArgs {
 };
 hipError_t launch_rx_verify_keep(const RxPreArgs& a, hipStream_t s);
 hipError_t launch_rx_compact(const RxPreArgs& a, hipStream_t s);
+// kSet (xsg_set_kernels.hip): k_set_scan with k_scan's ScanArgs and per-tile outputs (tile_cnt of every tile, tile_nl if
+// want_nl; emit: m_pos / m_chunk ascending) on a bounded grid; k_set_verify in k_rx_verify's place (c_len per candidate)
+hipError_t launch_set_count(const ScanArgs& a, bool want_nl, hipStream_t s);
+hipError_t launch_set_emit(const ScanArgs& a, hipStream_t s);
+hipError_t launch_set_verify(const RxPreArgs& a, hipStream_t s);
+void describe_set_scan(const ScanArgs& a, bool emit, char* out, size_t cap);
 // "xsg::k_scan<KIND, WANT_NL, WANT_LINES, EMIT, LOADS, ICASE>" + the stagger launch_scan would use, for reports
 void describe_scan(const ScanArgs& a, bool want_nl, bool want_lines, bool emit, char* out, size_t cap);
 
@@ -451,6 +463,7 @@ hipError_t launch_context_emit(const ContextArgs& a, hipStream_t s);   // o_pos,
 hipError_t warm_scan_kernels(hipStream_t s);
 hipError_t warm_list_kernels(hipStream_t s);
 hipError_t warm_rx_kernels(hipStream_t s);
+hipError_t warm_set_kernels(hipStream_t s);
 // one-sync route: the line index of every entry by one wave per entry (sparse lists: no prefix pass over the entries)
 hipError_t launch_line_index_waves(const LineOutArgs& a, hipStream_t s);
 

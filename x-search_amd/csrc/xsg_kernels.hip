@@ -1338,6 +1338,7 @@ static uint32_t pick_stagger(const ScanArgs& a, bool want_nl, bool want_lines, b
 void describe_scan(const ScanArgs& a, bool want_nl, bool want_lines, bool emit, char* out, size_t cap) {
   if (!out || !cap) return;
   const char* b[2] = {"false", "true"};
+  if (a.pat.kind == kSet) return describe_set_scan(a, emit, out, cap);
   if (a.pat.kind == kDfa) {
     // count passes: one wave per 4 KiB span (k_rx_count); the emit pass: the tile-cooperative k_rx_scan
     static const char* const rw = getenv("XSG_RX_WAVE");
@@ -1394,10 +1395,12 @@ static hipError_t launch_scan(const ScanArgs& a_in, bool want_nl, bool want_line
 
 hipError_t launch_scan_count(const ScanArgs& a, bool want_nl, bool want_lines, hipStream_t s) {
   if (a.pat.kind == kDfa) return launch_rx_count(a, want_nl, want_lines, s);
+  if (a.pat.kind == kSet) return want_lines ? hipErrorInvalidValue : launch_set_count(a, want_nl, s);  // (candidates; no line summaries)
   return launch_scan(a, want_nl, want_lines, false, s);
 }
 hipError_t launch_scan_emit(const ScanArgs& a, hipStream_t s) {
   if (a.pat.kind == kDfa) return launch_rx_emit(a, s);
+  if (a.pat.kind == kSet) return launch_set_emit(a, s);
   return launch_scan(a, false, false, true, s);
 }
 

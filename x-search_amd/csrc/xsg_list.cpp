@@ -19,7 +19,7 @@ static int d2h_u64(xsg_ctx* c, const uint64_t* d, uint64_t* h) {
 // XSG_FLAG_CONTEXT with a non-zero count (the line-list tags widen their list; every other tag ignores the bits)
 static bool context_on(const xsg_ctx* c) { return XSG_CONTEXT_BEFORE(c->flags) != 0 || XSG_CONTEXT_AFTER(c->flags) != 0; }
 
-bool xsg::newline_literal(const xsg_ctx* c) { return c->pat.has_newline && c->pat.kind != kClass && c->pat.kind != kDfa; }
+bool xsg::newline_literal(const xsg_ctx* c) { return c->pat.has_newline && c->pat.kind != kClass && c->pat.kind != kDfa && c->pat.kind != kSet; }
 
 // ---------------------------------------------------------------------------
 // argument blocks
@@ -85,7 +85,7 @@ static LineOutArgs line_out_args(const xsg_shard* s, const ScanArgs& a, const Li
 // not built where the factor turns out dense (most tiles would be marked) or the shard is small.
 int xsg::ensure_factor_mask(xsg_shard* s) {
   xsg_ctx* c = s->ctx;
-  if (c->pat.kind != kDfa || !c->rx_fac || s->ntiles == 0) return XSG_OK;
+  if (c->pat.kind != kDfa || !c->rx_fac || s->ntiles == 0) return XSG_OK;  // (kSet: no factor, no tile marks)
   if (s->mask_serial == c->pattern_serial || s->mask_dense_serial == c->pattern_serial) return XSG_OK;
   if (!c->rx_fac_forced && s->total_bytes < (512ull << 20)) return XSG_OK;
   hipStream_t st = c->stream;
@@ -134,11 +134,21 @@ int xsg::ensure_factor_mask(xsg_shard* s) {
   return XSG_OK;
 }
 
+// A literal list is served by the candidate route alone, whose walk keys a candidate by chunk number above 40 bits of offset.
+int xsg::set_route_serves(const xsg_shard* s) {
+  if (s->ctx->pat.kind == kSet && s->chunks.size() >= (1u << 24))
+    return fail(XSG_ENOTSUP, "a literal list is not served on a binding of 2^24 chunks or more");
+  return XSG_OK;
+}
+
 // The prefilter route is half a dozen kernels and three trips to the host where k_rx_scan is one pass: it pays on
 // shards where a pass takes longer than that (the file pipeline's 16 MiB chunks are walked by k_rx_scan in tens of
 // microseconds).
 bool xsg::use_prefilter(const xsg_shard* s, bool pre_off) {
   const xsg_ctx* c = s->ctx;
+  // a literal list has no other route: its candidates (k_set_scan) are always verified and walked here, on shards of
+  // any size and whatever their density (the entry points refuse a binding of 2^24 chunks and more: set_route_serves)
+  if (c->pat.kind == kSet) return true;
   return c->pat.kind == kDfa && c->rx_pre && !pre_off && (c->rx_pre_forced || s->total_bytes >= (512ull << 20)) &&
          s->chunks.size() < (1u << 24);  // k_rx_heads' keys: chunk number above 40 bits of offset
 }
@@ -173,6 +183,7 @@ static bool fast_route_serves(const xsg_shard* s, uint32_t mode, bool outputs, b
   if (c->flags & XSG_FLAG_INVERT) return false;                         // the complement stage sits on the exact route
   if (context_on(c) && mode != XSG_MATCH_BYTE_OFFSETS) return false;    // the widening stage sits on the exact route
   if (c->pat.kind == kDfa) return false;                                // k_rx_scan / the prefilter route: exact route
+  if (c->pat.kind == kSet) return false;                                // a literal list: the candidate route sits on the exact route
   if (mode != XSG_MATCH_BYTE_OFFSETS && c->pat.has_newline) return false;  // the line walk of a literal with '\n': a chain, exact route
   if (mode == XSG_MATCH_BYTE_OFFSETS && c->bordered && !overlap_free_known(s)) return false;  // greedy keep: exact route
   if (s->chunks.size() > (1u << 20)) return false;                      // the tail prefix is one workgroup's work
@@ -431,7 +442,8 @@ static int prefilter_candidates(xsg_shard* s, bool outputs, bool want_len, ScanA
   // lines once (k_rx_scan + finish, no list at all) than by listing, verifying and packing tens of millions of
   // entries -- measured on the bench corpus, where `Sher` is a lexicon word: count_lines of `lock(ed|s)?` 18 ms
   // by candidates against 10 ms by k_rx_scan (8 GiB).  The caller takes the other route.
-  if (!c->pat.rx_multiline && Mc * 128 > s->total_bytes) {
+  // (a literal list has no other route and no bail-out: dense candidates are slow but exact)
+  if (c->pat.kind != kSet && !c->pat.rx_multiline && Mc * 128 > s->total_bytes) {
     s->cnt_clean = false;
     s->pre_dense_serial = c->pattern_serial;  // later counts of this pattern on this binding go straight to k_rx_scan
     // a list: the same verdict (tens of millions of anchored scans, each up to 4 KiB, and chains between them, against
@@ -467,7 +479,8 @@ static int prefilter_candidates(xsg_shard* s, bool outputs, bool want_len, ScanA
   HIP_TRY(launch_rx_verify_keep(r, st));
   HIP_TRY(launch_exclusive_scan_u32(r.c_keep, s->d_c_pre.as<uint64_t>(), Mc, s->d_scan_tmp.as<uint64_t>(), st));
   uint32_t vflags = 0;
-  HIP_TRY(hipMemcpyAsync(&vflags, a.flags, 4, hipMemcpyDeviceToHost, st));
+  // (k_set_verify has no budget to outrun and raises nothing: a list's pass does not read the word at all)
+  if (c->pat.kind != kSet) HIP_TRY(hipMemcpyAsync(&vflags, a.flags, 4, hipMemcpyDeviceToHost, st));
   XSG_TRY(d2h_u64(c, s->d_c_pre.as<uint64_t>() + Mc, M));
   if (vflags & 2u) {  // a candidate outran the verification budget: walk the text once instead (the other route)
     HIP_TRY(hipMemsetAsync(a.flags, 0, 4, st));
@@ -837,7 +850,7 @@ int xsg::run_list(xsg_shard* s, uint32_t mode, bool outputs, bool want_nl_total,
   // XSG_MATCHES is the walk of XSG_MATCH_BYTE_OFFSETS up to the assembled list; only what leaves it differs
   const bool match_mode = mode == XSG_MATCH_BYTE_OFFSETS || mode == XSG_MATCHES;
   const bool line_mode = !match_mode;
-  const bool want_len = mode == XSG_MATCHES && c->pat.kind == kDfa;  // a length per emitted match (ScanArgs::m_len)
+  const bool want_len = mode == XSG_MATCHES && (c->pat.kind == kDfa || c->pat.kind == kSet);  // a length per emitted match (ScanArgs::m_len)
   // (the widening stage of XSG_FLAG_CONTEXT ranks lines by the per-tile newline counts)
   const bool want_nl = mode == XSG_LINE_INDICES || want_nl_total || (outputs && line_mode && context_on(c));
   const uint64_t nchunks = s->chunks.size();
@@ -854,6 +867,7 @@ int xsg::run_list(xsg_shard* s, uint32_t mode, bool outputs, bool want_nl_total,
   s->line_bytes = 0;
   s->fast_result = false;
   s->line_len_on_device = false;
+  XSG_TRY(set_route_serves(s));
   XSG_TRY(ensure_factor_mask(s));
 
   if (match_mode && c->bordered) XSG_TRY(ensure_overlap_check(s));
@@ -877,7 +891,7 @@ int xsg::run_list(xsg_shard* s, uint32_t mode, bool outputs, bool want_nl_total,
   }
   ScanArgs a = scan_args(s, scan_variant(scan_nl, false));
   const bool pre = use_prefilter(s, pre_off);  // candidates by the class-sequence matcher, then the automaton
-  if (pre) {
+  if (pre && c->pat.kind != kSet) {  // (a literal list's candidate scan is its own pattern's: k_set_scan)
     a.pat = c->pre_pat;
     a.pat.hot = 0;
     a.sketch = nullptr;

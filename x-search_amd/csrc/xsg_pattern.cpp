@@ -9,6 +9,7 @@
 
 #include "xsg_classseq.h"
 #include "xsg_regex.h"
+#include "xsg_set.h"
 #include "xsg_host.h"
 #include "xsg_sketch.h"
 
@@ -506,6 +507,60 @@ extern "C" int xsg_set_pattern(xsg_ctx* c, const void* pattern, size_t plen, uin
     return fail(XSG_ENOTSUP, "XSG_FLAG_CONTEXT: a search with context lines does not accept a pattern that can match '\\n'");
   }
   c->flags |= list_bits;
+  return XSG_OK;
+}
+
+// ---- a literal list (xsg_set.h) ---------------------------------------------------------------------------------------
+static int compile_list(const void* list, size_t n, uint32_t flags, xsg::SetProgram* prog) {
+  if (flags & XSG_FLAG_REGEX) return fail(XSG_EINVAL, "a literal list does not take XSG_FLAG_REGEX");
+  if (flags & ~(XSG_FLAG_EXACT_TAIL | XSG_FLAG_IGNORE_CASE | XSG_FLAG_INVERT | kContextBits))
+    return fail(XSG_EINVAL, "unknown pattern flags 0x%x", flags);
+  if (!list || n == 0) return fail(XSG_EINVAL, "empty literal list");
+  if (n > XSG_MAX_PATTERN) return fail(XSG_EINVAL, "literal list longer than %u bytes", XSG_MAX_PATTERN);
+  std::string err;
+  if (!xsg::compile_literal_set(static_cast<const uint8_t*>(list), n, (flags & XSG_FLAG_IGNORE_CASE) != 0, prog, &err))
+    return fail(XSG_EINVAL, "literal list: %s", err.c_str());
+  return XSG_OK;
+}
+
+extern "C" int xsg_literals_info(const void* list, size_t n, uint32_t flags, xsg_literal_list* info, uint8_t* filter) {
+  xsg::SetProgram prog;
+  XSG_TRY(compile_list(list, n, flags, &prog));
+  if (info) {
+    info->count = prog.count, info->min_len = prog.min_len, info->max_len = prog.max_len;
+    info->gram = prog.g, info->filter_bits_set = prog.filter_bits_set;
+  }
+  if (filter) memcpy(filter, prog.filter.data(), XSG_LITERAL_FILTER_BYTES);
+  return XSG_OK;
+}
+
+extern "C" int xsg_set_literals(xsg_ctx* c, const void* list, size_t n, uint32_t flags) {
+  if (!c) return fail(XSG_EINVAL, "ctx is null");
+  c->pattern.clear();  // a failed call leaves the context without a pattern
+  xsg::SetProgram prog;
+  XSG_TRY(compile_list(list, n, flags, &prog));
+  HIP_TRY(hipSetDevice(c->device));
+  uint32_t off[4];
+  const std::vector<uint8_t> blob = prog.blob(off);
+  XSG_TRY(upload_pattern_blob(c, c->d_pat, blob.data(), blob.size()));
+  c->pattern.assign(static_cast<const uint8_t*>(list), static_cast<const uint8_t*>(list) + n);
+  c->flags = flags;  // (XSG_FLAG_INVERT and the context counts live here alone: a list cannot match '\n')
+  ++c->pattern_serial;
+  c->koff_cands.clear();
+  c->sketch_hashes.clear();  // the sketch gate serves single literals
+  c->bordered = false;       // k_rx_heads / k_rx_chains walk the candidates as the reference does: no overlap is left
+  c->overlap_words.clear();
+  c->rx_pre = c->rx_fac = false;
+  PatternDev& P = c->pat;
+  P = PatternDev{};
+  P.plen = prog.min_len;  // what the list kernels may skip behind a match start before they look for the line's end
+  P.kind = kSet;
+  P.d_pat = c->d_pat.as<uint8_t>();
+  P.exact_tail = 1u;
+  P.icase = prog.icase ? 1u : 0u;
+  P.set_g = prog.g;
+  P.set_ngrams = (uint32_t)prog.keys.size();
+  P.set_keys = off[0], P.set_first = off[1], P.set_ent = off[2], P.set_bytes = off[3];
   return XSG_OK;
 }
 

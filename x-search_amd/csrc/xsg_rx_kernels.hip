@@ -990,8 +990,13 @@ __global__ void k_rx_compact(const RxPreArgs A) {
 
 hipError_t launch_rx_verify_keep(const RxPreArgs& a, hipStream_t s) {
   if (a.n) {
-    const size_t dyn = ((size_t)a.pat.rx_anc_n * 2u + 15u) & ~(size_t)15u;
-    hipLaunchKernelGGL(k_rx_verify, dim3((unsigned)((a.n + kBlock - 1) / kBlock)), dim3(kBlock), dyn, s, a);
+    if (a.pat.kind == kSet) {  // a literal list: the candidates' literals in listing order instead of an automaton
+      const hipError_t e = launch_set_verify(a, s);
+      if (e != hipSuccess) return e;
+    } else {
+      const size_t dyn = ((size_t)a.pat.rx_anc_n * 2u + 15u) & ~(size_t)15u;
+      hipLaunchKernelGGL(k_rx_verify, dim3((unsigned)((a.n + kBlock - 1) / kBlock)), dim3(kBlock), dyn, s, a);
+    }
     const uint64_t nb = (a.n + kRxScanBlock - 1) / kRxScanBlock;
     hipLaunchKernelGGL(k_rx_block_max, dim3((unsigned)nb), dim3(kBlock), 0, s, a, a.scan_tmp);
     uint32_t* head = reinterpret_cast<uint32_t*>(const_cast<uint64_t*>(a.c_pre));  // free until the scan of c_keep writes it

@@ -1,0 +1,101 @@
+// xsg_set.h -- a list of literals as ONE pattern (xsg_set_literals, include/xsg.h): the host-side compiler and the pieces
+// the kernels share with it (xsg_set_kernels.hip).  Plain C++ when compiled without hipcc: tests/cpp/set_selftest.cpp
+// drives the compiler, the filter and the verify step on the host, under the sanitizers.
+//
+// The search is leftmost-first over the literals in listing order: at the leftmost position where any literal occurs,
+// the first-listed literal that occurs there is the match, and the walk resumes at its end.
+//   FILTER  Let m be the shortest literal and g = min(m, 4).  Every literal starts with a g-gram; the filter holds one
+//           bit per hashed g-gram (65 536 bits = 8 KiB, the hash is the identity for g <= 2).  A position whose g-gram
+//           has no bit cannot start a literal: k_set_scan tests every position of the text against the filter in LDS.
+//   VERIFY  The distinct g-grams, sorted, each with the literals that start with it IN LISTING ORDER.  k_set_verify
+//           looks a candidate's gram up and compares those literals against the chunk bytes until one fits.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#if defined(__HIPCC__)
+#define XSG_SET_HD __host__ __device__ inline
+#else
+#define XSG_SET_HD inline
+#endif
+
+#include <string>
+#include <vector>
+
+namespace xsg {
+
+constexpr uint32_t kSetFilterBits = 65536;
+constexpr uint32_t kSetFilterBytes = kSetFilterBits / 8;
+constexpr uint32_t kSetFilterWords = kSetFilterBits / 32;
+
+// The filter bit of a gram: `v` holds the gram's g bytes, first byte lowest, upper bytes zero.  One function for the
+// compiler, the scan kernel and the host copies the tests drive.
+XSG_SET_HD uint32_t set_gram_hash(uint32_t v, uint32_t g) { return g <= 2u ? v : (v * 0x9E3779B1u) >> 16; }
+XSG_SET_HD uint32_t set_gram_mask(uint32_t g) { return g >= 4u ? 0xffffffffu : (1u << (8u * g)) - 1u; }
+XSG_SET_HD uint8_t set_fold(uint8_t b, bool icase) { return (icase && b >= 'A' && b <= 'Z') ? (uint8_t)(b + 32) : b; }
+// the gram that starts at d[0] (g readable bytes), folded under icase
+XSG_SET_HD uint32_t set_gram_at(const uint8_t* d, uint32_t g, bool icase) {
+  uint32_t v = 0;
+  for (uint32_t k = 0; k < g; ++k) v |= (uint32_t)set_fold(d[k], icase) << (8u * k);
+  return v;
+}
+XSG_SET_HD bool set_filter_has(const uint32_t* filter, uint32_t v, uint32_t g) {
+  const uint32_t h = set_gram_hash(v, g);
+  return (filter[h >> 5] >> (h & 31u)) & 1u;
+}
+
+// The verify table as the kernel reads it (all inside one blob; offsets in bytes from its start, multiples of 4):
+//   keys[ngrams]       the distinct grams, ascending
+//   first[ngrams + 1]  entries of gram k: ent[first[k] .. first[k + 1])
+//   ent[nlits]         (offset of the literal's bytes in `bytes`) << 8 | its length, listing order inside a gram
+//   bytes              the literals back to back (folded under ignore-case)
+struct SetTable {
+  const uint32_t* keys;
+  const uint32_t* first;
+  const uint32_t* ent;
+  const uint8_t* bytes;
+  uint32_t ngrams;
+  uint32_t g;
+};
+
+// Length of the first-listed literal that occurs at d[p] of a chunk of L bytes, or 0.  p + g <= L is the caller's to
+// ensure (the scan reports no other position); nothing at or beyond L is read.
+XSG_SET_HD uint32_t set_verify_at(const SetTable& T, const uint8_t* d, uint64_t p, uint64_t L, bool icase) {
+  const uint32_t v = set_gram_at(d + p, T.g, icase);
+  uint32_t lo = 0, hi = T.ngrams;
+  while (lo < hi) {  // first key >= v
+    const uint32_t mid = (lo + hi) >> 1;
+    if (T.keys[mid] < v)
+      lo = mid + 1u;
+    else
+      hi = mid;
+  }
+  if (lo == T.ngrams || T.keys[lo] != v) return 0u;
+  const uint64_t room = L - p;
+  for (uint32_t e = T.first[lo]; e < T.first[lo + 1u]; ++e) {
+    const uint32_t len = T.ent[e] & 0xffu;
+    if (len > room) continue;
+    const uint8_t* lit = T.bytes + (T.ent[e] >> 8);
+    uint32_t k = T.g;  // (the gram is the literal's start: already compared)
+    while (k < len && set_fold(d[p + k], icase) == lit[k]) ++k;
+    if (k == len) return len;
+  }
+  return 0u;
+}
+
+// What the host compiles a list into.
+struct SetProgram {
+  uint32_t count = 0, min_len = 0, max_len = 0, g = 0, filter_bits_set = 0;
+  bool icase = false;
+  std::vector<uint32_t> filter;  // kSetFilterWords
+  std::vector<uint32_t> keys, first, ent;
+  std::vector<uint8_t> bytes;
+  SetTable table() const { return SetTable{keys.data(), first.data(), ent.data(), bytes.data(), (uint32_t)keys.size(), g}; }
+  // the device image: filter, keys, first, ent, bytes (+ padding); *off receives the byte offsets of the last four
+  std::vector<uint8_t> blob(uint32_t off[4]) const;
+};
+// Parses `list` (literals separated by '\n', one final '\n' allowed) and compiles it.  False with *err set for: an empty
+// list, an empty literal, more than XSG_MAX_LITERALS literals, a literal over XSG_MAX_LITERAL_BYTES.
+bool compile_literal_set(const uint8_t* list, size_t n, bool icase, SetProgram* out, std::string* err);
+
+}  // namespace xsg

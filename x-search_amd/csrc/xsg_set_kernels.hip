@@ -1,0 +1,239 @@
+// xsg_set_kernels.hip -- the kernels of a literal LIST (kSet; xsg_set.h has the filter, the hash and the verify table).
+//   k_set_scan<EMIT, ICASE>  every position of the text against the filter of 65 536 bits (8 KiB of LDS per workgroup):
+//                            a position whose g-gram has its bit is a CANDIDATE.  Same ScanArgs and per-tile outputs as
+//                            k_scan -- tile_cnt, then m_pos / m_chunk ascending -- as a count pass and an emit pass.
+//   k_set_verify             one lane per candidate: the literals that start with its gram, in listing order, against the
+//                            chunk bytes -> c_len, in k_rx_verify's place; k_rx_heads / k_rx_chains / k_rx_compact and
+//                            the shared list pipeline take over from there (xsg_list.cpp: prefilter_candidates).
+#include "xsg_devutil.h"
+#include "xsg_set.h"
+
+namespace xsg {
+
+constexpr int kSetLoads = 4;                                // 16-byte units per lane: a wave covers 4 KiB, the tile 16 KiB
+constexpr uint32_t kSetWaveSpan = kWaveLoad * kSetLoads;
+constexpr uint32_t kSetTile = kSetWaveSpan * kWaves;
+constexpr uint32_t kSetGridPerCu = 8;                       // workgroups per compute unit of the bounded grid
+
+// ASCII-lower the four bytes of a dword: 0x20 is added to every byte in 'A'..'Z'
+__device__ __forceinline__ uint32_t set_fold4(uint32_t d) {
+  const uint32_t low7 = d & 0x7f7f7f7fu;
+  const uint32_t ge_A = low7 + 0x3f3f3f3fu;  // bit 7 of a byte set <=> its low 7 bits >= 'A'
+  const uint32_t gt_Z = low7 + 0x25252525u;  // ... <=> its low 7 bits > 'Z'
+  const uint32_t is_upper = ge_A & ~gt_Z & ~d & 0x80808080u;  // (bytes >= 0x80 are not letters)
+  return d | (is_upper >> 2);
+}
+
+// candidate bits of one unit: bit b set <=> the g-gram that starts at byte b of the unit has its filter bit.  w[0..3]:
+// the unit, w[4]: the dword behind it (the neighbour lane's first).
+template <int G>
+__device__ __forceinline__ uint32_t set_cand16(const uint32_t (&w)[5], const uint32_t* filter) {
+  uint32_t m = 0;
+#pragma unroll
+  for (int b = 0; b < 16; ++b) {
+    const int q = b >> 2, r = b & 3;
+    uint32_t v = r == 0 ? w[q] : __builtin_amdgcn_alignbyte(w[q + 1], w[q], (uint32_t)r);
+    if (G < 4) v &= (1u << (8 * G)) - 1u;
+    const uint32_t h = set_gram_hash(v, (uint32_t)G);
+    m |= ((filter[h >> 5] >> (h & 31u)) & 1u) << b;
+  }
+  return m;
+}
+
+template <bool EMIT, bool ICASE>
+__global__ __launch_bounds__(kBlock) void k_set_scan(const ScanArgs A, const uint32_t want_nl) {
+  __shared__ __attribute__((aligned(16))) uint32_t s_filter[kSetFilterWords];
+  __shared__ uint32_t s_cnt[kWaves];
+  __shared__ uint32_t s_nl[kWaves];
+  const PatternDev P = A.pat;
+  const uint32_t tid = threadIdx.x;
+  const uint32_t lane = tid & 63u;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  // the filter: once per workgroup, 16-byte loads (8 KiB = 512 units, two per thread)
+  {
+    const uint4* src = reinterpret_cast<const uint4*>(P.d_pat);
+    uint4* dst = reinterpret_cast<uint4*>(s_filter);
+    for (uint32_t k = tid; k < kSetFilterBytes / 16u; k += kBlock) dst[k] = src[k];
+  }
+  __syncthreads();
+  const uint32_t g = P.set_g;
+
+  for (uint64_t tile = blockIdx.x; tile < A.ntiles; tile += gridDim.x) {
+    if (EMIT && A.tile_cnt[tile] == 0) continue;  // (workgroup-uniform)
+    const uint32_t c = A.tile_chunk ? A.tile_chunk[tile] : 0u;
+    const ChunkDev ch = A.chunks[c];
+    const uint8_t* cbase = A.base + ch.offset;
+    const uint64_t L = ch.length;
+    const uint64_t Lr = (L + 15u) & ~(uint64_t)15u;
+    // a position p is a candidate only if its whole gram lies inside the chunk: p + g <= L.  Every bit at or beyond
+    // `limit` is cleared below, so no decision rests on a byte at or beyond the chunk's end.
+    const uint64_t limit = L >= g ? L - g + 1u : 0u;
+    const uint64_t toff = (tile - A.chunk_tile0[c]) * (uint64_t)kSetTile;
+    const uint64_t wbase = toff + (uint64_t)wave * kSetWaveSpan;
+
+    // ---- the wave's 4 KiB: four 16-byte loads per lane, all issued before any is used; units at or beyond the chunk's
+    // padded end are not read.  The dword behind the span (the next wave's or the next tile's first, same chunk) serves
+    // the last grams of lane 63's last unit.
+    uint4 u[kSetLoads];
+#pragma unroll
+    for (int j = 0; j < kSetLoads; ++j) {
+      const uint64_t off = wbase + (uint64_t)j * kWaveLoad + (uint64_t)lane * kUnit;
+      u[j] = off < Lr ? *reinterpret_cast<const uint4*>(cbase + off) : uint4{0u, 0u, 0u, 0u};
+    }
+    const uint64_t behind = wbase + kSetWaveSpan;
+    const uint32_t edge_last = behind < Lr ? *reinterpret_cast<const uint32_t*>(cbase + behind) : 0u;
+
+    uint32_t masks[kSetLoads];
+    uint32_t cnt = 0;
+#pragma unroll
+    for (int j = 0; j < kSetLoads; ++j) {
+      uint32_t w[5] = {u[j].x, u[j].y, u[j].z, u[j].w, 0u};
+      // lane 63's neighbour: lane 0 of the next wave-load, or the dword behind the span
+      const uint32_t edge = j + 1 < kSetLoads ? (uint32_t)__builtin_amdgcn_readfirstlane((int)u[j + 1 < kSetLoads ? j + 1 : j].x) : edge_last;
+      w[4] = from_next_lane(w[0], edge, lane);
+      if (ICASE) {
+#pragma unroll
+        for (int q = 0; q < 5; ++q) w[q] = set_fold4(w[q]);
+      }
+      uint32_t m;
+      switch (g) {  // (wave-uniform)
+        case 1: m = set_cand16<1>(w, s_filter); break;
+        case 2: m = set_cand16<2>(w, s_filter); break;
+        case 3: m = set_cand16<3>(w, s_filter); break;
+        default: m = set_cand16<4>(w, s_filter); break;
+      }
+      const uint64_t unit_off = wbase + (uint64_t)j * kWaveLoad + (uint64_t)lane * kUnit;
+      if (unit_off >= limit)
+        m = 0u;
+      else if (unit_off + kUnit > limit)
+        m &= (1u << (uint32_t)(limit - unit_off)) - 1u;
+      masks[j] = m;
+      cnt += (uint32_t)__popc(m);
+    }
+
+    if (!EMIT) {
+      const uint32_t wc = wave_sum_u32(cnt);
+      if (lane == 0) s_cnt[wave] = wc;
+      if (want_nl) {
+        // newlines of the tile: counted on bytes below L only
+        uint32_t n = 0;
+#pragma unroll
+        for (int j = 0; j < kSetLoads; ++j) {
+          const uint64_t unit_off = wbase + (uint64_t)j * kWaveLoad + (uint64_t)lane * kUnit;
+          if (unit_off < L) {
+            const uint32_t d8[8] = {u[j].x, u[j].y, u[j].z, u[j].w, 0u, 0u, 0u, 0u};
+            uint32_t nm = nl_mask16(d8) & 0xffffu;
+            if (unit_off + kUnit > L) nm &= (1u << (uint32_t)(L - unit_off)) - 1u;
+            n += (uint32_t)__popc(nm);
+          }
+        }
+        const uint32_t wn = wave_sum_u32(n);
+        if (lane == 0) s_nl[wave] = wn;
+      }
+      __syncthreads();
+      if (tid == 0) {
+        A.tile_cnt[tile] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+        if (want_nl) A.tile_nl[tile] = s_nl[0] + s_nl[1] + s_nl[2] + s_nl[3];
+      }
+      __syncthreads();  // s_cnt / s_nl are free for the next tile
+    } else {
+      // ---- ordered emission: wave spans are consecutive, loads within a span are consecutive, lanes within a load are
+      // consecutive, bits ascend (as k_scan's emit pass)
+      const uint32_t wc = wave_sum_u32(cnt);
+      if (lane == 0) s_cnt[wave] = wc;
+      __syncthreads();
+      uint64_t rank = A.tile_off[tile];
+      for (uint32_t w2 = 0; w2 < wave; ++w2) rank += s_cnt[w2];
+      __syncthreads();
+#pragma unroll
+      for (int j = 0; j < kSetLoads; ++j) {
+        const uint32_t m = masks[j];
+        const uint32_t pc = (uint32_t)__popc(m);
+        const uint32_t incl = wave_incl_scan_u32(pc, lane);
+        const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+        if (m) {
+          uint64_t r = rank + (incl - pc);
+          const uint64_t unit_off = wbase + (uint64_t)j * kWaveLoad + (uint64_t)lane * kUnit;
+          uint32_t mm = m;
+          while (mm) {
+            const uint32_t b = (uint32_t)__ffs((int)mm) - 1u;
+            mm &= mm - 1u;
+            if (A.m_cap == 0 || r < A.m_cap) {
+              A.m_pos[r] = unit_off + b;
+              A.m_chunk[r] = c;
+            }
+            ++r;
+          }
+        }
+        rank += total;
+      }
+    }
+  }
+}
+
+__global__ __launch_bounds__(kBlock) void k_set_verify(const RxPreArgs A) {
+  const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= A.n) return;
+  const PatternDev P = A.pat;
+  const ChunkDev ch = A.chunks[A.c_chunk[i]];
+  SetTable T;
+  T.keys = reinterpret_cast<const uint32_t*>(P.d_pat + P.set_keys);
+  T.first = reinterpret_cast<const uint32_t*>(P.d_pat + P.set_first);
+  T.ent = reinterpret_cast<const uint32_t*>(P.d_pat + P.set_ent);
+  T.bytes = P.d_pat + P.set_bytes;
+  T.ngrams = P.set_ngrams;
+  T.g = P.set_g;
+  const uint64_t p = A.c_pos[i];
+  // (the scan reports p only with p + g <= length; a position without that room holds nothing)
+  A.c_len[i] = p + T.g <= ch.length ? set_verify_at(T, A.base + ch.offset, p, ch.length, P.icase != 0) : 0u;
+}
+
+static unsigned set_grid(const ScanArgs& a) {
+  static const unsigned cus = [] {
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
+      n = 256;
+    return (unsigned)n;
+  }();
+  return (unsigned)std::min<uint64_t>(a.ntiles, (uint64_t)cus * kSetGridPerCu);
+}
+
+hipError_t launch_set_count(const ScanArgs& a, bool want_nl, hipStream_t s) {
+  if (a.ntiles == 0) return hipSuccess;
+  if (a.tile_bytes != kSetTile || a.pat.set_g < 1 || a.pat.set_g > 4) return hipErrorInvalidValue;
+  const dim3 grid(set_grid(a));
+  if (a.pat.icase)
+    hipLaunchKernelGGL((k_set_scan<false, true>), grid, dim3(kBlock), 0, s, a, want_nl ? 1u : 0u);
+  else
+    hipLaunchKernelGGL((k_set_scan<false, false>), grid, dim3(kBlock), 0, s, a, want_nl ? 1u : 0u);
+  return hipGetLastError();
+}
+
+hipError_t launch_set_emit(const ScanArgs& a, hipStream_t s) {
+  if (a.ntiles == 0) return hipSuccess;
+  if (a.tile_bytes != kSetTile || a.pat.set_g < 1 || a.pat.set_g > 4) return hipErrorInvalidValue;
+  const dim3 grid(set_grid(a));
+  if (a.pat.icase)
+    hipLaunchKernelGGL((k_set_scan<true, true>), grid, dim3(kBlock), 0, s, a, 0u);
+  else
+    hipLaunchKernelGGL((k_set_scan<true, false>), grid, dim3(kBlock), 0, s, a, 0u);
+  return hipGetLastError();
+}
+
+hipError_t launch_set_verify(const RxPreArgs& a, hipStream_t s) {
+  if (a.n) hipLaunchKernelGGL(k_set_verify, dim3((unsigned)((a.n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, a);
+  return hipGetLastError();
+}
+
+void describe_set_scan(const ScanArgs& a, bool emit, char* out, size_t cap) {
+  snprintf(out, cap, "xsg::k_set_scan<%s, %s> g=%u + xsg::k_set_verify", emit ? "true" : "false", a.pat.icase ? "true" : "false",
+           a.pat.set_g);
+}
+
+__global__ void k_warm_set() {}
+hipError_t warm_set_kernels(hipStream_t s) {
+  hipLaunchKernelGGL(k_warm_set, dim3(1), dim3(1), 0, s);
+  return hipGetLastError();
+}
+
+}  // namespace xsg

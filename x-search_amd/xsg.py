@@ -31,6 +31,9 @@ NUM_COUNTERS = 4
 LINE_BASE_AUTO = (1 << 64) - 1
 MAX_PATTERN = 32768
 MAX_REGEX = 1024
+MAX_LITERALS = 4096  # a literal list (xsg_set_literals): literals, bytes per literal, bytes of its filter image
+MAX_LITERAL_BYTES = 255
+LITERAL_FILTER_BYTES = 8192
 STATUS_OK, STATUS_OVERFLOW, STATUS_NONASCII = 0, 1, 2
 TILE = 16384
 
@@ -49,7 +52,13 @@ COMPRESSION_NONE, COMPRESSION_ZSTD, COMPRESSION_LZ4 = 1, 2, 3
 class JobOpts(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("mode", C.c_uint32), ("pattern_flags", C.c_uint32),
                 ("device", C.c_int32), ("num_threads", C.c_int32), ("num_max_readers", C.c_int32),
-                ("chunk_bytes", C.c_uint64), ("chunk_begin", C.c_uint64), ("chunk_end", C.c_uint64)]
+                ("chunk_bytes", C.c_uint64), ("chunk_begin", C.c_uint64), ("chunk_end", C.c_uint64),
+                ("pattern_is_list", C.c_uint32)]
+
+
+class LiteralList(C.Structure):  # xsg_literal_list
+    _fields_ = [("count", C.c_uint32), ("min_len", C.c_uint32), ("max_len", C.c_uint32), ("gram", C.c_uint32),
+                ("filter_bits_set", C.c_uint32)]
 
 
 class JobStats(C.Structure):
@@ -114,6 +123,9 @@ def load():
         "xsg_ctx_create": (ci, [ci, C.POINTER(vp)]),
         "xsg_ctx_destroy": (None, [vp]),
         "xsg_set_pattern": (ci, [vp, C.c_char_p, sz, u32]),
+        "xsg_set_literals": (ci, [vp, C.c_char_p, sz, u32]),
+        "xsg_literals_info": (ci, [C.c_char_p, sz, u32, C.POINTER(LiteralList), vp]),
+        "xsg_host_searcher_create_list": (ci, [ci, C.c_char_p, sz, u32, ci, C.POINTER(vp)]),
         "xsg_regex_check": (ci, [C.c_char_p, sz, u32, C.POINTER(u32), C.POINTER(u32)]),
         "xsg_regex_info": (ci, [C.c_char_p, sz, u32, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)]),
         "xsg_regex_factor": (ci, [C.c_char_p, sz, u32, C.POINTER(u32), C.POINTER(u32)]),
@@ -194,7 +206,8 @@ EXPORTS = ["xsg_abi_version", "xsg_strerror", "xsg_last_error", "xsg_device_coun
            "xsg_comm_size", "xsg_comm_library", "xsg_reduce_counts_async", "xsg_reduce_counts", "xsg_allgather_u64",
            "xsg_jobs_reduce_total", "xsg_device_numa", "xsg_regex_info", "xsg_regex_dfa_info", "xsg_regex_prefix", "xsg_regex_factor",
            "xsg_result_u64_view", "xsg_shard_invalidate", "xsg_result_lines_view", "xsg_count_async_status", "xsg_codec_name",
-           "xsg_host_matches", "xsg_result_context_edges"]
+           "xsg_host_matches", "xsg_result_context_edges", "xsg_set_literals", "xsg_literals_info",
+           "xsg_host_searcher_create_list"]
 
 
 def _check(rc):
@@ -225,6 +238,26 @@ def regex_check(expr: bytes, flags: int = 0):
     sets = np.zeros((32, 8), dtype=np.uint32)
     _check(lib.xsg_regex_check(expr, len(expr), flags, C.byref(n), sets.ctypes.data_as(C.POINTER(C.c_uint32))))
     return int(n.value), sets[:n.value].copy()
+
+
+def literal_list(literals) -> bytes:
+    """the byte string xsg_set_literals takes: the literals joined by '\\n' (the format of a grep -f file)"""
+    return b"\n".join(literals)
+
+
+def literals_info(lst: bytes, flags: int = 0, with_filter: bool = False):
+    """What xsg_set_literals would compile `lst` into -> dict(count, min_len, max_len, gram, filter_bits_set), and with
+    `with_filter` the filter image as 2048 uint32 words; raises XsgError (EINVAL) for a list it refuses.  No GPU needed."""
+    info = LiteralList()
+    filt = np.zeros(LITERAL_FILTER_BYTES // 4, dtype=np.uint32) if with_filter else None
+    _check(load().xsg_literals_info(lst, len(lst), flags, C.byref(info), filt.ctypes.data if with_filter else None))
+    d = {k: getattr(info, k) for k, _ in LiteralList._fields_}
+    return (d, filt) if with_filter else d
+
+
+def literal_gram_hash(v: int, g: int) -> int:
+    """the filter bit of a gram (include/xsg.h: xsg_literals_info)"""
+    return v if g <= 2 else ((v * 0x9E3779B1) & 0xFFFFFFFF) >> 16
 
 
 def regex_info(expr: bytes, flags: int = 0):
@@ -325,6 +358,10 @@ class Context:
 
     def set_pattern(self, pattern: bytes, flags: int = 0):
         _check(self._lib.xsg_set_pattern(self.h, pattern, len(pattern), flags))
+
+    def set_literals(self, lst: bytes, flags: int = 0):
+        """a list of literals separated by '\\n' as the pattern (xsg_set_literals; literal_list() joins one)"""
+        _check(self._lib.xsg_set_literals(self.h, lst, len(lst), flags))
 
     def info(self):
         arch = C.create_string_buffer(128)
@@ -616,7 +653,7 @@ class Job:
 
     def __init__(self, pattern: bytes, path: str, mode: int, meta_path: str | None = None, device: int = 0,
                  num_threads: int = 1, num_max_readers: int = 1, chunk_bytes: int = 16 << 20, flags: int = 0,
-                 chunk_range: tuple[int, int] | None = None):
+                 chunk_range: tuple[int, int] | None = None, pattern_is_list: bool = False):
         self._lib = load()
         o = JobOpts()
         self._lib.xsg_job_opts_init(C.byref(o))
@@ -624,6 +661,7 @@ class Job:
         o.num_threads, o.num_max_readers, o.chunk_bytes = num_threads, num_max_readers, chunk_bytes
         if chunk_range is not None:
             o.chunk_begin, o.chunk_end = chunk_range
+        o.pattern_is_list = 1 if pattern_is_list else 0
         h = C.c_void_p()
         _check(self._lib.xsg_job_start(pattern, len(pattern), os.fsencode(path),
                                        os.fsencode(meta_path) if meta_path else None, C.byref(o), C.byref(h)))
