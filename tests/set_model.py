@@ -8,7 +8,6 @@ the dict of all_modes() has the layout of gpu_util.oracle_rx_all_modes.  Literal
 UTF-8, which the oracle's reader refuses, are served here.  tests/test_set_host.py pins this model to the oracle on every
 list the oracle reads."""
 import bisect
-import re
 import string
 
 import numpy as np
@@ -40,8 +39,10 @@ class Occurrences:
         for idx, lit in enumerate(literals):
             assert lit and b"\n" not in lit
             needle = lit.lower() if icase else lit
-            for m in re.finditer(b"(?=" + re.escape(needle) + b")", d):  # every occurrence, overlapping ones included
-                best.setdefault(m.start(), len(lit))  # (an earlier literal at the position wins: idx ascends)
+            at = d.find(needle)  # every occurrence, overlapping ones included
+            while at >= 0:
+                best.setdefault(at, len(lit))  # (an earlier literal at the position wins: idx ascends)
+                at = d.find(needle, at + 1)
         self.pos = sorted(best)
         self.len = [best[p] for p in self.pos]
 
