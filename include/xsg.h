@@ -352,7 +352,12 @@ int xsg_regex_factor(const void* expr, size_t n, uint32_t flags, uint32_t* posit
  * xsg_count_async cannot -- it never waits for the device -- and uses the gate whenever no synchronous call has judged
  * the pattern on this binding; for such a needle every tile is then a candidate and the pass is SLOWER than the full
  * scan (measured 1.07 x on a 50 GiB binding): call a synchronous entry point once with the pattern,
- * or set XSG_SKETCH=0, where that matters.  Bindings of 64 MiB and more get the sketch from
+ * or set XSG_SKETCH=0, where that matters.  A plain match count behind the gate (no XSG_WITH_NEWLINES; a needle of
+ * at most 33 bytes, or XSG_FLAG_EXACT_TAIL) is ONE launch: the same kernel sums in registers, walks the end-of-chunk zones
+ * that hold an occurrence itself and writes the counters (50 GiB, `Sherlock`: 0.149 -> 0.110 ms per call).  It pays for a
+ * needle in a chunk's last plen + 31 bytes with a look back through that chunk for the previous occurrence: data with the
+ * needle at the end of EVERY chunk measured 1.6 x slower than the two launches (0.25 against 0.16 ms, 3200 chunks of 16 MiB,
+ * DESIGN.md section 5); XSG_GATE_FINISH=0 keeps the two launches.  Bindings of 64 MiB and more get the sketch from
  * xsg_shard_tune, or from the second such pass of a synchronous entry point (the build is enqueued on the context's
  * stream); xsg_count_async on a caller's stream never builds, it uses what is there.  XSG_SKETCH=0 switches the feature
  * off, XSG_SKETCH=1 builds before the first pass.  A caller that refills
@@ -670,7 +675,9 @@ int xsg_time_scan_kernel(xsg_shard* shard, uint32_t mode, int iters, float* avg_
 /* Name of the bulk-kernel instantiation the next pass of `mode` launches on this shard with the current pattern
  * ("xsg::k_scan<KIND, WANT_NL, WANT_LINES, EMIT, LOADS, ICASE> stagger=N"): what a profile of that pass shows.
  * " gated by xsg::k_sketch (512 B/tile)" follows when that pass would run behind the binding's sketch: this
- * instantiation on a bounded grid, which selects the candidate tiles and scans them.  A literal list:
+ * instantiation on a bounded grid, which selects the candidate tiles and scans them; " finishing (xsg::k_scan_fin)" in
+ * front of it: the count of this mode is that one launch, the finishing form, with no xsg::k_count_finish behind it
+ * (xsg_time_scan_kernel and xsg_shard_tune time that form for such a mode).  A literal list:
  * "xsg::k_set_scan<EMIT, ICASE> g=N + xsg::k_set_verify". */
 int xsg_scan_kernel_name(xsg_shard* shard, uint32_t mode, char* out, size_t cap);
 /* Measure and fix the bulk kernel's wave stagger for this shard, the current pattern and `mode` (a handful of

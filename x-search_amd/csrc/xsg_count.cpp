@@ -199,11 +199,13 @@ struct EventPair {
 };
 
 // `warm`: one untimed launch first (it pulls the code in); then *ms = the time of `n` launches of this variant
+// fin: the launches are the finishing form of the gated count (a plain match count's one kernel), into these counters
 static hipError_t time_scan(const ScanArgs& a, bool want_nl, bool want_lines, bool warm, int n, hipStream_t st,
-                            const EventPair& ev, float* ms) {
-  hipError_t e = warm ? launch_scan_count(a, want_nl, want_lines, st) : hipSuccess;
+                            const EventPair& ev, float* ms, const GateFinArgs* fin = nullptr) {
+  auto launch = [&] { return fin ? launch_scan_count_finishing(a, *fin, st) : launch_scan_count(a, want_nl, want_lines, st); };
+  hipError_t e = warm ? launch() : hipSuccess;
   if (e == hipSuccess) e = hipEventRecord(ev.a, st);
-  for (int i = 0; i < n && e == hipSuccess; ++i) e = launch_scan_count(a, want_nl, want_lines, st);
+  for (int i = 0; i < n && e == hipSuccess; ++i) e = launch();
   if (e == hipSuccess) e = hipEventRecord(ev.b, st);
   if (e == hipSuccess) e = hipEventSynchronize(ev.b);
   if (e == hipSuccess) e = hipEventElapsedTime(ms, ev.a, ev.b);
@@ -386,6 +388,25 @@ int xsg::choose_hot_filter(xsg_shard* s, hipStream_t st, bool want_nl, bool want
   return XSG_OK;
 }
 
+// the finishing form's own arguments: where the result goes, and its scratch words (1 + kFinGroups) behind
+// k_count_finish's partials and the 128 bytes of u32 words there (ticket, scan flags, the list route's two)
+static GateFinArgs fin_args(xsg_shard* s, uint64_t* d_counters, uint64_t* host_counters, uint64_t* d_status) {
+  GateFinArgs f{};
+  f.counters = d_counters;
+  f.host_counters = host_counters;
+  f.status = d_status;
+  f.word = reinterpret_cast<unsigned long long*>(s->d_finish.as<uint64_t>() + 3 * (size_t)kFinishBlocks + 16);
+  f.total_bytes = s->total_bytes;
+  return f;
+}
+
+// does a count of this mode over these arguments go through enqueue_count's finishing form?  (a needle that can overlap
+// itself in this data counts through its list: the storing form)
+static bool count_finishes(const xsg_shard* s, const ScanArgs& a, uint32_t m, bool want_nl) {
+  const xsg_ctx* c = s->ctx;
+  return m == XSG_COUNT_MATCHES && !want_nl && !(c->bordered && !overlap_free_known(s)) && scan_finishing(a, s->total_bytes);
+}
+
 static int enqueue_count(xsg_shard* s, bool want_matches, bool want_lines, bool want_nl, hipStream_t st,
                          uint64_t* d_counters, uint64_t* host_counters, const PatternDev* other_pattern = nullptr,
                          uint64_t* d_status = nullptr, bool may_sync = true) {
@@ -404,6 +425,13 @@ static int enqueue_count(xsg_shard* s, bool want_matches, bool want_lines, bool 
     a.sketch = nullptr;
     a.dense_hint = 0;
     if (s->tune_serial != 0) a.tune = kTuneAuto;
+  }
+  // A plain match count behind the gate finishes inside its own pass (k_scan_fin): one launch, the per-tile arrays are
+  // neither written nor read and stay as prepare_tiles left them.  Everything else -- newline totals, line counts,
+  // needles of 34 bytes and more with the lossy tail, the ungated kinds, another pattern -- keeps the two launches below.
+  if (want_matches && !want_lines && !rx_lines && !want_nl && !other_pattern && scan_finishing(a, s->total_bytes)) {
+    HIP_TRY(launch_scan_count_finishing(a, fin_args(s, d_counters, host_counters, d_status), st));
+    return XSG_OK;
   }
   // dirty until the finish kernel is in the queue behind the scan
   s->cnt_clean = false;
@@ -738,11 +766,15 @@ extern "C" int xsg_time_scan_kernel(xsg_shard* s, uint32_t mode, int iters, floa
   XSG_TRY(prepare_tiles(s, want_lines, c->stream));
   ScanArgs a = scan_args(s, scan_variant(want_nl, want_lines));
   a.lines_only = want_lines;  // XSG_COUNT_LINES: what xsg_count launches for it (enqueue_count)
-  s->cnt_clean = s->sum_clean = false;  // no finish kernel runs behind these launches
+  // a plain match count that enqueue_count would finish inside its pass is timed in that form (not in the storing form
+  // of the list routes), into the binding's scratch counters: the per-tile arrays stay clean
+  const bool fin = count_finishes(s, a, m, want_nl);
+  const GateFinArgs f = fin_args(s, s->d_counters.as<uint64_t>(), nullptr, nullptr);
+  if (!fin) s->cnt_clean = s->sum_clean = false;  // no finish kernel runs behind these launches
   EventPair ev;
   HIP_TRY(ev.init());
   float ms = 0;
-  HIP_TRY(time_scan(a, want_nl, want_lines, true, iters, c->stream, ev, &ms));  // a warm-up, then the timed launches
+  HIP_TRY(time_scan(a, want_nl, want_lines, true, iters, c->stream, ev, &ms, fin ? &f : nullptr));  // a warm-up, then the timed launches
   *avg_ms = ms / (float)iters;
   HIP_TRY(hipMemsetAsync(a.flags, 0, 4, c->stream));  // no finish kernel consumed what the scans may have raised
   return XSG_OK;
@@ -767,7 +799,9 @@ extern "C" int xsg_scan_kernel_name(xsg_shard* s, uint32_t mode, char* out, size
     describe_scan(a, want_nl, false, false, inner, sizeof inner);
     snprintf(out, cap, "%s + xsg::k_rx_verify (prefilter route; xsg_count_async: k_rx_scan)", inner);
   } else {
-    describe_scan(a, want_nl, !list && m == XSG_COUNT_LINES, false, out, cap);
+    // (a plain match count says which form of the gated pass it launches: the finishing one, or the storing one)
+    describe_scan(a, want_nl, !list && m == XSG_COUNT_LINES, false, out, cap,
+                  !list && count_finishes(s, a, m, (mode & XSG_WITH_NEWLINES) != 0), s->total_bytes);
   }
   if (inverted(s->ctx)) {  // the inverted form: the same scan, then the complement (of the list, or of the line count)
     const size_t n = strlen(out);

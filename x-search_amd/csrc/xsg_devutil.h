@@ -357,10 +357,14 @@ constexpr uint32_t kZoneStage = 96;  // bytes of a chunk's tail zone staged in L
 // by one lane through global memory cost ~10 us per chunk in dependent loads), ballots give the masks and the walk
 // itself runs on the scalar unit.  Returns (wave-uniform) the matches of the match-mode walk from `entry_m` and
 // of the line-mode walk from `entry_l`.  plen <= kTailMaskMaxPlen; all 64 lanes active.
-__device__ __forceinline__ void wave_tail_counts(const uint8_t* d, uint64_t L, const uint8_t* s_pat, uint32_t plen,
-                                                 bool icase, uint8_t* zone, uint32_t lane, bool want_m, uint64_t entry_m,
-                                                 bool want_l, uint64_t entry_l, uint32_t* n_m, uint32_t* n_l,
-                                                 uint64_t* out = nullptr, uint32_t out_cap = 0) {
+// The masks are a part of their own (wave_tail_masks): the finishing form of the gated count pass looks at `full` first
+// and walks only a zone that holds an occurrence (gated_pass).
+struct TailMasks {
+  unsigned long long full, nz, nlm;  // xsg_tail.h; wave-uniform
+  uint32_t k;                        // this lane's K[lane]
+};
+__device__ __forceinline__ TailMasks wave_tail_masks(const uint8_t* d, uint64_t L, const uint8_t* s_pat, uint32_t plen,
+                                                     bool icase, uint8_t* zone, uint32_t lane) {
   const uint64_t Z = tail_zone_begin(L, plen);
   const uint32_t n = (uint32_t)(L - Z);  // <= plen + 31 <= 64
   const uint64_t Zal = Z & ~(uint64_t)15;
@@ -385,9 +389,20 @@ __device__ __forceinline__ void wave_tail_counts(const uint8_t* d, uint64_t L, c
         alive = false;
     }
   }
-  const unsigned long long full = __ballot(room && k == plen);
-  const unsigned long long nz = __ballot(k != 0);
-  const unsigned long long nlm = __ballot(in_zone && zone[off + lane] == '\n');
+  TailMasks t;
+  t.full = __ballot(room && k == plen);
+  t.nz = __ballot(k != 0);
+  t.nlm = __ballot(in_zone && zone[off + lane] == '\n');
+  t.k = k;
+  return t;
+}
+__device__ __forceinline__ void wave_tail_counts(const uint8_t* d, uint64_t L, const uint8_t* s_pat, uint32_t plen,
+                                                 bool icase, uint8_t* zone, uint32_t lane, bool want_m, uint64_t entry_m,
+                                                 bool want_l, uint64_t entry_l, uint32_t* n_m, uint32_t* n_l,
+                                                 uint64_t* out = nullptr, uint32_t out_cap = 0) {
+  const TailMasks t = wave_tail_masks(d, L, s_pat, plen, icase, zone, lane);
+  const unsigned long long full = t.full, nz = t.nz, nlm = t.nlm;
+  const uint32_t k = t.k;
   auto k_at = [&](uint32_t j) { return (uint32_t)__builtin_amdgcn_readlane((int)k, (int)__builtin_amdgcn_readfirstlane(j)); };
   // (out: the positions of the ONE walk asked for -- the list kernels want either the match-mode or the line-mode walk)
   *n_m = want_m ? tail_walk_masks(L, plen, entry_m, false, full, nz, nlm, k_at, want_l ? nullptr : out, out_cap) : 0u;

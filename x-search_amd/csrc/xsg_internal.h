@@ -171,6 +171,26 @@ hipError_t launch_sketch_sample(const ScanArgs& a, uint64_t stride, uint32_t nsa
 // would launch_scan_count run the gated instantiation for these arguments?
 bool scan_gated(const ScanArgs& a, bool want_nl, bool want_lines);
 
+// The FINISHING form of the gated count pass (k_scan_fin: gated_pass<..., FIN>): a plain match count that sums in
+// registers, walks the end-of-chunk zones that hold an occurrence itself and writes the counters -- one launch, no
+// k_count_finish, no store to the per-tile arrays.  What it needs beyond ScanArgs travels as a second kernel parameter,
+// so that every other k_scan instantiation keeps its argument block.
+struct GateFinArgs {
+  uint64_t* counters;         // device, XSG_NUM_COUNTERS: {matches, 0, 0, total_bytes}
+  uint64_t* host_counters;    // optional pinned mirror
+  uint64_t* status;           // optional: receives 0
+  unsigned long long* word;   // 1 + kFinGroups words, zero at rest, each (arrivals << kFinTotalBits) | their matches so
+                              // far: workgroup b arrives at word 1 + b % kFinGroups, the last of a group at word 0; who
+                              // is last learns it and the sum from the value its atomicAdd returns and puts the word back
+  uint64_t total_bytes;
+};
+constexpr uint32_t kFinGroups = 64;
+constexpr uint32_t kFinTotalBits = 40;  // matches <= total_bytes < 2^40; the grid stays below 2^24 (scan_finishing)
+// would a plain match count over these arguments take the finishing form?  (gated, an end-of-chunk zone the wave walk
+// serves -- exact_tail or plen <= kTailMaskMaxPlen -- and both fields of GateFinArgs::word wide enough)
+bool scan_finishing(const ScanArgs& a, uint64_t total_bytes);
+hipError_t launch_scan_count_finishing(const ScanArgs& a, const GateFinArgs& f, hipStream_t s);
+
 constexpr int kFinishBlocks = 2048;  // upper bound of k_count_finish's grid (size of FinishArgs::partials / 3)
 
 struct FinishArgs {
@@ -237,7 +257,9 @@ hipError_t launch_set_emit(const ScanArgs& a, hipStream_t s);
 hipError_t launch_set_verify(const RxPreArgs& a, hipStream_t s);
 void describe_set_scan(const ScanArgs& a, bool emit, char* out, size_t cap);
 // "xsg::k_scan<KIND, WANT_NL, WANT_LINES, EMIT, LOADS, ICASE>" + the stagger launch_scan would use, for reports
-void describe_scan(const ScanArgs& a, bool want_nl, bool want_lines, bool emit, char* out, size_t cap);
+// finishing: the caller's pass is a plain match count that takes the finishing form where scan_finishing says so
+void describe_scan(const ScanArgs& a, bool want_nl, bool want_lines, bool emit, char* out, size_t cap,
+                   bool finishing = false, uint64_t total_bytes = 0);
 
 // exclusive scan: out[i] = sum_{k<i} in[k] for i in [0, n]; out has n+1 entries.
 // tmp must hold scan_tmp_elems(n) uint64 values.

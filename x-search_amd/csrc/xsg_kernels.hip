@@ -780,8 +780,11 @@ __device__ __forceinline__ TileGeom tile_geom(const ScanArgs& A, const uint64_t 
 // the geometry (and says whether the pattern still has to be staged: `stage`, workgroup-uniform); otherwise it is looked
 // up here, where it always was.  (The loads and their consumption are still one piece: a candidate's text is not
 // requested ahead of the previous candidate's compares.)
-template <int KIND, bool WANT_NL, bool WANT_LINES, bool EMIT, int LOADS, bool ICASE, bool ALIGNED, bool HAVE_GEOM>
-__device__ __forceinline__ void scan_tile_at(const ScanArgs& A, const uint64_t tile, const TileGeom& geom, const bool stage) {
+// FIN (the finishing form of the gated count, gated_pass): the wave's matches are added to *fin_acc (wave-uniform) and
+// nothing is stored per tile -- no tile_cnt, no tile_last, no wave mark.
+template <int KIND, bool WANT_NL, bool WANT_LINES, bool EMIT, int LOADS, bool ICASE, bool ALIGNED, bool HAVE_GEOM, bool FIN = false>
+__device__ __forceinline__ void scan_tile_at(const ScanArgs& A, const uint64_t tile, const TileGeom& geom, const bool stage,
+                                             uint64_t* fin_acc = nullptr) {
   constexpr int kLoads = LOADS;                          // 16-byte units per lane
   constexpr uint32_t kWaveSpan = kWaveLoad * kLoads;     // contiguous bytes per wave
   constexpr uint32_t kTile = kWaveSpan * kWaves;         // bytes per workgroup
@@ -1021,7 +1024,9 @@ __device__ __forceinline__ void scan_tile_at(const ScanArgs& A, const uint64_t t
         if (WANT_NL) A.tile_nl[tile] = tn;
       }
     } else {
-      if (wave_has) {
+      if (FIN) {
+        if (wave_has) *fin_acc += wave_sum_u32(cnt);
+      } else if (wave_has) {
         const uint32_t wc = wave_sum_u32(cnt);
         // the end of the wave's last match, relative to the tile start: it fits 16 bits, so the reduction runs on
         // 32-bit values (a 64-bit max costs three times the lane exchanges; a needle that is dense in the text pays
@@ -1114,10 +1119,104 @@ __device__ __forceinline__ uint64_t uniform_u64(const uint64_t v) {
   const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32));
   return ((uint64_t)hi << 32) | lo;
 }
+// ---------------------------------------------------------------------------
+// The FINISHING form (FIN; k_scan_fin): a plain match count that needs no k_count_finish behind it.  The waves add their
+// tiles' matches to a wave-uniform accumulator instead of storing them (scan_tile_at<..., FIN>), the workgroup leaves
+// through one 64-bit atomicAdd, and the last one to arrive writes the counters.  What k_count_finish did per chunk, the
+// end-of-chunk walk (xsg_tail.h), rests on two facts:
+//   1. the walk only ever reports positions >= Z at which the whole needle matches, so a zone without an occurrence
+//      in [Z, L - plen] contributes 0 from any entry.  An occurrence there lies wholly inside the chunk, so its home
+//      tile -- the tile its filter window starts in -- holds its grams, passes the gate and is scanned anyway: a
+//      candidate tile that is the home of some position of the zone takes the zone's masks (wave_tail_masks) and looks.
+//      Every tile that looks sees the same masks; the walk belongs to the home of the zone's FIRST occurrence alone.
+//   2. the walk's entry, the end of the last occurrence that starts below Z, is a function of the chunk's bytes: the
+//      owner finds it by walking the chunk's tiles backwards from the home of Z - 1, 64 sketches a step, and searching
+//      the tiles that pass (fin_last_in_tile).  No other workgroup's output is read.
+// Written for small code, not for speed: on text a handful of chunks per pass have a needle in their last plen + 31 bytes.
+// ---------------------------------------------------------------------------
+// The last occurrence o < Z whose home is tile `trel` of the chunk (its window starts at o + koff inside the tile):
+// o + 1, or 0 if there is none.  One wave, all lanes active, wave-uniform arguments and result.  1 KiB a step from the
+// top: a lane takes the bytes of its unit that equal the window's first byte and verifies those from memory.
+template <int LOADS>
+__device__ __forceinline__ uint64_t fin_last_in_tile(const uint8_t* cbase, const uint64_t L, const uint64_t Z, const uint64_t trel,
+                                                     const uint8_t* pat, const uint32_t plen, const uint32_t koff, const uint32_t lane) {
+  constexpr uint64_t kTile = (uint64_t)kWaveLoad * LOADS * kWaves;
+  constexpr uint64_t kStep = kWaveLoad;
+  const uint64_t w_lo = trel * kTile > koff ? trel * kTile : koff;                  // window starts [w_lo, w_hi)
+  const uint64_t w_hi = (trel + 1u) * kTile < Z + koff ? (trel + 1u) * kTile : Z + koff;
+  if (w_lo >= w_hi) return 0;
+  const uint32_t c0 = pat[koff];
+#pragma unroll 1
+  for (uint64_t base = (w_hi - 1u) & ~(kStep - 1u);; base -= kStep) {  // wave-uniform; w_hi <= L: every unit read holds a byte of the chunk
+    const uint64_t w0 = base + (uint64_t)lane * kUnit;
+    uint32_t cm = 0;  // bit b: byte b of the lane's unit is the window's first byte
+    if (w0 < w_hi) {
+      const uint4 v = *reinterpret_cast<const uint4*>(cbase + w0);
+      const uint32_t x[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+      for (int b = 0; b < 16; ++b) cm |= (uint32_t)(((x[b >> 2] >> (8 * (b & 3))) & 0xffu) == c0) << b;
+    }
+    uint32_t best = 0;  // 1 + the byte of the unit
+#pragma unroll 1
+    while (cm && !best) {  // the lane's positions ascend with the bit: the first hit from the top is its last occurrence
+      const uint32_t bit = 31u - (uint32_t)__builtin_clz(cm);
+      cm &= ~(1u << bit);
+      const uint64_t w = w0 + bit;
+      if (w >= w_lo && w < w_hi) {
+        const uint8_t* p = cbase + (w - koff);
+        uint32_t k = 0;
+#pragma unroll 1
+        while (k < plen && p[k] == pat[k]) ++k;
+        if (k == plen) best = bit + 1u;
+      }
+    }
+    const unsigned long long hit = __ballot(best != 0);
+    if (hit) {  // positions ascend with the lane as well
+      const int l = 63 - __builtin_clzll(hit);
+      return base + (uint64_t)l * kUnit + (uint32_t)__builtin_amdgcn_readlane((int)best, l) - koff;  // o + 1
+    }
+    if (base <= w_lo) return 0;
+  }
+}
+
+// Where the match-mode walk of a chunk enters its zone: plen + the largest o < Z at which the needle occurs, 0 if there
+// is none (Z == 0: a chunk that is all zone).  One wave; lane i tests the sketch of tile t - 64 + i of the chunk.
+template <int LOADS>
+__device__ __forceinline__ uint64_t fin_walk_entry(const ScanArgs& A, const uint8_t* cbase, const uint64_t L, const uint64_t Z,
+                                                   const uint64_t tile0, const uint32_t koff, const uint32_t lane) {
+  constexpr uint64_t kTile = (uint64_t)kWaveLoad * LOADS * kWaves;
+  if (Z == 0) return 0;
+  uint64_t t = (Z - 1u + koff) / kTile + 1u;  // tiles [0, t) of the chunk can be the home of an occurrence below Z
+#pragma unroll 1
+  while (t) {                                 // wave-uniform
+    const uint64_t lo = t > 64u ? t - 64u : 0u;
+    bool pass = false;
+    if (lo + lane < t) {
+      uint32_t miss = 0;
+#pragma unroll 1
+      for (uint32_t k = 0; k < A.sk_n; ++k) miss |= ~A.sketch[sketch_index(tile0 + lo + lane, A.sk_word[k])] & A.sk_mask[k];
+      pass = miss == 0;
+    }
+    unsigned long long bal = __ballot(pass);
+#pragma unroll 1
+    while (bal) {
+      const uint32_t hi = 63u - (uint32_t)__builtin_clzll(bal);
+      bal &= ~(1ull << hi);
+      const uint64_t r = fin_last_in_tile<LOADS>(cbase, L, Z, lo + hi, A.pat.d_pat, A.pat.plen, koff, lane);
+      if (r) return r - 1u + A.pat.plen;
+    }
+    t = lo;
+  }
+  return 0;
+}
+
 constexpr uint32_t kGateRegs = 6;  // sketch words a lane requests at once; entries beyond (long needles) follow in batches
-template <int KIND, int LOADS, bool ICASE, bool ALIGNED>
-__device__ __forceinline__ void gated_pass(const ScanArgs& A) {
+template <int KIND, int LOADS, bool ICASE, bool ALIGNED, bool FIN = false>
+__device__ __forceinline__ void gated_pass(const ScanArgs& A, const GateFinArgs* F = nullptr) {
   __shared__ unsigned long long s_bal[kWaves];
+  __shared__ __attribute__((aligned(16))) uint8_t s_zone[FIN ? kZoneStage : 16];  // FIN: the zone a tile looks at (wave 0)
+  __shared__ uint64_t s_fin[kWaves];
+  uint64_t fin_acc = 0;  // FIN: this wave's matches (wave-uniform)
   __shared__ uint64_t s_goff[kBlock], s_glen[kBlock];
   __shared__ uint32_t s_gt0[kBlock];  // the low half of the chunk's first tile: the tile's distance from it is below 2^32
   const uint32_t tid = threadIdx.x;
@@ -1201,12 +1300,71 @@ __device__ __forceinline__ void gated_pass(const ScanArgs& A) {
         tg.length = uniform_u64(len);
         tg.tile0 = tile - (uint32_t)((uint32_t)tile - (uint32_t)__builtin_amdgcn_readfirstlane(s_gt0[at]));
         tg.c = 0;  // (the emit pass names the chunk; a count pass does not)
-        scan_tile_at<KIND, false, false, false, LOADS, ICASE, ALIGNED, true>(A, tile, tg, stage_pat);
+        scan_tile_at<KIND, false, false, false, LOADS, ICASE, ALIGNED, true, FIN>(A, tile, tg, stage_pat, &fin_acc);
         stage_pat = false;
+        if constexpr (FIN) {
+          // a tile that is the home of a position of its chunk's zone looks at the zone; the home of the zone's first
+          // occurrence walks it (see above).  Workgroup-uniform tests; the work is wave 0's, the others go on.
+          const uint32_t plen = A.pat.plen, koff = KIND >= kLong ? A.pat.koff : 0u;
+          const uint64_t L = tg.length;
+          if (!A.pat.exact_tail && L >= plen && wave == 0) {
+            constexpr uint64_t kTile = (uint64_t)kWaveLoad * LOADS * kWaves;
+            const uint64_t Z = tail_zone_begin(L, plen), trel = tile - tg.tile0;
+            if (trel >= (Z + koff) / kTile && trel <= (L - plen + koff) / kTile) {
+              const uint8_t* cbase = A.base + tg.offset;
+              const TailMasks tm = wave_tail_masks(cbase, L, A.pat.d_pat, plen, false, s_zone, lane);
+              if (tm.full != 0 && (Z + (uint32_t)__builtin_ctzll(tm.full) + koff) / kTile == trel) {
+                const uint64_t entry = fin_walk_entry<LOADS>(A, cbase, L, Z, tg.tile0, koff, lane);
+                const uint32_t kk = tm.k;
+                auto k_at = [&](uint32_t j) { return (uint32_t)__builtin_amdgcn_readlane((int)kk, (int)__builtin_amdgcn_readfirstlane(j)); };
+                fin_acc += tail_walk_masks(L, plen, entry, false, tm.full, tm.nz, tm.nlm, k_at);
+              }
+            }
+          }
+        }
       }
     }
     __syncthreads();  // the unit's LDS words are rewritten for the next one
   }
+  if constexpr (FIN) {
+    // leaving: the workgroup's matches and its arrival in one atomicAdd; the value it returns tells the last workgroup
+    // that it is the last and what the others brought.
+    if (lane == 0) s_fin[wave] = fin_acc;
+    __syncthreads();
+    if (tid == 0) {
+      uint64_t mine = 0;
+#pragma unroll
+      for (uint32_t w = 0; w < (uint32_t)kWaves; ++w) mine += s_fin[w];
+      // two levels: workgroup b arrives at word 1 + b % kFinGroups, the last of a group carries the group's sum to word 0
+      // (thousands of returning atomics on ONE word queue up behind one another, ~8 ns each, and a workgroup holds its
+      // place on the compute unit until its own comes back)
+      constexpr unsigned long long kMask = (1ull << kFinTotalBits) - 1ull;
+      const uint32_t g = blockIdx.x % kFinGroups;
+      const uint32_t members = (gridDim.x + kFinGroups - 1u - g) / kFinGroups;
+      const unsigned long long old = atomicAdd(F->word + 1u + g, (1ull << kFinTotalBits) + mine);
+      if ((old >> kFinTotalBits) == (unsigned long long)members - 1ull) {
+        __hip_atomic_store(F->word + 1u + g, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // at rest for the next pass (stream order)
+        const uint32_t groups = gridDim.x < kFinGroups ? gridDim.x : kFinGroups;
+        const unsigned long long gsum = (old & kMask) + mine;
+        const unsigned long long top = atomicAdd(F->word, (1ull << kFinTotalBits) + gsum);
+        if ((top >> kFinTotalBits) == (unsigned long long)groups - 1ull) {
+          const uint64_t v[XSG_NUM_COUNTERS] = {(top & kMask) + gsum, 0ull, 0ull, F->total_bytes};
+          for (int k = 0; k < XSG_NUM_COUNTERS; ++k) {
+            F->counters[k] = v[k];
+            if (F->host_counters) F->host_counters[k] = v[k];
+          }
+          if (F->status) *F->status = 0ull;
+          __hip_atomic_store(F->word, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+      }
+    }
+  }
+}
+
+// The finishing form's entry point: ScanArgs as every k_scan has them, its own few words beside them.
+template <int KIND, int LOADS, bool ALIGNED>
+__global__ __launch_bounds__(kBlock) void k_scan_fin(const ScanArgs A, const GateFinArgs F) {
+  gated_pass<KIND, LOADS, false, ALIGNED, true>(A, &F);
 }
 
 // The kernel proper.  (Round 2 also measured an occupancy request for the class-sequence kinds -- they keep sixteen
@@ -1239,7 +1397,9 @@ __global__ __launch_bounds__(kBlock) void k_scan(const ScanArgs A) {
 
 // The plain count pass may run gated by the binding's sketch: literals of 4 bytes and more, case-sensitive, no newline
 // counts and no line summaries (those passes have something to write for every tile), and only while the arguments still
-// hold the pattern and filter window the sketch entries were computed for (scan_args).
+// hold the pattern and filter window the sketch entries were computed for (scan_args).  Two forms of it exist: the storing
+// one (k_scan<..., GATED>: per-tile words for k_count_finish or a list route) and the finishing one (k_scan_fin: a plain
+// match count's only launch, scan_finishing).
 static bool gate_kind(uint32_t kind) { return kind == kOne || kind == kMask2 || kind == kTwo || kind == kLong; }
 static bool gate_applies(const ScanArgs& a, bool want_nl, bool want_lines, bool emit) {
   return a.sketch != nullptr && a.sk_n != 0 && !emit && !want_nl &&
@@ -1255,15 +1415,22 @@ static dim3 gate_grid(const ScanArgs& a) {
 
 template <int KIND, bool ICASE, bool ALIGNED>
 static hipError_t launch_scan_kind(const ScanArgs& a, bool want_nl, bool want_lines, bool emit, dim3 grid,
-                                   hipStream_t s) {
+                                   hipStream_t s, const GateFinArgs* fin) {
   constexpr int LOADS = 4;  // 16 KiB tiles (32 KiB measured 8 % slower)
   if constexpr (!ICASE && (KIND == kOne || KIND == kMask2 || KIND == kTwo || KIND == kLong)) {
     if (gate_applies(a, want_nl, want_lines, emit)) {
-      // one launch selects and scans (gated_pass): stream-ordered, nothing for the host to wait for
+      // one launch selects and scans (gated_pass): stream-ordered, nothing for the host to wait for.  The storing form
+      // leaves tile_cnt / tile_last / tile_wmask for k_count_finish or a list route; the finishing form (a plain match
+      // count: launch_scan_count_finishing) leaves the counters and no per-tile word.
+      if (fin) {
+        hipLaunchKernelGGL((k_scan_fin<KIND, LOADS, ALIGNED>), gate_grid(a), dim3(kBlock), 0, s, a, *fin);
+        return hipGetLastError();
+      }
       hipLaunchKernelGGL((k_scan<KIND, false, false, false, LOADS, ICASE, ALIGNED, true>), gate_grid(a), dim3(kBlock), 0, s, a);
       return hipGetLastError();
     }
   }
+  if (fin) return hipErrorInvalidValue;  // the finishing form exists gated only: no other kernel stands in for it
 #define KSCAN_LAUNCH(NL, LINES, EM) hipLaunchKernelGGL((k_scan<KIND, NL, LINES, EM, LOADS, ICASE, ALIGNED>), grid, dim3(kBlock), 0, s, a)
   if (emit) {
     KSCAN_LAUNCH(false, false, true);
@@ -1284,14 +1451,14 @@ static hipError_t launch_scan_kind(const ScanArgs& a, bool want_nl, bool want_li
 
 template <int KIND>
 static hipError_t launch_scan_loads(const ScanArgs& a, bool want_nl, bool want_lines, bool emit, dim3 grid,
-                                    hipStream_t s) {
+                                    hipStream_t s, const GateFinArgs* fin) {
   if (a.tile_bytes != kDefaultTileBytes) return hipErrorInvalidValue;
   constexpr bool kWindow = KIND == kTwo || KIND == kLong || KIND == kClass;
   if (kWindow && a.pat.hot)  // the aligned-dword trigger exists for the 8-byte-window kinds only
-    return a.pat.icase ? launch_scan_kind<KIND, true, kWindow>(a, want_nl, want_lines, emit, grid, s)
-                       : launch_scan_kind<KIND, false, kWindow>(a, want_nl, want_lines, emit, grid, s);
-  return a.pat.icase ? launch_scan_kind<KIND, true, false>(a, want_nl, want_lines, emit, grid, s)
-                     : launch_scan_kind<KIND, false, false>(a, want_nl, want_lines, emit, grid, s);
+    return a.pat.icase ? launch_scan_kind<KIND, true, kWindow>(a, want_nl, want_lines, emit, grid, s, fin)
+                       : launch_scan_kind<KIND, false, kWindow>(a, want_nl, want_lines, emit, grid, s, fin);
+  return a.pat.icase ? launch_scan_kind<KIND, true, false>(a, want_nl, want_lines, emit, grid, s, fin)
+                     : launch_scan_kind<KIND, false, false>(a, want_nl, want_lines, emit, grid, s, fin);
 }
 
 static dim3 tile_grid(uint64_t ntiles) {
@@ -1335,7 +1502,8 @@ static uint32_t pick_stagger(const ScanArgs& a, bool want_nl, bool want_lines, b
   return !light ? 0u : a.dense_hint >= 2u ? 4u : kDefaultStagger;
 }
 
-void describe_scan(const ScanArgs& a, bool want_nl, bool want_lines, bool emit, char* out, size_t cap) {
+void describe_scan(const ScanArgs& a, bool want_nl, bool want_lines, bool emit, char* out, size_t cap, bool finishing,
+                   uint64_t total_bytes) {
   if (!out || !cap) return;
   const char* b[2] = {"false", "true"};
   if (a.pat.kind == kSet) return describe_set_scan(a, emit, out, cap);
@@ -1362,7 +1530,9 @@ void describe_scan(const ScanArgs& a, bool want_nl, bool want_lines, bool emit, 
            pick_stagger(r, want_nl, want_lines, emit), r.pat.kind != a.pat.kind ? " (dense: byte-parallel)" : "");
   if (gate_applies(r, want_nl, want_lines, emit)) {
     const size_t n = strlen(out);
-    snprintf(out + n, cap - n, " gated by xsg::k_sketch (512 B/tile)");
+    // (the suffix stays the end of the string; the finishing form of a plain match count says so in front of it)
+    snprintf(out + n, cap - n, "%s gated by xsg::k_sketch (512 B/tile)",
+             finishing && scan_finishing(a, total_bytes) ? " finishing (xsg::k_scan_fin)" : "");
   }
 }
 
@@ -1372,8 +1542,19 @@ bool scan_gated(const ScanArgs& a, bool want_nl, bool want_lines) {
   return gate_applies(r, want_nl, want_lines, false);
 }
 
-static hipError_t launch_scan(const ScanArgs& a_in, bool want_nl, bool want_lines, bool emit, hipStream_t s) {
-  if (a_in.ntiles == 0) return hipSuccess;
+// The finishing form serves the end-of-chunk zone with the wave walk on masks (or has none: exact_tail); a longer needle
+// with the lossy tail keeps the two launches.  GateFinArgs::word packs the arrivals above kFinTotalBits bits of matches.
+// (XSG_GATE_FINISH=0 keeps the two launches everywhere: the A/B switch.)
+bool scan_finishing(const ScanArgs& a, uint64_t total_bytes) {
+  static const bool on = [] { const char* e = getenv("XSG_GATE_FINISH"); return !(e && *e == '0'); }();
+  if (!on || a.ntiles == 0 || a.tile_bytes != kDefaultTileBytes || !scan_gated(a, false, false)) return false;
+  if (!a.pat.exact_tail && a.pat.plen > kTailMaskMaxPlen) return false;
+  return total_bytes < (1ull << kFinTotalBits) && gate_grid(a).x < (1u << (64u - kFinTotalBits));
+}
+
+static hipError_t launch_scan(const ScanArgs& a_in, bool want_nl, bool want_lines, bool emit, hipStream_t s,
+                              const GateFinArgs* fin = nullptr) {
+  if (a_in.ntiles == 0) return fin ? hipErrorInvalidValue : hipSuccess;
   ScanArgs a = a_in;
   if (dense_bytes_route(a, want_lines, emit)) a.pat.kind = kMask1;
   a.tune = pick_stagger(a, want_nl, want_lines, emit);
@@ -1381,15 +1562,15 @@ static hipError_t launch_scan(const ScanArgs& a_in, bool want_nl, bool want_line
   const dim3 grid = (emit && a.hit_tiles) ? dim3((unsigned)std::min<uint64_t>(std::max<uint64_t>(a.hit_cap, 1), emit_grid), 1, 1)
                                          : tile_grid(a.ntiles);
   switch (a.pat.kind) {
-    case kMask1: return launch_scan_loads<kMask1>(a, want_nl, want_lines, emit, grid, s);
-    case kOne: return launch_scan_loads<kOne>(a, want_nl, want_lines, emit, grid, s);
-    case kMask2: return launch_scan_loads<kMask2>(a, want_nl, want_lines, emit, grid, s);
-    case kTwo: return launch_scan_loads<kTwo>(a, want_nl, want_lines, emit, grid, s);
+    case kMask1: return launch_scan_loads<kMask1>(a, want_nl, want_lines, emit, grid, s, fin);
+    case kOne: return launch_scan_loads<kOne>(a, want_nl, want_lines, emit, grid, s, fin);
+    case kMask2: return launch_scan_loads<kMask2>(a, want_nl, want_lines, emit, grid, s, fin);
+    case kTwo: return launch_scan_loads<kTwo>(a, want_nl, want_lines, emit, grid, s, fin);
     case kClass:
       // a window that takes the exact 16 + 32 bit filter has its own instantiation (window filter only)
-      if (a.pat.cls_fast && !a.pat.hot) return launch_scan_loads<kClassFast>(a, want_nl, want_lines, emit, grid, s);
-      return launch_scan_loads<kClass>(a, want_nl, want_lines, emit, grid, s);
-    default: return launch_scan_loads<kLong>(a, want_nl, want_lines, emit, grid, s);
+      if (a.pat.cls_fast && !a.pat.hot) return launch_scan_loads<kClassFast>(a, want_nl, want_lines, emit, grid, s, fin);
+      return launch_scan_loads<kClass>(a, want_nl, want_lines, emit, grid, s, fin);
+    default: return launch_scan_loads<kLong>(a, want_nl, want_lines, emit, grid, s, fin);
   }
 }
 
@@ -1397,6 +1578,10 @@ hipError_t launch_scan_count(const ScanArgs& a, bool want_nl, bool want_lines, h
   if (a.pat.kind == kDfa) return launch_rx_count(a, want_nl, want_lines, s);
   if (a.pat.kind == kSet) return want_lines ? hipErrorInvalidValue : launch_set_count(a, want_nl, s);  // (candidates; no line summaries)
   return launch_scan(a, want_nl, want_lines, false, s);
+}
+hipError_t launch_scan_count_finishing(const ScanArgs& a, const GateFinArgs& f, hipStream_t s) {
+  if (!scan_finishing(a, f.total_bytes)) return hipErrorInvalidValue;
+  return launch_scan(a, false, false, false, s, &f);
 }
 hipError_t launch_scan_emit(const ScanArgs& a, hipStream_t s) {
   if (a.pat.kind == kDfa) return launch_rx_emit(a, s);

@@ -207,7 +207,7 @@ struct xsg_shard {
 
   DevBuf d_chunks, d_tile_chunk, d_chunk_tile0;
   DevBuf d_tile_cnt, d_tile_nl, d_tile_sum, d_tile_last, d_counters;
-  DevBuf d_finish;  // k_count_finish scratch: 3 x kFinishBlocks partial sums, then the ticket word
+  DevBuf d_finish;  // k_count_finish scratch: 3 x kFinishBlocks partial sums, then the ticket word; the finishing gated count's arrival words
   DevBuf d_tile_off, d_tile_nl_off, d_scan_tmp;
   DevBuf d_m_pos, d_m_chunk, d_m_ls, d_keep, d_keep_pre;
   DevBuf d_m_len, d_f_len;  // XSG_MATCHES on the automaton routes: a length per emitted match / per entry of the final list
