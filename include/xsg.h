@@ -342,9 +342,11 @@ int xsg_regex_factor(const void* expr, size_t n, uint32_t flags, uint32_t* posit
  * its gate pays for a pattern, the measured hot filter and filter window of a pattern, the tile marks and density
  * verdicts of the regex prefilters, whether a pattern's lists fit the one-sync route) and every later pass -- the
  * stream-ordered xsg_count_async included -- relies on them.
- * The sketch is 512 bytes of device memory per 16 KiB tile (3.1 % of the text; a
+ * The sketch is 512 bytes of device memory per 16 KiB tile (a
  * binding simply goes without if the allocation fails): one bit per hashed 4-gram that starts in the tile.  It does not
- * depend on the pattern.  The plain count pass of a case-sensitive literal of 4 bytes and more -- xsg_count,
+ * depend on the pattern.  A span locator of another 1 KiB per tile is built with it -- 2048 such bits for each of the
+ * tile's four 4 KiB spans -- so the two together take 9.4 % of the text (3.1 % before the locator existed); a binding
+ * without memory for the locator keeps the sketch alone.  The plain count pass of a case-sensitive literal of 4 bytes and more -- xsg_count,
  * xsg_count_begin, xsg_count_async, the count pass of xsg_search -- is then one launch of a bounded grid: its workgroups
  * test the sketches of 256 tiles at a time for the needle's first grams and scan the tiles that hold every one of them --
  * the candidate tiles -- and read no other text.  A needle whose grams are words of the text passes everywhere: the synchronous
@@ -357,7 +359,9 @@ int xsg_regex_factor(const void* expr, size_t n, uint32_t flags, uint32_t* posit
  * that hold an occurrence itself and writes the counters (50 GiB, `Sherlock`: 0.149 -> 0.110 ms per call).  It pays for a
  * needle in a chunk's last plen + 31 bytes with a look back through that chunk for the previous occurrence: data with the
  * needle at the end of EVERY chunk measured 1.6 x slower than the two launches (0.25 against 0.16 ms, 3200 chunks of 16 MiB,
- * DESIGN.md section 5); XSG_GATE_FINISH=0 keeps the two launches.  Bindings of 64 MiB and more get the sketch from
+ * DESIGN.md section 5); XSG_GATE_FINISH=0 keeps the two launches.  With the span locator that launch reads, of a
+ * candidate tile, only the 4 KiB spans whose own bits hold the needle's grams (XSG_GATE_SPANS=0: the whole tile;
+ * xsg_scan_kernel_name says " by 4 KiB spans" in front of " finishing").  Bindings of 64 MiB and more get the sketch from
  * xsg_shard_tune, or from the second such pass of a synchronous entry point (the build is enqueued on the context's
  * stream); xsg_count_async on a caller's stream never builds, it uses what is there.  XSG_SKETCH=0 switches the feature
  * off, XSG_SKETCH=1 builds before the first pass.  A caller that refills

@@ -98,11 +98,15 @@ static int build_sketch(xsg_shard* s) {
   b.chunk_tile0 = s->d_chunk_tile0.as<uint64_t>();
   b.ntiles = s->ntiles;
   b.sketch = s->d_sketch.as<uint32_t>();
+  // the span locator rides along; without memory for it the binding keeps the tile sketch and whole-tile reads
+  const bool spans = s->d_spans.ensure((size_t)span_alloc_words(s->ntiles) * 4) == XSG_OK;
+  b.spans = spans ? s->d_spans.as<uint32_t>() : nullptr;
   HIP_TRY(launch_sketch_build(b, c->stream));
   // a pass on a caller's stream must find it complete: the event that orders the chunk table orders the sketch as well
   HIP_TRY(hipEventRecord(s->table_ev, c->stream));
   s->table_pending = true;
   s->sketch_tiles = s->ntiles;
+  s->span_tiles = spans ? s->ntiles : 0;
   s->gate_serial = 0;
   return XSG_OK;
 }
@@ -390,13 +394,29 @@ int xsg::choose_hot_filter(xsg_shard* s, hipStream_t st, bool want_nl, bool want
 
 // the finishing form's own arguments: where the result goes, and its scratch words (1 + kFinGroups) behind
 // k_count_finish's partials and the 128 bytes of u32 words there (ticket, scan flags, the list route's two)
-static GateFinArgs fin_args(xsg_shard* s, uint64_t* d_counters, uint64_t* host_counters, uint64_t* d_status) {
+// The span locator serves these arguments' pass: the binding holds one for its tiles, the arguments gate on the binding's
+// sketch with the context's pattern, and XSG_GATE_SPANS is not 0 (the A/B switch: whole-tile reads in the same build).
+static bool spans_apply(const xsg_shard* s, const ScanArgs& a) {
+  const char* e = XSG_TOGGLE("XSG_GATE_SPANS");
+  if (e && *e == '0') return false;
+  const xsg_ctx* c = s->ctx;
+  return a.sketch != nullptr && a.sk_n != 0 && a.sk_pat == a.pat.d_pat && s->span_tiles != 0 && s->span_tiles == s->ntiles &&
+         s->d_spans.p && c->span_hashes.size() == c->sketch_hashes.size() && a.sk_koff + 4u <= a.pat.plen;
+}
+static GateFinArgs fin_args(xsg_shard* s, const ScanArgs& a, uint64_t* d_counters, uint64_t* host_counters, uint64_t* d_status) {
   GateFinArgs f{};
   f.counters = d_counters;
   f.host_counters = host_counters;
   f.status = d_status;
   f.word = reinterpret_cast<unsigned long long*>(s->d_finish.as<uint64_t>() + 3 * (size_t)kFinishBlocks + 16);
   f.total_bytes = s->total_bytes;
+  if (spans_apply(s, a)) {
+    // the grams the tile sketch tests (sketch_fields), as (word, mask) pairs of a span's bits (span_entries)
+    const xsg_ctx* c = s->ctx;
+    const uint32_t first = a.sk_koff, n = sketch_pattern_grams(a.pat.plen, first);
+    if (n != 0 && first + n <= c->span_hashes.size()) f.sp_n = span_entries(c->span_hashes.data() + first, n, f.sp_word, f.sp_mask);
+    if (f.sp_n) f.spans = s->d_spans.as<uint32_t>();
+  }
   return f;
 }
 
@@ -430,7 +450,7 @@ static int enqueue_count(xsg_shard* s, bool want_matches, bool want_lines, bool 
   // neither written nor read and stay as prepare_tiles left them.  Everything else -- newline totals, line counts,
   // needles of 34 bytes and more with the lossy tail, the ungated kinds, another pattern -- keeps the two launches below.
   if (want_matches && !want_lines && !rx_lines && !want_nl && !other_pattern && scan_finishing(a, s->total_bytes)) {
-    HIP_TRY(launch_scan_count_finishing(a, fin_args(s, d_counters, host_counters, d_status), st));
+    HIP_TRY(launch_scan_count_finishing(a, fin_args(s, a, d_counters, host_counters, d_status), st));
     return XSG_OK;
   }
   // dirty until the finish kernel is in the queue behind the scan
@@ -769,7 +789,7 @@ extern "C" int xsg_time_scan_kernel(xsg_shard* s, uint32_t mode, int iters, floa
   // a plain match count that enqueue_count would finish inside its pass is timed in that form (not in the storing form
   // of the list routes), into the binding's scratch counters: the per-tile arrays stay clean
   const bool fin = count_finishes(s, a, m, want_nl);
-  const GateFinArgs f = fin_args(s, s->d_counters.as<uint64_t>(), nullptr, nullptr);
+  const GateFinArgs f = fin_args(s, a, s->d_counters.as<uint64_t>(), nullptr, nullptr);
   if (!fin) s->cnt_clean = s->sum_clean = false;  // no finish kernel runs behind these launches
   EventPair ev;
   HIP_TRY(ev.init());
@@ -801,7 +821,7 @@ extern "C" int xsg_scan_kernel_name(xsg_shard* s, uint32_t mode, char* out, size
   } else {
     // (a plain match count says which form of the gated pass it launches: the finishing one, or the storing one)
     describe_scan(a, want_nl, !list && m == XSG_COUNT_LINES, false, out, cap,
-                  !list && count_finishes(s, a, m, (mode & XSG_WITH_NEWLINES) != 0), s->total_bytes);
+                  !list && count_finishes(s, a, m, (mode & XSG_WITH_NEWLINES) != 0), s->total_bytes, spans_apply(s, a));
   }
   if (inverted(s->ctx)) {  // the inverted form: the same scan, then the complement (of the list, or of the line count)
     const size_t n = strlen(out);

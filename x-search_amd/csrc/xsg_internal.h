@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "../../include/xsg.h"
+#include "xsg_sketch.h"
 
 namespace xsg {
 
@@ -163,6 +164,7 @@ struct SketchArgs {
   const uint64_t* chunk_tile0;
   uint64_t ntiles;
   uint32_t* sketch;             // sketch_alloc_words(ntiles), at sketch_index(tile, word)
+  uint32_t* spans;              // the span locator: span_alloc_words(ntiles), at span_index(tile, word, span); null: not built
 };
 hipError_t launch_sketch_build(const SketchArgs& a, hipStream_t s);
 // k_sketch_sample: *passed += the number of tiles among 0, stride, 2 * stride, ... (nsamp of them, all < ntiles) whose
@@ -175,6 +177,7 @@ bool scan_gated(const ScanArgs& a, bool want_nl, bool want_lines);
 // registers, walks the end-of-chunk zones that hold an occurrence itself and writes the counters -- one launch, no
 // k_count_finish, no store to the per-tile arrays.  What it needs beyond ScanArgs travels as a second kernel parameter,
 // so that every other k_scan instantiation keeps its argument block.
+constexpr uint32_t kGateRegs = 6;  // sketch words a lane requests at once; entries beyond (long needles) follow in batches
 struct GateFinArgs {
   uint64_t* counters;         // device, XSG_NUM_COUNTERS: {matches, 0, 0, total_bytes}
   uint64_t* host_counters;    // optional pinned mirror
@@ -183,6 +186,14 @@ struct GateFinArgs {
                               // far: workgroup b arrives at word 1 + b % kFinGroups, the last of a group at word 0; who
                               // is last learns it and the sum from the value its atomicAdd returns and puts the word back
   uint64_t total_bytes;
+  // The span locator of the binding (xsg_sketch.h; null: whole-tile reads) and the pattern's bits in a span's kSpanBits,
+  // one entry per distinct word like sk_word / sk_mask: a candidate tile's wave reads its 4 KiB only if its span holds
+  // them all.  At most kSpanRegs entries: fewer grams are still a superset filter.  (Here, not in ScanArgs: every other
+  // k_scan instantiation keeps its argument block.)
+  const uint32_t* spans;
+  uint32_t sp_n;
+  uint32_t sp_word[kSpanRegs];
+  uint32_t sp_mask[kSpanRegs];
 };
 constexpr uint32_t kFinGroups = 64;
 constexpr uint32_t kFinTotalBits = 40;  // matches <= total_bytes < 2^40; the grid stays below 2^24 (scan_finishing)
@@ -257,9 +268,10 @@ hipError_t launch_set_emit(const ScanArgs& a, hipStream_t s);
 hipError_t launch_set_verify(const RxPreArgs& a, hipStream_t s);
 void describe_set_scan(const ScanArgs& a, bool emit, char* out, size_t cap);
 // "xsg::k_scan<KIND, WANT_NL, WANT_LINES, EMIT, LOADS, ICASE>" + the stagger launch_scan would use, for reports
-// finishing: the caller's pass is a plain match count that takes the finishing form where scan_finishing says so
+// finishing: the caller's pass is a plain match count that takes the finishing form where scan_finishing says so;
+// spans: that form would run with the binding's span locator (GateFinArgs::spans)
 void describe_scan(const ScanArgs& a, bool want_nl, bool want_lines, bool emit, char* out, size_t cap,
-                   bool finishing = false, uint64_t total_bytes = 0);
+                   bool finishing = false, uint64_t total_bytes = 0, bool spans = false);
 
 // exclusive scan: out[i] = sum_{k<i} in[k] for i in [0, n]; out has n+1 entries.
 // tmp must hold scan_tmp_elems(n) uint64 values.

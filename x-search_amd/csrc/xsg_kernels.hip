@@ -781,10 +781,10 @@ __device__ __forceinline__ TileGeom tile_geom(const ScanArgs& A, const uint64_t 
 // up here, where it always was.  (The loads and their consumption are still one piece: a candidate's text is not
 // requested ahead of the previous candidate's compares.)
 // FIN (the finishing form of the gated count, gated_pass): the wave's matches are added to *fin_acc (wave-uniform) and
-// nothing is stored per tile -- no tile_cnt, no tile_last, no wave mark.
+// nothing is stored per tile -- no tile_cnt, no tile_last, no wave mark; span_on (wave-uniform): this wave's span is read.
 template <int KIND, bool WANT_NL, bool WANT_LINES, bool EMIT, int LOADS, bool ICASE, bool ALIGNED, bool HAVE_GEOM, bool FIN = false>
 __device__ __forceinline__ void scan_tile_at(const ScanArgs& A, const uint64_t tile, const TileGeom& geom, const bool stage,
-                                             uint64_t* fin_acc = nullptr) {
+                                             uint64_t* fin_acc = nullptr, const bool span_on = true) {
   constexpr int kLoads = LOADS;                          // 16-byte units per lane
   constexpr uint32_t kWaveSpan = kWaveLoad * kLoads;     // contiguous bytes per wave
   constexpr uint32_t kTile = kWaveSpan * kWaves;         // bytes per workgroup
@@ -808,6 +808,10 @@ __device__ __forceinline__ void scan_tile_at(const ScanArgs& A, const uint64_t t
     for (uint32_t k = tid; k < P.plen && k < kLdsPattern; k += kBlock) s_pat[k] = P.d_pat[k];
     __syncthreads();
   }
+  // FIN with the span locator (gated_pass): a wave whose span cannot hold a window start issues no load and adds nothing,
+  // like the emit pass's `!wave_on`.  Behind the staging barrier above; the finishing form of the gate kinds has no other.
+  static_assert(!FIN || (!EMIT && !WANT_NL && !WANT_LINES && !is_cls(KIND) && KIND != kMask1), "the finishing form: no barrier behind this point");
+  if (FIN && !span_on) return;
 
   const TileGeom tg = HAVE_GEOM ? geom : tile_geom(A, tile);
   const uint32_t c = tg.c;
@@ -1102,6 +1106,11 @@ __device__ __forceinline__ void scan_tile(const ScanArgs& A, const uint64_t tile
 // ballots are the unit's candidate list; all four waves walk their set bits in the same order.  A tile that is no
 // candidate gets no store: "nothing found" is the rest state of the per-tile arrays.
 //
+// The finishing form with a span locator (GateFinArgs::spans) reads, of a candidate, only the 4 KiB spans whose own bits
+// hold the pattern's span entries: a passing lane requests word k of its tile's four spans -- one 16-byte load per entry --
+// together with its geometry, reduces them to a 4-bit mask that goes to LDS with the geometry, and wave s of the
+// workgroup scans the candidate only if bit s is set (scan_tile_at: span_on).
+//
 // Per unit: the lane's sk_n words and its tile's chunk number (tile_chunk) are requested, all before any is used; the
 // words are tested and the ballot taken; lanes that pass request their chunk's entry and first tile; ballots and the
 // passing lanes' geometry go to LDS; the candidates are scanned (scan_tile_at) with their geometry ready, so a
@@ -1210,7 +1219,6 @@ __device__ __forceinline__ uint64_t fin_walk_entry(const ScanArgs& A, const uint
   return 0;
 }
 
-constexpr uint32_t kGateRegs = 6;  // sketch words a lane requests at once; entries beyond (long needles) follow in batches
 template <int KIND, int LOADS, bool ICASE, bool ALIGNED, bool FIN = false>
 __device__ __forceinline__ void gated_pass(const ScanArgs& A, const GateFinArgs* F = nullptr) {
   __shared__ unsigned long long s_bal[kWaves];
@@ -1219,6 +1227,7 @@ __device__ __forceinline__ void gated_pass(const ScanArgs& A, const GateFinArgs*
   uint64_t fin_acc = 0;  // FIN: this wave's matches (wave-uniform)
   __shared__ uint64_t s_goff[kBlock], s_glen[kBlock];
   __shared__ uint32_t s_gt0[kBlock];  // the low half of the chunk's first tile: the tile's distance from it is below 2^32
+  __shared__ uint32_t s_gsp[FIN ? kBlock : 1];  // FIN: the candidate's span mask, bit s = wave s reads its 4 KiB
   const uint32_t tid = threadIdx.x;
   const uint32_t lane = tid & 63u;
   const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1252,8 +1261,8 @@ __device__ __forceinline__ void gated_pass(const ScanArgs& A, const GateFinArgs*
   // the verdict on those words; a passing lane requests its tile's geometry
   unsigned long long bal = 0;
   uint64_t g_off = 0, g_len = 0;
-  uint32_t g_t0 = 0;
-  auto pass_stage = [&]() {
+  uint32_t g_t0 = 0, g_sp = 0;
+  auto pass_stage = [&](const uint64_t u) {
     uint32_t m = miss;
 #pragma unroll
     for (uint32_t k = 0; k < kGateRegs; ++k)
@@ -1261,22 +1270,49 @@ __device__ __forceinline__ void gated_pass(const ScanArgs& A, const GateFinArgs*
     const bool pass = m == 0;
     bal = __ballot(pass);
     if (pass) {
+      // FIN with a span locator: the lane's locator words -- word k of the tile's four spans is one 16-byte load
+      // (span_index) -- are requested in the same batch as its geometry, so they add no round trip
+      uint4 x[kSpanRegs];
+      uint32_t sn = 0;
+      if constexpr (FIN) {
+        if (F->spans) {
+          sn = F->sp_n;
+          const uint4* sp = reinterpret_cast<const uint4*>(F->spans + span_index(u * kBlock + tid, 0, 0));
+#pragma unroll
+          for (uint32_t k = 0; k < kSpanRegs; ++k)
+            if (k < sn) x[k] = sp[F->sp_word[k]];
+        }
+      }
       const ChunkDev ch = A.chunks[wc];
       g_off = ch.offset;
       g_len = ch.length;
       g_t0 = reinterpret_cast<const uint32_t*>(A.chunk_tile0 + wc)[0];
+      if constexpr (FIN) {
+        g_sp = (1u << kSpansPerTile) - 1u;  // no locator: every wave reads
+        if (sn) {
+          uint32_t mx = 0, my = 0, mz = 0, mw = 0;  // per span: the bits that are missing
+#pragma unroll
+          for (uint32_t k = 0; k < kSpanRegs; ++k)
+            if (k < sn) {
+              const uint32_t b = F->sp_mask[k];
+              mx |= ~x[k].x & b, my |= ~x[k].y & b, mz |= ~x[k].z & b, mw |= ~x[k].w & b;
+            }
+          g_sp = (mx == 0 ? 1u : 0u) | (my == 0 ? 2u : 0u) | (mz == 0 ? 4u : 0u) | (mw == 0 ? 8u : 0u);
+        }
+      }
     }
   };
 
   bool stage_pat = true;
   for (uint64_t u1 = blockIdx.x; u1 < nunits; u1 += gridDim.x) {
     sketch_stage(u1);
-    pass_stage();
+    pass_stage(u1);
     if (lane == 0) s_bal[wave] = bal;
     if ((bal >> lane) & 1ull) {
       s_goff[tid] = g_off;
       s_glen[tid] = g_len;
       s_gt0[tid] = g_t0;
+      if constexpr (FIN) s_gsp[tid] = g_sp;
     }
     __syncthreads();
 #pragma unroll 1
@@ -1300,11 +1336,16 @@ __device__ __forceinline__ void gated_pass(const ScanArgs& A, const GateFinArgs*
         tg.length = uniform_u64(len);
         tg.tile0 = tile - (uint32_t)((uint32_t)tile - (uint32_t)__builtin_amdgcn_readfirstlane(s_gt0[at]));
         tg.c = 0;  // (the emit pass names the chunk; a count pass does not)
-        scan_tile_at<KIND, false, false, false, LOADS, ICASE, ALIGNED, true, FIN>(A, tile, tg, stage_pat, &fin_acc);
+        bool span_on = true;  // wave-uniform: this wave's 4 KiB of the candidate can hold a window start
+        if constexpr (FIN) span_on = (((uint32_t)__builtin_amdgcn_readfirstlane(s_gsp[at]) >> wave) & 1u) != 0;
+        scan_tile_at<KIND, false, false, false, LOADS, ICASE, ALIGNED, true, FIN>(A, tile, tg, stage_pat, &fin_acc, span_on);
         stage_pat = false;
         if constexpr (FIN) {
           // a tile that is the home of a position of its chunk's zone looks at the zone; the home of the zone's first
           // occurrence walks it (see above).  Workgroup-uniform tests; the work is wave 0's, the others go on.
+          // Per candidate TILE, whatever its span mask: the zone's occurrences are kept out of the scan by `limit` and
+          // found by the walk alone, so no span bit decides about them, and the tile that is the home of the zone's
+          // first occurrence holds its grams and is a candidate whether or not any of its spans is read.
           const uint32_t plen = A.pat.plen, koff = KIND >= kLong ? A.pat.koff : 0u;
           const uint64_t L = tg.length;
           if (!A.pat.exact_tail && L >= plen && wave == 0) {
@@ -1363,7 +1404,10 @@ __device__ __forceinline__ void gated_pass(const ScanArgs& A, const GateFinArgs*
 
 // The finishing form's entry point: ScanArgs as every k_scan has them, its own few words beside them.
 template <int KIND, int LOADS, bool ALIGNED>
-__global__ __launch_bounds__(kBlock) void k_scan_fin(const ScanArgs A, const GateFinArgs F) {
+// (The occupancy request: with the span locator's loads the instantiations came out at 79 .. 84 VGPRs, half of them
+// past the 80 that six waves per SIMD allow; asked for six, the compiler fits all of them into 74 .. 78 without scratch
+// -- profiles/spans_registers.txt.)
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(6))) void k_scan_fin(const ScanArgs A, const GateFinArgs F) {
   gated_pass<KIND, LOADS, false, ALIGNED, true>(A, &F);
 }
 
@@ -1503,7 +1547,7 @@ static uint32_t pick_stagger(const ScanArgs& a, bool want_nl, bool want_lines, b
 }
 
 void describe_scan(const ScanArgs& a, bool want_nl, bool want_lines, bool emit, char* out, size_t cap, bool finishing,
-                   uint64_t total_bytes) {
+                   uint64_t total_bytes, bool spans) {
   if (!out || !cap) return;
   const char* b[2] = {"false", "true"};
   if (a.pat.kind == kSet) return describe_set_scan(a, emit, out, cap);
@@ -1530,9 +1574,11 @@ void describe_scan(const ScanArgs& a, bool want_nl, bool want_lines, bool emit, 
            pick_stagger(r, want_nl, want_lines, emit), r.pat.kind != a.pat.kind ? " (dense: byte-parallel)" : "");
   if (gate_applies(r, want_nl, want_lines, emit)) {
     const size_t n = strlen(out);
-    // (the suffix stays the end of the string; the finishing form of a plain match count says so in front of it)
-    snprintf(out + n, cap - n, "%s gated by xsg::k_sketch (512 B/tile)",
-             finishing && scan_finishing(a, total_bytes) ? " finishing (xsg::k_scan_fin)" : "");
+    // (the suffix stays the end of the string; the finishing form of a plain match count says so in front of it, and
+    // in front of that whether it reads the candidates' passing 4 KiB spans only)
+    const bool fin = finishing && scan_finishing(a, total_bytes);
+    snprintf(out + n, cap - n, "%s%s gated by xsg::k_sketch (512 B/tile)", fin && spans ? " by 4 KiB spans" : "",
+             fin ? " finishing (xsg::k_scan_fin)" : "");
   }
 }
 
@@ -1785,11 +1831,17 @@ hipError_t launch_count_finish(const FinishArgs& a, hipStream_t s) {
 // a 128-word bitmap in LDS: tested first, OR-ed only where still clear (text repeats its grams: most are already there,
 // and atomics on one word serialise).  The tile's 128 words go to their places in the group (sketch_index: a dword every
 // 256 bytes).
+// kSpans: the span locator is built by the same pass.  Round r of the tile IS span r: each gram also sets its span bit
+// (span_hash: other bits of the same mixed value) in a second LDS bitmap laid out as the words are stored, [word][span],
+// with the same test-then-atomicOr; the grams of the first 29 positions of round r + 1 belong to span r as well.  The
+// tile's 256 locator words leave as one contiguous 1 KiB block (span_index).
 // Reads stay inside the chunk's rounded length (a unit behind it re-reads the last one, as in k_scan).  Grams that
 // reach beyond `length`, and what a clamped neighbour contributes, may set bits: the sketch is a superset.
 // ---------------------------------------------------------------------------
+template <bool kSpans>
 __global__ __launch_bounds__(kBlock) void k_sketch_build(const SketchArgs A) {
   __shared__ uint32_t s_bits[kSketchWords];
+  __shared__ uint32_t s_span[kSpans ? kSpanWords * kSpansPerTile : 1];  // the span locator's words of the tile, as they are stored
   // Workgroups are dealt round-robin to the card's eight XCDs, each with an L2 of its own, and the words of a group of 64
   // tiles interleave (sketch_index): the 64 workgroups of a group are made ones of the SAME XCD -- 512 consecutive
   // workgroups build eight groups, one per residue of 8 -- so that one L2 collects a group's 32 KiB before it writes them.
@@ -1803,6 +1855,9 @@ __global__ __launch_bounds__(kBlock) void k_sketch_build(const SketchArgs A) {
   const uint32_t lane = tid & 63u;
   const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   if (tid < kSketchWords) s_bits[tid] = 0u;
+  if (kSpans) {
+    for (uint32_t k = tid; k < kSpanWords * kSpansPerTile; k += kBlock) s_span[k] = 0u;
+  }
   __syncthreads();
   const uint32_t c = A.tile_chunk ? A.tile_chunk[tile] : 0u;
   const ChunkDev ch = A.chunks[c];
@@ -1824,26 +1879,49 @@ __global__ __launch_bounds__(kBlock) void k_sketch_build(const SketchArgs A) {
     const uint32_t d[5] = {t.x, t.y, t.z, t.w, from_next_lane(t.x, e0, lane)};
     const bool own = off < Lr && (r < kRounds || lane < 2u);
     const uint32_t npos = (r == kRounds && lane == 1u) ? kSketchReach + 1u - kUnit : kUnit;
+    // The span locator: round r is span r, and the first kSketchReach + 1 positions of round r + 1 -- its units 0 and 1,
+    // 16 and 13 positions -- belong to span r as well (behind round 3 they are the two units behind the tile).
+    // (only the first wave runs the round behind the tile: there tid is the lane)
+    const uint32_t reach = r == 0u ? 0u : tid == 0u ? kUnit : tid == 1u ? kSketchReach + 1u - kUnit : 0u;
     if (own) {
 #pragma unroll
       for (uint32_t b = 0; b < kUnit; ++b) {
         if (b < npos) {
           const uint32_t q = b >> 2, sh = b & 3u;
           const uint32_t g = sh ? __builtin_amdgcn_alignbyte(d[q + 1], d[q], sh) : d[q];
-          const uint32_t h = sketch_hash(g);
+          const uint32_t mix = sketch_mix(g);
+          const uint32_t h = mix >> 20;  // sketch_hash(g)
           const uint32_t bit = 1u << (h & 31u);
           if (!(s_bits[h >> 5] & bit)) atomicOr(&s_bits[h >> 5], bit);
+          if (kSpans) {
+            const uint32_t sh2 = span_hash_of_mix(mix), sbit = 1u << (sh2 & 31u);
+            if (r < kRounds) {
+              uint32_t* w = &s_span[(sh2 >> 5) * kSpansPerTile + r];
+              if (!(*w & sbit)) atomicOr(w, sbit);
+            }
+            if (b < reach) {
+              uint32_t* w = &s_span[(sh2 >> 5) * kSpansPerTile + (r - 1u)];
+              if (!(*w & sbit)) atomicOr(w, sbit);
+            }
+          }
         }
       }
     }
   }
   __syncthreads();
   if (tid < kSketchWords) A.sketch[sketch_index(tile, tid)] = s_bits[tid];
+  if (kSpans) {  // the tile's locator words leave as one contiguous block (span_index: [word][span])
+    for (uint32_t k = tid; k < kSpanWords * kSpansPerTile; k += kBlock) A.spans[span_index(tile, 0, 0) + k] = s_span[k];
+  }
 }
 
 hipError_t launch_sketch_build(const SketchArgs& a, hipStream_t s) {
   if (a.ntiles == 0) return hipSuccess;
-  hipLaunchKernelGGL(k_sketch_build, tile_grid((a.ntiles + 511u) & ~(uint64_t)511u), dim3(kBlock), 0, s, a);
+  const dim3 grid = tile_grid((a.ntiles + 511u) & ~(uint64_t)511u);
+  if (a.spans)
+    hipLaunchKernelGGL(k_sketch_build<true>, grid, dim3(kBlock), 0, s, a);
+  else
+    hipLaunchKernelGGL(k_sketch_build<false>, grid, dim3(kBlock), 0, s, a);
   return hipGetLastError();
 }
 

@@ -157,6 +157,7 @@ struct xsg_ctx {
   // a literal of 4 bytes and more: sketch_hash of the gram at every pattern offset 0 .. plen - 4 (xsg_sketch.h), computed
   // by xsg_set_pattern; scan_args picks the ones behind the filter window in use.  Empty: the pattern has no gate.
   std::vector<uint16_t> sketch_hashes;
+  std::vector<uint16_t> span_hashes;               // span_hash of the same grams: their bits in a span's locator (xsg_sketch.h)
   uint64_t sketch_min_bytes = 64ull << 20;         // bindings below this never build a sketch (XSG_SKETCH_MIN_BYTES; tests set 0)
   char arch[128] = "";
   int cus = 0;
@@ -225,6 +226,10 @@ struct xsg_shard {
   uint64_t sketch_tiles = 0;      // != 0: d_sketch holds the sketch of this binding's `ntiles` tiles
   uint32_t sketch_passes = 0;     // eligible synchronous passes this binding has seen
   bool sketch_refused = false;    // its allocation failed: the binding goes without
+  // The span locator beside it (xsg_sketch.h): another 1 KiB per tile, built by the same launch.  A binding without memory
+  // for it keeps the tile sketch and whole-tile reads.
+  DevBuf d_spans;
+  uint64_t span_tiles = 0;        // != 0: d_spans holds the locator of this binding's `ntiles` tiles
   uint64_t gate_serial = 0;       // ctx->pattern_serial the verdict below was taken for (0: none)
   uint32_t gate_koff = 0;         // ... with this filter window
   bool gate_on = false;           // ... fewer than a quarter of the sampled tiles pass: the gate pays
@@ -281,7 +286,7 @@ struct xsg_shard {
                      &d_f_chunk, &d_out_u64, &d_line_len, &d_line_off, &d_line_bytes, &d_dropped, &d_c_pos, &d_c_chunk, &d_c_len, &d_c_keep,
                      &d_c_pre, &d_tile_mask, &d_tot, &d_hit, &d_scan2, &d_wmask, &d_inv_lo, &d_inv_cnt,
                      &d_inv_off, &d_inv_pos, &d_inv_chunk, &d_m_len, &d_f_len, &d_cx_lo, &d_cx_hi, &d_cx_cnt,
-                     &d_cx_slot, &d_cx_pos, &d_cx_chunk, &d_cx_edge, &d_sketch};
+                     &d_cx_slot, &d_cx_pos, &d_cx_chunk, &d_cx_edge, &d_sketch, &d_spans};
     for (DevBuf* b : all) b->release();
     if (h_stage) (void)hipHostFree(h_stage);
     if (h_counters) (void)hipHostFree(h_counters);

@@ -210,6 +210,7 @@ static int set_dfa_pattern(xsg_ctx* c, const uint8_t* re, size_t n, uint32_t fla
   ++c->pattern_serial;
   c->koff_cands.clear();
   c->sketch_hashes.clear();
+  c->span_hashes.clear();
   c->bordered = false;  // the kernel walks every line as the reference does: what it reports is already non-overlapping
   c->overlap_words.clear();
   // The table the line walks step (k_rx_scan / k_rx_count): the anchored automaton for the line-anchor form (`^` walks
@@ -350,6 +351,7 @@ static int set_class_pattern(xsg_ctx* c, const uint8_t* re, size_t n, uint32_t f
   ++c->pattern_serial;
   c->koff_cands.clear();
   c->sketch_hashes.clear();
+  c->span_hashes.clear();
   c->bordered = xsg::sequence_can_overlap(seq);
   c->overlap_words.clear();
   std::vector<uint8_t> blob;
@@ -548,6 +550,7 @@ extern "C" int xsg_set_literals(xsg_ctx* c, const void* list, size_t n, uint32_t
   ++c->pattern_serial;
   c->koff_cands.clear();
   c->sketch_hashes.clear();  // the sketch gate serves single literals
+  c->span_hashes.clear();
   c->bordered = false;       // k_rx_heads / k_rx_chains walk the candidates as the reference does: no overlap is left
   c->overlap_words.clear();
   c->rx_pre = c->rx_fac = false;
@@ -616,6 +619,8 @@ static int set_pattern_plain(xsg_ctx* c, const void* pattern, size_t plen, uint3
   c->sketch_hashes.clear();  // the gate of the plain count pass: case-sensitive literals of 4 bytes and more
   if (plen >= 4 && !(flags & XSG_FLAG_IGNORE_CASE))
     for (size_t k = 0; k + 4 <= plen; ++k) c->sketch_hashes.push_back((uint16_t)sketch_hash(sketch_gram(p + k)));
+  c->span_hashes.clear();  // ... and the same grams' bits in a span's locator (k_scan_fin)
+  for (size_t k = 0; k < c->sketch_hashes.size(); ++k) c->span_hashes.push_back((uint16_t)span_hash(sketch_gram(p + k)));
   c->rx_pre = false;
   c->rx_fac = false;
   P.kind = plen < 4 ? kMask1 : plen == 4 ? kOne : plen < 8 ? kMask2 : plen == 8 ? kTwo : kLong;
