@@ -417,6 +417,11 @@ static GateFinArgs fin_args(xsg_shard* s, const ScanArgs& a, uint64_t* d_counter
     if (n != 0 && first + n <= c->span_hashes.size()) f.sp_n = span_entries(c->span_hashes.data() + first, n, f.sp_word, f.sp_mask);
     if (f.sp_n) f.spans = s->d_spans.as<uint32_t>();
   }
+  // with a locator the pass runs as a wave per sketch group (gated_pass_waves); XSG_GATE_WAVES=0 is the A/B switch that
+  // keeps the workgroup form in the same build
+  const char* e = XSG_TOGGLE("XSG_GATE_WAVES");
+  // (chunk offsets below 2^48: the wave form keeps a passing lane's geometry in four registers)
+  f.waves = f.spans != nullptr && !(e && *e == '0') && s->capacity < (1ull << 48);
   return f;
 }
 
@@ -821,7 +826,8 @@ extern "C" int xsg_scan_kernel_name(xsg_shard* s, uint32_t mode, char* out, size
   } else {
     // (a plain match count says which form of the gated pass it launches: the finishing one, or the storing one)
     describe_scan(a, want_nl, !list && m == XSG_COUNT_LINES, false, out, cap,
-                  !list && count_finishes(s, a, m, (mode & XSG_WITH_NEWLINES) != 0), s->total_bytes, spans_apply(s, a));
+                  !list && count_finishes(s, a, m, (mode & XSG_WITH_NEWLINES) != 0), s->total_bytes, spans_apply(s, a),
+                  fin_args(s, a, nullptr, nullptr, nullptr).waves != 0);
   }
   if (inverted(s->ctx)) {  // the inverted form: the same scan, then the complement (of the list, or of the line count)
     const size_t n = strlen(out);
@@ -882,7 +888,17 @@ extern "C" int xsg_shard_tune(xsg_shard* s, uint32_t mode, uint32_t* chosen) {
     const int more = (int)std::min(40.0f, std::max(0.0f, 150.0f / std::max(ms, 0.05f) - 3.0f));
     if (more > 0 && (r = xsg_time_scan_kernel(s, mode, more, &ms)) != XSG_OK) return give_up(r);
   }
+  // The wave form of the finishing pass (gated_pass_waves) has no stagger: no four waves share a tile there.  Both hot
+  // filters are still timed at full size, once each per round and with as many launches as a sweep would spend; the
+  // stagger stays kTuneAuto -- a pick among eight identical timings would be noise, and the value applies to the
+  // binding's other passes, where 16 against 0 is worth 5 %.
+  bool waves = false;
+  {
+    const ScanArgs a = scan_args(s, v);
+    waves = count_finishes(s, a, mode & 0xffu, tune_nl) && fin_args(s, a, nullptr, nullptr, nullptr).waves != 0;
+  }
   constexpr int kCand = (int)(sizeof cand / sizeof cand[0]);
+  const int ncand = waves ? 1 : kCand;
   float t_ms[2][kCand];
   for (auto& row : t_ms)
     for (float& x : row) x = 1e30f;
@@ -892,20 +908,21 @@ extern "C" int xsg_shard_tune(xsg_shard* s, uint32_t mode, uint32_t* chosen) {
         s->hot_v[v] = (uint8_t)hot;
         s->hot_known |= (uint8_t)(1u << v);
       }
-      for (int k = 0; k < kCand; ++k) {
-        s->tune = cand[k];
+      for (int k = 0; k < ncand; ++k) {
+        s->tune = waves ? kTuneAuto : cand[k];
         float ms = 0;
-        const int r = xsg_time_scan_kernel(s, mode, 3, &ms);
+        const int r = xsg_time_scan_kernel(s, mode, waves ? 3 * kCand : 3, &ms);
         if (r != XSG_OK) return give_up(r);
         t_ms[hot][k] = std::min(t_ms[hot][k], ms);
       }
     }
   }
+  bool have = false;
   for (uint32_t hot = 0; hot < nhot; ++hot)
-    for (int k = 0; k < kCand; ++k)
-      if (best == kTuneAuto || t_ms[hot][k] < best_ms) best_ms = t_ms[hot][k], best = cand[k], best_hot = hot;
+    for (int k = 0; k < ncand; ++k)
+      if (!have || t_ms[hot][k] < best_ms) have = true, best_ms = t_ms[hot][k], best = waves ? kTuneAuto : cand[k], best_hot = hot;
   s->tune = best;
-  s->tune_serial = c->pattern_serial;
+  s->tune_serial = best == kTuneAuto ? 0 : c->pattern_serial;
   s->tune_probe = false;
   if (nhot == 2) s->hot_v[v] = (uint8_t)best_hot;
   if (chosen) *chosen = best;

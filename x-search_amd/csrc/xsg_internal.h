@@ -194,6 +194,10 @@ struct GateFinArgs {
   uint32_t sp_n;
   uint32_t sp_word[kSpanRegs];
   uint32_t sp_mask[kSpanRegs];
+  // The wave form (k_scan_fin<..., true>: gated_pass_waves): a wave owns a sketch group of 64 tiles from its sketch words
+  // to its text, no workgroup barrier in the pass.  Only with `spans` (a 4 KiB span is one wave's load batch);
+  // XSG_GATE_WAVES=0 keeps the workgroup form.
+  uint32_t waves;
 };
 constexpr uint32_t kFinGroups = 64;
 constexpr uint32_t kFinTotalBits = 40;  // matches <= total_bytes < 2^40; the grid stays below 2^24 (scan_finishing)
@@ -269,9 +273,9 @@ hipError_t launch_set_verify(const RxPreArgs& a, hipStream_t s);
 void describe_set_scan(const ScanArgs& a, bool emit, char* out, size_t cap);
 // "xsg::k_scan<KIND, WANT_NL, WANT_LINES, EMIT, LOADS, ICASE>" + the stagger launch_scan would use, for reports
 // finishing: the caller's pass is a plain match count that takes the finishing form where scan_finishing says so;
-// spans: that form would run with the binding's span locator (GateFinArgs::spans)
+// spans: that form would run with the binding's span locator (GateFinArgs::spans); waves: and as the wave form
 void describe_scan(const ScanArgs& a, bool want_nl, bool want_lines, bool emit, char* out, size_t cap,
-                   bool finishing = false, uint64_t total_bytes = 0, bool spans = false);
+                   bool finishing = false, uint64_t total_bytes = 0, bool spans = false, bool waves = false);
 
 // exclusive scan: out[i] = sum_{k<i} in[k] for i in [0, n]; out has n+1 entries.
 // tmp must hold scan_tmp_elems(n) uint64 values.

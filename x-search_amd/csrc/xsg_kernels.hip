@@ -782,9 +782,13 @@ __device__ __forceinline__ TileGeom tile_geom(const ScanArgs& A, const uint64_t 
 // requested ahead of the previous candidate's compares.)
 // FIN (the finishing form of the gated count, gated_pass): the wave's matches are added to *fin_acc (wave-uniform) and
 // nothing is stored per tile -- no tile_cnt, no tile_last, no wave mark; span_on (wave-uniform): this wave's span is read.
-template <int KIND, bool WANT_NL, bool WANT_LINES, bool EMIT, int LOADS, bool ICASE, bool ALIGNED, bool HAVE_GEOM, bool FIN = false>
+// WAVE (the wave form of the finishing pass, gated_pass_waves): which 4 KiB of the tile this wave reads is the caller's
+// `span` (wave-uniform), not the wave's place in its workgroup -- a span's result does not depend on who scans it -- and
+// the loads are issued at once: the stagger spreads the four bursts of one tile, and here no four waves share a tile.
+template <int KIND, bool WANT_NL, bool WANT_LINES, bool EMIT, int LOADS, bool ICASE, bool ALIGNED, bool HAVE_GEOM, bool FIN = false,
+          bool WAVE = false>
 __device__ __forceinline__ void scan_tile_at(const ScanArgs& A, const uint64_t tile, const TileGeom& geom, const bool stage,
-                                             uint64_t* fin_acc = nullptr, const bool span_on = true) {
+                                             uint64_t* fin_acc = nullptr, const bool span_on = true, const uint32_t span = 0) {
   constexpr int kLoads = LOADS;                          // 16-byte units per lane
   constexpr uint32_t kWaveSpan = kWaveLoad * kLoads;     // contiguous bytes per wave
   constexpr uint32_t kTile = kWaveSpan * kWaves;         // bytes per workgroup
@@ -802,7 +806,9 @@ __device__ __forceinline__ void scan_tile_at(const ScanArgs& A, const uint64_t t
   const PatternDev P = A.pat;
   const uint32_t tid = threadIdx.x;
   const uint32_t lane = tid & 63u;
-  const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // wave-uniform: keeps wbase and the branches on it scalar
+  static_assert(!WAVE || FIN, "a caller's span: the finishing form only (no per-wave store, no LDS meeting of the four waves)");
+  // wave-uniform: keeps wbase and the branches on it scalar
+  const uint32_t wave = WAVE ? (uint32_t)__builtin_amdgcn_readfirstlane(span) : (uint32_t)__builtin_amdgcn_readfirstlane(tid >> 6);
 
   if (KIND == kLong && (!HAVE_GEOM || stage)) {  // the first KiB of the pattern; a candidate of a longer one is verified against the device copy beyond it
     for (uint32_t k = tid; k < P.plen && k < kLdsPattern; k += kBlock) s_pat[k] = P.d_pat[k];
@@ -833,7 +839,7 @@ __device__ __forceinline__ void scan_tile_at(const ScanArgs& A, const uint64_t t
   // Measured on the 50 GiB shard, plain count (scripts/tune_sweep.py): 7.07 TB/s
   // without, 7.22 / 7.35 / 7.46 / 7.41 / 7.23 TB/s at stagger 9 / 12 / 14 / 16 / 20,
   // 6.56 at 32.  launch_scan picks the value per kernel variant (0 for VALU-bound ones).
-  {
+  if (!WAVE) {
     const uint32_t n = (A.tune & 0xffu) * wave;
     for (uint32_t i = 0; i < n; ++i) __builtin_amdgcn_s_sleep(1);
   }
@@ -1219,6 +1225,42 @@ __device__ __forceinline__ uint64_t fin_walk_entry(const ScanArgs& A, const uint
   return 0;
 }
 
+// Leaving the finishing pass (both forms): the workgroup's matches and its arrival in one atomicAdd; the value it returns
+// tells the last workgroup that it is the last and what the others brought.  Every wave of the workgroup comes here once,
+// with all its work done: the barrier below is the only one the waves of the wave form meet behind the top of the kernel.
+__device__ __forceinline__ void fin_leave(const GateFinArgs& F, uint64_t* s_fin, const uint64_t fin_acc, const uint32_t lane,
+                                          const uint32_t wave) {
+  if (lane == 0) s_fin[wave] = fin_acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint64_t mine = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < (uint32_t)kWaves; ++w) mine += s_fin[w];
+    // two levels: workgroup b arrives at word 1 + b % kFinGroups, the last of a group carries the group's sum to word 0
+    // (thousands of returning atomics on ONE word queue up behind one another, ~8 ns each, and a workgroup holds its
+    // place on the compute unit until its own comes back)
+    constexpr unsigned long long kMask = (1ull << kFinTotalBits) - 1ull;
+    const uint32_t g = blockIdx.x % kFinGroups;
+    const uint32_t members = (gridDim.x + kFinGroups - 1u - g) / kFinGroups;
+    const unsigned long long old = atomicAdd(F.word + 1u + g, (1ull << kFinTotalBits) + mine);
+    if ((old >> kFinTotalBits) == (unsigned long long)members - 1ull) {
+      __hip_atomic_store(F.word + 1u + g, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // at rest for the next pass (stream order)
+      const uint32_t groups = gridDim.x < kFinGroups ? gridDim.x : kFinGroups;
+      const unsigned long long gsum = (old & kMask) + mine;
+      const unsigned long long top = atomicAdd(F.word, (1ull << kFinTotalBits) + gsum);
+      if ((top >> kFinTotalBits) == (unsigned long long)groups - 1ull) {
+        const uint64_t v[XSG_NUM_COUNTERS] = {(top & kMask) + gsum, 0ull, 0ull, F.total_bytes};
+        for (int k = 0; k < XSG_NUM_COUNTERS; ++k) {
+          F.counters[k] = v[k];
+          if (F.host_counters) F.host_counters[k] = v[k];
+        }
+        if (F.status) *F.status = 0ull;
+        __hip_atomic_store(F.word, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+    }
+  }
+}
+
 template <int KIND, int LOADS, bool ICASE, bool ALIGNED, bool FIN = false>
 __device__ __forceinline__ void gated_pass(const ScanArgs& A, const GateFinArgs* F = nullptr) {
   __shared__ unsigned long long s_bal[kWaves];
@@ -1367,48 +1409,160 @@ __device__ __forceinline__ void gated_pass(const ScanArgs& A, const GateFinArgs*
     }
     __syncthreads();  // the unit's LDS words are rewritten for the next one
   }
-  if constexpr (FIN) {
-    // leaving: the workgroup's matches and its arrival in one atomicAdd; the value it returns tells the last workgroup
-    // that it is the last and what the others brought.
-    if (lane == 0) s_fin[wave] = fin_acc;
-    __syncthreads();
-    if (tid == 0) {
-      uint64_t mine = 0;
+  if constexpr (FIN) fin_leave(*F, s_fin, fin_acc, lane, wave);
+}
+
+// ---------------------------------------------------------------------------
+// The WAVE form of the finishing pass: a wave per sketch group, no workgroup barrier in the pass.  With the span locator
+// the unit of text work is a 4 KiB span -- one wave's load batch -- so the workgroup is not needed to scan a candidate,
+// and in the form above three waves of four wait while one reads the ~1.00 span a candidate lets through.  Here a wave
+// owns a sketch group (64 consecutive tiles, lane l <-> tile g * 64 + l) from its sketch words to its text: wave w of
+// workgroup b takes the groups b * kWaves + w, + gridDim.x * kWaves, ... (the same static stride, the same grid).  Per
+// group: the lane's sketch words and tile_chunk, all requested before any use; the ballot; passing lanes request chunk
+// entry, first tile and locator words in one batch and reduce them to the span mask; the wave walks the set bits of its
+// OWN ballot, geometry and mask by readlane from the passing lane's registers, and scans every set span of the mask
+// (scan_tile_at<..., WAVE>).  No LDS hand-off and no __syncthreads() on any path a single wave takes -- waves run
+// different numbers of groups and candidates: the kLong pattern is staged once at the top, where all four waves still
+// are, and the only other barrier stands in front of the leaving atomicAdd (fin_leave).  The end-of-chunk zone of a
+// candidate tile is looked at by the wave that owns the tile, in its own row of s_zone; the rule is gated_pass's.
+// Used when the binding has a span locator (GateFinArgs::waves); without one, four spans read in turn by one wave are
+// not what whole-tile reads want, and gated_pass<..., FIN> serves.
+// ---------------------------------------------------------------------------
+template <int KIND, int LOADS, bool ALIGNED>
+__device__ __forceinline__ void gated_pass_waves(const ScanArgs& A, const GateFinArgs& F) {
+  __shared__ __attribute__((aligned(16))) uint8_t s_zone[kWaves][kZoneStage];  // the zone a candidate tile looks at, per wave
+  __shared__ uint64_t s_fin[kWaves];
+  uint64_t fin_acc = 0;  // this wave's matches (wave-uniform)
+  const uint32_t tid = threadIdx.x;
+  const uint32_t lane = tid & 63u;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const uint64_t ngroups = (A.ntiles + kSketchGroup - 1) / kSketchGroup;
+  const uint32_t n = A.sk_n, sn = F.sp_n;
+  static_assert(kSketchGroup == 64, "a sketch group is a wave: one tile per lane");
+
+  // the kLong pattern goes to LDS here, behind the pass's only barrier ahead of the leaving one: a call that stages and
+  // reads no span (ntiles >= 1: scan_finishing)
+  scan_tile_at<KIND, false, false, false, LOADS, false, ALIGNED, true, true, true>(A, 0, TileGeom{}, true, &fin_acc, false, 0u);
+
+#pragma unroll 1
+  for (uint64_t g = (uint64_t)blockIdx.x * kWaves + wave; g < ngroups; g += (uint64_t)gridDim.x * kWaves) {
+    // the loads of this lane's tile, all issued here; `miss` takes what does not fit kGateRegs
+    const uint64_t mytile = g * kSketchGroup + lane;
+    uint32_t w[kGateRegs], wc = 0, miss = 1u;  // a tile at or beyond ntiles does not pass
 #pragma unroll
-      for (uint32_t w = 0; w < (uint32_t)kWaves; ++w) mine += s_fin[w];
-      // two levels: workgroup b arrives at word 1 + b % kFinGroups, the last of a group carries the group's sum to word 0
-      // (thousands of returning atomics on ONE word queue up behind one another, ~8 ns each, and a workgroup holds its
-      // place on the compute unit until its own comes back)
-      constexpr unsigned long long kMask = (1ull << kFinTotalBits) - 1ull;
-      const uint32_t g = blockIdx.x % kFinGroups;
-      const uint32_t members = (gridDim.x + kFinGroups - 1u - g) / kFinGroups;
-      const unsigned long long old = atomicAdd(F->word + 1u + g, (1ull << kFinTotalBits) + mine);
-      if ((old >> kFinTotalBits) == (unsigned long long)members - 1ull) {
-        __hip_atomic_store(F->word + 1u + g, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // at rest for the next pass (stream order)
-        const uint32_t groups = gridDim.x < kFinGroups ? gridDim.x : kFinGroups;
-        const unsigned long long gsum = (old & kMask) + mine;
-        const unsigned long long top = atomicAdd(F->word, (1ull << kFinTotalBits) + gsum);
-        if ((top >> kFinTotalBits) == (unsigned long long)groups - 1ull) {
-          const uint64_t v[XSG_NUM_COUNTERS] = {(top & kMask) + gsum, 0ull, 0ull, F->total_bytes};
-          for (int k = 0; k < XSG_NUM_COUNTERS; ++k) {
-            F->counters[k] = v[k];
-            if (F->host_counters) F->host_counters[k] = v[k];
+    for (uint32_t k = 0; k < kGateRegs; ++k) w[k] = 0xffffffffu;
+    if (mytile < A.ntiles) {
+      const uint32_t* sk = A.sketch + sketch_index(mytile, 0);
+      miss = 0;
+#pragma unroll
+      for (uint32_t k = 0; k < kGateRegs; ++k)
+        if (k < n) w[k] = sk[A.sk_word[k] * kSketchGroup];
+      if (A.tile_chunk) wc = A.tile_chunk[mytile];
+      for (uint32_t i = kGateRegs; i < n; i += kGateRegs) {  // (more than kGateRegs distinct words: long needles only)
+        uint32_t x[kGateRegs];
+#pragma unroll
+        for (uint32_t k = 0; k < kGateRegs; ++k) x[k] = i + k < n ? sk[A.sk_word[i + k] * kSketchGroup] : 0xffffffffu;
+#pragma unroll
+        for (uint32_t k = 0; k < kGateRegs; ++k) miss |= i + k < n ? ~x[k] & A.sk_mask[i + k] : 0u;
+      }
+    }
+#pragma unroll
+    for (uint32_t k = 0; k < kGateRegs; ++k)
+      if (k < n) miss |= ~w[k] & A.sk_mask[k];
+    const bool pass = miss == 0;
+    const unsigned long long bal = __ballot(pass);
+    if (bal == 0) continue;
+    // a passing lane: its locator words -- word k of the tile's four spans is one 16-byte load (span_index) -- and its
+    // geometry in one batch, reduced to the 4-bit span mask
+    // (four registers a lane across the scans, not six: the offset is below 2^48 -- fin_args asks for the wave form only
+    // on such a buffer -- and the length below 2^kFinTotalBits, so their high halves and the span mask share g_hi:
+    // bits 0-15, 16-23 and 24-27)
+    static_assert(kFinTotalBits <= 40 && kSpansPerTile <= 8, "g_hi: 16 + 8 + 8 bits");
+    uint32_t g_off = 0, g_len = 0, g_hi = 0, g_t0 = 0;
+    if (pass) {
+      uint4 x[kSpanRegs];
+      const uint4* sp = reinterpret_cast<const uint4*>(F.spans + span_index(mytile, 0, 0));
+#pragma unroll
+      for (uint32_t k = 0; k < kSpanRegs; ++k) {  // (every x[k] defined: an undefined one is carried round the group loop)
+        x[k] = make_uint4(~0u, ~0u, ~0u, ~0u);
+        if (k < sn) x[k] = sp[F.sp_word[k]];
+      }
+      const ChunkDev ch = A.chunks[wc];
+      g_off = (uint32_t)ch.offset;
+      g_len = (uint32_t)ch.length;
+      g_hi = ((uint32_t)(ch.offset >> 32) & 0xffffu) | (((uint32_t)(ch.length >> 32) & 0xffu) << 16);
+      g_t0 = reinterpret_cast<const uint32_t*>(A.chunk_tile0 + wc)[0];  // the low half: the tile's distance from it is below 2^32
+      uint32_t mx = 0, my = 0, mz = 0, mw = 0;  // per span: the bits that are missing
+#pragma unroll
+      for (uint32_t k = 0; k < kSpanRegs; ++k)
+        if (k < sn) {
+          const uint32_t b = F.sp_mask[k];
+          mx |= ~x[k].x & b, my |= ~x[k].y & b, mz |= ~x[k].z & b, mw |= ~x[k].w & b;
+        }
+      g_hi |= ((mx == 0 ? 1u : 0u) | (my == 0 ? 2u : 0u) | (mz == 0 ? 4u : 0u) | (mw == 0 ? 8u : 0u)) << 24;
+    }
+    // the wave's own candidates, in tile order
+    uint32_t lo = (uint32_t)bal, hi = (uint32_t)(bal >> 32);
+#pragma unroll 1
+    while (lo | hi) {
+      uint32_t l;
+      if (lo) {
+        l = (uint32_t)__builtin_ctz(lo);
+        lo &= lo - 1u;
+      } else {
+        l = 32u + (uint32_t)__builtin_ctz(hi);
+        hi &= hi - 1u;
+      }
+      const uint64_t tile = g * kSketchGroup + l;
+      TileGeom tg;
+      auto at = [&](const uint32_t v) { return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)l); };
+      const uint32_t hi16 = at(g_hi);
+      tg.offset = ((uint64_t)(hi16 & 0xffffu) << 32) | at(g_off);
+      tg.length = ((uint64_t)((hi16 >> 16) & 0xffu) << 32) | at(g_len);
+      tg.tile0 = tile - (uint32_t)((uint32_t)tile - at(g_t0));
+      tg.c = 0;  // (the emit pass names the chunk; a count pass does not)
+      uint32_t sm = hi16 >> 24;
+#pragma unroll 1
+      while (sm) {  // every span of the candidate that can hold a window start: this wave's 4 KiB loads, one batch each
+        const uint32_t s = (uint32_t)__builtin_ctz(sm);
+        sm &= sm - 1u;
+        scan_tile_at<KIND, false, false, false, LOADS, false, ALIGNED, true, true, true>(A, tile, tg, false, &fin_acc, true, s);
+      }
+      // the end-of-chunk zone: one look per candidate TILE, whatever its span mask, by the wave that owns the tile (see
+      // gated_pass: the home of the zone's first occurrence walks it, from fin_walk_entry)
+      const uint32_t plen = A.pat.plen, koff = KIND >= kLong ? A.pat.koff : 0u;
+      const uint64_t L = tg.length;
+      if (!A.pat.exact_tail && L >= plen) {
+        constexpr uint64_t kTile = (uint64_t)kWaveLoad * LOADS * kWaves;
+        const uint64_t Z = tail_zone_begin(L, plen), trel = tile - tg.tile0;
+        if (trel >= (Z + koff) / kTile && trel <= (L - plen + koff) / kTile) {
+          const uint8_t* cbase = A.base + tg.offset;
+          const TailMasks tm = wave_tail_masks(cbase, L, A.pat.d_pat, plen, false, s_zone[wave], lane);
+          if (tm.full != 0 && (Z + (uint32_t)__builtin_ctzll(tm.full) + koff) / kTile == trel) {
+            const uint64_t entry = fin_walk_entry<LOADS>(A, cbase, L, Z, tg.tile0, koff, lane);
+            const uint32_t kk = tm.k;
+            auto k_at = [&](uint32_t j) { return (uint32_t)__builtin_amdgcn_readlane((int)kk, (int)__builtin_amdgcn_readfirstlane(j)); };
+            fin_acc += tail_walk_masks(L, plen, entry, false, tm.full, tm.nz, tm.nlm, k_at);
           }
-          if (F->status) *F->status = 0ull;
-          __hip_atomic_store(F->word, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
       }
     }
   }
+  fin_leave(F, s_fin, fin_acc, lane, wave);
 }
 
 // The finishing form's entry point: ScanArgs as every k_scan has them, its own few words beside them.
-template <int KIND, int LOADS, bool ALIGNED>
+// WAVES: the wave form (gated_pass_waves; the binding has a span locator), otherwise the workgroup form.
+template <int KIND, int LOADS, bool ALIGNED, bool WAVES>
 // (The occupancy request: with the span locator's loads the instantiations came out at 79 .. 84 VGPRs, half of them
 // past the 80 that six waves per SIMD allow; asked for six, the compiler fits all of them into 74 .. 78 without scratch
-// -- profiles/spans_registers.txt.)
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(6))) void k_scan_fin(const ScanArgs A, const GateFinArgs F) {
-  gated_pass<KIND, LOADS, false, ALIGNED, true>(A, &F);
+// -- profiles/spans_registers.txt.  The wave form is bounded to six from above as well, so that the compiler does not
+// squeeze it towards seven: it comes out at 69 .. 72, without a spill -- profiles/waves_registers.txt.)
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(6, WAVES ? 6 : 8))) void k_scan_fin(const ScanArgs A, const GateFinArgs F) {
+  if constexpr (WAVES)
+    gated_pass_waves<KIND, LOADS, ALIGNED>(A, F);
+  else
+    gated_pass<KIND, LOADS, false, ALIGNED, true>(A, &F);
 }
 
 // The kernel proper.  (Round 2 also measured an occupancy request for the class-sequence kinds -- they keep sixteen
@@ -1467,7 +1621,11 @@ static hipError_t launch_scan_kind(const ScanArgs& a, bool want_nl, bool want_li
       // leaves tile_cnt / tile_last / tile_wmask for k_count_finish or a list route; the finishing form (a plain match
       // count: launch_scan_count_finishing) leaves the counters and no per-tile word.
       if (fin) {
-        hipLaunchKernelGGL((k_scan_fin<KIND, LOADS, ALIGNED>), gate_grid(a), dim3(kBlock), 0, s, a, *fin);
+        if (fin->waves && !fin->spans) return hipErrorInvalidValue;  // the wave form reads by spans only
+        if (fin->waves)
+          hipLaunchKernelGGL((k_scan_fin<KIND, LOADS, ALIGNED, true>), gate_grid(a), dim3(kBlock), 0, s, a, *fin);
+        else
+          hipLaunchKernelGGL((k_scan_fin<KIND, LOADS, ALIGNED, false>), gate_grid(a), dim3(kBlock), 0, s, a, *fin);
         return hipGetLastError();
       }
       hipLaunchKernelGGL((k_scan<KIND, false, false, false, LOADS, ICASE, ALIGNED, true>), gate_grid(a), dim3(kBlock), 0, s, a);
@@ -1547,7 +1705,7 @@ static uint32_t pick_stagger(const ScanArgs& a, bool want_nl, bool want_lines, b
 }
 
 void describe_scan(const ScanArgs& a, bool want_nl, bool want_lines, bool emit, char* out, size_t cap, bool finishing,
-                   uint64_t total_bytes, bool spans) {
+                   uint64_t total_bytes, bool spans, bool waves) {
   if (!out || !cap) return;
   const char* b[2] = {"false", "true"};
   if (a.pat.kind == kSet) return describe_set_scan(a, emit, out, cap);
@@ -1577,8 +1735,9 @@ void describe_scan(const ScanArgs& a, bool want_nl, bool want_lines, bool emit, 
     // (the suffix stays the end of the string; the finishing form of a plain match count says so in front of it, and
     // in front of that whether it reads the candidates' passing 4 KiB spans only)
     const bool fin = finishing && scan_finishing(a, total_bytes);
-    snprintf(out + n, cap - n, "%s%s gated by xsg::k_sketch (512 B/tile)", fin && spans ? " by 4 KiB spans" : "",
-             fin ? " finishing (xsg::k_scan_fin)" : "");
+    // and, in front of that, whether a wave owns a sketch group from its sketch words to its text (gated_pass_waves)
+    snprintf(out + n, cap - n, "%s%s%s gated by xsg::k_sketch (512 B/tile)", fin && spans && waves ? " a wave per group" : "",
+             fin && spans ? " by 4 KiB spans" : "", fin ? " finishing (xsg::k_scan_fin)" : "");
   }
 }
 
