@@ -40,7 +40,7 @@ extern "C" {
  * grew and the line tags accept a literal that contains '\n' (round 4); still 4: XSG_FLAG_INVERT, XSG_MATCHES,
  * XSG_FLAG_CONTEXT and xsg_result_context_edges joined; xsg_set_literals, xsg_literals_info, xsg_host_searcher_create_list
  * and xsg_job_opts.pattern_is_list joined (the structure grew: see there for what that asks of a program built before);
- * no entry point was removed or changed in meaning */
+ * xsg_count_chunks and xsg_count_chunks_async joined; no entry point was removed or changed in meaning */
 #define XSG_ABI_VERSION 4
 
 /* ---- status codes ------------------------------------------------------- */
@@ -431,6 +431,36 @@ int xsg_count(xsg_shard* shard, uint32_t mode, uint64_t counters[XSG_NUM_COUNTER
  * _end blocks until it is done and hands out the counters.  One pass in flight per shard. */
 int xsg_count_begin(xsg_shard* shard, uint32_t mode);
 int xsg_count_end(xsg_shard* shard, uint64_t counters[XSG_NUM_COUNTERS]);
+
+/* ---- counts per chunk ------------------------------------------------------ */
+/* A shard is a table of chunks searched independently; a caller who binds many documents as the chunks of one resident
+ * buffer asks here which of them hold the needle and how often (grep -c over many files; grep -l / -L follow), in one pass.
+ * counts[c], c in [0, nchunks): what xsg_count(mode) would put into XSG_CTR_MATCHES (XSG_COUNT_MATCHES) or XSG_CTR_LINES
+ * (XSG_COUNT_LINES) for a binding that holds chunk c alone -- same pattern, same flags (XSG_FLAG_EXACT_TAIL or the
+ * lossy tail, IGNORE_CASE, REGEX, INVERT; CONTEXT bits are ignored as by every count).  Under XSG_FLAG_INVERT the lines
+ * of a chunk are those defined there, and counts[c] = lines of chunk c - its matching lines.
+ * newlines (optional; requires mode | XSG_WITH_NEWLINES, XSG_EINVAL otherwise; with the flag and without the array only
+ * the total is produced): newlines[c] = number of '\n' in chunk c.
+ * totals (optional): the four counters exactly as xsg_count(mode) returns them for the binding.
+ * Always: sum(counts) == totals[XSG_CTR_MATCHES or XSG_CTR_LINES], sum(newlines) == totals[XSG_CTR_NEWLINES].
+ * cap_chunks < the number of bound chunks, counts == NULL, a list mode, unknown mode bits: XSG_EINVAL.  A chunk of length
+ * 0 counts 0; a binding of 0 chunks is XSG_OK and writes nothing to counts.  XSG_COUNT_MATCHES under XSG_FLAG_INVERT:
+ * XSG_ENOTSUP, as everywhere.  An expression that is exact on ASCII data only, on a binding that holds a byte >= 0x80,
+ * is refused for the WHOLE binding as by xsg_count (never per chunk): XSG_ENOTSUP, counts unspecified.
+ * Serves every pattern kind and flag xsg_count serves.  Patterns whose count is a list (the prefilter route of an
+ * expression, a literal list, a bordered literal whose occurrences do overlap in the data, XSG_COUNT_LINES of a literal
+ * that contains '\n') run that list route and sort its entries by chunk on the device; everything else is the scan in
+ * its storing form and one finish kernel that keeps the chunk boundaries (a plain xsg_count keeps its one launch). */
+int xsg_count_chunks(xsg_shard* shard, uint32_t mode, uint64_t* counts, uint64_t* newlines, uint64_t cap_chunks,
+                     uint64_t totals[XSG_NUM_COUNTERS]);
+/* Stream-ordered form: every output is DEVICE memory, nothing waits.  d_counts: cap_chunks words; d_newlines optional as
+ * above; d_counters (XSG_NUM_COUNTERS words) and d_status (one word) are required and follow xsg_count_async_status:
+ * status != 0 => the four counters AND every d_counts[c] / d_newlines[c] read zero (XSG_STATUS_NONASCII for the refusal
+ * above).  Serves what xsg_count_async_status serves through scan + finish: not a literal list, not a bordered literal
+ * that is not yet known overlap-free on this binding (a synchronous call establishes that), not XSG_COUNT_LINES of a
+ * pattern that contains '\n' -- XSG_ENOTSUP for those; xsg_count_chunks serves them. */
+int xsg_count_chunks_async(xsg_shard* shard, uint32_t mode, void* stream, uint64_t* d_counts, uint64_t* d_newlines,
+                           uint64_t cap_chunks, uint64_t* d_counters, uint64_t* d_status);
 
 /* ---- list results (replace byte_offsets_match/_line, line; :136-154,187-207) */
 /* Runs the search for one of the list modes on the ctx stream and waits.

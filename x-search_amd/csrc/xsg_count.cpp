@@ -434,7 +434,7 @@ static bool count_finishes(const xsg_shard* s, const ScanArgs& a, uint32_t m, bo
 
 static int enqueue_count(xsg_shard* s, bool want_matches, bool want_lines, bool want_nl, hipStream_t st,
                          uint64_t* d_counters, uint64_t* host_counters, const PatternDev* other_pattern = nullptr,
-                         uint64_t* d_status = nullptr, bool may_sync = true) {
+                         uint64_t* d_status = nullptr, bool may_sync = true, const ChunkCountArgs* per_chunk = nullptr) {
   if (want_nl) XSG_TRY(ensure_tile_nl(s));
   const uint64_t nchunks = s->chunks.size();
   // kDfa: k_rx_scan counts matching lines directly into tile_cnt (a line is one lane's work): no line summaries
@@ -454,7 +454,9 @@ static int enqueue_count(xsg_shard* s, bool want_matches, bool want_lines, bool 
   // A plain match count behind the gate finishes inside its own pass (k_scan_fin): one launch, the per-tile arrays are
   // neither written nor read and stay as prepare_tiles left them.  Everything else -- newline totals, line counts,
   // needles of 34 bytes and more with the lossy tail, the ungated kinds, another pattern -- keeps the two launches below.
-  if (want_matches && !want_lines && !rx_lines && !want_nl && !other_pattern && scan_finishing(a, s->total_bytes)) {
+  // So does a count per chunk (per_chunk): the finishing form writes no per-tile words for k_count_chunks to sort by chunk;
+  // the gate stays, in its storing form.
+  if (want_matches && !want_lines && !rx_lines && !want_nl && !other_pattern && !per_chunk && scan_finishing(a, s->total_bytes)) {
     HIP_TRY(launch_scan_count_finishing(a, fin_args(s, a, d_counters, host_counters, d_status), st));
     return XSG_OK;
   }
@@ -487,7 +489,13 @@ static int enqueue_count(xsg_shard* s, bool want_matches, bool want_lines, bool 
   f.want_lines = want_lines;
   f.want_matches = want_matches || rx_lines;
   f.cnt_is_lines = rx_lines ? 1u : 0u;
-  HIP_TRY(launch_count_finish(f, st));
+  if (per_chunk) {
+    ChunkCountArgs cc = *per_chunk;
+    cc.tile_chunk = a.tile_chunk;
+    HIP_TRY(launch_count_chunks(f, cc, st));
+  } else {
+    HIP_TRY(launch_count_finish(f, st));
+  }
   s->cnt_clean = true;
   if (want_lines) s->sum_clean = true;
   if (scan_nl) s->nl_cached = true;
@@ -730,6 +738,162 @@ extern "C" int xsg_count(xsg_shard* s, uint32_t mode, uint64_t counters[XSG_NUM_
   memcpy(counters, s->h_counters, 8 * XSG_NUM_COUNTERS);
   if (!inv) note_density(s, counters[m == XSG_COUNT_MATCHES ? XSG_CTR_MATCHES : XSG_CTR_LINES]);  // (of the needle, not of its complement)
   return refuse_if_poisoned(counters);
+}
+
+// ---- counts per chunk (xsg_count_chunks, xsg_count_chunks_async) -----------------------------------------------------------
+// The scan in its storing form, k_count_chunks behind it, and -- for an inverted line count, or a pattern whose pass can
+// be refused -- the small kernel that turns the chunks' words round or zeroes them.  d_counts / d_nl: nchunks words each;
+// d_nl is the caller's array (want_nl) or scratch (an inverted count needs every chunk's newlines either way), else null.
+static int enqueue_count_chunks(xsg_shard* s, uint32_t m, bool want_nl, hipStream_t st, uint64_t* d_counts, uint64_t* d_nl,
+                                uint64_t* d_counters, uint64_t* host_counters, uint64_t* d_status, bool may_sync) {
+  xsg_ctx* c = s->ctx;
+  const uint64_t nchunks = s->chunks.size();
+  const bool inv = inverted(c);  // (XSG_COUNT_LINES: the callers refused the other)
+  if (nchunks) HIP_TRY(hipMemsetAsync(d_counts, 0, 8 * nchunks, st));
+  if (nchunks && d_nl) HIP_TRY(hipMemsetAsync(d_nl, 0, 8 * nchunks, st));
+  ChunkCountArgs cc{};
+  cc.counts = d_counts;
+  cc.newlines = d_nl;
+  XSG_TRY(enqueue_count(s, m == XSG_COUNT_MATCHES, m == XSG_COUNT_LINES, want_nl || inv, st, d_counters, host_counters, nullptr,
+                        d_status, may_sync, &cc));
+  if (inv) XSG_TRY(enqueue_invert_lines(s, st, d_counters, host_counters, d_status, want_nl));
+  const bool refusable = (c->pat.kind == kClass || c->pat.kind == kDfa) && c->pat.ascii_only;
+  if (inv || refusable)
+    HIP_TRY(launch_chunk_counts_post(s->base, s->d_chunks.as<ChunkDev>(), nchunks, d_counts, d_nl, d_counters, d_status,
+                                     inv ? 1u : 0u, st));
+  return XSG_OK;
+}
+
+// the per-chunk figures behind run_list(outputs = false): from the chunk column of the raw entries, what the walk kept of
+// them and the chunks' tail entries (k_list_chunk_counts); newlines from the prefix of the per-tile counts
+static int enqueue_list_chunk_counts(xsg_shard* s, uint64_t* d_counts, uint64_t* d_nl, bool with_nl, bool inv) {
+  ListChunkArgs a{};
+  a.base = s->base;
+  a.chunks = s->d_chunks.as<ChunkDev>();
+  a.chunk_tile0 = s->d_chunk_tile0.as<uint64_t>();
+  a.nchunks = s->chunks.size();
+  a.M = s->list_entries;
+  a.m_chunk = s->d_m_chunk.as<uint32_t>();
+  a.keep_pre = s->d_keep_pre.as<uint64_t>();
+  a.tail_cnt = s->d_tail_cnt.as<uint32_t>();
+  a.tile_nl_off = with_nl || inv ? s->d_tile_nl_off.as<uint64_t>() : nullptr;
+  a.counts = d_counts;
+  a.newlines = with_nl ? d_nl : nullptr;
+  a.invert = inv ? 1u : 0u;
+  HIP_TRY(launch_list_chunk_counts(a, s->ctx->stream));
+  return XSG_OK;
+}
+
+static int count_chunks_args(xsg_shard* s, uint32_t mode, const uint64_t* counts, const uint64_t* newlines, uint64_t cap_chunks,
+                             uint32_t* m, bool* want_nl) {
+  XSG_TRY(check_ready(s));
+  if (!counts) return fail(XSG_EINVAL, "counts is null");
+  if (!is_count_mode(mode)) return fail(XSG_EINVAL, "mode %u is not a count mode", mode & 0xffu);
+  XSG_TRY(parse_count_mode(mode, m, want_nl));
+  if (newlines && !*want_nl) return fail(XSG_EINVAL, "newlines per chunk need mode | XSG_WITH_NEWLINES");
+  if (cap_chunks < s->chunks.size())
+    return fail(XSG_EINVAL, "room for %llu chunks, the binding holds %llu", (unsigned long long)cap_chunks,
+                (unsigned long long)s->chunks.size());
+  if (*m == XSG_COUNT_MATCHES && inverted(s->ctx)) return fail(XSG_ENOTSUP, "%s", kInvertMatchMsg);
+  return XSG_OK;
+}
+
+extern "C" int xsg_count_chunks(xsg_shard* s, uint32_t mode, uint64_t* counts, uint64_t* newlines, uint64_t cap_chunks,
+                                uint64_t totals[XSG_NUM_COUNTERS]) {
+  uint32_t m = 0;
+  bool want_nl = false;
+  XSG_TRY(count_chunks_args(s, mode, counts, newlines, cap_chunks, &m, &want_nl));
+  xsg_ctx* c = s->ctx;
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t st = c->stream;
+  const uint64_t nchunks = s->chunks.size();
+  uint64_t tot[XSG_NUM_COUNTERS] = {0, 0, 0, 0};
+  if (nchunks == 0) {  // nothing to write per chunk; the totals are xsg_count's
+    if (totals) XSG_TRY(xsg_count(s, mode, totals));
+    return XSG_OK;
+  }
+  const bool inv = inverted(c);
+  const bool per_nl = newlines != nullptr;
+  XSG_TRY(s->d_chunk_counts.ensure(16 * nchunks));
+  XSG_TRY(s->h_chunk_counts.ensure(16 * nchunks));
+  uint64_t* d_counts = s->d_chunk_counts.as<uint64_t>();
+  uint64_t* d_nl = d_counts + nchunks;
+  // the same routes as xsg_count, in the same order
+  bool listed = false;
+  XSG_TRY(ensure_factor_mask(s));
+  if (use_prefilter(s, false) && s->pre_dense_serial != c->pattern_serial) {
+    if (m == XSG_COUNT_LINES && c->pat.has_newline) return fail(XSG_ENOTSUP, "%s", kNewlineExprMsg);
+    const int r = run_list(s, m == XSG_COUNT_MATCHES ? XSG_MATCH_BYTE_OFFSETS : XSG_LINE_BYTE_OFFSETS, false, want_nl || inv);
+    if (r != kDenseCandidates) {
+      XSG_TRY(r);
+      XSG_TRY(enqueue_list_chunk_counts(s, d_counts, d_nl, per_nl, inv));
+      tot[m == XSG_COUNT_MATCHES ? XSG_CTR_MATCHES : XSG_CTR_LINES] = s->total;
+      tot[XSG_CTR_BYTES] = s->total_bytes;
+      if (want_nl || inv) tot[XSG_CTR_NEWLINES] = s->last_newlines;
+      s->last_mode = -1;
+      if (inv) XSG_TRY(invert_lines_sync(s, tot, want_nl));
+      listed = true;
+    }
+  }
+  if (!listed) {
+    if (m == XSG_COUNT_MATCHES && c->bordered) XSG_TRY(ensure_overlap_check(s));
+    const bool chain_lines = m == XSG_COUNT_LINES && newline_literal(c);
+    if ((m == XSG_COUNT_MATCHES && c->bordered && !overlap_free_known(s)) || chain_lines) {
+      XSG_TRY(run_list(s, chain_lines ? XSG_LINE_BYTE_OFFSETS : XSG_MATCH_BYTE_OFFSETS, false, want_nl));
+      note_density(s, s->total);
+      XSG_TRY(enqueue_list_chunk_counts(s, d_counts, d_nl, per_nl, false));
+      tot[chain_lines ? XSG_CTR_LINES : XSG_CTR_MATCHES] = s->total;
+      tot[XSG_CTR_BYTES] = s->total_bytes;
+      if (want_nl) tot[XSG_CTR_NEWLINES] = s->last_newlines;
+      s->last_mode = -1;
+      listed = true;
+    }
+  }
+  if (!listed) {
+    if (m == XSG_COUNT_LINES && c->pat.has_newline) return fail(XSG_ENOTSUP, "%s", kNewlineExprMsg);
+    XSG_TRY(enqueue_count_chunks(s, m, want_nl, st, d_counts, per_nl || inv ? d_nl : nullptr, s->d_counters.as<uint64_t>(),
+                                 s->h_counters, nullptr, true));
+  }
+  uint64_t* h = s->h_chunk_counts.as<uint64_t>();
+  HIP_TRY(hipMemcpyAsync(h, d_counts, 8 * nchunks * (per_nl ? 2 : 1), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  s->table_pending = false;
+  if (!listed) {
+    memcpy(tot, s->h_counters, sizeof tot);
+    XSG_TRY(refuse_if_poisoned(tot));
+    if (!inv) note_density(s, tot[m == XSG_COUNT_MATCHES ? XSG_CTR_MATCHES : XSG_CTR_LINES]);
+  }
+  memcpy(counts, h, 8 * nchunks);
+  if (per_nl) memcpy(newlines, h + nchunks, 8 * nchunks);
+  if (totals) memcpy(totals, tot, sizeof tot);
+  return XSG_OK;
+}
+
+extern "C" int xsg_count_chunks_async(xsg_shard* s, uint32_t mode, void* stream, uint64_t* d_counts, uint64_t* d_newlines,
+                                      uint64_t cap_chunks, uint64_t* d_counters, uint64_t* d_status) {
+  uint32_t m = 0;
+  bool want_nl = false;
+  XSG_TRY(count_chunks_args(s, mode, d_counts, d_newlines, cap_chunks, &m, &want_nl));
+  if (!d_counters) return fail(XSG_EINVAL, "d_counters is null");
+  if (!d_status) return fail(XSG_EINVAL, "d_status is null");
+  xsg_ctx* c = s->ctx;
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : c->stream;
+  // what the stream-ordered counts serve through scan + finish, and nothing else: the counts that are lists need sizes
+  if (c->pat.kind == kSet)
+    return fail(XSG_ENOTSUP, "a literal list fetches sizes from the device: xsg_count_chunks_async does not serve it, xsg_count_chunks() does");
+  if (m == XSG_COUNT_MATCHES && c->bordered && !overlap_free_known(s))
+    return fail(XSG_ENOTSUP, "pattern can overlap itself and is not known overlap-free on this binding: its matches per chunk "
+                             "come from the ordered list, xsg_count_chunks() serves them");
+  if (m == XSG_COUNT_LINES && c->pat.has_newline)
+    return fail(XSG_ENOTSUP, "count_lines of a pattern that contains '\\n' walks a chain of occurrences: xsg_count_chunks_async "
+                             "does not serve it, xsg_count_chunks() does");
+  uint64_t* d_nl = d_newlines;
+  if (!d_nl && inverted(c) && !s->chunks.empty()) {  // an inverted count needs every chunk's newlines: the shard's scratch
+    XSG_TRY(s->d_chunk_counts.ensure(16 * s->chunks.size()));
+    d_nl = s->d_chunk_counts.as<uint64_t>() + s->chunks.size();
+  }
+  return enqueue_count_chunks(s, m, want_nl, st, d_counts, d_nl, d_counters, nullptr, d_status, false);
 }
 
 // Split-phase xsg_count for host pipelines: begin enqueues the pass on the ctx stream (results go to the shard's

@@ -235,6 +235,41 @@ struct FinishArgs {
   uint32_t cnt_is_lines;  // kDfa, XSG_COUNT_LINES: tile_cnt holds matching lines, its sum is reported as XSG_CTR_LINES
 };
 
+// k_count_chunks (xsg_count_chunks*): k_count_finish's work with the chunk boundaries kept.  What it needs beyond
+// FinishArgs travels as a second kernel parameter, so that k_count_finish keeps its argument block.  Both arrays hold
+// nchunks words and are ZERO before the launch (the kernel adds; a chunk in which nothing is found is never touched).
+struct ChunkCountArgs {
+  const uint32_t* tile_chunk;  // tile -> chunk (null when the shard has one chunk)
+  uint64_t* counts;            // per chunk: what the pass puts into XSG_CTR_MATCHES (want_matches) or XSG_CTR_LINES
+                               // (want_lines); null: not asked for (a pass for the newline counts alone)
+  uint64_t* newlines;          // per chunk: its '\n' (needs FinishArgs::want_nl); null: not asked for
+};
+hipError_t launch_count_chunks(const FinishArgs& a, const ChunkCountArgs& c, hipStream_t s);
+// behind it, one lane per chunk: a refusal (*status != 0, or the poisoned counters of a pass without a status word)
+// zeroes counts[c] and newlines[c]; otherwise, `invert`, counts[c] = lines of chunk c (newlines[c], plus one for a last
+// line without its '\n') - counts[c]: the per-chunk form of k_invert_count_lines.  `newlines` may be null unless `invert`.
+hipError_t launch_chunk_counts_post(const uint8_t* base, const ChunkDev* chunks, uint64_t nchunks, uint64_t* counts,
+                                    uint64_t* newlines, const uint64_t* counters, const uint64_t* status, uint32_t invert,
+                                    hipStream_t s);
+// The per-chunk figures of a count that IS a list (xsg_list_kernels.hip: k_list_chunk_counts): one lane per chunk, two
+// binary searches in the chunk column of the M raw entries (ascending), the kept ones between them from keep_pre, plus
+// the chunk's tail entries; newlines[c] (if asked for, or `invert`) from the prefix of the per-tile newline counts.
+struct ListChunkArgs {
+  const uint8_t* base;
+  const ChunkDev* chunks;
+  const uint64_t* chunk_tile0;
+  uint64_t nchunks;
+  uint64_t M;
+  const uint32_t* m_chunk;
+  const uint64_t* keep_pre;     // M + 1 entries
+  const uint32_t* tail_cnt;     // per chunk
+  const uint64_t* tile_nl_off;  // exclusive prefix of tile_nl (ntiles + 1); null: no newline figures
+  uint64_t* counts;
+  uint64_t* newlines;           // optional
+  uint32_t invert;              // counts[c] = lines of chunk c - counts[c] (needs tile_nl_off)
+};
+hipError_t launch_list_chunk_counts(const ListChunkArgs& a, hipStream_t s);
+
 // ---- launchers (xsg_kernels.hip) --------------------------------------------
 hipError_t launch_scan_count(const ScanArgs& a, bool want_nl, bool want_lines, hipStream_t s);
 hipError_t launch_scan_emit(const ScanArgs& a, hipStream_t s);

@@ -25,6 +25,7 @@
 #include <cstring>
 #include <type_traits>
 
+#include "xsg_chunkcount.h"
 #include "xsg_devutil.h"
 #include "xsg_linesum.h"
 #include "xsg_sketch.h"
@@ -1803,6 +1804,143 @@ hipError_t launch_scan_emit(const ScanArgs& a, hipStream_t s) {
 // host mirror), so the counters need no zeroing either.
 // ---------------------------------------------------------------------------
 
+// One chunk's share of the finish, by one wave: where the reference walk stands at the end of the bulk part (from the last
+// tile that holds a match), the chunk's matching lines from its tiles' summaries (tile_sum goes back to zero as it is
+// read), then its tail zone.  Lane 0 adds the tail zone's matches to `cm` and the chunk's matching lines to `lines`.
+// Shared by k_count_finish (which sums over its chunks) and k_count_chunks (which keeps each chunk's figures).
+__device__ __forceinline__ void finish_chunk(const FinishArgs& A, uint64_t c, uint32_t lane, uint32_t wave, bool need_tail,
+                                             bool mask_tail, const uint8_t* s_pat, uint8_t (*s_zone)[kZoneStage], uint64_t& cm,
+                                             uint64_t& lines) {
+  const uint64_t t0 = A.chunk_tile0[c], t1 = A.chunk_tile0[c + 1];
+  const ChunkDev ch = A.chunks[c];
+  const uint8_t* d = A.base + ch.offset;
+  uint64_t last_end = 0;
+  if (need_tail) {
+    uint64_t t = t1;
+    while (t > t0 && last_end == 0) {  // wave-uniform; 256 tiles a step, four independent loads
+      const uint64_t lo = t - t0 >= 256 ? t - 256 : t0;
+      uint32_t v[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const uint64_t idx = lo + (uint64_t)u * 64u + lane;
+        const uint32_t x = idx < t ? A.tile_last[idx] : 0u;
+        v[u] = (x >> 16) == A.epoch ? (x & 0xffffu) : 0u;  // words of older passes do not count
+      }
+#pragma unroll
+      for (int u = 3; u >= 0; --u) {
+        const unsigned long long bal = __ballot(v[u] != 0);
+        if (bal && last_end == 0) {
+          const int hi = 63 - __clzll((long long)bal);
+          const uint32_t vv = (uint32_t)__builtin_amdgcn_readlane((int)v[u], hi);
+          last_end = (lo + (uint64_t)u * 64u + (uint64_t)hi - t0) * (uint64_t)A.tile_bytes + vv;
+        }
+      }
+      t = lo;
+    }
+  }
+  if (A.want_lines) {
+    // 4 per-wave summaries per tile, 256 entries a step.  An entry that was never written reads 0 = "a newline,
+    // no match"; a group of 64 such entries combines to the same, so the common step is four ballots.
+    uint32_t run = 0;  // identity
+    const uint64_t e1 = t1 * kWaves;
+    for (uint64_t e0 = t0 * kWaves; e0 < e1; e0 += 256) {
+      uint32_t raw[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const uint64_t e = e0 + (uint64_t)u * 64u + lane;
+        raw[u] = e < e1 ? A.tile_sum[e] : kSumNl;  // beyond the chunk: the identity (0 after the XOR)
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        if (e0 + (uint64_t)u * 64u >= e1) break;  // wave-uniform
+        const uint64_t e = e0 + (uint64_t)u * 64u + lane;
+        if (__ballot(raw[u] != 0) == 0) {
+          run = sum_combine(run, kSumNl);
+        } else {
+          const uint32_t v = raw[u] ^ kSumNl;
+          if (raw[u] != 0 && e < e1) A.tile_sum[e] = 0u;  // back to "nothing found"
+          const uint32_t csum = wave_sum_u32(v >> kSumCShift);
+          run = sum_combine(run, sum_combine_lanes(__ballot(v & kSumNl), __ballot(v & kSumF), __ballot(v & kSumL), csum));
+        }
+      }
+    }
+    if (lane == 0) lines += sum_total_lines(run);
+  }
+  if (need_tail && ch.length) {
+    // the line-mode entry point may lie a whole huge line away: found by the wave, not by lane 0 alone
+    const uint64_t entry_lines = A.want_lines ? wave_walk_entry(d, ch.length, last_end, true, lane) : 0;
+    if (mask_tail) {
+      uint32_t nm = 0, nl = 0;
+      wave_tail_counts(d, ch.length, s_pat, A.pat.plen, A.pat.icase != 0, s_zone[wave], lane, A.want_matches != 0,
+                       last_end, A.want_lines != 0, entry_lines, &nm, &nl);
+      if (lane == 0) cm += nm, lines += nl;
+    } else {
+      // long patterns: the zone does not fit one position per lane.  One lane walks it byte by byte after a
+      // coalesced sweep of the whole wave has pulled the zone into the caches.
+      const uint64_t Lr = (ch.length + 15u) & ~(uint64_t)15u;
+      for (uint64_t off = (tail_zone_begin(ch.length, A.pat.plen) & ~(uint64_t)15u) + (uint64_t)lane * kUnit; off < Lr;
+           off += kWaveLoad) {
+        const uint4 v = *reinterpret_cast<const uint4*>(d + off);
+        asm volatile("" ::"v"(v.x), "v"(v.y), "v"(v.z), "v"(v.w));
+      }
+      if (lane == 0) {
+        if (A.want_matches)
+          cm += tail_walk(d, ch.length, A.pat.d_pat, A.pat.plen, last_end, false, nullptr, 0, A.pat.icase != 0);
+        if (A.want_lines)
+          lines += tail_walk(d, ch.length, A.pat.d_pat, A.pat.plen, entry_lines, true, nullptr, 0, A.pat.icase != 0);
+      }
+    }
+  }
+}
+
+// The end of a finish kernel: per-block partial sums; the last block to arrive adds them up, writes the four counters
+// (and the pinned mirror and the status word, if given) and leaves the flags and the ticket at rest.
+__device__ __forceinline__ void finish_totals(const FinishArgs& A, uint64_t cm, uint64_t lines, uint64_t cn, uint64_t* sh,
+                                              uint32_t* s_is_last) {
+  // ---- per-block partial sums; the last block to arrive adds them up
+  uint64_t t;
+  t = block_sum_u64(cm, sh);
+  if (threadIdx.x == 0) A.partials[3u * blockIdx.x + 0u] = t;
+  t = block_sum_u64(lines, sh);
+  if (threadIdx.x == 0) A.partials[3u * blockIdx.x + 1u] = t;
+  t = block_sum_u64(cn, sh);
+  if (threadIdx.x == 0) {
+    A.partials[3u * blockIdx.x + 2u] = t;
+    __threadfence();  // partials before the ticket
+    // (one ticket word for up to 2048 workgroups is not what the kernel's time goes to: a two-level ticket, 16 group
+    // words in front of it, left the 50 GiB shard's finish at its 48 us under rocprofv3 -- measured, removed)
+    *s_is_last = atomicAdd(A.ticket, 1u) == gridDim.x - 1u;
+  }
+  __syncthreads();
+  if (!*s_is_last) return;
+  __threadfence();
+  uint64_t a0 = 0, a1 = 0, a2 = 0;
+  for (uint32_t b = threadIdx.x; b < gridDim.x; b += kBlock) {
+    a0 += __hip_atomic_load(A.partials + 3u * b + 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    a1 += __hip_atomic_load(A.partials + 3u * b + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    a2 += __hip_atomic_load(A.partials + 3u * b + 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  a0 = block_sum_u64(a0, sh);
+  a1 = block_sum_u64(a1, sh);
+  a2 = block_sum_u64(a2, sh);
+  if (threadIdx.x == 0) {
+    // an ascii_only expression met non-ASCII data: no number is handed out (all four counters read UINT64_MAX)
+    const bool refuse = (A.pat.kind == kClass || A.pat.kind == kDfa) && A.pat.ascii_only &&
+                        (__hip_atomic_load(A.flags, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & 1u) != 0;
+    if (A.cnt_is_lines) a1 = a0, a0 = 0;  // k_rx_scan counted matching lines into tile_cnt
+    // a refusal poisons the counters (UINT64_MAX) -- or, for a caller that gave a status word, zeroes them and says why
+    const uint64_t bad = A.status ? 0ull : UINT64_MAX;
+    if (A.status) *A.status = refuse ? (uint64_t)XSG_STATUS_NONASCII : 0ull;
+    const uint64_t v[XSG_NUM_COUNTERS] = {refuse ? bad : a0, refuse ? bad : a1, refuse ? bad : a2, refuse ? bad : A.total_bytes};
+    for (int k = 0; k < XSG_NUM_COUNTERS; ++k) {
+      A.counters[k] = v[k];
+      if (A.host_counters) A.host_counters[k] = v[k];
+    }
+    *A.flags = 0u;
+    *A.ticket = 0u;  // at rest for the next launch (stream order)
+  }
+}
+
 __global__ __launch_bounds__(kBlock) void k_count_finish(const FinishArgs A) {
   __shared__ uint64_t sh[kWaves];
   __shared__ __attribute__((aligned(16))) uint8_t s_zone[kWaves][kZoneStage];
@@ -1842,131 +1980,10 @@ __global__ __launch_bounds__(kBlock) void k_count_finish(const FinishArgs A) {
   // last tile that holds a match), the chunk's matching lines, then its tail zone
   uint64_t lines = 0;
   const uint64_t wave_id = gid >> 6, nwaves = gsz >> 6;
-  for (uint64_t c = wave_id; c < A.nchunks; c += nwaves) {
-    const uint64_t t0 = A.chunk_tile0[c], t1 = A.chunk_tile0[c + 1];
-    const ChunkDev ch = A.chunks[c];
-    const uint8_t* d = A.base + ch.offset;
-    uint64_t last_end = 0;
-    if (need_tail) {
-      uint64_t t = t1;
-      while (t > t0 && last_end == 0) {  // wave-uniform; 256 tiles a step, four independent loads
-        const uint64_t lo = t - t0 >= 256 ? t - 256 : t0;
-        uint32_t v[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const uint64_t idx = lo + (uint64_t)u * 64u + lane;
-          const uint32_t x = idx < t ? A.tile_last[idx] : 0u;
-          v[u] = (x >> 16) == A.epoch ? (x & 0xffffu) : 0u;  // words of older passes do not count
-        }
-#pragma unroll
-        for (int u = 3; u >= 0; --u) {
-          const unsigned long long bal = __ballot(v[u] != 0);
-          if (bal && last_end == 0) {
-            const int hi = 63 - __clzll((long long)bal);
-            const uint32_t vv = (uint32_t)__builtin_amdgcn_readlane((int)v[u], hi);
-            last_end = (lo + (uint64_t)u * 64u + (uint64_t)hi - t0) * (uint64_t)A.tile_bytes + vv;
-          }
-        }
-        t = lo;
-      }
-    }
-    if (A.want_lines) {
-      // 4 per-wave summaries per tile, 256 entries a step.  An entry that was never written reads 0 = "a newline,
-      // no match"; a group of 64 such entries combines to the same, so the common step is four ballots.
-      uint32_t run = 0;  // identity
-      const uint64_t e1 = t1 * kWaves;
-      for (uint64_t e0 = t0 * kWaves; e0 < e1; e0 += 256) {
-        uint32_t raw[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const uint64_t e = e0 + (uint64_t)u * 64u + lane;
-          raw[u] = e < e1 ? A.tile_sum[e] : kSumNl;  // beyond the chunk: the identity (0 after the XOR)
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          if (e0 + (uint64_t)u * 64u >= e1) break;  // wave-uniform
-          const uint64_t e = e0 + (uint64_t)u * 64u + lane;
-          if (__ballot(raw[u] != 0) == 0) {
-            run = sum_combine(run, kSumNl);
-          } else {
-            const uint32_t v = raw[u] ^ kSumNl;
-            if (raw[u] != 0 && e < e1) A.tile_sum[e] = 0u;  // back to "nothing found"
-            const uint32_t csum = wave_sum_u32(v >> kSumCShift);
-            run = sum_combine(run, sum_combine_lanes(__ballot(v & kSumNl), __ballot(v & kSumF), __ballot(v & kSumL), csum));
-          }
-        }
-      }
-      if (lane == 0) lines += sum_total_lines(run);
-    }
-    if (need_tail && ch.length) {
-      // the line-mode entry point may lie a whole huge line away: found by the wave, not by lane 0 alone
-      const uint64_t entry_lines = A.want_lines ? wave_walk_entry(d, ch.length, last_end, true, lane) : 0;
-      if (mask_tail) {
-        uint32_t nm = 0, nl = 0;
-        wave_tail_counts(d, ch.length, s_pat, A.pat.plen, A.pat.icase != 0, s_zone[wave], lane, A.want_matches != 0,
-                         last_end, A.want_lines != 0, entry_lines, &nm, &nl);
-        if (lane == 0) cm += nm, lines += nl;
-      } else {
-        // long patterns: the zone does not fit one position per lane.  One lane walks it byte by byte after a
-        // coalesced sweep of the whole wave has pulled the zone into the caches.
-        const uint64_t Lr = (ch.length + 15u) & ~(uint64_t)15u;
-        for (uint64_t off = (tail_zone_begin(ch.length, A.pat.plen) & ~(uint64_t)15u) + (uint64_t)lane * kUnit; off < Lr;
-             off += kWaveLoad) {
-          const uint4 v = *reinterpret_cast<const uint4*>(d + off);
-          asm volatile("" ::"v"(v.x), "v"(v.y), "v"(v.z), "v"(v.w));
-        }
-        if (lane == 0) {
-          if (A.want_matches)
-            cm += tail_walk(d, ch.length, A.pat.d_pat, A.pat.plen, last_end, false, nullptr, 0, A.pat.icase != 0);
-          if (A.want_lines)
-            lines += tail_walk(d, ch.length, A.pat.d_pat, A.pat.plen, entry_lines, true, nullptr, 0, A.pat.icase != 0);
-        }
-      }
-    }
-  }
+  for (uint64_t c = wave_id; c < A.nchunks; c += nwaves)
+    finish_chunk(A, c, lane, wave, need_tail, mask_tail, s_pat, s_zone, cm, lines);
 
-  // ---- per-block partial sums; the last block to arrive adds them up
-  uint64_t t;
-  t = block_sum_u64(cm, sh);
-  if (threadIdx.x == 0) A.partials[3u * blockIdx.x + 0u] = t;
-  t = block_sum_u64(lines, sh);
-  if (threadIdx.x == 0) A.partials[3u * blockIdx.x + 1u] = t;
-  t = block_sum_u64(cn, sh);
-  if (threadIdx.x == 0) {
-    A.partials[3u * blockIdx.x + 2u] = t;
-    __threadfence();  // partials before the ticket
-    // (one ticket word for up to 2048 workgroups is not what the kernel's time goes to: a two-level ticket, 16 group
-    // words in front of it, left the 50 GiB shard's finish at its 48 us under rocprofv3 -- measured, removed)
-    s_is_last = atomicAdd(A.ticket, 1u) == gridDim.x - 1u;
-  }
-  __syncthreads();
-  if (!s_is_last) return;
-  __threadfence();
-  uint64_t a0 = 0, a1 = 0, a2 = 0;
-  for (uint32_t b = threadIdx.x; b < gridDim.x; b += kBlock) {
-    a0 += __hip_atomic_load(A.partials + 3u * b + 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    a1 += __hip_atomic_load(A.partials + 3u * b + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    a2 += __hip_atomic_load(A.partials + 3u * b + 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  a0 = block_sum_u64(a0, sh);
-  a1 = block_sum_u64(a1, sh);
-  a2 = block_sum_u64(a2, sh);
-  if (threadIdx.x == 0) {
-    // an ascii_only expression met non-ASCII data: no number is handed out (all four counters read UINT64_MAX)
-    const bool refuse = (A.pat.kind == kClass || A.pat.kind == kDfa) && A.pat.ascii_only &&
-                        (__hip_atomic_load(A.flags, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & 1u) != 0;
-    if (A.cnt_is_lines) a1 = a0, a0 = 0;  // k_rx_scan counted matching lines into tile_cnt
-    // a refusal poisons the counters (UINT64_MAX) -- or, for a caller that gave a status word, zeroes them and says why
-    const uint64_t bad = A.status ? 0ull : UINT64_MAX;
-    if (A.status) *A.status = refuse ? (uint64_t)XSG_STATUS_NONASCII : 0ull;
-    const uint64_t v[XSG_NUM_COUNTERS] = {refuse ? bad : a0, refuse ? bad : a1, refuse ? bad : a2, refuse ? bad : A.total_bytes};
-    for (int k = 0; k < XSG_NUM_COUNTERS; ++k) {
-      A.counters[k] = v[k];
-      if (A.host_counters) A.host_counters[k] = v[k];
-    }
-    *A.flags = 0u;
-    *A.ticket = 0u;  // at rest for the next launch (stream order)
-  }
+  finish_totals(A, cm, lines, cn, sh, &s_is_last);
 }
 
 hipError_t launch_count_finish(const FinishArgs& a, hipStream_t s) {
@@ -1978,6 +1995,169 @@ hipError_t launch_count_finish(const FinishArgs& a, hipStream_t s) {
   if (blocks < 1) blocks = 1;
   if (blocks > kFinishBlocks) blocks = kFinishBlocks;
   hipLaunchKernelGGL(k_count_finish, dim3((unsigned)blocks), dim3(kBlock), 0, s, a);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// k_count_chunks: k_count_finish with the chunk boundaries kept (xsg_count_chunks*).  Same discipline on the per-tile
+// arrays, same totals through the same ticket; on the way every chunk's own figure is added to counts[chunk] (and its
+// newlines to newlines[chunk]), both zeroed by the caller in stream order.
+// Tiles: a wave takes 64 consecutive tiles, one per lane.  Tiles are numbered chunk by chunk, so the lanes fall into runs
+// of one chunk each (xsg_chunkcount.h: heads and ends from the ballot of "my chunk differs from my left neighbour's").
+// One inclusive scan over the wave gives every run its sum as a difference of two prefix values, and the run's head adds
+// a sum that is not zero with one 64-bit atomic: no atomic at all for 64 tiles without a hit, at most one per (wave,
+// chunk) run for a dense needle, and the same work whether the bytes are one chunk or a hundred thousand.  A run that
+// reaches the end of its 64 tiles is kept pending in the wave and merged with the next block's first run where that is
+// the same chunk (add_run_sums), and what the four waves still hold at the end is merged through LDS: a chunk of many
+// GiB gets a few adds per workgroup, not one per 64 tiles on one address.
+// Chunks: one wave per chunk runs finish_chunk (tail zone, line summaries) and adds its result the same way.
+// ---------------------------------------------------------------------------
+// The sums of one array over the runs of 64 tiles, to out[chunk].  (pid, psum) is the wave's PENDING run, wave-uniform:
+// the last run of the block the wave took before, not added yet.  The blocks a wave takes lie far apart but in ascending
+// order, so in a chunk of many tiles the next block's first run is the same chunk again: it is folded into the pending
+// sum instead of added to the same word once more (a dense needle in one chunk of 50 GiB would otherwise serialise 50 000
+// atomics on one address).  Every other run's head adds its sum, if it is not zero, at once.
+__device__ __forceinline__ void add_run_sums(uint32_t v, uint32_t id, uint32_t lane, uint64_t heads, uint32_t end, uint64_t* out,
+                                             uint32_t& pid, uint64_t& psum) {
+  const bool head = (heads >> lane) & 1ull;
+  const uint32_t incl = wave_incl_scan_u32(v, lane);
+  const uint32_t hi = (uint32_t)__shfl((int)incl, (int)end - 1);
+  const uint32_t lo = (uint32_t)__shfl_up((int)incl, 1);
+  const uint32_t sum = hi - (lane ? lo : 0u);  // valid in head lanes
+  const int last = 63 - __clzll((long long)heads);  // the block's last run (heads has bit 0 set)
+  const unsigned long long same = __ballot(head && id == pid);  // the run that continues the pending one: at most one
+  const int cont = same ? __builtin_ctzll(same) : -1;
+  if (cont >= 0) psum += (uint32_t)__builtin_amdgcn_readlane((int)sum, cont);
+  if (cont != last) {  // the pending run ends here: add it, and the block's last run is the pending one now
+    if (psum && lane == 0) atomicAdd(reinterpret_cast<unsigned long long*>(out + pid), (unsigned long long)psum);
+    pid = (uint32_t)__builtin_amdgcn_readlane((int)id, last);
+    psum = (uint32_t)__builtin_amdgcn_readlane((int)sum, last);
+  }
+  if (head && sum && (int)lane != last && (int)lane != cont)
+    atomicAdd(reinterpret_cast<unsigned long long*>(out + id), (unsigned long long)sum);
+}
+
+__global__ __launch_bounds__(kBlock) void k_count_chunks(const FinishArgs A, const ChunkCountArgs C) {
+  __shared__ uint64_t sh[kWaves];
+  __shared__ __attribute__((aligned(16))) uint8_t s_zone[kWaves][kZoneStage];
+  __shared__ uint8_t s_pat[kTailMaskMaxPlen + 3];
+  __shared__ uint32_t s_is_last;
+  __shared__ uint32_t s_pid[2][kWaves];   // the waves' pending runs at the end of the tile part: counts, newlines
+  __shared__ uint64_t s_psum[2][kWaves];
+  const uint64_t gid = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+  const uint64_t gsz = (uint64_t)gridDim.x * kBlock;
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const bool need_tail = !A.pat.exact_tail && A.pat.plen > 1;
+  const bool mask_tail = need_tail && A.pat.plen <= kTailMaskMaxPlen;
+  if (mask_tail) {
+    if (threadIdx.x < A.pat.plen) s_pat[threadIdx.x] = A.pat.d_pat[threadIdx.x];
+    __syncthreads();
+  }
+
+  // ---- per-tile sums, by chunk; tile_cnt goes back to zero as it is read (every word has exactly one reader)
+  uint64_t cm = 0, cn = 0;
+  const uint64_t wave_id = gid >> 6, nwaves = gsz >> 6;
+  const bool cnt_out = C.counts != nullptr && A.want_matches != 0;  // (a line count of a literal comes from tile_sum)
+  const bool nl_out = C.newlines != nullptr && A.want_nl != 0;
+  uint32_t pid_c = 0xffffffffu, pid_n = 0xffffffffu;  // no chunk (the table holds fewer than 2^32)
+  uint64_t psum_c = 0, psum_n = 0;
+  for (uint64_t b = wave_id * 64u; b < A.ntiles; b += 4u * 64u * nwaves) {
+    uint32_t v[4], w[4], id[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const uint64_t tt = b + (uint64_t)u * 64u * nwaves + lane;
+      const bool ok = tt < A.ntiles;
+      v[u] = ok ? A.tile_cnt[tt] : 0u;
+      w[u] = (A.want_nl && ok) ? A.tile_nl[tt] : 0u;
+      id[u] = (C.tile_chunk && ok) ? C.tile_chunk[tt] : 0u;
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const uint64_t first = b + (uint64_t)u * 64u * nwaves;  // wave-uniform
+      if (first >= A.ntiles) break;
+      if (v[u]) A.tile_cnt[first + lane] = 0u;
+      cm += v[u];
+      cn += w[u];
+      const bool any_v = cnt_out && __ballot(v[u] != 0) != 0;
+      const bool any_w = nl_out && __ballot(w[u] != 0) != 0;
+      if (!any_v && !any_w) continue;  // 64 tiles with nothing to report: no run arithmetic, no atomic
+      const uint64_t active = run_active_mask(A.ntiles - first);
+      const uint32_t left = (uint32_t)__shfl_up((int)id[u], 1);
+      const uint64_t heads = run_heads(__ballot(id[u] != left), active);
+      const uint32_t end = run_end(heads, active, lane);
+      if (any_v) add_run_sums(v[u], id[u], lane, heads, end, C.counts, pid_c, psum_c);
+      if (any_w) add_run_sums(w[u], id[u], lane, heads, end, C.newlines, pid_n, psum_n);
+    }
+  }
+  if (!A.want_matches) cm = 0;
+  // what is still pending: the workgroup's four waves often hold the same chunk -- one add for them together
+  if (lane == 0) {
+    s_pid[0][wave] = pid_c, s_psum[0][wave] = psum_c;
+    s_pid[1][wave] = pid_n, s_psum[1][wave] = psum_n;
+  }
+  __syncthreads();
+  if (threadIdx.x < 2) {
+    uint64_t* out = threadIdx.x ? C.newlines : C.counts;
+    for (uint32_t w0 = 0; w0 < (uint32_t)kWaves;) {
+      const uint32_t id = s_pid[threadIdx.x][w0];
+      uint64_t sum = s_psum[threadIdx.x][w0];
+      uint32_t w1 = w0 + 1;
+      while (w1 < (uint32_t)kWaves && s_pid[threadIdx.x][w1] == id) sum += s_psum[threadIdx.x][w1++];
+      if (sum) atomicAdd(reinterpret_cast<unsigned long long*>(out + id), (unsigned long long)sum);  // (sum != 0: `out` is given, id a chunk)
+      w0 = w1;
+    }
+  }
+
+  // ---- one wave per chunk, as in k_count_finish; what it finds goes to the chunk's word as well
+  uint64_t lines = 0;
+  for (uint64_t c = wave_id; c < A.nchunks; c += nwaves) {
+    uint64_t m = 0, l = 0;
+    finish_chunk(A, c, lane, wave, need_tail, mask_tail, s_pat, s_zone, m, l);
+    if (lane == 0) {
+      cm += m;
+      lines += l;
+      const uint64_t x = A.want_lines ? l : m;
+      if (C.counts && x) atomicAdd(reinterpret_cast<unsigned long long*>(C.counts + c), (unsigned long long)x);
+    }
+  }
+
+  finish_totals(A, cm, lines, cn, sh, &s_is_last);
+}
+
+hipError_t launch_count_chunks(const FinishArgs& a, const ChunkCountArgs& c, hipStream_t s) {
+  // k_count_finish's grid: a wave per chunk, and a wave sums ~8 blocks of 64 tiles
+  uint64_t blocks = (a.nchunks + kWaves - 1) / kWaves;
+  const uint64_t for_tiles = (a.ntiles + (uint64_t)kBlock * 8 - 1) / ((uint64_t)kBlock * 8);
+  if (for_tiles > blocks) blocks = for_tiles;
+  if (blocks < 1) blocks = 1;
+  if (blocks > kFinishBlocks) blocks = kFinishBlocks;
+  hipLaunchKernelGGL(k_count_chunks, dim3((unsigned)blocks), dim3(kBlock), 0, s, a, c);
+  return hipGetLastError();
+}
+
+__global__ __launch_bounds__(kBlock) void k_chunk_counts_post(const uint8_t* base, const ChunkDev* chunks, uint64_t nchunks,
+                                                              uint64_t* counts, uint64_t* newlines, const uint64_t* counters,
+                                                              const uint64_t* status, uint32_t invert) {
+  const uint64_t c = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (c >= nchunks) return;
+  if ((status && *status) || counters[XSG_CTR_BYTES] == UINT64_MAX) {  // a refusal: no number is handed out
+    counts[c] = 0;
+    if (newlines) newlines[c] = 0;
+    return;
+  }
+  if (!invert) return;
+  const ChunkDev ch = chunks[c];
+  const uint64_t open = ch.length != 0 && base[ch.offset + ch.length - 1] != '\n';  // a last line without its '\n'
+  counts[c] = newlines[c] + open - counts[c];
+}
+hipError_t launch_chunk_counts_post(const uint8_t* base, const ChunkDev* chunks, uint64_t nchunks, uint64_t* counts,
+                                    uint64_t* newlines, const uint64_t* counters, const uint64_t* status, uint32_t invert,
+                                    hipStream_t s) {
+  if (nchunks == 0) return hipSuccess;
+  if (invert && !newlines) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_chunk_counts_post, dim3((unsigned)((nchunks + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, base, chunks, nchunks, counts, newlines, counters,
+                     status, invert);
   return hipGetLastError();
 }
 

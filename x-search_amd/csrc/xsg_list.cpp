@@ -950,6 +950,7 @@ int xsg::run_list(xsg_shard* s, uint32_t mode, bool outputs, bool want_nl_total,
   XSG_TRY(decide_keep(s, l, chain_lines));
 
   // 5. the tail zone of every chunk and the totals; 6. the final list
+  s->list_entries = M;  // (xsg_count_chunks reads the chunk column and keep_pre behind a pass without outputs)
   uint64_t total = 0;
   XSG_TRY(tails_and_total(s, a, l, want_nl_total, &total));
   if (!outputs) return XSG_OK;

@@ -1369,6 +1369,39 @@ hipError_t launch_invert_count_lines(const uint8_t* base, const ChunkDev* chunks
   return hipGetLastError();
 }
 
+// xsg_count_chunks for a count that is a list (ListChunkArgs, xsg_internal.h): one lane per chunk.  The raw entries are in
+// chunk order, so chunk c's are [first index with m_chunk >= c, first index with m_chunk > c): two binary searches, no
+// atomics; what the walk kept of them is a difference in keep_pre, and the tail zone's entries are the chunk's own word.
+__device__ __forceinline__ uint64_t first_entry_of_chunk(const uint32_t* m_chunk, uint64_t M, uint64_t c) {
+  uint64_t lo = 0, hi = M;  // the first i in [0, M] with m_chunk[i] >= c (M: none)
+  while (lo < hi) {
+    const uint64_t mid = lo + (hi - lo) / 2;
+    if ((uint64_t)m_chunk[mid] < c) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+__global__ __launch_bounds__(kBlock) void k_list_chunk_counts(const ListChunkArgs A) {
+  const uint64_t c = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (c >= A.nchunks) return;
+  const uint64_t i0 = first_entry_of_chunk(A.m_chunk, A.M, c), i1 = first_entry_of_chunk(A.m_chunk, A.M, c + 1);
+  uint64_t n = A.keep_pre[i1] - A.keep_pre[i0] + A.tail_cnt[c];
+  uint64_t nl = 0;
+  if (A.tile_nl_off) nl = A.tile_nl_off[A.chunk_tile0[c + 1]] - A.tile_nl_off[A.chunk_tile0[c]];
+  if (A.invert) {
+    const ChunkDev ch = A.chunks[c];
+    const uint64_t open = ch.length != 0 && A.base[ch.offset + ch.length - 1] != '\n';  // a last line without its '\n'
+    n = nl + open - n;
+  }
+  A.counts[c] = n;
+  if (A.newlines) A.newlines[c] = nl;
+}
+hipError_t launch_list_chunk_counts(const ListChunkArgs& a, hipStream_t s) {
+  if (a.nchunks == 0) return hipSuccess;
+  if ((a.invert || a.newlines) && !a.tile_nl_off) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_list_chunk_counts, grid_for(a.nchunks), dim3(kBlock), 0, s, a);
+  return hipGetLastError();
+}
+
 
 // ---------------------------------------------------------------------------
 // XSG_FLAG_CONTEXT: the lines around the reported ones (ContextArgs, xsg_internal.h)

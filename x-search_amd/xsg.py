@@ -139,6 +139,8 @@ def load():
         "xsg_count_async": (ci, [vp, u32, vp, vp]),
         "xsg_count_async_status": (ci, [vp, u32, vp, vp, vp]),
         "xsg_count": (ci, [vp, u32, _u64p]),
+        "xsg_count_chunks": (ci, [vp, u32, vp, vp, u64, vp]),
+        "xsg_count_chunks_async": (ci, [vp, u32, vp, vp, vp, u64, vp, vp]),
         "xsg_count_begin": (ci, [vp, u32]),
         "xsg_count_end": (ci, [vp, _u64p]),
         "xsg_search": (ci, [vp, u32, _u64p]),
@@ -207,7 +209,7 @@ EXPORTS = ["xsg_abi_version", "xsg_strerror", "xsg_last_error", "xsg_device_coun
            "xsg_jobs_reduce_total", "xsg_device_numa", "xsg_regex_info", "xsg_regex_dfa_info", "xsg_regex_prefix", "xsg_regex_factor",
            "xsg_result_u64_view", "xsg_shard_invalidate", "xsg_result_lines_view", "xsg_count_async_status", "xsg_codec_name",
            "xsg_host_matches", "xsg_result_context_edges", "xsg_set_literals", "xsg_literals_info",
-           "xsg_host_searcher_create_list"]
+           "xsg_host_searcher_create_list", "xsg_count_chunks", "xsg_count_chunks_async"]
 
 
 def _check(rc):
@@ -427,6 +429,23 @@ class Shard:
         out = np.zeros(NUM_COUNTERS, dtype=np.uint64)
         _check(self._lib.xsg_count(self.h, mode, out.ctypes.data_as(_u64p)))
         return out
+
+    def count_chunks(self, mode: int):
+        """one count per bound chunk in one pass (xsg_count_chunks): (counts, newlines or None, totals) -- counts[c] is what
+        count(mode) would report for chunk c alone, newlines[c] (with WITH_NEWLINES) its '\\n', totals what count(mode) returns"""
+        counts = np.zeros(self.nchunks, dtype=np.uint64)
+        newlines = np.zeros(self.nchunks, dtype=np.uint64) if mode & WITH_NEWLINES else None
+        totals = np.zeros(NUM_COUNTERS, dtype=np.uint64)
+        _check(self._lib.xsg_count_chunks(self.h, mode, C.c_void_p(counts.ctypes.data),
+                                          C.c_void_p(newlines.ctypes.data) if newlines is not None else None, self.nchunks,
+                                          C.c_void_p(totals.ctypes.data)))
+        return counts, newlines, totals
+
+    def count_chunks_async(self, mode: int, stream: int, d_counts: int, d_newlines: int, cap: int, d_counters: int, d_status: int):
+        """the stream-ordered form (xsg_count_chunks_async): raw device addresses, d_newlines may be 0 / None"""
+        _check(self._lib.xsg_count_chunks_async(self.h, mode, C.c_void_p(stream), C.c_void_p(d_counts),
+                                                C.c_void_p(d_newlines) if d_newlines else None, cap, C.c_void_p(d_counters),
+                                                C.c_void_p(d_status)))
 
     def count_begin(self, mode: int):
         _check(self._lib.xsg_count_begin(self.h, mode))
