@@ -40,7 +40,8 @@ extern "C" {
  * grew and the line tags accept a literal that contains '\n' (round 4); still 4: XSG_FLAG_INVERT, XSG_MATCHES,
  * XSG_FLAG_CONTEXT and xsg_result_context_edges joined; xsg_set_literals, xsg_literals_info, xsg_host_searcher_create_list
  * and xsg_job_opts.pattern_is_list joined (the structure grew: see there for what that asks of a program built before);
- * xsg_count_chunks and xsg_count_chunks_async joined; no entry point was removed or changed in meaning */
+ * xsg_count_chunks and xsg_count_chunks_async joined; xsg_count_literals, xsg_count_literals_async and xsg_literal_counter_*
+ * joined; no entry point was removed or changed in meaning */
 #define XSG_ABI_VERSION 4
 
 /* ---- status codes ------------------------------------------------------- */
@@ -462,6 +463,31 @@ int xsg_count_chunks(xsg_shard* shard, uint32_t mode, uint64_t* counts, uint64_t
 int xsg_count_chunks_async(xsg_shard* shard, uint32_t mode, void* stream, uint64_t* d_counts, uint64_t* d_newlines,
                            uint64_t cap_chunks, uint64_t* d_counters, uint64_t* d_status);
 
+/* ---- counts per literal ---------------------------------------------------- */
+/* The other axis: which literals of a list (xsg_set_literals) occur in the bound chunks, and how often -- a keyword table
+ * in one pass over the text.  Let l_0 .. l_{k-1} be the literals in the order xsg_set_literals parsed them.
+ * counts[j] = the number of pairs (chunk c, position p) with p + len(l_j) <= length(c) and the chunk bytes
+ * [p, p + len(l_j)) equal to l_j; under XSG_FLAG_IGNORE_CASE both sides are ASCII-lowered first.  These are OCCURRENCES,
+ * not the matches of the list's leftmost-first walk: overlapping occurrences all count (`aa` in `aaaa`: 3), a literal
+ * covered by another still counts (`ab`, `abc` on `abc`: 1 and 1), duplicates in the list get the same number each, and
+ * counts[j] depends on l_j's bytes and the bound data only, never on the rest of the list.  No byte at or beyond a chunk's
+ * end decides anything.
+ * Relation to the rest of the ABI: counts[j] equals XSG_CTR_MATCHES of xsg_count(XSG_COUNT_MATCHES) under
+ * XSG_FLAG_EXACT_TAIL with l_j as the only pattern whenever no two occurrences of l_j overlap in the data -- always, for a
+ * literal without a border (no proper prefix of it is also its suffix).
+ * Both calls write counts[0 .. k), every entry, zeros included; a binding of 0 chunks is XSG_OK with k zeros.
+ * XSG_ESTATE: the ctx holds no pattern.  XSG_ENOTSUP: the pattern is not a list set by xsg_set_literals (a single
+ * literal goes in as a list of one); XSG_FLAG_INVERT is set (a count of occurrences has no inverted form); a binding of
+ * 2^24 chunks or more, as for every list search.  XSG_EINVAL: counts == NULL, cap_literals < k.  The CONTEXT bits and
+ * XSG_FLAG_EXACT_TAIL are accepted and ignored, as by every count of a list.
+ * One launch: the candidate scan of the list with the verify step inside its own pass (no candidate list, no size fetched
+ * from the device), a histogram per workgroup, 64-bit atomics into counts.  The list tags (xsg_count, xsg_search) are
+ * unchanged and may be called before and after on the same binding. */
+int xsg_count_literals(xsg_shard* shard, uint64_t* counts, uint64_t cap_literals); /* host memory; waits */
+/* Stream-ordered form: d_counts is DEVICE memory (cap_literals words), overwritten; nothing waits and nothing is fetched.
+ * Unlike the other stream-ordered counts of a list (XSG_ENOTSUP there) this one needs no size from the device. */
+int xsg_count_literals_async(xsg_shard* shard, void* stream, uint64_t* d_counts, uint64_t cap_literals);
+
 /* ---- list results (replace byte_offsets_match/_line, line; :136-154,187-207) */
 /* Runs the search for one of the list modes on the ctx stream and waits.
  * *n_results = number of elements (offsets / indices / lines).  Results stay
@@ -618,6 +644,20 @@ int xsg_host_lines(xsg_host_searcher* hs, const void* data, uint64_t len, uint64
 /* XSG_MATCHES of the chunk: n matches, lengths[i] bytes each, packed in *bytes; both malloc'ed (xsg_free) */
 int xsg_host_matches(xsg_host_searcher* hs, const void* data, uint64_t len, uint64_t** lengths, char** bytes,
                      uint64_t* n, uint64_t* nbytes);
+
+/* Counts per literal (xsg_count_literals) over chunks in host memory, ACCUMULATED: a reader loop that hands in the
+ * newline-aligned chunks of a file gets the file's table -- a literal holds no '\n', so no occurrence straddles a cut.
+ * The counter owns a context with the list, two pinned staging slots with device buffers and a stream each: _add copies
+ * the chunk into a slot, enqueues its transfer and its pass and returns, so the transfer of one chunk overlaps the pass
+ * over the one before; the running sums stay on the device.  _get waits for what is in flight and copies the sums out
+ * (counts[0 .. k), cap_literals >= k or XSG_EINVAL; *bytes, optional: the bytes added so far); it may be called between
+ * adds.  len == 0 adds nothing.  `flags`: those of xsg_set_literals; XSG_FLAG_INVERT is XSG_ENOTSUP.  One counter is used
+ * from one thread at a time. */
+typedef struct xsg_literal_counter xsg_literal_counter;
+int xsg_literal_counter_create(int device, const void* list, size_t n, uint32_t flags, xsg_literal_counter** out);
+int xsg_literal_counter_add(xsg_literal_counter* lc, const void* data, uint64_t len);
+int xsg_literal_counter_get(xsg_literal_counter* lc, uint64_t* counts, uint64_t cap_literals, uint64_t* bytes);
+void xsg_literal_counter_destroy(xsg_literal_counter* lc);
 
 /* ---- chunk plans and metafiles (host only: usable without a GPU) ------------- */
 /* One record of the reference's metafile (decoded from test/files/ *.meta,

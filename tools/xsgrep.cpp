@@ -3,6 +3,7 @@
 //
 //   xsgrep [-c] [-i] [-o] [-v] [-E|-F] [-x] [-A N] [-B N] [-C N] [-j THREADS] [-m METAFILE] PATTERN FILE|-
 //   xsgrep -F [-c] [-i] [-o] [-v] [-A N] [-B N] [-C N] [-j THREADS] [-m METAFILE] (-e PATTERN)... [-f FILE]... FILE|-
+//   xsgrep -F [-i] --count-each (-e PATTERN)... [-f FILE]... FILE|-
 //
 // -c  print only a count of matching lines   (grep.cpp:45-46 -> xs::count_lines)
 // -i  ignore ASCII case                      (grep.cpp:47-48)
@@ -25,11 +26,18 @@
 //     leftmost-FIRST in listing order: at a position where several literals occur the first-listed one is printed (-e ab
 //     -e abc prints `ab` for `abc`); GNU grep prints the longest.  An empty pattern among several is refused (grep lets
 //     it match every line).
+// --count-each  a keyword table: one line per literal in listing order, COUNT<TAB>LITERAL, where COUNT is the number of the
+//     literal's OCCURRENCES in the input (xsg_literal_counter_* -> xsg_count_literals: overlapping occurrences, literals
+//     covered by another one and duplicates all count; under -i both sides are ASCII-lowered).  One pass over the input
+//     however many literals there are.  Requires -F; a single -e or the positional PATTERN is a list of one.  Excludes
+//     -c -o -v -x -A -B -C -m: it prints no lines and counts no lines.  The input is read in newline-aligned chunks, FILE
+//     and stdin alike; a literal holds no newline, so no occurrence straddles a cut and the sums are the input's.
 // The one-letter options without an argument may be bundled (-vc, -ci, -oi).
 // otherwise print the matching lines, live, as they are found (grep.cpp:74-79).
 #include <xsearch/tasks/gpu_searchers.h>
 #include <xsearch/xsearch.h>
 
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -42,13 +50,16 @@
 static const char kUsage[] =
     "usage: %s [-c] [-i] [-o] [-v] [-E|-F] [-x] [-A N] [-B N] [-C N] [-j THREADS] [-m METAFILE] PATTERN FILE|-\n"
     "       %s -F [-c] [-i] [-o] [-v] [-A N] [-B N] [-C N] [-j THREADS] [-m METAFILE] (-e PATTERN)... [-f FILE]... FILE|-\n"
+    "       %s -F [-i] --count-each (-e PATTERN)... [-f FILE]... FILE|-\n"
     "  -e PATTERN, -f FILE (one literal per line) search for any of several literals; both may repeat, need -F and exclude -x\n"
     "     when they give more than one pattern; -o then prints the FIRST-listed literal that occurs at a position (GNU grep: the longest)\n"
     "  -A N, -B N, -C N also print N lines after / before / around every selected line (N <= 4095), each line once and\n"
     "     without group separators; nothing changes under -c and -o; not with FILE = -\n"
     "  -o, --only-matching prints only the matched text, every match on its own line (not with -v)\n"
     "  -v, --invert-match selects the lines WITHOUT a match (with -c: counts them)\n"
-    "  -x searches (?m)^(?:PATTERN)$; PATTERN must not be empty\n";
+    "  -x searches (?m)^(?:PATTERN)$; PATTERN must not be empty\n"
+    "  --count-each prints COUNT<TAB>LITERAL for every literal in listing order: its occurrences in the input, overlapping\n"
+    "     ones and those inside another literal's included; needs -F, excludes -c -o -v -x -A -B -C -m\n";
 
 // PATTERN without a leading `^` and a trailing unescaped `$`: under -x they say what the wrap says already
 static std::string strip_edge_anchors(std::string p) {
@@ -79,8 +90,71 @@ static bool context_number(const std::string& text, long* out) {
   return *out <= (long)XSG_CONTEXT_MAX;
 }
 
+// The input in newline-aligned chunks of about 16 MiB: each is cut behind its last newline and the rest opens the next
+// one; a line longer than the target grows the chunk; the last chunk ends where the input does.  XSGREP_CHUNK_BYTES sets
+// another target (the tests cut a small input into many chunks with it).
+template <typename F>
+static void for_each_aligned_chunk(std::FILE* in, F&& f) {
+  size_t target = 16u << 20;
+  if (const char* e = std::getenv("XSGREP_CHUNK_BYTES"))
+    if (std::atoll(e) > 0) target = (size_t)std::atoll(e);
+  const size_t step = std::min<size_t>(target, 1u << 20);
+  std::vector<char> buf;  // bytes read and not handed out yet
+  size_t want = target;
+  bool eof = false;
+  for (;;) {
+    while (!eof && buf.size() < want) {
+      const size_t at = buf.size();
+      buf.resize(at + step);
+      const size_t got = std::fread(buf.data() + at, 1, step, in);
+      buf.resize(at + got);
+      if (got == 0) eof = true;
+    }
+    if (buf.empty()) break;
+    size_t cut = buf.size();
+    if (!eof) {  // cut after the last newline; the rest opens the next chunk
+      while (cut > 0 && buf[cut - 1] != '\n') --cut;
+      if (cut == 0) {  // one line longer than the chunk target: keep reading
+        want = buf.size() + target;
+        continue;
+      }
+    }
+    std::vector<char> chunk(buf.begin(), buf.begin() + (ptrdiff_t)cut);
+    buf.erase(buf.begin(), buf.begin() + (ptrdiff_t)cut);
+    want = target;
+    f(chunk);
+  }
+}
+
+// --count-each: the table of xsg_literal_counter_* over the input's chunks; -> the exit status
+static int count_each(const std::vector<std::string>& lits, bool icase, const std::string& file) {
+  std::string list;
+  for (const std::string& l : lits) list += (list.empty() ? "" : "\n") + l;
+  std::FILE* in = file == "-" ? stdin : std::fopen(file.c_str(), "rb");
+  if (!in) {
+    std::fprintf(stderr, "xsgrep: cannot read '%s'\n", file.c_str());
+    return 2;
+  }
+  xsg_literal_counter* lc = nullptr;
+  int rc = xsg_literal_counter_create(0, list.data(), list.size(), icase ? XSG_FLAG_IGNORE_CASE : 0u, &lc);
+  if (rc == XSG_OK)
+    for_each_aligned_chunk(in, [&](const std::vector<char>& chunk) {
+      if (rc == XSG_OK) rc = xsg_literal_counter_add(lc, chunk.data(), chunk.size());
+    });
+  std::vector<uint64_t> counts(lits.size(), 0);
+  if (rc == XSG_OK) rc = xsg_literal_counter_get(lc, counts.data(), counts.size(), nullptr);
+  if (rc != XSG_OK) {
+    std::fprintf(stderr, "xsgrep: %s\n", xsg_last_error());
+    return rc == XSG_EINVAL ? 2 : 1;
+  }
+  for (size_t j = 0; j < lits.size(); ++j) std::cout << counts[j] << '\t' << lits[j] << '\n';
+  std::cout.flush();
+  return 0;
+}
+
 int main(int argc, char** argv) {
   bool count = false, icase = false, fixed = false, extended = false, whole_lines = false, invert = false, only = false;
+  bool each = false, context_given = false;
   int threads = 2;  // grep.cpp:21
   long before = 0, after = 0;
   std::string meta, pattern, file;
@@ -103,6 +177,8 @@ int main(int argc, char** argv) {
       invert = true;
     } else if (a == "-o" || a == "--only-matching") {
       only = true;
+    } else if (a == "--count-each") {
+      each = true;
     } else if (a == "-c" || a == "--count") {
       count = true;
     } else if (a == "-i" || a == "--ignore-case") {
@@ -121,6 +197,7 @@ int main(int argc, char** argv) {
       }
       if (a != "-A") before = n;
       if (a != "-B") after = n;
+      context_given = true;
     } else if ((a == "-j" || a == "--threads") && i + 1 < nargs) {
       threads = std::atoi(args[++i].c_str());
     } else if ((a == "-m" || a == "--meta") && i + 1 < nargs) {
@@ -147,7 +224,7 @@ int main(int argc, char** argv) {
       }
       have_patterns = true;
     } else if (a == "-h" || a == "--help") {
-      std::printf(kUsage, argv[0], argv[0]);
+      std::printf(kUsage, argv[0], argv[0], argv[0]);
       return 0;
     } else if (pos == 0 && !have_patterns) {
       pattern = a;
@@ -170,8 +247,32 @@ int main(int argc, char** argv) {
     pos = 2;
   }
   if (pos != 2) {
-    std::fprintf(stderr, kUsage, argv[0], argv[0]);
+    std::fprintf(stderr, kUsage, argv[0], argv[0], argv[0]);
     return 2;
+  }
+  if (each) {  // a keyword table: no lines are selected, printed or counted
+    const char* clash = !fixed ? "needs -F: it counts literals" : count ? "excludes -c (it counts occurrences per literal, not lines)"
+                        : only ? "excludes -o (it prints counts, not matched text)" : invert ? "excludes -v (an occurrence count has no inverted form)"
+                        : whole_lines ? "excludes -x (it counts occurrences, not whole lines)"
+                        : context_given ? "excludes -A, -B and -C (it prints no lines)"
+                        : !meta.empty() ? "excludes -m (it reads the input in chunks of its own)" : extended ? "excludes -E" : nullptr;
+    if (clash) {
+      std::fprintf(stderr, "xsgrep: --count-each %s\n", clash);
+      return 2;
+    }
+    if (!have_patterns) patterns.push_back(pattern);
+    if (patterns.empty()) {
+      std::fprintf(stderr, "xsgrep: -f: the pattern file holds no pattern\n");
+      return 2;
+    }
+    for (const std::string& p : patterns)
+      if (p.empty() || p.find('\n') != std::string::npos) {
+        std::fprintf(stderr, "xsgrep: --count-each: an empty pattern (or one with a newline) is not served\n");
+        return 2;
+      }
+    const int rc = count_each(patterns, icase, file);
+    std::fflush(stdout);
+    std::_Exit(rc);  // (as at the end of main: the runtime's teardown is left to the kernel)
   }
   bool list = false;
   if (have_patterns) {
@@ -238,31 +339,8 @@ int main(int argc, char** argv) {
       xs::GpuLineSearcher<std::vector<char>> lines(pattern, 0, 1, flags, list);
       xs::GpuMatchSearcher<std::vector<char>> matches(pattern, 0, 1, flags, list);
       xs::GpuCountSearcher<std::vector<char>> counter(pattern, true, 0, 1, flags, list);
-      const size_t target = 16u << 20;
-      std::vector<char> buf;  // bytes read and not searched yet
-      size_t want = target;
       uint64_t total = 0;
-      bool eof = false;
-      for (;;) {
-        while (!eof && buf.size() < want) {
-          const size_t at = buf.size();
-          buf.resize(at + (1u << 20));
-          const size_t got = std::fread(buf.data() + at, 1, 1u << 20, stdin);
-          buf.resize(at + got);
-          if (got == 0) eof = true;
-        }
-        if (buf.empty()) break;
-        size_t cut = buf.size();
-        if (!eof) {  // cut after the last newline; the rest opens the next chunk
-          while (cut > 0 && buf[cut - 1] != '\n') --cut;
-          if (cut == 0) {  // one line longer than the chunk target: keep reading
-            want = buf.size() + target;
-            continue;
-          }
-        }
-        std::vector<char> chunk(buf.begin(), buf.begin() + (ptrdiff_t)cut);
-        buf.erase(buf.begin(), buf.begin() + (ptrdiff_t)cut);
-        want = target;
+      for_each_aligned_chunk(stdin, [&](const std::vector<char>& chunk) {
         if (count) {
           if (auto c = counter(chunk)) total += *c;
         } else if (only) {
@@ -271,7 +349,7 @@ int main(int argc, char** argv) {
         } else if (auto ls = lines(chunk)) {
           for (const auto& l : *ls) std::cout << l << '\n';
         }
-      }
+      });
       if (count) std::cout << total << std::endl;
       return 0;
     }

@@ -1,7 +1,7 @@
 // xsg_host.h -- what the host files of the C ABI share besides the objects of xsg_objects.h: xsg_ctx.cpp (errors,
 // trace, contexts), xsg_pattern.cpp (compilation and upload), xsg_shard.cpp (bindings), xsg_count.cpp (count passes,
-// probe, tuner) and xsg_list.cpp (both list routes and the result accessors).  Everything else in those files is
-// static.  Not installed.
+// probe, tuner), xsg_count_literals.cpp and xsg_litcount.cpp (counts per literal and their host-memory seam) and
+// xsg_list.cpp (both list routes and the result accessors).  Everything else in those files is static.  Not installed.
 #pragma once
 #include "xsg_objects.h"
 
@@ -28,6 +28,11 @@ bool sketch_ready(const xsg_shard* s);                  // the binding holds a s
 void sketch_fields(const xsg_shard* s, ScanArgs* a);    // ScanArgs::sketch, cand_*, gate_grid, sk_* for a->pat's filter window
 int ensure_overlap_check(xsg_shard* s);
 bool overlap_free_known(const xsg_shard* s);
+
+// ---- xsg_count_literals.cpp --------------------------------------------------------------------------------------
+// The pass of xsg_count_literals on `st` for the context's list (the callers checked that it is one): d_counts[j] += the
+// occurrences of literal j in the bound chunks, behind a memset of the words when `zero` (xsg_litcount.cpp accumulates).
+int enqueue_count_literals(xsg_shard* s, hipStream_t st, uint64_t* d_counts, bool zero);
 
 inline const char* const kNonAsciiMsg =
     "the expression uses '.', a negated class or \\D \\W \\S, which match whole code points in RE2; the data holds "

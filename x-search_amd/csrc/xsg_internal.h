@@ -306,6 +306,17 @@ hipError_t launch_set_count(const ScanArgs& a, bool want_nl, hipStream_t s);
 hipError_t launch_set_emit(const ScanArgs& a, hipStream_t s);
 hipError_t launch_set_verify(const RxPreArgs& a, hipStream_t s);
 void describe_set_scan(const ScanArgs& a, bool emit, char* out, size_t cap);
+// k_set_count_literals (xsg_count_literals*): k_set_scan's pass with the verify step inside it, one count per literal.  What
+// it needs beyond ScanArgs travels as a second kernel parameter, so that every other kernel keeps its argument block.  The
+// kernel ADDS to counts[0 .. nlits): the caller zeroes them on the stream in front of the launch, or accumulates.
+struct LitCountArgs {
+  unsigned long long* counts;  // device, one word per literal in listing order
+  uint32_t nlits;              // literals of the list (SetProgram::count)
+  uint32_t idx_off;            // byte offset of SetTable::idx inside PatternDev::d_pat (SetProgram::idx_offset)
+  uint32_t keys_lds;           // the sorted keys are copied into LDS (XSG_LITCOUNT_KEYS=0 is the A/B switch)
+  uint32_t compact;            // a wave's candidates are packed through LDS before they are verified (XSG_LITCOUNT_COMPACT=0: in-lane)
+};
+hipError_t launch_set_count_literals(const ScanArgs& a, const LitCountArgs& c, hipStream_t s);
 // "xsg::k_scan<KIND, WANT_NL, WANT_LINES, EMIT, LOADS, ICASE>" + the stagger launch_scan would use, for reports
 // finishing: the caller's pass is a plain match count that takes the finishing form where scan_finishing says so;
 // spans: that form would run with the binding's span locator (GateFinArgs::spans); waves: and as the wave form

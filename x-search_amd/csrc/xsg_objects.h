@@ -134,6 +134,9 @@ struct xsg_ctx {
   uint64_t aux_serial = 0;  // ... of which pattern_serial
   xsg::PatternDev pat{};
   DevBuf d_pat;
+  // kSet (xsg_set_literals): the literals of the list and where the listing index of every verify-table entry lies in
+  // d_pat (SetProgram::idx_offset) -- what xsg_count_literals needs beyond `pat`
+  uint32_t set_count = 0, set_idx_off = 0;
   // kDfa with a selective start (xsg_regex.h: RegexDfa::prefix): the class-sequence pattern that finds the candidates
   bool rx_pre = false;
   bool rx_pre_forced = false;  // XSG_RX_PRE=1: on shards of any size
@@ -258,6 +261,9 @@ struct xsg_shard {
   // ask for.  Grow-only, sized by the call: not derived from the bound bytes.
   DevBuf d_chunk_counts;
   PinBuf h_chunk_counts;
+  // xsg_count_literals: the synchronous form's word per literal and its pinned mirror
+  DevBuf d_lit_counts;
+  PinBuf h_lit_counts;
   uint64_t list_entries = 0;  // raw entries (ListArgs::M) the last exact list pass left in d_m_chunk / d_keep_pre
   bool begin_sync_result = false;  // xsg_count_begin had to run synchronously: _end hands out begin_counters
   uint64_t begin_counters[XSG_NUM_COUNTERS] = {0, 0, 0, 0};
@@ -292,13 +298,13 @@ struct xsg_shard {
                      &d_f_chunk, &d_out_u64, &d_line_len, &d_line_off, &d_line_bytes, &d_dropped, &d_c_pos, &d_c_chunk, &d_c_len, &d_c_keep,
                      &d_c_pre, &d_tile_mask, &d_tot, &d_hit, &d_scan2, &d_wmask, &d_inv_lo, &d_inv_cnt,
                      &d_inv_off, &d_inv_pos, &d_inv_chunk, &d_m_len, &d_f_len, &d_cx_lo, &d_cx_hi, &d_cx_cnt,
-                     &d_cx_slot, &d_cx_pos, &d_cx_chunk, &d_cx_edge, &d_sketch, &d_spans, &d_chunk_counts};
+                     &d_cx_slot, &d_cx_pos, &d_cx_chunk, &d_cx_edge, &d_sketch, &d_spans, &d_chunk_counts, &d_lit_counts};
     for (DevBuf* b : all) b->release();
     if (h_stage) (void)hipHostFree(h_stage);
     if (h_counters) (void)hipHostFree(h_counters);
     if (h_tot) (void)hipHostFree(h_tot);
     h_tot = nullptr;
-    for (PinBuf* b : {&h_result, &hp_line_len, &hp_line_bytes, &h_chunk_counts}) b->release();
+    for (PinBuf* b : {&h_result, &hp_line_len, &hp_line_bytes, &h_chunk_counts, &h_lit_counts}) b->release();
     if (table_ev) (void)hipEventDestroy(table_ev);
     h_stage = nullptr;
     h_counters = nullptr;

@@ -564,6 +564,8 @@ extern "C" int xsg_set_literals(xsg_ctx* c, const void* list, size_t n, uint32_t
   P.set_g = prog.g;
   P.set_ngrams = (uint32_t)prog.keys.size();
   P.set_keys = off[0], P.set_first = off[1], P.set_ent = off[2], P.set_bytes = off[3];
+  c->set_count = prog.count;
+  c->set_idx_off = prog.idx_offset();
   return XSG_OK;
 }
 

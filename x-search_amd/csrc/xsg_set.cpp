@@ -9,6 +9,8 @@
 
 namespace xsg {
 
+static_assert(XSG_MAX_LITERALS <= 65536, "SetProgram::idx holds listing indices as uint16");
+
 bool compile_literal_set(const uint8_t* list, size_t n, bool icase, SetProgram* out, std::string* err) {
   *out = SetProgram{};
   out->icase = icase;
@@ -55,29 +57,46 @@ bool compile_literal_set(const uint8_t* list, size_t n, bool icase, SetProgram* 
     }
     const Lit& l = lits[by_gram[i].second];
     out->ent.push_back(l.off << 8 | l.len);
+    out->idx.push_back((uint16_t)by_gram[i].second);  // (XSG_MAX_LITERALS <= 65 536)
   }
   out->first.push_back((uint32_t)by_gram.size());
   for (uint32_t w : out->filter) out->filter_bits_set += (uint32_t)__builtin_popcount(w);
   return true;
 }
 
-std::vector<uint8_t> SetProgram::blob(uint32_t off[4]) const {
+// where the arrays lie in the device image: off[0..3] as blob hands them out, off[4] = idx, off[5] = the end
+static void set_layout(const SetProgram& p, uint32_t off[6]) {
   size_t at = kSetFilterBytes;
   auto place = [&](size_t bytes_) {
     const size_t o = at;
     at = (at + bytes_ + 15) & ~(size_t)15;
     return (uint32_t)o;
   };
-  off[0] = place(4 * keys.size());
-  off[1] = place(4 * first.size());
-  off[2] = place(4 * ent.size());
-  off[3] = place(bytes.size());
-  std::vector<uint8_t> b(at + 16, 0);
+  off[0] = place(4 * p.keys.size());
+  off[1] = place(4 * p.first.size());
+  off[2] = place(4 * p.ent.size());
+  off[3] = place(p.bytes.size());
+  off[4] = place(2 * p.idx.size());
+  off[5] = (uint32_t)at;
+}
+
+uint32_t SetProgram::idx_offset() const {
+  uint32_t o[6];
+  set_layout(*this, o);
+  return o[4];
+}
+
+std::vector<uint8_t> SetProgram::blob(uint32_t off[4]) const {
+  uint32_t o[6];
+  set_layout(*this, o);
+  memcpy(off, o, 4 * sizeof(uint32_t));
+  std::vector<uint8_t> b((size_t)o[5] + 16, 0);
   memcpy(b.data(), filter.data(), kSetFilterBytes);
   memcpy(b.data() + off[0], keys.data(), 4 * keys.size());
   memcpy(b.data() + off[1], first.data(), 4 * first.size());
   memcpy(b.data() + off[2], ent.data(), 4 * ent.size());
   memcpy(b.data() + off[3], bytes.data(), bytes.size());
+  memcpy(b.data() + o[4], idx.data(), 2 * idx.size());
   return b;
 }
 

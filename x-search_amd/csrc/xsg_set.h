@@ -49,6 +49,8 @@ XSG_SET_HD bool set_filter_has(const uint32_t* filter, uint32_t v, uint32_t g) {
 //   first[ngrams + 1]  entries of gram k: ent[first[k] .. first[k + 1])
 //   ent[nlits]         (offset of the literal's bytes in `bytes`) << 8 | its length, listing order inside a gram
 //   bytes              the literals back to back (folded under ignore-case)
+//   idx[nlits]         the LISTING index of every entry of `ent`, uint16 (xsg_count_literals: set_count_at; the search
+//                      routes never read it, and a table built without it leaves it null)
 struct SetTable {
   const uint32_t* keys;
   const uint32_t* first;
@@ -56,6 +58,7 @@ struct SetTable {
   const uint8_t* bytes;
   uint32_t ngrams;
   uint32_t g;
+  const uint16_t* idx = nullptr;
 };
 
 // Length of the first-listed literal that occurs at d[p] of a chunk of L bytes, or 0.  p + g <= L is the caller's to
@@ -83,6 +86,39 @@ XSG_SET_HD uint32_t set_verify_at(const SetTable& T, const uint8_t* d, uint64_t 
   return 0u;
 }
 
+// EVERY literal that occurs at d[p] of a chunk of L bytes: visit(listing index) once per literal whose len bytes fit the
+// room L - p and equal the chunk's (folded under icase) -- prefixes, infixes and duplicates of one another included, which
+// is what xsg_count_literals counts.  p + g <= L is the caller's to ensure, as for set_verify_at; nothing at or beyond L is
+// read.  `keys`: T.keys, or a copy of them that is cheaper to reach (the kernel's lies in LDS).
+template <typename Visit>
+XSG_SET_HD void set_count_at(const SetTable& T, const uint8_t* d, uint64_t p, uint64_t L, bool icase, Visit&& visit,
+                             const uint32_t* keys) {
+  const uint32_t v = set_gram_at(d + p, T.g, icase);
+  uint32_t lo = 0, hi = T.ngrams;
+  while (lo < hi) {  // first key >= v
+    const uint32_t mid = (lo + hi) >> 1;
+    if (keys[mid] < v)
+      lo = mid + 1u;
+    else
+      hi = mid;
+  }
+  if (lo == T.ngrams || keys[lo] != v) return;
+  const uint64_t room = L - p;
+  for (uint32_t e = T.first[lo]; e < T.first[lo + 1u]; ++e) {
+    const uint32_t len = T.ent[e] & 0xffu;
+    if (len > room) continue;
+    const uint8_t* lit = T.bytes + (T.ent[e] >> 8);
+    uint32_t k = T.g;
+    while (k < len && set_fold(d[p + k], icase) == lit[k]) ++k;
+    if (k == len) visit((uint32_t)T.idx[e]);
+  }
+}
+
+template <typename Visit>
+XSG_SET_HD void set_count_at(const SetTable& T, const uint8_t* d, uint64_t p, uint64_t L, bool icase, Visit&& visit) {
+  set_count_at(T, d, p, L, icase, visit, T.keys);
+}
+
 // What the host compiles a list into.
 struct SetProgram {
   uint32_t count = 0, min_len = 0, max_len = 0, g = 0, filter_bits_set = 0;
@@ -90,9 +126,14 @@ struct SetProgram {
   std::vector<uint32_t> filter;  // kSetFilterWords
   std::vector<uint32_t> keys, first, ent;
   std::vector<uint8_t> bytes;
-  SetTable table() const { return SetTable{keys.data(), first.data(), ent.data(), bytes.data(), (uint32_t)keys.size(), g}; }
-  // the device image: filter, keys, first, ent, bytes (+ padding); *off receives the byte offsets of the last four
+  std::vector<uint16_t> idx;  // listing index of every entry of `ent`
+  SetTable table() const {
+    return SetTable{keys.data(), first.data(), ent.data(), bytes.data(), (uint32_t)keys.size(), g, idx.data()};
+  }
+  // the device image: filter, keys, first, ent, bytes, idx (+ padding); *off receives the byte offsets of keys, first,
+  // ent and bytes; idx lies behind bytes, at idx_offset()
   std::vector<uint8_t> blob(uint32_t off[4]) const;
+  uint32_t idx_offset() const;
 };
 // Parses `list` (literals separated by '\n', one final '\n' allowed) and compiles it.  False with *err set for: an empty
 // list, an empty literal, more than XSG_MAX_LITERALS literals, a literal over XSG_MAX_LITERAL_BYTES.

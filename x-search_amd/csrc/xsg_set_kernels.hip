@@ -5,6 +5,7 @@
 //   k_set_verify             one lane per candidate: the literals that start with its gram, in listing order, against the
 //                            chunk bytes -> c_len, in k_rx_verify's place; k_rx_heads / k_rx_chains / k_rx_compact and
 //                            the shared list pipeline take over from there (xsg_list.cpp: prefilter_candidates).
+//   k_set_count_literals     xsg_count_literals: the scan with the verify step inside its own pass, one count per literal
 #include "xsg_devutil.h"
 #include "xsg_set.h"
 
@@ -188,6 +189,144 @@ __global__ __launch_bounds__(kBlock) void k_set_verify(const RxPreArgs A) {
   A.c_len[i] = p + T.g <= ch.length ? set_verify_at(T, A.base + ch.offset, p, ch.length, P.icase != 0) : 0u;
 }
 
+// ---- xsg_count_literals: one count per literal, the verify step inside the candidate scan's own pass ---------------------------
+// k_set_scan<false, ICASE>'s tile loop, loads, fold and candidate masks as they are (copied, not factored out: the
+// existing instantiations keep their code byte for byte).  Instead of summing popc, every candidate bit is decided
+// here: set_count_at looks the gram up and compares EVERY literal under it; each one that fits the room and compares
+// equal adds 1 to its word of a workgroup histogram in LDS.  No candidate list, no size leaves the device; behind its
+// grid-stride loop the workgroup adds its non-zero words to LitCountArgs::counts with 64-bit atomics.
+//   KEYS_LDS  the sorted keys (at most 16 KiB) are copied into LDS once per workgroup: the binary search, up to 12
+//             dependent loads per candidate, stays out of global memory
+//   COMPACT   a wave's candidates of one wave-load are first packed into a queue in LDS, so that all 64 lanes verify;
+//             otherwise a lane verifies the bits of its own unit as it finds them
+// Dynamic LDS: the histogram (nlits words, at most 16 KiB), then the keys, then the queues.
+// A histogram word cannot wrap: it counts positions at which ITS literal occurs, at most one per position the workgroup
+// looks at, and a workgroup looks at no more than ceil(ntiles / grid) tiles of 16 Ki positions -- the launcher keeps that
+// quotient below 2^18, so a word stays below 2^32.
+constexpr uint32_t kLitQueue = kWaveLoad;  // candidates of one wave-load: 64 lanes x 16 positions
+
+__host__ __device__ constexpr uint32_t lit_round4(uint32_t n) { return (n + 3u) & ~3u; }
+
+template <bool ICASE, bool KEYS_LDS, bool COMPACT>
+__global__ __launch_bounds__(kBlock) void k_set_count_literals(const ScanArgs A, const LitCountArgs C) {
+  __shared__ __attribute__((aligned(16))) uint32_t s_filter[kSetFilterWords];
+  extern __shared__ __attribute__((aligned(16))) uint32_t s_lit[];
+  const PatternDev P = A.pat;
+  const uint32_t tid = threadIdx.x;
+  const uint32_t lane = tid & 63u;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  uint32_t* const s_hist = s_lit;
+  uint32_t* const s_keys = s_lit + lit_round4(C.nlits);
+  uint16_t* const s_queue =
+      reinterpret_cast<uint16_t*>(s_keys + (KEYS_LDS ? lit_round4(P.set_ngrams) : 0u)) + (size_t)wave * kLitQueue;
+  {
+    const uint4* src = reinterpret_cast<const uint4*>(P.d_pat);
+    uint4* dst = reinterpret_cast<uint4*>(s_filter);
+    for (uint32_t k = tid; k < kSetFilterBytes / 16u; k += kBlock) dst[k] = src[k];
+    for (uint32_t k = tid; k < C.nlits; k += kBlock) s_hist[k] = 0u;
+    if (KEYS_LDS) {
+      const uint32_t* keys = reinterpret_cast<const uint32_t*>(P.d_pat + P.set_keys);
+      for (uint32_t k = tid; k < P.set_ngrams; k += kBlock) s_keys[k] = keys[k];
+    }
+  }
+  __syncthreads();
+  const uint32_t g = P.set_g;
+  SetTable T;
+  T.keys = reinterpret_cast<const uint32_t*>(P.d_pat + P.set_keys);
+  T.first = reinterpret_cast<const uint32_t*>(P.d_pat + P.set_first);
+  T.ent = reinterpret_cast<const uint32_t*>(P.d_pat + P.set_ent);
+  T.bytes = P.d_pat + P.set_bytes;
+  T.ngrams = P.set_ngrams;
+  T.g = g;
+  T.idx = reinterpret_cast<const uint16_t*>(P.d_pat + C.idx_off);
+  auto hit = [&](uint32_t i) { atomicAdd(&s_hist[i], 1u); };
+
+  for (uint64_t tile = blockIdx.x; tile < A.ntiles; tile += gridDim.x) {
+    const uint32_t c = A.tile_chunk ? A.tile_chunk[tile] : 0u;
+    const ChunkDev ch = A.chunks[c];
+    const uint8_t* cbase = A.base + ch.offset;
+    const uint64_t L = ch.length;
+    const uint64_t Lr = (L + 15u) & ~(uint64_t)15u;
+    // as in k_set_scan: a candidate's whole gram lies inside the chunk, p + g <= L; no bit at or beyond `limit` survives
+    const uint64_t limit = L >= g ? L - g + 1u : 0u;
+    const uint64_t toff = (tile - A.chunk_tile0[c]) * (uint64_t)kSetTile;
+    const uint64_t wbase = toff + (uint64_t)wave * kSetWaveSpan;
+
+    uint4 u[kSetLoads];
+#pragma unroll
+    for (int j = 0; j < kSetLoads; ++j) {
+      const uint64_t off = wbase + (uint64_t)j * kWaveLoad + (uint64_t)lane * kUnit;
+      u[j] = off < Lr ? *reinterpret_cast<const uint4*>(cbase + off) : uint4{0u, 0u, 0u, 0u};
+    }
+    const uint64_t behind = wbase + kSetWaveSpan;
+    const uint32_t edge_last = behind < Lr ? *reinterpret_cast<const uint32_t*>(cbase + behind) : 0u;
+
+    uint32_t masks[kSetLoads];
+#pragma unroll
+    for (int j = 0; j < kSetLoads; ++j) {
+      uint32_t w[5] = {u[j].x, u[j].y, u[j].z, u[j].w, 0u};
+      const uint32_t edge = j + 1 < kSetLoads ? (uint32_t)__builtin_amdgcn_readfirstlane((int)u[j + 1 < kSetLoads ? j + 1 : j].x) : edge_last;
+      w[4] = from_next_lane(w[0], edge, lane);
+      if (ICASE) {
+#pragma unroll
+        for (int q = 0; q < 5; ++q) w[q] = set_fold4(w[q]);
+      }
+      uint32_t m;
+      switch (g) {  // (wave-uniform)
+        case 1: m = set_cand16<1>(w, s_filter); break;
+        case 2: m = set_cand16<2>(w, s_filter); break;
+        case 3: m = set_cand16<3>(w, s_filter); break;
+        default: m = set_cand16<4>(w, s_filter); break;
+      }
+      const uint64_t unit_off = wbase + (uint64_t)j * kWaveLoad + (uint64_t)lane * kUnit;
+      if (unit_off >= limit)
+        m = 0u;
+      else if (unit_off + kUnit > limit)
+        m &= (1u << (uint32_t)(limit - unit_off)) - 1u;
+      masks[j] = m;
+    }
+
+    // ---- verify: every candidate, every literal under its gram (the bytes were just loaded: these reads hit the caches)
+#pragma unroll
+    for (int j = 0; j < kSetLoads; ++j) {
+      uint32_t m = masks[j];
+      const uint64_t load_off = wbase + (uint64_t)j * kWaveLoad;
+      if (!COMPACT) {
+        while (m) {
+          const uint32_t b = (uint32_t)__ffs((int)m) - 1u;
+          m &= m - 1u;
+          set_count_at(T, cbase, load_off + (uint64_t)lane * kUnit + b, L, ICASE, hit, KEYS_LDS ? s_keys : T.keys);
+        }
+      } else {
+        const uint32_t pc = (uint32_t)__popc(m);
+        const uint32_t incl = wave_incl_scan_u32(pc, lane);
+        const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+        if (total == 0u) continue;  // (wave-uniform)
+        uint32_t r = incl - pc;
+        while (m) {
+          const uint32_t b = (uint32_t)__ffs((int)m) - 1u;
+          m &= m - 1u;
+          s_queue[r++] = (uint16_t)(lane * kUnit + b);
+        }
+        // the queue belongs to this wave alone: a wavefront-scope release/acquire orders its lanes' LDS accesses
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        for (uint32_t i = lane; i < total; i += 64u)
+          set_count_at(T, cbase, load_off + s_queue[i], L, ICASE, hit, KEYS_LDS ? s_keys : T.keys);
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();  // the next wave-load refills the queue
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      }
+    }
+  }
+  __syncthreads();
+  for (uint32_t k = tid; k < C.nlits; k += kBlock) {
+    const uint32_t v = s_hist[k];
+    if (v) atomicAdd(&C.counts[k], (unsigned long long)v);
+  }
+}
+
 static unsigned set_grid(const ScanArgs& a) {
   static const unsigned cus = [] {
     int dev = 0, n = 0;
@@ -222,6 +361,31 @@ hipError_t launch_set_emit(const ScanArgs& a, hipStream_t s) {
 
 hipError_t launch_set_verify(const RxPreArgs& a, hipStream_t s) {
   if (a.n) hipLaunchKernelGGL(k_set_verify, dim3((unsigned)((a.n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, a);
+  return hipGetLastError();
+}
+
+template <bool ICASE, bool KEYS_LDS>
+static void launch_lit(const ScanArgs& a, const LitCountArgs& c, dim3 grid, size_t lds, hipStream_t s) {
+  if (c.compact)
+    hipLaunchKernelGGL((k_set_count_literals<ICASE, KEYS_LDS, true>), grid, dim3(kBlock), lds, s, a, c);
+  else
+    hipLaunchKernelGGL((k_set_count_literals<ICASE, KEYS_LDS, false>), grid, dim3(kBlock), lds, s, a, c);
+}
+
+hipError_t launch_set_count_literals(const ScanArgs& a, const LitCountArgs& c, hipStream_t s) {
+  if (a.ntiles == 0) return hipSuccess;
+  if (a.tile_bytes != kSetTile || a.pat.set_g < 1 || a.pat.set_g > 4 || !c.counts || c.nlits == 0 || c.nlits > XSG_MAX_LITERALS ||
+      a.pat.set_ngrams > XSG_MAX_LITERALS)
+    return hipErrorInvalidValue;
+  // (a histogram word stays below 2^32: fewer than 2^18 tiles per workgroup, see the kernel)
+  const uint64_t per = (1u << 18) - 1u;
+  const dim3 grid((unsigned)std::max<uint64_t>(set_grid(a), (a.ntiles + per - 1u) / per));
+  const size_t lds = 4u * (size_t)lit_round4(c.nlits) + (c.keys_lds ? 4u * (size_t)lit_round4(a.pat.set_ngrams) : 0u) +
+                     (c.compact ? 2u * (size_t)kLitQueue * kWaves : 0u);
+  if (a.pat.icase)
+    c.keys_lds ? launch_lit<true, true>(a, c, grid, lds, s) : launch_lit<true, false>(a, c, grid, lds, s);
+  else
+    c.keys_lds ? launch_lit<false, true>(a, c, grid, lds, s) : launch_lit<false, false>(a, c, grid, lds, s);
   return hipGetLastError();
 }
 

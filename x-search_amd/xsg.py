@@ -141,6 +141,12 @@ def load():
         "xsg_count": (ci, [vp, u32, _u64p]),
         "xsg_count_chunks": (ci, [vp, u32, vp, vp, u64, vp]),
         "xsg_count_chunks_async": (ci, [vp, u32, vp, vp, vp, u64, vp, vp]),
+        "xsg_count_literals": (ci, [vp, vp, u64]),
+        "xsg_count_literals_async": (ci, [vp, vp, vp, u64]),
+        "xsg_literal_counter_create": (ci, [ci, C.c_char_p, sz, u32, C.POINTER(vp)]),
+        "xsg_literal_counter_add": (ci, [vp, vp, u64]),
+        "xsg_literal_counter_get": (ci, [vp, vp, u64, _u64p]),
+        "xsg_literal_counter_destroy": (None, [vp]),
         "xsg_count_begin": (ci, [vp, u32]),
         "xsg_count_end": (ci, [vp, _u64p]),
         "xsg_search": (ci, [vp, u32, _u64p]),
@@ -209,7 +215,9 @@ EXPORTS = ["xsg_abi_version", "xsg_strerror", "xsg_last_error", "xsg_device_coun
            "xsg_jobs_reduce_total", "xsg_device_numa", "xsg_regex_info", "xsg_regex_dfa_info", "xsg_regex_prefix", "xsg_regex_factor",
            "xsg_result_u64_view", "xsg_shard_invalidate", "xsg_result_lines_view", "xsg_count_async_status", "xsg_codec_name",
            "xsg_host_matches", "xsg_result_context_edges", "xsg_set_literals", "xsg_literals_info",
-           "xsg_host_searcher_create_list", "xsg_count_chunks", "xsg_count_chunks_async"]
+           "xsg_host_searcher_create_list", "xsg_count_chunks", "xsg_count_chunks_async", "xsg_count_literals",
+           "xsg_count_literals_async", "xsg_literal_counter_create", "xsg_literal_counter_add", "xsg_literal_counter_get",
+           "xsg_literal_counter_destroy"]
 
 
 def _check(rc):
@@ -333,6 +341,7 @@ class Context:
         _check(self._lib.xsg_ctx_create(device, C.byref(h)))
         self.h = h
         self.device = device
+        self.nliterals = 0  # literals of the list set_literals put in place; 0: the pattern is no list
         # The C ABI wants shards and communicators destroyed before their context.  Python finalises the members
         # of a reference cycle in no particular order (e.g. everything a caught exception's traceback keeps
         # alive), so the context closes whatever is still open on it first; closing twice is harmless.
@@ -359,11 +368,14 @@ class Context:
             pass
 
     def set_pattern(self, pattern: bytes, flags: int = 0):
+        self.nliterals = 0
         _check(self._lib.xsg_set_pattern(self.h, pattern, len(pattern), flags))
 
     def set_literals(self, lst: bytes, flags: int = 0):
         """a list of literals separated by '\\n' as the pattern (xsg_set_literals; literal_list() joins one)"""
+        self.nliterals = 0
         _check(self._lib.xsg_set_literals(self.h, lst, len(lst), flags))
+        self.nliterals = literals_info(lst, flags)["count"]  # what Shard.count_literals sizes its result by
 
     def info(self):
         arch = C.create_string_buffer(128)
@@ -446,6 +458,18 @@ class Shard:
         _check(self._lib.xsg_count_chunks_async(self.h, mode, C.c_void_p(stream), C.c_void_p(d_counts),
                                                 C.c_void_p(d_newlines) if d_newlines else None, cap, C.c_void_p(d_counters),
                                                 C.c_void_p(d_status)))
+
+    def count_literals(self) -> np.ndarray:
+        """one count per literal of the context's list, in listing order (xsg_count_literals): occurrences in the bound
+        chunks -- overlapping ones, covered ones and duplicates of the list included"""
+        k = self.ctx.nliterals
+        out = np.zeros(k if k else MAX_LITERALS, dtype=np.uint64)  # (no list: the library says what is wrong)
+        _check(self._lib.xsg_count_literals(self.h, C.c_void_p(out.ctypes.data), out.size))
+        return out[:k]
+
+    def count_literals_async(self, stream: int, d_counts: int, cap: int):
+        """the stream-ordered form (xsg_count_literals_async): d_counts is a device address of `cap` uint64 words"""
+        _check(self._lib.xsg_count_literals_async(self.h, C.c_void_p(stream), C.c_void_p(d_counts) if d_counts else None, cap))
 
     def count_begin(self, mode: int):
         _check(self._lib.xsg_count_begin(self.h, mode))
@@ -534,6 +558,42 @@ class Shard:
         ms = C.c_float(0)
         _check(self._lib.xsg_time_scan_kernel(self.h, mode, iters, C.byref(ms)))
         return ms.value
+
+
+class LiteralCounter:
+    """Counts per literal over chunks in host memory, accumulated (xsg_literal_counter_*): add() the newline-aligned
+    chunks of a file, get() its table."""
+
+    def __init__(self, device: int, lst: bytes, flags: int = 0):
+        self._lib = load()
+        self.h = None
+        self.k = literals_info(lst, flags)["count"]
+        h = C.c_void_p()
+        _check(self._lib.xsg_literal_counter_create(device, lst, len(lst), flags, C.byref(h)))
+        self.h = h
+
+    def add(self, data):
+        """one chunk: bytes, or a contiguous uint8 array"""
+        a = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, dtype=np.uint8)
+        _check(self._lib.xsg_literal_counter_add(self.h, C.c_void_p(a.ctypes.data) if a.size else None, a.size))
+
+    def get(self):
+        """-> (counts per literal so far, bytes added so far); waits for what is in flight"""
+        out = np.zeros(self.k, dtype=np.uint64)
+        n = C.c_uint64(0)
+        _check(self._lib.xsg_literal_counter_get(self.h, C.c_void_p(out.ctypes.data), self.k, C.byref(n)))
+        return out, int(n.value)
+
+    def close(self):
+        if self.h:
+            self._lib.xsg_literal_counter_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 COMM_ID_BYTES = 128
