@@ -41,7 +41,8 @@ extern "C" {
  * XSG_FLAG_CONTEXT and xsg_result_context_edges joined; xsg_set_literals, xsg_literals_info, xsg_host_searcher_create_list
  * and xsg_job_opts.pattern_is_list joined (the structure grew: see there for what that asks of a program built before);
  * xsg_count_chunks and xsg_count_chunks_async joined; xsg_count_literals, xsg_count_literals_async and xsg_literal_counter_*
- * joined; no entry point was removed or changed in meaning */
+ * joined; xsg_count_literals_chunks, xsg_count_literals_chunks_async and xsg_literals_chunks_touched_capacity joined; no
+ * entry point was removed or changed in meaning */
 #define XSG_ABI_VERSION 4
 
 /* ---- status codes ------------------------------------------------------- */
@@ -487,6 +488,38 @@ int xsg_count_literals(xsg_shard* shard, uint64_t* counts, uint64_t cap_literals
 /* Stream-ordered form: d_counts is DEVICE memory (cap_literals words), overwritten; nothing waits and nothing is fetched.
  * Unlike the other stream-ordered counts of a list (XSG_ENOTSUP there) this one needs no size from the device. */
 int xsg_count_literals_async(xsg_shard* shard, void* stream, uint64_t* d_counts, uint64_t cap_literals);
+
+/* ---- counts per chunk and literal -------------------------------------------- */
+/* Both axes at once: a term-document matrix, the keyword table of every bound chunk from ONE pass.  Let k be the number
+ * of literals xsg_set_literals parsed and n the number of bound chunks.  counts[c * k + j], row-major by chunk, is what
+ * xsg_count_literals would put into counts[j] for a binding that holds chunk c alone: the same pattern, flags, definition
+ * of an occurrence (overlapping ones, covered ones and duplicates of the list all count) and ignore-case folding, and
+ * again no byte at or beyond a chunk's end decides anything.  Hence, for every j,
+ *     sum over c of counts[c * k + j]  ==  xsg_count_literals' counts[j] on the same binding.
+ * chunks_with (optional, NULL: not wanted; cap_literals >= k): chunks_with[j] = the number of chunks c with
+ * counts[c * k + j] > 0, the literal's document frequency; duplicates in the list get the same number each.
+ * Every one of the n * k words is written, zeros included, and every chunks_with[j]; a chunk of length 0 yields a row of
+ * zeros; a binding of 0 chunks is XSG_OK, writes nothing to counts and k zeros to chunks_with.  Words behind n * k and
+ * behind k are not touched.
+ * XSG_ESTATE: the ctx holds no pattern.  XSG_ENOTSUP: the pattern is no list set by xsg_set_literals; XSG_FLAG_INVERT is
+ * set; a binding of 2^24 chunks or more.  XSG_EINVAL: counts == NULL, cap_words < n * k, chunks_with != NULL with
+ * cap_literals < k.  The CONTEXT bits and XSG_FLAG_EXACT_TAIL are accepted and ignored.
+ * The matrix is DENSE: n * k words whatever they hold.  A sparse result (COO / CSR) is not offered.
+ * One launch behind the memsets of both results (k_set_count_literals_chunks): a workgroup owns a contiguous range of
+ * tiles, keeps one histogram in LDS and adds it to row c with 64-bit atomics whenever the next tile belongs to another
+ * chunk; an add that finds its word 0 is the chunk's first for that literal and counts 1 for chunks_with[j] (exact: every
+ * addend is positive, so a word leaves 0 once).  No candidate list, no size fetched from the device.
+ * The synchronous form keeps the matrix in device memory of the shard's and a pinned mirror: a matrix of more than 2^28
+ * words (2 GiB) is XSG_ENOTSUP there -- the stream-ordered form, whose memory is the caller's, has no such limit. */
+int xsg_count_literals_chunks(xsg_shard* shard, uint64_t* counts, uint64_t cap_words,
+                              uint64_t* chunks_with, uint64_t cap_literals);               /* host memory; waits */
+/* Stream-ordered form: d_counts (cap_words words) and d_chunks_with (cap_literals words, or NULL) are DEVICE memory,
+ * overwritten; nothing waits and nothing is fetched. */
+int xsg_count_literals_chunks_async(xsg_shard* shard, void* stream, uint64_t* d_counts, uint64_t cap_words,
+                                    uint64_t* d_chunks_with, uint64_t cap_literals);       /* device memory; nothing waits */
+/* The literals a workgroup of that pass can note between two flushes before a flush sweeps its whole histogram instead
+ * of walking the noted ones (results do not depend on it; tests place their lists around it). */
+uint32_t xsg_literals_chunks_touched_capacity(void);
 
 /* ---- list results (replace byte_offsets_match/_line, line; :136-154,187-207) */
 /* Runs the search for one of the list modes on the ctx stream and waits.

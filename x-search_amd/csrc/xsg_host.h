@@ -33,6 +33,9 @@ bool overlap_free_known(const xsg_shard* s);
 // The pass of xsg_count_literals on `st` for the context's list (the callers checked that it is one): d_counts[j] += the
 // occurrences of literal j in the bound chunks, behind a memset of the words when `zero` (xsg_litcount.cpp accumulates).
 int enqueue_count_literals(xsg_shard* s, hipStream_t st, uint64_t* d_counts, bool zero);
+// The pass of xsg_count_literals_chunks on `st`: both results zeroed on the stream, then one launch.  d_counts: chunks x
+// literals words, d_chunks_with: a word per literal or null.
+int enqueue_count_literals_chunks(xsg_shard* s, hipStream_t st, uint64_t* d_counts, uint64_t* d_chunks_with);
 
 inline const char* const kNonAsciiMsg =
     "the expression uses '.', a negated class or \\D \\W \\S, which match whole code points in RE2; the data holds "

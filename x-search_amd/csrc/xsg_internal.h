@@ -317,6 +317,19 @@ struct LitCountArgs {
   uint32_t compact;            // a wave's candidates are packed through LDS before they are verified (XSG_LITCOUNT_COMPACT=0: in-lane)
 };
 hipError_t launch_set_count_literals(const ScanArgs& a, const LitCountArgs& c, hipStream_t s);
+// k_set_count_literals_chunks (xsg_count_literals_chunks*): the same pass with the chunk boundaries kept.  The kernel ADDS
+// to counts[c * nlits + j] and, where a word leaves 0, 1 to chunks_with[j]: the caller zeroes both on the stream in front
+// of the launch.  forced_grid: XSG_LITMATRIX_GRID, 0 when unset (xsg_litmatrix.h: litmatrix_grid).
+struct LitMatrixArgs {
+  unsigned long long* counts;       // device, nchunks x nlits words, row-major by chunk
+  unsigned long long* chunks_with;  // device, one word per literal, or null: not wanted
+  uint32_t nlits;                   // literals of the list (SetProgram::count)
+  uint32_t idx_off;                 // byte offset of SetTable::idx inside PatternDev::d_pat
+  uint32_t keys_lds;                // the sorted keys are copied into LDS (XSG_LITCOUNT_KEYS=0 is the A/B switch)
+  uint32_t touched;                 // the flush walks the touched list (XSG_LITMATRIX_TOUCHED=0: it always sweeps)
+};
+hipError_t launch_set_count_literals_chunks(const ScanArgs& a, const LitMatrixArgs& c, uint32_t forced_grid, hipStream_t s);
+unsigned set_litmatrix_grid(const ScanArgs& a, uint32_t forced);  // the workgroups that launch would use
 // "xsg::k_scan<KIND, WANT_NL, WANT_LINES, EMIT, LOADS, ICASE>" + the stagger launch_scan would use, for reports
 // finishing: the caller's pass is a plain match count that takes the finishing form where scan_finishing says so;
 // spans: that form would run with the binding's span locator (GateFinArgs::spans); waves: and as the wave form

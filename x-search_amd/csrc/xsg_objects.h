@@ -264,6 +264,10 @@ struct xsg_shard {
   // xsg_count_literals: the synchronous form's word per literal and its pinned mirror
   DevBuf d_lit_counts;
   PinBuf h_lit_counts;
+  // xsg_count_literals_chunks: the synchronous form's matrix (chunks x literals words, the literals' chunks_with behind
+  // them) and its pinned mirror.  Grow-only, sized by the call.
+  DevBuf d_lit_matrix;
+  PinBuf h_lit_matrix;
   uint64_t list_entries = 0;  // raw entries (ListArgs::M) the last exact list pass left in d_m_chunk / d_keep_pre
   bool begin_sync_result = false;  // xsg_count_begin had to run synchronously: _end hands out begin_counters
   uint64_t begin_counters[XSG_NUM_COUNTERS] = {0, 0, 0, 0};
@@ -298,13 +302,14 @@ struct xsg_shard {
                      &d_f_chunk, &d_out_u64, &d_line_len, &d_line_off, &d_line_bytes, &d_dropped, &d_c_pos, &d_c_chunk, &d_c_len, &d_c_keep,
                      &d_c_pre, &d_tile_mask, &d_tot, &d_hit, &d_scan2, &d_wmask, &d_inv_lo, &d_inv_cnt,
                      &d_inv_off, &d_inv_pos, &d_inv_chunk, &d_m_len, &d_f_len, &d_cx_lo, &d_cx_hi, &d_cx_cnt,
-                     &d_cx_slot, &d_cx_pos, &d_cx_chunk, &d_cx_edge, &d_sketch, &d_spans, &d_chunk_counts, &d_lit_counts};
+                     &d_cx_slot, &d_cx_pos, &d_cx_chunk, &d_cx_edge, &d_sketch, &d_spans, &d_chunk_counts, &d_lit_counts,
+                     &d_lit_matrix};
     for (DevBuf* b : all) b->release();
     if (h_stage) (void)hipHostFree(h_stage);
     if (h_counters) (void)hipHostFree(h_counters);
     if (h_tot) (void)hipHostFree(h_tot);
     h_tot = nullptr;
-    for (PinBuf* b : {&h_result, &hp_line_len, &hp_line_bytes, &h_chunk_counts, &h_lit_counts}) b->release();
+    for (PinBuf* b : {&h_result, &hp_line_len, &hp_line_bytes, &h_chunk_counts, &h_lit_counts, &h_lit_matrix}) b->release();
     if (table_ev) (void)hipEventDestroy(table_ev);
     h_stage = nullptr;
     h_counters = nullptr;

@@ -6,7 +6,10 @@
 //                            chunk bytes -> c_len, in k_rx_verify's place; k_rx_heads / k_rx_chains / k_rx_compact and
 //                            the shared list pipeline take over from there (xsg_list.cpp: prefilter_candidates).
 //   k_set_count_literals     xsg_count_literals: the scan with the verify step inside its own pass, one count per literal
+//   k_set_count_literals_chunks   xsg_count_literals_chunks: the same pass with the chunk boundaries kept, a count per
+//                            chunk and literal and the number of chunks that hold each literal
 #include "xsg_devutil.h"
+#include "xsg_litmatrix.h"
 #include "xsg_set.h"
 
 namespace xsg {
@@ -327,6 +330,187 @@ __global__ __launch_bounds__(kBlock) void k_set_count_literals(const ScanArgs A,
   }
 }
 
+// ---- xsg_count_literals_chunks: a count per chunk AND literal -------------------------------------------------------------------
+// k_set_count_literals' tile loop in its default form -- candidates compacted through the per-wave queue -- with the chunk
+// boundaries kept (copied again, not factored out: the instantiations above keep their code).  What differs:
+//   PARTITION  a workgroup owns a CONTIGUOUS range of tiles (xsg_litmatrix.h), not a grid stride: tiles ascend by chunk, so
+//              the histogram in LDS always belongs to ONE chunk, and the workgroup meets each boundary in its range once.
+//   FLUSH      when the next tile belongs to another chunk, and behind the last tile: barrier, the non-zero words are added
+//              to row c of the matrix (64-bit atomics: neighbouring workgroups may share a chunk) and zeroed, barrier.  All
+//              four waves work on the same tile, so the decision is workgroup-uniform.
+//   TOUCHED    with documents of a few KiB every tile is a boundary, and a sweep of the histogram would cost O(literals)
+//              per tile.  hit() therefore notes a literal whose word it moved from 0 in a list of kLitTouched uint16
+//              through a counter in LDS; the flush walks the list, or sweeps all words when more literals were hit than
+//              the list holds.  The counter is never reset: it runs on, and `t_base`, its value at the last flush, is
+//              subtracted -- every lane reads the same word between the flush's two barriers, where nobody adds to it.
+//              (It grows by at most nlits per flush and a workgroup flushes fewer than 2^18 times: no wrap.)
+//   FREQUENCY  an add that finds the matrix word 0 is the first that chunk gets for that literal -- every addend is
+//              positive, so a word leaves 0 exactly once -- and adds 1 to chunks_with[j]: exact, no second pass.  For a
+//              list of at most kLitWithLds literals the workgroup sums these ones in LDS and adds them behind its last
+//              tile: the few words of a short list, added to by every chunk, serialise in the L2 otherwise.
+// Dynamic LDS: the histogram, the keys (KEYS_LDS), the queues, the touched list, chunks_with's sums (short lists).
+template <bool ICASE, bool KEYS_LDS>
+__global__ __launch_bounds__(kBlock) void k_set_count_literals_chunks(const ScanArgs A, const LitMatrixArgs C) {
+  __shared__ __attribute__((aligned(16))) uint32_t s_filter[kSetFilterWords];
+  __shared__ uint32_t s_ntouched;
+  extern __shared__ __attribute__((aligned(16))) uint32_t s_lit[];
+  const PatternDev P = A.pat;
+  const uint32_t tid = threadIdx.x;
+  const uint32_t lane = tid & 63u;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  uint32_t* const s_hist = s_lit;
+  uint32_t* const s_keys = s_lit + lit_round4(C.nlits);
+  uint16_t* const s_queues = reinterpret_cast<uint16_t*>(s_keys + (KEYS_LDS ? lit_round4(P.set_ngrams) : 0u));
+  uint16_t* const s_queue = s_queues + (size_t)wave * kLitQueue;
+  uint16_t* const s_touched = s_queues + (size_t)kWaves * kLitQueue;
+  uint32_t* const s_with = reinterpret_cast<uint32_t*>(s_touched + kLitTouched);
+  const bool with_lds = C.chunks_with && C.nlits <= kLitWithLds;  // (the launcher sized the LDS by the same rule)
+  {
+    const uint4* src = reinterpret_cast<const uint4*>(P.d_pat);
+    uint4* dst = reinterpret_cast<uint4*>(s_filter);
+    for (uint32_t k = tid; k < kSetFilterBytes / 16u; k += kBlock) dst[k] = src[k];
+    for (uint32_t k = tid; k < C.nlits; k += kBlock) s_hist[k] = 0u;
+    if (KEYS_LDS) {
+      const uint32_t* keys = reinterpret_cast<const uint32_t*>(P.d_pat + P.set_keys);
+      for (uint32_t k = tid; k < P.set_ngrams; k += kBlock) s_keys[k] = keys[k];
+    }
+    if (with_lds)
+      for (uint32_t k = tid; k < C.nlits; k += kBlock) s_with[k] = 0u;
+    if (tid == 0) s_ntouched = 0u;
+  }
+  __syncthreads();
+  const uint32_t g = P.set_g;
+  SetTable T;
+  T.keys = reinterpret_cast<const uint32_t*>(P.d_pat + P.set_keys);
+  T.first = reinterpret_cast<const uint32_t*>(P.d_pat + P.set_first);
+  T.ent = reinterpret_cast<const uint32_t*>(P.d_pat + P.set_ent);
+  T.bytes = P.d_pat + P.set_bytes;
+  T.ngrams = P.set_ngrams;
+  T.g = g;
+  T.idx = reinterpret_cast<const uint16_t*>(P.d_pat + C.idx_off);
+  const bool listed = C.touched != 0u;  // (XSG_LITMATRIX_TOUCHED=0, the A/B switch: every flush sweeps)
+  uint32_t t_base = 0u;
+  auto hit = [&](uint32_t i) {
+    if (!listed) {
+      atomicAdd(&s_hist[i], 1u);
+    } else if (atomicAdd(&s_hist[i], 1u) == 0u) {
+      const uint32_t slot = atomicAdd(&s_ntouched, 1u) - t_base;
+      if (slot < kLitTouched) s_touched[slot] = (uint16_t)i;
+    }
+  };
+
+  const uint64_t per = litmatrix_per(A.ntiles, gridDim.x);
+  const uint64_t tile_end = litmatrix_last(blockIdx.x, per, A.ntiles);
+  for (uint64_t tile = litmatrix_first(blockIdx.x, per, A.ntiles); tile < tile_end; ++tile) {
+    const uint32_t c = A.tile_chunk ? A.tile_chunk[tile] : 0u;
+    // (workgroup-uniform) the histogram is flushed behind this tile
+    const bool boundary = tile + 1u == tile_end || (A.tile_chunk && A.tile_chunk[tile + 1u] != c);
+    const ChunkDev ch = A.chunks[c];
+    const uint8_t* cbase = A.base + ch.offset;
+    const uint64_t L = ch.length;
+    const uint64_t Lr = (L + 15u) & ~(uint64_t)15u;
+    // as in k_set_scan: a candidate's whole gram lies inside the chunk, p + g <= L; no bit at or beyond `limit` survives
+    const uint64_t limit = L >= g ? L - g + 1u : 0u;
+    const uint64_t toff = (tile - A.chunk_tile0[c]) * (uint64_t)kSetTile;
+    const uint64_t wbase = toff + (uint64_t)wave * kSetWaveSpan;
+
+    uint4 u[kSetLoads];
+#pragma unroll
+    for (int j = 0; j < kSetLoads; ++j) {
+      const uint64_t off = wbase + (uint64_t)j * kWaveLoad + (uint64_t)lane * kUnit;
+      u[j] = off < Lr ? *reinterpret_cast<const uint4*>(cbase + off) : uint4{0u, 0u, 0u, 0u};
+    }
+    const uint64_t behind = wbase + kSetWaveSpan;
+    const uint32_t edge_last = behind < Lr ? *reinterpret_cast<const uint32_t*>(cbase + behind) : 0u;
+
+    uint32_t masks[kSetLoads];
+#pragma unroll
+    for (int j = 0; j < kSetLoads; ++j) {
+      uint32_t w[5] = {u[j].x, u[j].y, u[j].z, u[j].w, 0u};
+      const uint32_t edge = j + 1 < kSetLoads ? (uint32_t)__builtin_amdgcn_readfirstlane((int)u[j + 1 < kSetLoads ? j + 1 : j].x) : edge_last;
+      w[4] = from_next_lane(w[0], edge, lane);
+      if (ICASE) {
+#pragma unroll
+        for (int q = 0; q < 5; ++q) w[q] = set_fold4(w[q]);
+      }
+      uint32_t m;
+      switch (g) {  // (wave-uniform)
+        case 1: m = set_cand16<1>(w, s_filter); break;
+        case 2: m = set_cand16<2>(w, s_filter); break;
+        case 3: m = set_cand16<3>(w, s_filter); break;
+        default: m = set_cand16<4>(w, s_filter); break;
+      }
+      const uint64_t unit_off = wbase + (uint64_t)j * kWaveLoad + (uint64_t)lane * kUnit;
+      if (unit_off >= limit)
+        m = 0u;
+      else if (unit_off + kUnit > limit)
+        m &= (1u << (uint32_t)(limit - unit_off)) - 1u;
+      masks[j] = m;
+    }
+
+    // ---- verify: a wave-load's candidates packed into the wave's queue, then every lane decides one
+#pragma unroll
+    for (int j = 0; j < kSetLoads; ++j) {
+      uint32_t m = masks[j];
+      const uint64_t load_off = wbase + (uint64_t)j * kWaveLoad;
+      const uint32_t pc = (uint32_t)__popc(m);
+      const uint32_t incl = wave_incl_scan_u32(pc, lane);
+      const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+      if (total == 0u) continue;  // (wave-uniform)
+      uint32_t r = incl - pc;
+      while (m) {
+        const uint32_t b = (uint32_t)__ffs((int)m) - 1u;
+        m &= m - 1u;
+        s_queue[r++] = (uint16_t)(lane * kUnit + b);
+      }
+      // the queue belongs to this wave alone: a wavefront-scope release/acquire orders its lanes' LDS accesses
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      for (uint32_t i = lane; i < total; i += 64u)
+        set_count_at(T, cbase, load_off + s_queue[i], L, ICASE, hit, KEYS_LDS ? s_keys : T.keys);
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();  // the next wave-load refills the queue
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
+
+    if (!boundary) continue;
+    // ---- flush into row c
+    __syncthreads();
+    unsigned long long* const row = C.counts + (uint64_t)c * C.nlits;
+    auto add = [&](uint32_t j, uint32_t v) {
+      s_hist[j] = 0u;
+      if (atomicAdd(&row[j], (unsigned long long)v) == 0ull && C.chunks_with) {
+        if (with_lds)
+          atomicAdd(&s_with[j], 1u);  // (at most one per chunk of the range: fewer than 2^18)
+        else
+          atomicAdd(&C.chunks_with[j], 1ull);
+      }
+    };
+    const uint32_t t_now = s_ntouched;
+    const uint32_t nt = t_now - t_base;
+    t_base = t_now;
+    if (listed && nt <= kLitTouched) {
+      for (uint32_t k = tid; k < nt; k += kBlock) {
+        const uint32_t j = s_touched[k];
+        add(j, s_hist[j]);
+      }
+    } else {
+      for (uint32_t k = tid; k < C.nlits; k += kBlock) {
+        const uint32_t v = s_hist[k];
+        if (v) add(k, v);
+      }
+    }
+    __syncthreads();
+  }
+  // (behind the last flush's barrier) the chunks of this range that hold each literal
+  if (with_lds)
+    for (uint32_t k = tid; k < C.nlits; k += kBlock) {
+      const uint32_t v = s_with[k];
+      if (v) atomicAdd(&C.chunks_with[k], (unsigned long long)v);
+    }
+}
+
 static unsigned set_grid(const ScanArgs& a) {
   static const unsigned cus = [] {
     int dev = 0, n = 0;
@@ -386,6 +570,37 @@ hipError_t launch_set_count_literals(const ScanArgs& a, const LitCountArgs& c, h
     c.keys_lds ? launch_lit<true, true>(a, c, grid, lds, s) : launch_lit<true, false>(a, c, grid, lds, s);
   else
     c.keys_lds ? launch_lit<false, true>(a, c, grid, lds, s) : launch_lit<false, false>(a, c, grid, lds, s);
+  return hipGetLastError();
+}
+
+unsigned set_litmatrix_grid(const ScanArgs& a, uint32_t forced) {
+  ScanArgs all{};  // (set_grid of a binding with tiles to spare: workgroups per compute unit x compute units)
+  all.ntiles = ~0ull;
+  return (unsigned)litmatrix_grid(a.ntiles, (uint64_t)set_grid(all) / kSetGridPerCu * kLitMatrixGridPerCu, forced);
+}
+
+hipError_t launch_set_count_literals_chunks(const ScanArgs& a, const LitMatrixArgs& c, uint32_t forced_grid, hipStream_t s) {
+  if (a.ntiles == 0) return hipSuccess;
+  if (a.tile_bytes != kSetTile || a.pat.set_g < 1 || a.pat.set_g > 4 || !c.counts || c.nlits == 0 || c.nlits > XSG_MAX_LITERALS ||
+      a.pat.set_ngrams > XSG_MAX_LITERALS)
+    return hipErrorInvalidValue;
+  const dim3 grid(set_litmatrix_grid(a, forced_grid));
+  // (a histogram word stays below 2^32: fewer than 2^18 tiles per workgroup, xsg_litmatrix.h)
+  if (litmatrix_per(a.ntiles, grid.x) >= kLitMatrixPerLimit) return hipErrorInvalidValue;
+  const size_t lds = 4u * (size_t)lit_round4(c.nlits) + (c.keys_lds ? 4u * (size_t)lit_round4(a.pat.set_ngrams) : 0u) +
+                     2u * (size_t)kLitQueue * kWaves + 2u * (size_t)kLitTouched +
+                     (c.chunks_with && c.nlits <= kLitWithLds ? 4u * (size_t)lit_round4(c.nlits) : 0u);
+  if (a.pat.icase) {
+    if (c.keys_lds)
+      hipLaunchKernelGGL((k_set_count_literals_chunks<true, true>), grid, dim3(kBlock), lds, s, a, c);
+    else
+      hipLaunchKernelGGL((k_set_count_literals_chunks<true, false>), grid, dim3(kBlock), lds, s, a, c);
+  } else {
+    if (c.keys_lds)
+      hipLaunchKernelGGL((k_set_count_literals_chunks<false, true>), grid, dim3(kBlock), lds, s, a, c);
+    else
+      hipLaunchKernelGGL((k_set_count_literals_chunks<false, false>), grid, dim3(kBlock), lds, s, a, c);
+  }
   return hipGetLastError();
 }
 

@@ -143,6 +143,9 @@ def load():
         "xsg_count_chunks_async": (ci, [vp, u32, vp, vp, vp, u64, vp, vp]),
         "xsg_count_literals": (ci, [vp, vp, u64]),
         "xsg_count_literals_async": (ci, [vp, vp, vp, u64]),
+        "xsg_count_literals_chunks": (ci, [vp, vp, u64, vp, u64]),
+        "xsg_count_literals_chunks_async": (ci, [vp, vp, vp, u64, vp, u64]),
+        "xsg_literals_chunks_touched_capacity": (u32, []),
         "xsg_literal_counter_create": (ci, [ci, C.c_char_p, sz, u32, C.POINTER(vp)]),
         "xsg_literal_counter_add": (ci, [vp, vp, u64]),
         "xsg_literal_counter_get": (ci, [vp, vp, u64, _u64p]),
@@ -217,7 +220,8 @@ EXPORTS = ["xsg_abi_version", "xsg_strerror", "xsg_last_error", "xsg_device_coun
            "xsg_host_matches", "xsg_result_context_edges", "xsg_set_literals", "xsg_literals_info",
            "xsg_host_searcher_create_list", "xsg_count_chunks", "xsg_count_chunks_async", "xsg_count_literals",
            "xsg_count_literals_async", "xsg_literal_counter_create", "xsg_literal_counter_add", "xsg_literal_counter_get",
-           "xsg_literal_counter_destroy"]
+           "xsg_literal_counter_destroy", "xsg_count_literals_chunks", "xsg_count_literals_chunks_async",
+           "xsg_literals_chunks_touched_capacity"]
 
 
 def _check(rc):
@@ -263,6 +267,12 @@ def literals_info(lst: bytes, flags: int = 0, with_filter: bool = False):
     _check(load().xsg_literals_info(lst, len(lst), flags, C.byref(info), filt.ctypes.data if with_filter else None))
     d = {k: getattr(info, k) for k, _ in LiteralList._fields_}
     return (d, filt) if with_filter else d
+
+
+def literals_chunks_touched_capacity() -> int:
+    """the literals a workgroup of count_literals_chunks' pass notes between two flushes before a flush sweeps its whole
+    histogram (xsg_literals_chunks_touched_capacity); results do not depend on it.  No GPU needed."""
+    return int(load().xsg_literals_chunks_touched_capacity())
 
 
 def literal_gram_hash(v: int, g: int) -> int:
@@ -470,6 +480,24 @@ class Shard:
     def count_literals_async(self, stream: int, d_counts: int, cap: int):
         """the stream-ordered form (xsg_count_literals_async): d_counts is a device address of `cap` uint64 words"""
         _check(self._lib.xsg_count_literals_async(self.h, C.c_void_p(stream), C.c_void_p(d_counts) if d_counts else None, cap))
+
+    def count_literals_chunks(self, with_chunks: bool = True):
+        """-> (matrix of shape (nchunks, k) uint64, chunks_with or None) (xsg_count_literals_chunks): matrix[c, j] is what
+        count_literals() would give for literal j on a binding that holds chunk c alone; chunks_with[j] is the number of
+        chunks in which literal j occurs.  The matrix is dense."""
+        k = self.ctx.nliterals
+        n = self.nchunks
+        m = np.zeros((n, k) if k else (1, MAX_LITERALS), dtype=np.uint64)  # (no list: the library says what is wrong)
+        w = np.zeros(m.shape[1], dtype=np.uint64) if with_chunks else None
+        _check(self._lib.xsg_count_literals_chunks(self.h, C.c_void_p(m.ctypes.data), m.size,
+                                                   C.c_void_p(w.ctypes.data) if with_chunks else None, w.size if with_chunks else 0))
+        return m, w
+
+    def count_literals_chunks_async(self, stream: int, d_counts: int, cap_words: int, d_chunks_with: int = 0, cap_literals: int = 0):
+        """the stream-ordered form (xsg_count_literals_chunks_async): device addresses of cap_words and cap_literals
+        uint64 words; d_chunks_with 0: not wanted"""
+        _check(self._lib.xsg_count_literals_chunks_async(self.h, C.c_void_p(stream), C.c_void_p(d_counts) if d_counts else None, cap_words,
+                                                         C.c_void_p(d_chunks_with) if d_chunks_with else None, cap_literals))
 
     def count_begin(self, mode: int):
         _check(self._lib.xsg_count_begin(self.h, mode))
