@@ -355,7 +355,8 @@ int xsg_regex_factor(const void* expr, size_t n, uint32_t flags, uint32_t* posit
  * entry points find that out first (a sample of the sketch, once per binding and pattern) and keep the full scan.
  * xsg_count_async cannot -- it never waits for the device -- and uses the gate whenever no synchronous call has judged
  * the pattern on this binding; for such a needle every tile is then a candidate and the pass is SLOWER than the full
- * scan (measured 1.07 x on a 50 GiB binding): call a synchronous entry point once with the pattern,
+ * scan (measured 1.07 x on a 50 GiB binding; the wave form's grid of one resident round adds 6 % to
+ * that case -- `this`, every tile a candidate: 8.27 -> 8.75 ms, XSG_GATE_GRID=8192 takes it back): call a synchronous entry point once with the pattern,
  * or set XSG_SKETCH=0, where that matters.  A plain match count behind the gate (no XSG_WITH_NEWLINES; a needle of
  * at most 33 bytes, or XSG_FLAG_EXACT_TAIL) is ONE launch: the same kernel sums in registers, walks the end-of-chunk zones
  * that hold an occurrence itself and writes the counters (50 GiB, `Sherlock`: 0.149 -> 0.110 ms per call).  It pays for a
@@ -366,8 +367,12 @@ int xsg_regex_factor(const void* expr, size_t n, uint32_t flags, uint32_t* posit
  * xsg_scan_kernel_name says " by 4 KiB spans" in front of " finishing").  With the locator the launch also runs as a wave
  * per sketch group of 64 tiles -- every wave tests its own tiles and reads its own candidates' spans, none waits for
  * another before the kernel's end (50 GiB, `Sherlock`: 0.083 -> 0.076 ms per call; the name says " a wave per group" in
- * front of " by 4 KiB spans").  XSG_GATE_WAVES=0 keeps the workgroup form; XSG_GATE_GRID=N sets the number of workgroups
- * of either form (default 8192, never more than one per 256 tiles).  Bindings of 64 MiB and more get the sketch from
+ * front of " by 4 KiB spans").  A wave takes its groups four at a time: the sketch words of all four are requested together,
+ * the batch's candidates are looked up in one round trip and then scanned (50 GiB, `Sherlock`: 0.076 -> 0.062 ms per call;
+ * the name says " in batches of 4" in front of " a wave per group"; XSG_GATE_BATCH=1 keeps one group at a time).
+ * XSG_GATE_WAVES=0 keeps the workgroup form; XSG_GATE_GRID=N sets the number of workgroups of either form (default 1536
+ * for the wave form, 8192 for the workgroup form and the storing pass; never more than one per 256 tiles).  Bindings of
+ * 64 MiB and more get the sketch from
  * xsg_shard_tune, or from the second such pass of a synchronous entry point (the build is enqueued on the context's
  * stream); xsg_count_async on a caller's stream never builds, it uses what is there.  XSG_SKETCH=0 switches the feature
  * off, XSG_SKETCH=1 builds before the first pass.  A caller that refills

@@ -422,6 +422,10 @@ static GateFinArgs fin_args(xsg_shard* s, const ScanArgs& a, uint64_t* d_counter
   const char* e = XSG_TOGGLE("XSG_GATE_WAVES");
   // (chunk offsets below 2^48: the wave form keeps a passing lane's geometry in four registers)
   f.waves = f.spans != nullptr && !(e && *e == '0') && s->capacity < (1ull << 48);
+  // the wave form selects, locates and scans kGateBatch of a wave's groups at a time; XSG_GATE_BATCH=1 is the A/B switch
+  // that keeps one group at a time in the same build
+  const char* b = XSG_TOGGLE("XSG_GATE_BATCH");
+  f.batch = b && *b == '1' && b[1] == 0 ? 1u : kGateBatch;
   return f;
 }
 
@@ -989,9 +993,10 @@ extern "C" int xsg_scan_kernel_name(xsg_shard* s, uint32_t mode, char* out, size
     snprintf(out, cap, "%s + xsg::k_rx_verify (prefilter route; xsg_count_async: k_rx_scan)", inner);
   } else {
     // (a plain match count says which form of the gated pass it launches: the finishing one, or the storing one)
+    const GateFinArgs f = fin_args(s, a, nullptr, nullptr, nullptr);
     describe_scan(a, want_nl, !list && m == XSG_COUNT_LINES, false, out, cap,
                   !list && count_finishes(s, a, m, (mode & XSG_WITH_NEWLINES) != 0), s->total_bytes, spans_apply(s, a),
-                  fin_args(s, a, nullptr, nullptr, nullptr).waves != 0);
+                  f.waves != 0, f.batch);
   }
   if (inverted(s->ctx)) {  // the inverted form: the same scan, then the complement (of the list, or of the line count)
     const size_t n = strlen(out);

@@ -198,7 +198,20 @@ struct GateFinArgs {
   // to its text, no workgroup barrier in the pass.  Only with `spans` (a 4 KiB span is one wave's load batch);
   // XSG_GATE_WAVES=0 keeps the workgroup form.
   uint32_t waves;
+  // The wave form takes its groups in batches: a wave's next `batch` rounds (1 .. kGateBatch) are selected together,
+  // their candidates located in one round trip and then scanned.  XSG_GATE_BATCH=1 keeps one group at a time.
+  uint32_t batch;
 };
+#ifndef XSG_GATE_BATCH_N
+#define XSG_GATE_BATCH_N 4
+#endif
+constexpr uint32_t kGateBatch = XSG_GATE_BATCH_N;  // rounds of a wave per batch (gated_pass_waves): DESIGN.md section 5
+static_assert(kGateBatch >= 1 && kGateBatch <= 8, "a candidate's place in its batch: 3 + 6 bits; 7 registers a round in the select phase");
+// workgroups of the wave form when XSG_GATE_GRID does not say (the storing form and the workgroup finishing form:
+// kGateGrid): one resident round at six waves per SIMD on 256 compute units, every wave taking its groups in batches.
+// On 50 GiB level with 3200; on 10 GiB (2560 units) ahead of one workgroup per unit, where no wave has a second group
+// to batch ("Batches")
+constexpr uint32_t kGateGridWaves = 1536;
 constexpr uint32_t kFinGroups = 64;
 constexpr uint32_t kFinTotalBits = 40;  // matches <= total_bytes < 2^40; the grid stays below 2^24 (scan_finishing)
 // would a plain match count over these arguments take the finishing form?  (gated, an end-of-chunk zone the wave walk
@@ -332,9 +345,10 @@ hipError_t launch_set_count_literals_chunks(const ScanArgs& a, const LitMatrixAr
 unsigned set_litmatrix_grid(const ScanArgs& a, uint32_t forced);  // the workgroups that launch would use
 // "xsg::k_scan<KIND, WANT_NL, WANT_LINES, EMIT, LOADS, ICASE>" + the stagger launch_scan would use, for reports
 // finishing: the caller's pass is a plain match count that takes the finishing form where scan_finishing says so;
-// spans: that form would run with the binding's span locator (GateFinArgs::spans); waves: and as the wave form
+// spans: that form would run with the binding's span locator (GateFinArgs::spans); waves: and as the wave form, taking
+// `batch` groups at a time (GateFinArgs::batch)
 void describe_scan(const ScanArgs& a, bool want_nl, bool want_lines, bool emit, char* out, size_t cap,
-                   bool finishing = false, uint64_t total_bytes = 0, bool spans = false, bool waves = false);
+                   bool finishing = false, uint64_t total_bytes = 0, bool spans = false, bool waves = false, uint32_t batch = 1);
 
 // exclusive scan: out[i] = sum_{k<i} in[k] for i in [0, n]; out has n+1 entries.
 // tmp must hold scan_tmp_elems(n) uint64 values.

@@ -1418,13 +1418,22 @@ __device__ __forceinline__ void gated_pass(const ScanArgs& A, const GateFinArgs*
 // the unit of text work is a 4 KiB span -- one wave's load batch -- so the workgroup is not needed to scan a candidate,
 // and in the form above three waves of four wait while one reads the ~1.00 span a candidate lets through.  Here a wave
 // owns a sketch group (64 consecutive tiles, lane l <-> tile g * 64 + l) from its sketch words to its text: wave w of
-// workgroup b takes the groups b * kWaves + w, + gridDim.x * kWaves, ... (the same static stride, the same grid).  Per
-// group: the lane's sketch words and tile_chunk, all requested before any use; the ballot; passing lanes request chunk
-// entry, first tile and locator words in one batch and reduce them to the span mask; the wave walks the set bits of its
-// OWN ballot, geometry and mask by readlane from the passing lane's registers, and scans every set span of the mask
-// (scan_tile_at<..., WAVE>).  No LDS hand-off and no __syncthreads() on any path a single wave takes -- waves run
-// different numbers of groups and candidates: the kLong pattern is staged once at the top, where all four waves still
-// are, and the only other barrier stands in front of the leaving atomicAdd (fin_leave).  The end-of-chunk zone of a
+// workgroup b takes the groups b * kWaves + w, + gridDim.x * kWaves, ... (the same static stride).  The wave takes its
+// groups a BATCH at a time -- its next GateFinArgs::batch rounds, at most kGateBatch -- in three phases whose registers
+// are dead before the next begins, so that a batch costs about three dependent round trips where its groups one by one
+// cost up to three each:
+//   1. select: the lane's sketch words and tile_chunk for every group of the batch, all requested before any use,
+//      reduced to one ballot a group (scalar registers);
+//   2. locate: the passing (round, lane) pairs, compacted in that order by ballot prefix and mbcnt into the wave's own
+//      LDS row of 64 entries {place in the batch, chunk number}; lane i takes candidate i and requests chunk entry,
+//      first tile and locator words in one batch and reduces them to the span mask.  (More than 64 candidates in a
+//      batch: the groups one at a time, the passing lane keeping its own tile and reading tile_chunk again.)
+//   3. scan: the wave walks the candidates, place, geometry and mask by readlane from the lane that holds them, and
+//      scans every set span of the mask (scan_tile_at<..., WAVE>).
+// The row is written and read by one wave: ordered by a wavefront fence, no workgroup barrier.  No __syncthreads() on
+// any path a single wave takes -- waves run different numbers of groups and candidates: the kLong pattern is staged
+// once at the top, where all four waves still are, and the only other barrier stands in front of the leaving atomicAdd
+// (fin_leave).  Nothing depends on how many workgroups are resident: the grid is a speed setting.  The end-of-chunk zone of a
 // candidate tile is looked at by the wave that owns the tile, in its own row of s_zone; the rule is gated_pass's.
 // Used when the binding has a span locator (GateFinArgs::waves); without one, four spans read in turn by one wave are
 // not what whole-tile reads want, and gated_pass<..., FIN> serves.
@@ -1433,6 +1442,7 @@ template <int KIND, int LOADS, bool ALIGNED>
 __device__ __forceinline__ void gated_pass_waves(const ScanArgs& A, const GateFinArgs& F) {
   __shared__ __attribute__((aligned(16))) uint8_t s_zone[kWaves][kZoneStage];  // the zone a candidate tile looks at, per wave
   __shared__ uint64_t s_fin[kWaves];
+  __shared__ uint2 s_cand[kWaves][kSketchGroup];  // a batch's candidates, per wave: {place in the batch, chunk number}
   uint64_t fin_acc = 0;  // this wave's matches (wave-uniform)
   const uint32_t tid = threadIdx.x;
   const uint32_t lane = tid & 63u;
@@ -1445,105 +1455,163 @@ __device__ __forceinline__ void gated_pass_waves(const ScanArgs& A, const GateFi
   // reads no span (ntiles >= 1: scan_finishing)
   scan_tile_at<KIND, false, false, false, LOADS, false, ALIGNED, true, true, true>(A, 0, TileGeom{}, true, &fin_acc, false, 0u);
 
+  // four registers a lane across the scans for its candidate's geometry, not six: the offset is below 2^48 -- fin_args
+  // asks for the wave form only on such a buffer -- and the length below 2^kFinTotalBits, so their high halves and the
+  // span mask share g_hi: bits 0-15, 16-23 and 24-27.  A fifth says which tile of the batch the candidate is.
+  static_assert(kFinTotalBits <= 40 && kSpansPerTile <= 8, "g_hi: 16 + 8 + 8 bits");
+  constexpr uint32_t B = kGateBatch;
+  const uint32_t bn = F.batch - 1u < B ? F.batch : B;  // rounds per batch, 1 .. B (XSG_GATE_BATCH=1: one group at a time)
+  const uint64_t stride = (uint64_t)gridDim.x * kWaves;
+
 #pragma unroll 1
-  for (uint64_t g = (uint64_t)blockIdx.x * kWaves + wave; g < ngroups; g += (uint64_t)gridDim.x * kWaves) {
-    // the loads of this lane's tile, all issued here; `miss` takes what does not fit kGateRegs
-    const uint64_t mytile = g * kSketchGroup + lane;
-    uint32_t w[kGateRegs], wc = 0, miss = 1u;  // a tile at or beyond ntiles does not pass
+  for (uint64_t g0 = (uint64_t)blockIdx.x * kWaves + wave; g0 < ngroups; g0 += stride * bn) {
+    // ---- 1. select: the sketch words and tile_chunk of every group of the batch, all requested before any use, reduced
+    // to one ballot per group (scalar); the words are dead behind this block.  Group j of the batch is g0 + j * stride.
+    unsigned long long bal[B];
+    uint32_t total = 0;
+    {
+      uint32_t w[B][kGateRegs], wc[B], miss[B];
 #pragma unroll
-    for (uint32_t k = 0; k < kGateRegs; ++k) w[k] = 0xffffffffu;
-    if (mytile < A.ntiles) {
-      const uint32_t* sk = A.sketch + sketch_index(mytile, 0);
-      miss = 0;
+      for (uint32_t j = 0; j < B; ++j) {
+        const uint64_t g = g0 + j * stride, mytile = g * kSketchGroup + lane;
+        miss[j] = 1u;  // a round at or beyond bn or ngroups and a tile at or beyond ntiles do not pass
+        wc[j] = 0;
 #pragma unroll
-      for (uint32_t k = 0; k < kGateRegs; ++k)
-        if (k < n) w[k] = sk[A.sk_word[k] * kSketchGroup];
-      if (A.tile_chunk) wc = A.tile_chunk[mytile];
-      for (uint32_t i = kGateRegs; i < n; i += kGateRegs) {  // (more than kGateRegs distinct words: long needles only)
-        uint32_t x[kGateRegs];
+        for (uint32_t k = 0; k < kGateRegs; ++k) w[j][k] = 0xffffffffu;
+        if (j < bn && g < ngroups && mytile < A.ntiles) {
+          const uint32_t* sk = A.sketch + sketch_index(mytile, 0);
+          miss[j] = 0;
 #pragma unroll
-        for (uint32_t k = 0; k < kGateRegs; ++k) x[k] = i + k < n ? sk[A.sk_word[i + k] * kSketchGroup] : 0xffffffffu;
+          for (uint32_t k = 0; k < kGateRegs; ++k)
+            if (k < n) w[j][k] = sk[A.sk_word[k] * kSketchGroup];
+          if (A.tile_chunk) wc[j] = A.tile_chunk[mytile];
+          for (uint32_t i = kGateRegs; i < n; i += kGateRegs) {  // (more than kGateRegs distinct words: long needles only)
+            uint32_t x[kGateRegs];
 #pragma unroll
-        for (uint32_t k = 0; k < kGateRegs; ++k) miss |= i + k < n ? ~x[k] & A.sk_mask[i + k] : 0u;
-      }
-    }
+            for (uint32_t k = 0; k < kGateRegs; ++k) x[k] = i + k < n ? sk[A.sk_word[i + k] * kSketchGroup] : 0xffffffffu;
 #pragma unroll
-    for (uint32_t k = 0; k < kGateRegs; ++k)
-      if (k < n) miss |= ~w[k] & A.sk_mask[k];
-    const bool pass = miss == 0;
-    const unsigned long long bal = __ballot(pass);
-    if (bal == 0) continue;
-    // a passing lane: its locator words -- word k of the tile's four spans is one 16-byte load (span_index) -- and its
-    // geometry in one batch, reduced to the 4-bit span mask
-    // (four registers a lane across the scans, not six: the offset is below 2^48 -- fin_args asks for the wave form only
-    // on such a buffer -- and the length below 2^kFinTotalBits, so their high halves and the span mask share g_hi:
-    // bits 0-15, 16-23 and 24-27)
-    static_assert(kFinTotalBits <= 40 && kSpansPerTile <= 8, "g_hi: 16 + 8 + 8 bits");
-    uint32_t g_off = 0, g_len = 0, g_hi = 0, g_t0 = 0;
-    if (pass) {
-      uint4 x[kSpanRegs];
-      const uint4* sp = reinterpret_cast<const uint4*>(F.spans + span_index(mytile, 0, 0));
-#pragma unroll
-      for (uint32_t k = 0; k < kSpanRegs; ++k) {  // (every x[k] defined: an undefined one is carried round the group loop)
-        x[k] = make_uint4(~0u, ~0u, ~0u, ~0u);
-        if (k < sn) x[k] = sp[F.sp_word[k]];
-      }
-      const ChunkDev ch = A.chunks[wc];
-      g_off = (uint32_t)ch.offset;
-      g_len = (uint32_t)ch.length;
-      g_hi = ((uint32_t)(ch.offset >> 32) & 0xffffu) | (((uint32_t)(ch.length >> 32) & 0xffu) << 16);
-      g_t0 = reinterpret_cast<const uint32_t*>(A.chunk_tile0 + wc)[0];  // the low half: the tile's distance from it is below 2^32
-      uint32_t mx = 0, my = 0, mz = 0, mw = 0;  // per span: the bits that are missing
-#pragma unroll
-      for (uint32_t k = 0; k < kSpanRegs; ++k)
-        if (k < sn) {
-          const uint32_t b = F.sp_mask[k];
-          mx |= ~x[k].x & b, my |= ~x[k].y & b, mz |= ~x[k].z & b, mw |= ~x[k].w & b;
+            for (uint32_t k = 0; k < kGateRegs; ++k) miss[j] |= i + k < n ? ~x[k] & A.sk_mask[i + k] : 0u;
+          }
         }
-      g_hi |= ((mx == 0 ? 1u : 0u) | (my == 0 ? 2u : 0u) | (mz == 0 ? 4u : 0u) | (mw == 0 ? 8u : 0u)) << 24;
+      }
+#pragma unroll
+      for (uint32_t j = 0; j < B; ++j) {
+#pragma unroll
+        for (uint32_t k = 0; k < kGateRegs; ++k)
+          if (k < n) miss[j] |= ~w[j][k] & A.sk_mask[k];
+        bal[j] = __ballot(miss[j] == 0);
+        total += (uint32_t)__builtin_popcountll(bal[j]);
+      }
+      if (total == 0) continue;
+      // ---- 2a. the batch's passing (group, lane) pairs, compacted in (round, lane) order into the wave's row: entry
+      // i = {j * 64 + lane, tile_chunk}.  64 entries; a batch with more takes its groups one at a time (below).
+      if (total <= kSketchGroup) {
+        uint32_t before = 0;
+#pragma unroll
+        for (uint32_t j = 0; j < B; ++j) {
+          if ((bal[j] >> lane) & 1ull) {
+            const uint32_t at = before + __builtin_amdgcn_mbcnt_hi((uint32_t)(bal[j] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal[j], 0u));
+            s_cand[wave][at] = make_uint2(j * kSketchGroup + lane, wc[j]);
+          }
+          before += (uint32_t)__builtin_popcountll(bal[j]);
+        }
+        // the row is written and read by this wave alone: LDS serves a wave's requests in order
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      }
     }
-    // the wave's own candidates, in tile order
-    uint32_t lo = (uint32_t)bal, hi = (uint32_t)(bal >> 32);
+    // one pass over the whole batch, or -- more than 64 candidates -- one per group, the lane then keeping its own tile
+    const bool packed = total <= kSketchGroup;
 #pragma unroll 1
-    while (lo | hi) {
-      uint32_t l;
-      if (lo) {
-        l = (uint32_t)__builtin_ctz(lo);
-        lo &= lo - 1u;
-      } else {
-        l = 32u + (uint32_t)__builtin_ctz(hi);
-        hi &= hi - 1u;
+    for (uint32_t j0 = 0; j0 < bn; j0 = packed ? bn : j0 + 1u) {
+      // ---- 2b. locate: lane i takes candidate i -- chunk entry, the chunk's first tile and the locator words (word k of
+      // the tile's four spans is one 16-byte load: span_index) in one batch, reduced to the 4-bit span mask
+      unsigned long long cand = total == kSketchGroup ? ~0ull : (1ull << (total & 63u)) - 1ull;  // lanes that hold a candidate
+      if (!packed) {
+        cand = 0;
+#pragma unroll
+        for (uint32_t j = 0; j < B; ++j)
+          if (j == j0) cand = bal[j];
+        if (cand == 0) continue;
       }
-      const uint64_t tile = g * kSketchGroup + l;
-      TileGeom tg;
-      auto at = [&](const uint32_t v) { return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)l); };
-      const uint32_t hi16 = at(g_hi);
-      tg.offset = ((uint64_t)(hi16 & 0xffffu) << 32) | at(g_off);
-      tg.length = ((uint64_t)((hi16 >> 16) & 0xffu) << 32) | at(g_len);
-      tg.tile0 = tile - (uint32_t)((uint32_t)tile - at(g_t0));
-      tg.c = 0;  // (the emit pass names the chunk; a count pass does not)
-      uint32_t sm = hi16 >> 24;
+      uint32_t g_off = 0, g_len = 0, g_hi = 0, g_t0 = 0, g_at = 0;
+      if ((cand >> lane) & 1ull) {
+        uint32_t wc;
+        if (packed) {
+          const uint2 e = s_cand[wave][lane];
+          g_at = e.x;
+          wc = e.y;
+        } else {
+          g_at = j0 * kSketchGroup + lane;
+          wc = A.tile_chunk ? A.tile_chunk[(g0 + j0 * stride) * kSketchGroup + lane] : 0u;
+        }
+        const uint64_t mytile = (g0 + (g_at >> 6) * stride) * kSketchGroup + (g_at & 63u);
+        uint4 x[kSpanRegs];
+        const uint4* sp = reinterpret_cast<const uint4*>(F.spans + span_index(mytile, 0, 0));
+#pragma unroll
+        for (uint32_t k = 0; k < kSpanRegs; ++k) {  // (every x[k] defined: an undefined one is carried round the loop)
+          x[k] = make_uint4(~0u, ~0u, ~0u, ~0u);
+          if (k < sn) x[k] = sp[F.sp_word[k]];
+        }
+        const ChunkDev ch = A.chunks[wc];
+        g_off = (uint32_t)ch.offset;
+        g_len = (uint32_t)ch.length;
+        g_hi = ((uint32_t)(ch.offset >> 32) & 0xffffu) | (((uint32_t)(ch.length >> 32) & 0xffu) << 16);
+        g_t0 = reinterpret_cast<const uint32_t*>(A.chunk_tile0 + wc)[0];  // the low half: the tile's distance from it is below 2^32
+        uint32_t mx = 0, my = 0, mz = 0, mw = 0;  // per span: the bits that are missing
+#pragma unroll
+        for (uint32_t k = 0; k < kSpanRegs; ++k)
+          if (k < sn) {
+            const uint32_t b = F.sp_mask[k];
+            mx |= ~x[k].x & b, my |= ~x[k].y & b, mz |= ~x[k].z & b, mw |= ~x[k].w & b;
+          }
+        g_hi |= ((mx == 0 ? 1u : 0u) | (my == 0 ? 2u : 0u) | (mz == 0 ? 4u : 0u) | (mw == 0 ? 8u : 0u)) << 24;
+      }
+      // ---- 3. scan: the candidates in (round, tile) order, geometry and mask by readlane from the lane that holds them
+      uint32_t lo = (uint32_t)cand, hi = (uint32_t)(cand >> 32);
 #pragma unroll 1
-      while (sm) {  // every span of the candidate that can hold a window start: this wave's 4 KiB loads, one batch each
-        const uint32_t s = (uint32_t)__builtin_ctz(sm);
-        sm &= sm - 1u;
-        scan_tile_at<KIND, false, false, false, LOADS, false, ALIGNED, true, true, true>(A, tile, tg, false, &fin_acc, true, s);
-      }
-      // the end-of-chunk zone: one look per candidate TILE, whatever its span mask, by the wave that owns the tile (see
-      // gated_pass: the home of the zone's first occurrence walks it, from fin_walk_entry)
-      const uint32_t plen = A.pat.plen, koff = KIND >= kLong ? A.pat.koff : 0u;
-      const uint64_t L = tg.length;
-      if (!A.pat.exact_tail && L >= plen) {
-        constexpr uint64_t kTile = (uint64_t)kWaveLoad * LOADS * kWaves;
-        const uint64_t Z = tail_zone_begin(L, plen), trel = tile - tg.tile0;
-        if (trel >= (Z + koff) / kTile && trel <= (L - plen + koff) / kTile) {
-          const uint8_t* cbase = A.base + tg.offset;
-          const TailMasks tm = wave_tail_masks(cbase, L, A.pat.d_pat, plen, false, s_zone[wave], lane);
-          if (tm.full != 0 && (Z + (uint32_t)__builtin_ctzll(tm.full) + koff) / kTile == trel) {
-            const uint64_t entry = fin_walk_entry<LOADS>(A, cbase, L, Z, tg.tile0, koff, lane);
-            const uint32_t kk = tm.k;
-            auto k_at = [&](uint32_t j) { return (uint32_t)__builtin_amdgcn_readlane((int)kk, (int)__builtin_amdgcn_readfirstlane(j)); };
-            fin_acc += tail_walk_masks(L, plen, entry, false, tm.full, tm.nz, tm.nlm, k_at);
+      while (lo | hi) {
+        uint32_t l;
+        if (lo) {
+          l = (uint32_t)__builtin_ctz(lo);
+          lo &= lo - 1u;
+        } else {
+          l = 32u + (uint32_t)__builtin_ctz(hi);
+          hi &= hi - 1u;
+        }
+        TileGeom tg;
+        auto at = [&](const uint32_t v) { return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)l); };
+        const uint32_t slot = at(g_at);
+        const uint64_t tile = (g0 + (slot >> 6) * stride) * kSketchGroup + (slot & 63u);
+        const uint32_t hi16 = at(g_hi);
+        tg.offset = ((uint64_t)(hi16 & 0xffffu) << 32) | at(g_off);
+        tg.length = ((uint64_t)((hi16 >> 16) & 0xffu) << 32) | at(g_len);
+        tg.tile0 = tile - (uint32_t)((uint32_t)tile - at(g_t0));
+        tg.c = 0;  // (the emit pass names the chunk; a count pass does not)
+        uint32_t sm = (hi16 >> 24) & 0xfu;
+#pragma unroll 1
+        while (sm) {  // every span of the candidate that can hold a window start: this wave's 4 KiB loads, one batch each
+          const uint32_t s = (uint32_t)__builtin_ctz(sm);
+          sm &= sm - 1u;
+          scan_tile_at<KIND, false, false, false, LOADS, false, ALIGNED, true, true, true>(A, tile, tg, false, &fin_acc, true, s);
+        }
+        // the end-of-chunk zone: one look per candidate TILE, whatever its span mask, by the wave that owns the tile (see
+        // gated_pass: the home of the zone's first occurrence walks it, from fin_walk_entry)
+        const uint32_t plen = A.pat.plen, koff = KIND >= kLong ? A.pat.koff : 0u;
+        const uint64_t L = tg.length;
+        if (!A.pat.exact_tail && L >= plen) {
+          constexpr uint64_t kTile = (uint64_t)kWaveLoad * LOADS * kWaves;
+          const uint64_t Z = tail_zone_begin(L, plen), trel = tile - tg.tile0;
+          if (trel >= (Z + koff) / kTile && trel <= (L - plen + koff) / kTile) {
+            const uint8_t* cbase = A.base + tg.offset;
+            const TailMasks tm = wave_tail_masks(cbase, L, A.pat.d_pat, plen, false, s_zone[wave], lane);
+            if (tm.full != 0 && (Z + (uint32_t)__builtin_ctzll(tm.full) + koff) / kTile == trel) {
+              const uint64_t entry = fin_walk_entry<LOADS>(A, cbase, L, Z, tg.tile0, koff, lane);
+              const uint32_t kk = tm.k;
+              auto k_at = [&](uint32_t j) { return (uint32_t)__builtin_amdgcn_readlane((int)kk, (int)__builtin_amdgcn_readfirstlane(j)); };
+              fin_acc += tail_walk_masks(L, plen, entry, false, tm.full, tm.nz, tm.nlm, k_at);
+            }
           }
         }
       }
@@ -1558,7 +1626,9 @@ template <int KIND, int LOADS, bool ALIGNED, bool WAVES>
 // (The occupancy request: with the span locator's loads the instantiations came out at 79 .. 84 VGPRs, half of them
 // past the 80 that six waves per SIMD allow; asked for six, the compiler fits all of them into 74 .. 78 without scratch
 // -- profiles/spans_registers.txt.  The wave form is bounded to six from above as well, so that the compiler does not
-// squeeze it towards seven: it comes out at 69 .. 72, without a spill -- profiles/waves_registers.txt.)
+// squeeze it towards seven: it came out at 69 .. 72, and with batches of four at 76 .. 79, without a spill of a vector
+// register -- profiles/waves_registers.txt, batch_registers.txt; batches of eight spill: 7 registers a round in the
+// select phase.)
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(6, WAVES ? 6 : 8))) void k_scan_fin(const ScanArgs A, const GateFinArgs F) {
   if constexpr (WAVES)
     gated_pass_waves<KIND, LOADS, ALIGNED>(A, F);
@@ -1606,9 +1676,9 @@ static bool gate_applies(const ScanArgs& a, bool want_nl, bool want_lines, bool 
 }
 
 // The grid of the gated pass: bounded, persistent workgroups that claim units of 256 tiles (ScanArgs::gate_grid, 0:
-// kGateGrid); never more workgroups than units
-static dim3 gate_grid(const ScanArgs& a) {
-  const uint64_t g = a.gate_grid ? a.gate_grid : kGateGrid;
+// kGateGrid, the wave form of the finishing pass: kGateGridWaves); never more workgroups than units
+static dim3 gate_grid(const ScanArgs& a, const bool waves = false) {
+  const uint64_t g = a.gate_grid ? a.gate_grid : waves ? kGateGridWaves : kGateGrid;
   return dim3((unsigned)std::min<uint64_t>(std::max<uint64_t>((a.ntiles + kBlock - 1) / kBlock, 1), g), 1, 1);
 }
 
@@ -1624,7 +1694,7 @@ static hipError_t launch_scan_kind(const ScanArgs& a, bool want_nl, bool want_li
       if (fin) {
         if (fin->waves && !fin->spans) return hipErrorInvalidValue;  // the wave form reads by spans only
         if (fin->waves)
-          hipLaunchKernelGGL((k_scan_fin<KIND, LOADS, ALIGNED, true>), gate_grid(a), dim3(kBlock), 0, s, a, *fin);
+          hipLaunchKernelGGL((k_scan_fin<KIND, LOADS, ALIGNED, true>), gate_grid(a, true), dim3(kBlock), 0, s, a, *fin);
         else
           hipLaunchKernelGGL((k_scan_fin<KIND, LOADS, ALIGNED, false>), gate_grid(a), dim3(kBlock), 0, s, a, *fin);
         return hipGetLastError();
@@ -1706,7 +1776,7 @@ static uint32_t pick_stagger(const ScanArgs& a, bool want_nl, bool want_lines, b
 }
 
 void describe_scan(const ScanArgs& a, bool want_nl, bool want_lines, bool emit, char* out, size_t cap, bool finishing,
-                   uint64_t total_bytes, bool spans, bool waves) {
+                   uint64_t total_bytes, bool spans, bool waves, uint32_t batch) {
   if (!out || !cap) return;
   const char* b[2] = {"false", "true"};
   if (a.pat.kind == kSet) return describe_set_scan(a, emit, out, cap);
@@ -1737,7 +1807,10 @@ void describe_scan(const ScanArgs& a, bool want_nl, bool want_lines, bool emit, 
     // in front of that whether it reads the candidates' passing 4 KiB spans only)
     const bool fin = finishing && scan_finishing(a, total_bytes);
     // and, in front of that, whether a wave owns a sketch group from its sketch words to its text (gated_pass_waves)
-    snprintf(out + n, cap - n, "%s%s%s gated by xsg::k_sketch (512 B/tile)", fin && spans && waves ? " a wave per group" : "",
+    // and, in front of that, how many of its groups the wave takes at a time (GateFinArgs::batch), if more than one
+    char bt[32] = "";
+    if (fin && spans && waves && batch > 1) snprintf(bt, sizeof bt, " in batches of %u", batch);
+    snprintf(out + n, cap - n, "%s%s%s%s gated by xsg::k_sketch (512 B/tile)", bt, fin && spans && waves ? " a wave per group" : "",
              fin && spans ? " by 4 KiB spans" : "", fin ? " finishing (xsg::k_scan_fin)" : "");
   }
 }
@@ -1755,7 +1828,8 @@ bool scan_finishing(const ScanArgs& a, uint64_t total_bytes) {
   static const bool on = [] { const char* e = getenv("XSG_GATE_FINISH"); return !(e && *e == '0'); }();
   if (!on || a.ntiles == 0 || a.tile_bytes != kDefaultTileBytes || !scan_gated(a, false, false)) return false;
   if (!a.pat.exact_tail && a.pat.plen > kTailMaskMaxPlen) return false;
-  return total_bytes < (1ull << kFinTotalBits) && gate_grid(a).x < (1u << (64u - kFinTotalBits));
+  // (the arrival field holds the grid of either form: which of the two launches is fin_args' choice, not known here)
+  return total_bytes < (1ull << kFinTotalBits) && std::max(gate_grid(a, false).x, gate_grid(a, true).x) < (1u << (64u - kFinTotalBits));
 }
 
 static hipError_t launch_scan(const ScanArgs& a_in, bool want_nl, bool want_lines, bool emit, hipStream_t s,

@@ -572,8 +572,8 @@ class Shard:
         return (np.ctypeslib.as_array(lens, shape=(nl.value,)), raw, np.ctypeslib.as_array(offs, shape=(nl.value,)))
 
     def scan_kernel_name(self, mode: int) -> str:
-        buf = C.create_string_buffer(160)
-        _check(self._lib.xsg_scan_kernel_name(self.h, mode, buf, 160))
+        buf = C.create_string_buffer(256)
+        _check(self._lib.xsg_scan_kernel_name(self.h, mode, buf, 256))
         return buf.value.decode()
 
     def tune(self, mode: int) -> int | None:
