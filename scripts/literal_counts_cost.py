@@ -5,14 +5,17 @@
 lexicon words and the 300 words of that script, 4096 seven-byte literals with 4096 distinct grams, and the dense list
 `e`, `th`.  For each list, on one binding in one process, --runs interleaved runs of
   parent xsg_count        xsg_count(XSG_COUNT_MATCHES) of the PARENT build (--parent TREE: a checkout of the parent commit
-                          with its library built): the only count a list has there
-  new xsg_count           the same call of this build (the list route is unchanged: a control)
-  count_literals K/C      xsg_count_literals of this build in its four forms: K = keys in LDS (1) or in global memory (0),
-                          C = candidates compacted through LDS (1) or verified in-lane (0)
+                          with its library built)
+  new xsg_count           the same call of this build
+  parent count_literals   xsg_count_literals of the parent build, where it has one
+  count_literals          xsg_count_literals of this build (keys in LDS, candidates compacted: the one form there is)
 a run = --calls timed synchronous calls (host clock) behind --warm untimed ones.  `scan_ms` is xsg_time_scan_kernel of
 the list: k_set_scan's count pass alone, the same loads and the same filter, the floor of any one-pass design.  One JSON
-line per (list, call) with every run's median, the ratio to the parent and to the scan, the parent's own max / min spread
-and the share of positions that are candidates (from the filter image, on one 16 MiB template)."""
+line per (list, call) with every run's median, the ratio to the parent's xsg_count and to the scan, that call's own
+max / min spread, for this build's calls the parent's run medians of the same call, the ratio to it (`ratio_to_same`)
+and the parent's spread of it (the runs alternate between the listed order and its reverse, so that neither build always
+runs behind the other), and the share of positions that are candidates (from the filter image, on one 16 MiB template).  The two builds'
+results are compared word for word before anything is timed."""
 import argparse
 import importlib.util
 import json
@@ -118,12 +121,6 @@ def main():
         sides[label] = (mod, ctx, mod.Shard(ctx, t.data_ptr(), cap, mod.make_chunks(off, ln)))
     sink = open(a.out, "a") if a.out else None
 
-    def variant(keys, compact):
-        def call():
-            os.environ["XSG_LITCOUNT_KEYS"], os.environ["XSG_LITCOUNT_COMPACT"] = keys, compact
-            return sides["new"][2].count_literals()
-        return call
-
     for name, lits in lists():
         lst = new.literal_list(lits)
         for _, ctx, _ in sides.values():
@@ -135,36 +132,34 @@ def main():
             ps = sides["parent"][2]
             calls["parent xsg_count"] = lambda ps=ps: ps.count(parent.COUNT_MATCHES)
         calls["new xsg_count"] = lambda: ns.count(new.COUNT_MATCHES)
-        for keys in ("1", "0"):
-            for compact in ("0", "1"):
-                calls[f"count_literals K{keys}C{compact}"] = variant(keys, compact)
-        ref = None
-        for k, fn in calls.items():  # parity: the four forms agree word for word; the list counts agree with each other
-            r = fn()
-            if k.startswith("count_literals"):
-                if ref is None:
-                    ref = r.tolist()
-                elif r.tolist() != ref:
-                    raise SystemExit(f"PARITY FAILURE ({name}): {k} differs from the first form")
-        if parent and calls["parent xsg_count"]().tolist() != calls["new xsg_count"]().tolist():
-            raise SystemExit(f"PARITY FAILURE ({name}): xsg_count of the two builds differs")
+        if parent and hasattr(ps, "count_literals"):
+            calls["parent count_literals"] = lambda ps=ps: ps.count_literals()
+        calls["count_literals"] = lambda: ns.count_literals()
+        ref = calls["count_literals"]().tolist()
+        # parity: the two builds agree word for word, call by call
+        for k in [k for k in calls if k.startswith("parent ")]:
+            if calls[k]().tolist() != calls[k.replace("parent ", "new " if k.endswith("xsg_count") else "")]().tolist():
+                raise SystemExit(f"PARITY FAILURE ({name}): {k[7:]} of the two builds differs")
         matches = int(calls["new xsg_count"]()[new.CTR_MATCHES])
         med = {k: [] for k in calls}
-        for _ in range(a.runs):  # interleaved: one run of each, a.runs times over
-            for k, fn in calls.items():
+        for r in range(a.runs):  # interleaved: one run of each, a.runs times over, every other time in reverse order
+            for k, fn in (list(calls.items()) if r % 2 == 0 else list(calls.items())[::-1]):
                 med[k].append(float(np.median(timed(fn, a.warm, a.calls))))
         scan_ms = ns.time_scan_kernel(new.COUNT_MATCHES, 10)
         base_key = "parent xsg_count" if parent else "new xsg_count"
         base = float(np.median(med[base_key]))
-        spread = max(med[base_key]) / min(med[base_key])
         for k, v in med.items():
             m = float(np.median(v))
+            same = "parent " + k.replace("new ", "")  # the parent's same call, for this build's
             row = {"what": "literal_counts", "list": name, "literals": len(lits), "gram": g, "candidate_rate": round(rate, 5),
                    "call": k, "bytes": total, "chunks": int(len(ln)), "list_matches": matches, "occurrences": int(sum(ref)),
                    "literals_that_occur": int(np.count_nonzero(ref)), "runs": a.runs, "calls_per_run": a.calls,
                    "run_median_ms": [round(x, 4) for x in v], "ms": round(m, 4), "ratio_to": base_key,
-                   "ratio": round(m / base, 4), "base_max_over_min": round(spread, 4), "scan_ms": round(scan_ms, 4),
+                   "ratio": round(m / base, 4), "max_over_min": round(max(v) / min(v), 4), "scan_ms": round(scan_ms, 4),
                    "ratio_to_scan": round(m / scan_ms, 3)}
+            if same in med and same != k:
+                row.update({"same_run_median_ms": [round(x, 4) for x in med[same]], "same_ms": round(float(np.median(med[same])), 4), "ratio_to_same": round(m / float(np.median(med[same])), 4),
+                            "same_max_over_min": round(max(med[same]) / min(med[same]), 4)})
             line = json.dumps(row)
             print(line, flush=True)
             if sink:

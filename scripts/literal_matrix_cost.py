@@ -15,7 +15,12 @@ median of its runs and their min..max.
           4096 seven-byte literals (a 2 GiB matrix, stream-ordered form only): every tile, or every other one, ends a chunk.  With the
           touched list and with XSG_LITMATRIX_TOUCHED=0 (every flush sweeps the histogram), and the memsets alone.
 The device legs also time the pass without chunks_with and under --grids workgroups (XSG_LITMATRIX_GRID): what the
-default grid and the summing of chunks_with in LDS were chosen by."""
+default grid and the summing of chunks_with in LDS were chosen by.  With --parent TREE (a checkout of the parent commit
+with its library built) they time the parent build's same calls on the same binding, interleaved with this build's,
+after comparing the two builds' count vectors, matrices and chunks_with word for word; a row of this build then carries
+the parent's run medians of the same call (`same_run_ms`), the ratio to it (`ratio_to_same`) and the parent's own
+max / min spread of it.  The runs alternate between the listed order and its reverse, so that neither build always
+runs behind the other: with one build in both seats the second seat measured up to 0.5 % off the first."""
 import argparse
 import ctypes as C
 import json
@@ -54,6 +59,7 @@ def main():
     ap.add_argument("--legs", default="floor,today,hard")
     ap.add_argument("--grids", type=int, nargs="*", default=[2048, 4096, 65536],
                     help="XSG_LITMATRIX_GRID values timed beside the default grid (64 workgroups per compute unit)")
+    ap.add_argument("--parent", default="", help="a tree of the parent commit with x-search_amd/lib/libxsg.so built")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     import torch
@@ -77,6 +83,12 @@ def main():
     ctx = xsg.Context(0)
     ctx.set_pattern(b"x")
     shard = xsg.Shard(ctx, t.data_ptr(), cap, xsg.make_chunks(off, ln))
+    pctx = pshard = None
+    if a.parent:
+        pxsg = literal_counts_cost.load_xsg(Path(a.parent).resolve(), "xsg_parent")
+        pctx = pxsg.Context(0)
+        pctx.set_pattern(b"x")
+        pshard = pxsg.Shard(pctx, t.data_ptr(), cap, pxsg.make_chunks(off, ln))
     # a stream of the caller's for the stream-ordered forms, the events and everything that reads their results (the null
     # stream would stand for the context's own, which no event recorded here sees)
     side = torch.cuda.Stream()
@@ -119,15 +131,15 @@ def main():
 
     def interleaved(calls, measure):
         runs = {k: [] for k in calls}
-        for _ in range(a.runs):
-            for k, fn in calls.items():
+        for r in range(a.runs):  # every other run in reverse order: no call always follows the same neighbour
+            for k, fn in (list(calls.items()) if r % 2 == 0 else list(calls.items())[::-1]):
                 runs[k].append(measure(fn))
         return runs
 
     def stats(v):
         return {"run_ms": [round(x, 4) for x in v], "ms": round(float(np.median(v)), 4), "min_ms": round(min(v), 4), "max_ms": round(max(v), 4)}
 
-    def matrix_calls(n, k, d_m, d_w, d_c):
+    def matrix_calls(shard, n, k, d_m, d_w, d_c):
         def matrix(touched, grid=None, with_chunks=True):
             def call():
                 os.environ["XSG_LITMATRIX_TOUCHED"] = touched
@@ -152,7 +164,16 @@ def main():
         d_m = torch.empty(n * k, dtype=torch.int64, device=dev)
         d_w = torch.empty(k, dtype=torch.int64, device=dev)
         d_c = torch.empty(k, dtype=torch.int64, device=dev)
-        calls = matrix_calls(n, k, d_m, d_w, d_c)
+        calls = matrix_calls(shard, n, k, d_m, d_w, d_c)
+        if pshard:  # the parent's same calls, each beside this build's
+            pctx.set_literals(xsg.literal_list(lits), 0)
+            parent_calls = matrix_calls(pshard, n, k, d_m, d_w, d_c)
+            paired = {}
+            for call, fn in calls.items():
+                if "grid" not in call and call != "memsets alone":
+                    paired["parent " + call] = parent_calls[call]
+                paired[call] = fn
+            calls = paired
         # parity before any timing: both forms of the flush agree, and the columns sum to xsg_count_literals' counts
         calls["matrix"]()
         torch.cuda.synchronize()
@@ -164,12 +185,26 @@ def main():
             raise SystemExit(f"PARITY FAILURE ({what}, {name}): the two forms of the flush differ")
         if not torch.equal(first.view(n, k).sum(dim=0), d_c) or not torch.equal((first.view(n, k) > 0).sum(dim=0), first_w):
             raise SystemExit(f"PARITY FAILURE ({what}, {name}): column sums or chunks_with")
+        if pshard:  # the two builds agree word for word: both forms of the flush, chunks_with, the count vector
+            counts = d_c.clone()
+            for form in ("parent matrix", "parent matrix, no touched list"):
+                d_m.fill_(-1), d_w.fill_(-1), d_c.fill_(-1)
+                calls[form]()
+                calls["parent count_literals (floor)"]()
+                torch.cuda.synchronize()
+                if not (torch.equal(first, d_m) and torch.equal(first_w, d_w) and torch.equal(counts, d_c)):
+                    raise SystemExit(f"PARITY FAILURE ({what}, {name}): {form} or its count vector differs from this build's")
+            del counts
         runs = interleaved(calls, device_ms)
         floor = stats(runs["count_literals (floor)"])
         memset = float(np.median(runs["memsets alone"]))
         for call, v in runs.items():
             row = {"what": what, "list": name, "literals": k, "chunks": n, "chunk_bytes": chunk_bytes, "matrix_words": n * k,
                    "call": call, "clock": "device (events)", "runs": a.runs, "calls_per_run": a.calls, **stats(v)}
+            if "parent " + call in runs:
+                same = runs["parent " + call]
+                row.update({"same_run_ms": [round(x, 4) for x in same], "same_ms": round(float(np.median(same)), 4), "ratio_to_same": round(row["ms"] / float(np.median(same)), 4),
+                            "same_max_over_min": round(max(same) / min(same), 4)})
             if call.startswith("matrix"):
                 m = row["ms"]
                 row.update({"floor_ms": floor["ms"], "floor_min_ms": floor["min_ms"], "floor_max_ms": floor["max_ms"],
@@ -212,7 +247,8 @@ def main():
         total = int(a.gib * 2**30)
         for name, lits, size in (("8-words", named["8-words"], 2048), ("4096-distinct-grams", named["4096-distinct-grams"], 32768)):
             m = total // size
-            shard.rebind(t.data_ptr(), cap, xsg.make_chunks(np.arange(m, dtype=np.uint64) * size, np.full(m, size, dtype=np.uint64)))
+            for sh in filter(None, (shard, pshard)):
+                sh.rebind(t.data_ptr(), cap, xsg.make_chunks(np.arange(m, dtype=np.uint64) * size, np.full(m, size, dtype=np.uint64)))
             device_leg("hard", name, lits, m, size)
 
 

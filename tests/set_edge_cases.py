@@ -21,7 +21,7 @@ import xsg
 from set_cases import TILE, u8
 
 # ---- A. the bounded grid of k_set_scan -----------------------------------------------------------------------------------------
-GRID_PER_CU = 8  # x-search_amd/csrc/xsg_set_kernels.hip:16 (kSetGridPerCu); set_grid launches min(ntiles, 8 * CUs) workgroups
+GRID_PER_CU = 8  # kSetGridPerCu of x-search_amd/csrc/xsg_set_kernels.hip; set_grid launches min(ntiles, 8 * CUs) workgroups
 GRID_LITS = SC.END_LITS[4]  # (b"kqzw", b"needle"): g = 4
 _FILLER = SC._LINE * 3  # (holds no byte of `kqzw` and no `need`)
 

@@ -1,12 +1,10 @@
 """xsg_count_literals / xsg_count_literals_async / xsg_literal_counter_*: one count per literal of a list in one pass.
 
 Expected values are tests/literal_counts_model.py's (bytes.find per literal and chunk; tests/test_literal_counts_host.py
-pins it to the oracle): exact equality everywhere.  Every case runs the synchronous form in all four builds of the
-kernel (keys in LDS or not, candidates verified in-lane or compacted: the A/B switches XSG_LITCOUNT_KEYS and
-XSG_LITCOUNT_COMPACT), the stream-ordered form on a side stream into a buffer pre-filled with 0xFF, and a LiteralCounter
-fed the same blocks.  The cases are those of the literal-list tests, which sit at the edges of k_set_scan's tile loop."""
+pins it to the oracle): exact equality everywhere.  Every case runs the synchronous form, the stream-ordered form on a
+side stream into a buffer pre-filled with 0xFF, and a LiteralCounter fed the same blocks.  The cases are those of the
+literal-list tests, which sit at the edges of k_set_scan's tile loop."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
@@ -21,7 +19,6 @@ from set_gpu_util import IC, bind_tight, list_all_modes
 
 pytestmark = pytest.mark.gpu
 TILE, WAVE_LOAD = SC.TILE, SC.WAVE_LOAD
-VARIANTS = [(k, c) for k in ("1", "0") for c in ("0", "1")]  # (XSG_LITCOUNT_KEYS, XSG_LITCOUNT_COMPACT)
 
 
 @pytest.fixture(scope="module")
@@ -55,19 +52,6 @@ def side():
     return Side()
 
 
-def with_variant(keys, compact, fn):
-    saved = {k: os.environ.get(k) for k in ("XSG_LITCOUNT_KEYS", "XSG_LITCOUNT_COMPACT")}
-    os.environ["XSG_LITCOUNT_KEYS"], os.environ["XSG_LITCOUNT_COMPACT"] = keys, compact
-    try:
-        return fn()
-    finally:
-        for k, v in saved.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-
-
 def check(gs, side, blocks, lits, flags, what, counter=True):
     """all three forms against the model -> the expected counts"""
     blocks = list(blocks)
@@ -77,8 +61,6 @@ def check(gs, side, blocks, lits, flags, what, counter=True):
     got = gs.shard.count_literals()
     print(what, "k", len(lits), "sum", int(got.sum()), "first", got.tolist()[:12], "want", want[:12])
     assert got.dtype == np.uint64 and got.tolist() == want, (what, "synchronous")
-    for keys, compact in VARIANTS:
-        assert with_variant(keys, compact, lambda: gs.shard.count_literals().tolist()) == want, (what, "keys", keys, "compact", compact)
     assert side.run(gs.shard, len(lits)) == want, (what, "stream-ordered")
     if counter:
         lc = xsg.LiteralCounter(0, lst, flags)

@@ -2,10 +2,9 @@
 of chunks that hold each literal, in one pass.
 
 Expected values are tests/literal_matrix_model.py's (tests/literal_counts_model.py per chunk): exact equality everywhere.
-Every case runs the synchronous form with the keys in LDS and in global memory (XSG_LITCOUNT_KEYS), with every flush a
-sweep (XSG_LITMATRIX_TOUCHED=0), once more without chunks_with, and the stream-ordered form on a side stream into buffers
-pre-filled with 0xFF that are 8 words longer than needed; the column sums are compared with xsg_count_literals on the same
-binding."""
+Every case runs the synchronous form, the same with every flush a sweep (XSG_LITMATRIX_TOUCHED=0), once more without
+chunks_with, and the stream-ordered form on a side stream into buffers pre-filled with 0xFF that are 8 words longer than
+needed; the column sums are compared with xsg_count_literals on the same binding."""
 import ctypes as C
 import os
 
@@ -94,8 +93,6 @@ def check(gs, side, blocks, lits, flags, what, want=None):
     print(what, "n", n, "k", k, "sum", sum(map(sum, rows)), "chunks_with", freq[:12], "got", got[1][:12])
     assert got[0] == rows, (what, "synchronous, matrix")
     assert got[1] == freq, (what, "synchronous, chunks_with")
-    for keys in ("1", "0"):
-        assert with_env({"XSG_LITCOUNT_KEYS": keys}, lambda: sync(gs)) == (rows, freq), (what, "keys", keys)
     assert with_env({"XSG_LITMATRIX_TOUCHED": "0"}, lambda: sync(gs)) == (rows, freq), (what, "every flush a sweep")
     assert sync(gs, False) == (rows, None), (what, "synchronous, no chunks_with")
     assert side.run(gs.shard, n, k) == (rows, freq), (what, "stream-ordered")

@@ -72,7 +72,7 @@ def test_walk_blocks(gs, oracle, name, blocks, lits):
     assert want["count_matches"] > 300_000
 
 
-# ---- C. set_fold4 against set_fold ---------------------------------------------------------------------------------------------------
+# ---- C. fold4 against set_fold -------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("g,gi", E.FOLD_CASES, ids=["g%d-%s" % (g, E.FOLD_GROUPS[gi].name) for g, gi in E.FOLD_CASES])
 def test_fold(gs, oracle, g, gi):
     """every byte value but '\\n' at every gram position and behind the gram, verbatim, case-swapped and replaced by its

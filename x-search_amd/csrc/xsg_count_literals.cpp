@@ -34,12 +34,6 @@ int xsg::enqueue_count_literals(xsg_shard* s, hipStream_t st, uint64_t* d_counts
   l.counts = reinterpret_cast<unsigned long long*>(d_counts);
   l.nlits = c->set_count;
   l.idx_off = c->set_idx_off;
-  // the two design choices of DESIGN.md 3.5e as measured there -- keys in LDS, candidates compacted -- and their A/B
-  // switches in the same build (XSG_LITCOUNT_KEYS=0: keys in global memory; XSG_LITCOUNT_COMPACT=0: verify in-lane)
-  const char* k = XSG_TOGGLE("XSG_LITCOUNT_KEYS");
-  l.keys_lds = !(k && *k == '0');
-  const char* q = XSG_TOGGLE("XSG_LITCOUNT_COMPACT");
-  l.compact = !(q && *q == '0');
   HIP_TRY(launch_set_count_literals(a, l, st));
   return XSG_OK;
 }
@@ -93,8 +87,6 @@ int xsg::enqueue_count_literals_chunks(xsg_shard* s, hipStream_t st, uint64_t* d
   l.chunks_with = reinterpret_cast<unsigned long long*>(d_chunks_with);
   l.nlits = c->set_count;
   l.idx_off = c->set_idx_off;
-  const char* k = XSG_TOGGLE("XSG_LITCOUNT_KEYS");
-  l.keys_lds = !(k && *k == '0');
   // the touched list of DESIGN.md 3.5f and its A/B switch (XSG_LITMATRIX_TOUCHED=0: every flush sweeps the histogram)
   const char* t = XSG_TOGGLE("XSG_LITMATRIX_TOUCHED");
   l.touched = !(t && *t == '0');

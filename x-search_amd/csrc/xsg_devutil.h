@@ -97,6 +97,16 @@ __device__ __forceinline__ uint32_t wave_units_combine(uint32_t us) {
 // ---------------------------------------------------------------------------
 // per-unit byte tests
 // ---------------------------------------------------------------------------
+// simd::toLower on 4 bytes at once (src/utils/string_utils.cpp:11-33): bytes in
+// 'A'..'Z' get bit 5 set, everything else (incl. bytes >= 0x80) is unchanged.
+__device__ __forceinline__ uint32_t fold4(uint32_t x) {
+  const uint32_t t = x & 0x7f7f7f7fu;
+  const uint32_t ge_A = t + 0x3f3f3f3fu;  // bit 7 set <=> low 7 bits >= 0x41
+  const uint32_t gt_Z = t + 0x25252525u;  // bit 7 set <=> low 7 bits >= 0x5b
+  const uint32_t upper = ge_A & ~gt_Z & ~x & 0x80808080u;
+  return x | (upper >> 2);
+}
+
 // exact 0x80-per-byte flags of bytes equal to '\n'
 __device__ __forceinline__ uint32_t nl_flags(uint32_t d) {
   const uint32_t x = d ^ 0x0a0a0a0au;

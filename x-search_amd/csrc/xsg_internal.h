@@ -321,13 +321,12 @@ hipError_t launch_set_verify(const RxPreArgs& a, hipStream_t s);
 void describe_set_scan(const ScanArgs& a, bool emit, char* out, size_t cap);
 // k_set_count_literals (xsg_count_literals*): k_set_scan's pass with the verify step inside it, one count per literal.  What
 // it needs beyond ScanArgs travels as a second kernel parameter, so that every other kernel keeps its argument block.  The
-// kernel ADDS to counts[0 .. nlits): the caller zeroes them on the stream in front of the launch, or accumulates.
+// kernel ADDS to counts[0 .. nlits): the caller zeroes them on the stream in front of the launch, or accumulates.  One
+// form: the sorted keys in LDS, a wave's candidates packed through LDS before they are verified.
 struct LitCountArgs {
   unsigned long long* counts;  // device, one word per literal in listing order
   uint32_t nlits;              // literals of the list (SetProgram::count)
   uint32_t idx_off;            // byte offset of SetTable::idx inside PatternDev::d_pat (SetProgram::idx_offset)
-  uint32_t keys_lds;           // the sorted keys are copied into LDS (XSG_LITCOUNT_KEYS=0 is the A/B switch)
-  uint32_t compact;            // a wave's candidates are packed through LDS before they are verified (XSG_LITCOUNT_COMPACT=0: in-lane)
 };
 hipError_t launch_set_count_literals(const ScanArgs& a, const LitCountArgs& c, hipStream_t s);
 // k_set_count_literals_chunks (xsg_count_literals_chunks*): the same pass with the chunk boundaries kept.  The kernel ADDS
@@ -338,7 +337,6 @@ struct LitMatrixArgs {
   unsigned long long* chunks_with;  // device, one word per literal, or null: not wanted
   uint32_t nlits;                   // literals of the list (SetProgram::count)
   uint32_t idx_off;                 // byte offset of SetTable::idx inside PatternDev::d_pat
-  uint32_t keys_lds;                // the sorted keys are copied into LDS (XSG_LITCOUNT_KEYS=0 is the A/B switch)
   uint32_t touched;                 // the flush walks the touched list (XSG_LITMATRIX_TOUCHED=0: it always sweeps)
 };
 hipError_t launch_set_count_literals_chunks(const ScanArgs& a, const LitMatrixArgs& c, uint32_t forced_grid, hipStream_t s);

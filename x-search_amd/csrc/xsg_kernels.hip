@@ -33,21 +33,11 @@
 
 namespace xsg {
 
-// (cross-lane helpers, byte tests and newline searches: xsg_devutil.h)
+// (cross-lane helpers, byte tests, fold4 and newline searches: xsg_devutil.h)
 
 constexpr uint32_t kLdsPattern = 1024;  // bytes of a long pattern kept in LDS (k_scan<kLong>); the rest is read from its device copy
 
 // w[b] = the 4 bytes starting at byte b of the lane's 32-byte view (own unit + neighbour's)
-// simd::toLower on 4 bytes at once (src/utils/string_utils.cpp:11-33): bytes in
-// 'A'..'Z' get bit 5 set, everything else (incl. bytes >= 0x80) is unchanged.
-__device__ __forceinline__ uint32_t fold4(uint32_t x) {
-  const uint32_t t = x & 0x7f7f7f7fu;
-  const uint32_t ge_A = t + 0x3f3f3f3fu;  // bit 7 set <=> low 7 bits >= 0x41
-  const uint32_t gt_Z = t + 0x25252525u;  // bit 7 set <=> low 7 bits >= 0x5b
-  const uint32_t upper = ge_A & ~gt_Z & ~x & 0x80808080u;
-  return x | (upper >> 2);
-}
-
 template <int N>
 __device__ __forceinline__ void windows(const uint32_t (&d)[8], uint32_t (&w)[N]) {
 #pragma unroll

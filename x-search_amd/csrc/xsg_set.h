@@ -61,28 +61,38 @@ struct SetTable {
   const uint16_t* idx = nullptr;
 };
 
-// Length of the first-listed literal that occurs at d[p] of a chunk of L bytes, or 0.  p + g <= L is the caller's to
-// ensure (the scan reports no other position); nothing at or beyond L is read.
-XSG_SET_HD uint32_t set_verify_at(const SetTable& T, const uint8_t* d, uint64_t p, uint64_t L, bool icase) {
-  const uint32_t v = set_gram_at(d + p, T.g, icase);
-  uint32_t lo = 0, hi = T.ngrams;
+// The two steps of a verify.  set_gram_find: is gram v one of the sorted keys[0 .. ngrams)?  *k receives the index of
+// the first key >= v (binary search), the gram's own when it is found.  set_entry_at: do the bytes of entry e's literal
+// fit the `room` left in the chunk at `at` and equal the chunk's there (folded under icase)?  *len receives the literal's
+// length; no byte at or beyond at + room is read.
+XSG_SET_HD bool set_gram_find(const uint32_t* keys, uint32_t ngrams, uint32_t v, uint32_t* k) {
+  uint32_t lo = 0, hi = ngrams;
   while (lo < hi) {  // first key >= v
     const uint32_t mid = (lo + hi) >> 1;
-    if (T.keys[mid] < v)
+    if (keys[mid] < v)
       lo = mid + 1u;
     else
       hi = mid;
   }
-  if (lo == T.ngrams || T.keys[lo] != v) return 0u;
-  const uint64_t room = L - p;
-  for (uint32_t e = T.first[lo]; e < T.first[lo + 1u]; ++e) {
-    const uint32_t len = T.ent[e] & 0xffu;
-    if (len > room) continue;
-    const uint8_t* lit = T.bytes + (T.ent[e] >> 8);
-    uint32_t k = T.g;  // (the gram is the literal's start: already compared)
-    while (k < len && set_fold(d[p + k], icase) == lit[k]) ++k;
-    if (k == len) return len;
-  }
+  *k = lo;
+  return lo != ngrams && keys[lo] == v;
+}
+XSG_SET_HD bool set_entry_at(const SetTable& T, uint32_t e, const uint8_t* at, uint64_t room, bool icase, uint32_t* len) {
+  const uint32_t n = *len = T.ent[e] & 0xffu;
+  if (n > room) return false;
+  const uint8_t* lit = T.bytes + (T.ent[e] >> 8);
+  uint32_t k = T.g;  // (the gram is the literal's start: already compared)
+  while (k < n && set_fold(at[k], icase) == lit[k]) ++k;
+  return k == n;
+}
+
+// Length of the first-listed literal that occurs at d[p] of a chunk of L bytes, or 0.  p + g <= L is the caller's to
+// ensure (the scan reports no other position); nothing at or beyond L is read.
+XSG_SET_HD uint32_t set_verify_at(const SetTable& T, const uint8_t* d, uint64_t p, uint64_t L, bool icase) {
+  uint32_t k, len;
+  if (!set_gram_find(T.keys, T.ngrams, set_gram_at(d + p, T.g, icase), &k)) return 0u;
+  for (uint32_t e = T.first[k]; e < T.first[k + 1u]; ++e)
+    if (set_entry_at(T, e, d + p, L - p, icase, &len)) return len;
   return 0u;
 }
 
@@ -93,25 +103,10 @@ XSG_SET_HD uint32_t set_verify_at(const SetTable& T, const uint8_t* d, uint64_t 
 template <typename Visit>
 XSG_SET_HD void set_count_at(const SetTable& T, const uint8_t* d, uint64_t p, uint64_t L, bool icase, Visit&& visit,
                              const uint32_t* keys) {
-  const uint32_t v = set_gram_at(d + p, T.g, icase);
-  uint32_t lo = 0, hi = T.ngrams;
-  while (lo < hi) {  // first key >= v
-    const uint32_t mid = (lo + hi) >> 1;
-    if (keys[mid] < v)
-      lo = mid + 1u;
-    else
-      hi = mid;
-  }
-  if (lo == T.ngrams || keys[lo] != v) return;
-  const uint64_t room = L - p;
-  for (uint32_t e = T.first[lo]; e < T.first[lo + 1u]; ++e) {
-    const uint32_t len = T.ent[e] & 0xffu;
-    if (len > room) continue;
-    const uint8_t* lit = T.bytes + (T.ent[e] >> 8);
-    uint32_t k = T.g;
-    while (k < len && set_fold(d[p + k], icase) == lit[k]) ++k;
-    if (k == len) visit((uint32_t)T.idx[e]);
-  }
+  uint32_t k, len;
+  if (!set_gram_find(keys, T.ngrams, set_gram_at(d + p, T.g, icase), &k)) return;
+  for (uint32_t e = T.first[k]; e < T.first[k + 1u]; ++e)
+    if (set_entry_at(T, e, d + p, L - p, icase, &len)) visit((uint32_t)T.idx[e]);
 }
 
 template <typename Visit>

@@ -8,6 +8,9 @@
 //   k_set_count_literals     xsg_count_literals: the scan with the verify step inside its own pass, one count per literal
 //   k_set_count_literals_chunks   xsg_count_literals_chunks: the same pass with the chunk boundaries kept, a count per
 //                            chunk and literal and the number of chunks that hold each literal
+// The three scanning kernels share one copy of each stage: set_stage_filter, set_tile_masks (from the chunk lookup to the
+// clipped candidate masks), set_verify_load (the compacted verify of one wave-load) and lit_stage (histogram and keys);
+// LitLds is the one layout of the counting kernels' dynamic LDS, for the kernels' pointers and the launchers' byte count.
 #include "xsg_devutil.h"
 #include "xsg_litmatrix.h"
 #include "xsg_set.h"
@@ -18,15 +21,6 @@ constexpr int kSetLoads = 4;                                // 16-byte units per
 constexpr uint32_t kSetWaveSpan = kWaveLoad * kSetLoads;
 constexpr uint32_t kSetTile = kSetWaveSpan * kWaves;
 constexpr uint32_t kSetGridPerCu = 8;                       // workgroups per compute unit of the bounded grid
-
-// ASCII-lower the four bytes of a dword: 0x20 is added to every byte in 'A'..'Z'
-__device__ __forceinline__ uint32_t set_fold4(uint32_t d) {
-  const uint32_t low7 = d & 0x7f7f7f7fu;
-  const uint32_t ge_A = low7 + 0x3f3f3f3fu;  // bit 7 of a byte set <=> its low 7 bits >= 'A'
-  const uint32_t gt_Z = low7 + 0x25252525u;  // ... <=> its low 7 bits > 'Z'
-  const uint32_t is_upper = ge_A & ~gt_Z & ~d & 0x80808080u;  // (bytes >= 0x80 are not letters)
-  return d | (is_upper >> 2);
-}
 
 // candidate bits of one unit: bit b set <=> the g-gram that starts at byte b of the unit has its filter bit.  w[0..3]:
 // the unit, w[4]: the dword behind it (the neighbour lane's first).
@@ -44,6 +38,97 @@ __device__ __forceinline__ uint32_t set_cand16(const uint32_t (&w)[5], const uin
   return m;
 }
 
+// the filter into LDS: once per workgroup, 16-byte loads (8 KiB = 512 units, two per thread).  The barrier is the caller's.
+__device__ __forceinline__ void set_stage_filter(const PatternDev& P, uint32_t* s_filter, uint32_t tid) {
+  const uint4* src = reinterpret_cast<const uint4*>(P.d_pat);
+  uint4* dst = reinterpret_cast<uint4*>(s_filter);
+  for (uint32_t k = tid; k < kSetFilterBytes / 16u; k += kBlock) dst[k] = src[k];
+}
+
+// the verify table inside the pattern's blob; the counting kernels pass the offset of SetTable::idx, the search leaves it null
+__device__ __forceinline__ SetTable set_table(const PatternDev& P) {
+  SetTable T;
+  T.keys = reinterpret_cast<const uint32_t*>(P.d_pat + P.set_keys);
+  T.first = reinterpret_cast<const uint32_t*>(P.d_pat + P.set_first);
+  T.ent = reinterpret_cast<const uint32_t*>(P.d_pat + P.set_ent);
+  T.bytes = P.d_pat + P.set_bytes;
+  T.ngrams = P.set_ngrams;
+  T.g = P.set_g;
+  return T;
+}
+__device__ __forceinline__ SetTable set_table(const PatternDev& P, uint32_t idx_off) {
+  SetTable T = set_table(P);
+  T.idx = reinterpret_cast<const uint16_t*>(P.d_pat + idx_off);
+  return T;
+}
+
+// ---- the tile stage ------------------------------------------------------------------------------------------------------------
+// What a kernel still needs of a tile behind its candidate masks: the chunk, its bytes and length, and where this wave's
+// 4 KiB begin inside the chunk.
+struct SetTile {
+  uint32_t c;
+  const uint8_t* cbase;
+  uint64_t L;
+  uint64_t wbase;
+};
+// masks[j]: the candidate bits of this lane's unit of load j.  u[j]: the unit as loaded (k_set_scan counts newlines on it;
+// the counting kernels do not read it).
+template <bool ICASE>
+__device__ __forceinline__ SetTile set_tile_masks(const ScanArgs& A, uint64_t tile, uint32_t g, const uint32_t* s_filter,
+                                                  uint32_t lane, uint32_t wave, uint4 (&u)[kSetLoads],
+                                                  uint32_t (&masks)[kSetLoads]) {
+  SetTile t;
+  t.c = A.tile_chunk ? A.tile_chunk[tile] : 0u;
+  const ChunkDev ch = A.chunks[t.c];
+  t.cbase = A.base + ch.offset;
+  t.L = ch.length;
+  const uint64_t Lr = (t.L + 15u) & ~(uint64_t)15u;
+  // a position p is a candidate only if its whole gram lies inside the chunk: p + g <= L.  Every bit at or beyond
+  // `limit` is cleared below, so no decision rests on a byte at or beyond the chunk's end.
+  const uint64_t limit = t.L >= g ? t.L - g + 1u : 0u;
+  const uint64_t toff = (tile - A.chunk_tile0[t.c]) * (uint64_t)kSetTile;
+  t.wbase = toff + (uint64_t)wave * kSetWaveSpan;
+
+  // ---- the wave's 4 KiB: four 16-byte loads per lane, all issued before any is used; units at or beyond the chunk's
+  // padded end are not read.  The dword behind the span (the next wave's or the next tile's first, same chunk) serves
+  // the last grams of lane 63's last unit.
+#pragma unroll
+  for (int j = 0; j < kSetLoads; ++j) {
+    const uint64_t off = t.wbase + ((uint32_t)j * kWaveLoad + lane * kUnit);  // (inside the span: 32 bits)
+    u[j] = off < Lr ? *reinterpret_cast<const uint4*>(t.cbase + off) : uint4{0u, 0u, 0u, 0u};
+  }
+  const uint64_t behind = t.wbase + kSetWaveSpan;
+  const uint32_t edge_last = behind < Lr ? *reinterpret_cast<const uint32_t*>(t.cbase + behind) : 0u;
+
+#pragma unroll
+  for (int j = 0; j < kSetLoads; ++j) {
+    uint32_t w[5] = {u[j].x, u[j].y, u[j].z, u[j].w, 0u};
+    // lane 63's neighbour: lane 0 of the next wave-load, or the dword behind the span
+    const uint32_t edge = j + 1 < kSetLoads ? (uint32_t)__builtin_amdgcn_readfirstlane((int)u[j + 1 < kSetLoads ? j + 1 : j].x) : edge_last;
+    w[4] = from_next_lane(w[0], edge, lane);
+    if (ICASE) {
+#pragma unroll
+      for (int q = 0; q < 5; ++q) w[q] = fold4(w[q]);
+    }
+    uint32_t m;
+    switch (g) {  // (wave-uniform)
+      case 1: m = set_cand16<1>(w, s_filter); break;
+      case 2: m = set_cand16<2>(w, s_filter); break;
+      case 3: m = set_cand16<3>(w, s_filter); break;
+      default: m = set_cand16<4>(w, s_filter); break;
+    }
+    // (the offset the load above used, added in 64 bits: spelled as one expression for both, the compiler keeps all four
+    // alive from the loads to here -- 6 to 8 VGPRs and a wave per SIMD in the emit pass, profiles/set_refactor_registers.txt)
+    const uint64_t unit_off = t.wbase + (uint64_t)j * kWaveLoad + (uint64_t)lane * kUnit;
+    if (unit_off >= limit)
+      m = 0u;
+    else if (unit_off + kUnit > limit)
+      m &= (1u << (uint32_t)(limit - unit_off)) - 1u;
+    masks[j] = m;
+  }
+  return t;
+}
+
 template <bool EMIT, bool ICASE>
 __global__ __launch_bounds__(kBlock) void k_set_scan(const ScanArgs A, const uint32_t want_nl) {
   __shared__ __attribute__((aligned(16))) uint32_t s_filter[kSetFilterWords];
@@ -53,67 +138,19 @@ __global__ __launch_bounds__(kBlock) void k_set_scan(const ScanArgs A, const uin
   const uint32_t tid = threadIdx.x;
   const uint32_t lane = tid & 63u;
   const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  // the filter: once per workgroup, 16-byte loads (8 KiB = 512 units, two per thread)
-  {
-    const uint4* src = reinterpret_cast<const uint4*>(P.d_pat);
-    uint4* dst = reinterpret_cast<uint4*>(s_filter);
-    for (uint32_t k = tid; k < kSetFilterBytes / 16u; k += kBlock) dst[k] = src[k];
-  }
+  set_stage_filter(P, s_filter, tid);
   __syncthreads();
   const uint32_t g = P.set_g;
 
   for (uint64_t tile = blockIdx.x; tile < A.ntiles; tile += gridDim.x) {
     if (EMIT && A.tile_cnt[tile] == 0) continue;  // (workgroup-uniform)
-    const uint32_t c = A.tile_chunk ? A.tile_chunk[tile] : 0u;
-    const ChunkDev ch = A.chunks[c];
-    const uint8_t* cbase = A.base + ch.offset;
-    const uint64_t L = ch.length;
-    const uint64_t Lr = (L + 15u) & ~(uint64_t)15u;
-    // a position p is a candidate only if its whole gram lies inside the chunk: p + g <= L.  Every bit at or beyond
-    // `limit` is cleared below, so no decision rests on a byte at or beyond the chunk's end.
-    const uint64_t limit = L >= g ? L - g + 1u : 0u;
-    const uint64_t toff = (tile - A.chunk_tile0[c]) * (uint64_t)kSetTile;
-    const uint64_t wbase = toff + (uint64_t)wave * kSetWaveSpan;
-
-    // ---- the wave's 4 KiB: four 16-byte loads per lane, all issued before any is used; units at or beyond the chunk's
-    // padded end are not read.  The dword behind the span (the next wave's or the next tile's first, same chunk) serves
-    // the last grams of lane 63's last unit.
     uint4 u[kSetLoads];
-#pragma unroll
-    for (int j = 0; j < kSetLoads; ++j) {
-      const uint64_t off = wbase + (uint64_t)j * kWaveLoad + (uint64_t)lane * kUnit;
-      u[j] = off < Lr ? *reinterpret_cast<const uint4*>(cbase + off) : uint4{0u, 0u, 0u, 0u};
-    }
-    const uint64_t behind = wbase + kSetWaveSpan;
-    const uint32_t edge_last = behind < Lr ? *reinterpret_cast<const uint32_t*>(cbase + behind) : 0u;
-
     uint32_t masks[kSetLoads];
+    const SetTile t = set_tile_masks<ICASE>(A, tile, g, s_filter, lane, wave, u, masks);
+    const uint64_t L = t.L, wbase = t.wbase;
     uint32_t cnt = 0;
 #pragma unroll
-    for (int j = 0; j < kSetLoads; ++j) {
-      uint32_t w[5] = {u[j].x, u[j].y, u[j].z, u[j].w, 0u};
-      // lane 63's neighbour: lane 0 of the next wave-load, or the dword behind the span
-      const uint32_t edge = j + 1 < kSetLoads ? (uint32_t)__builtin_amdgcn_readfirstlane((int)u[j + 1 < kSetLoads ? j + 1 : j].x) : edge_last;
-      w[4] = from_next_lane(w[0], edge, lane);
-      if (ICASE) {
-#pragma unroll
-        for (int q = 0; q < 5; ++q) w[q] = set_fold4(w[q]);
-      }
-      uint32_t m;
-      switch (g) {  // (wave-uniform)
-        case 1: m = set_cand16<1>(w, s_filter); break;
-        case 2: m = set_cand16<2>(w, s_filter); break;
-        case 3: m = set_cand16<3>(w, s_filter); break;
-        default: m = set_cand16<4>(w, s_filter); break;
-      }
-      const uint64_t unit_off = wbase + (uint64_t)j * kWaveLoad + (uint64_t)lane * kUnit;
-      if (unit_off >= limit)
-        m = 0u;
-      else if (unit_off + kUnit > limit)
-        m &= (1u << (uint32_t)(limit - unit_off)) - 1u;
-      masks[j] = m;
-      cnt += (uint32_t)__popc(m);
-    }
+    for (int j = 0; j < kSetLoads; ++j) cnt += (uint32_t)__popc(masks[j]);
 
     if (!EMIT) {
       const uint32_t wc = wave_sum_u32(cnt);
@@ -157,14 +194,14 @@ __global__ __launch_bounds__(kBlock) void k_set_scan(const ScanArgs A, const uin
         const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
         if (m) {
           uint64_t r = rank + (incl - pc);
-          const uint64_t unit_off = wbase + (uint64_t)j * kWaveLoad + (uint64_t)lane * kUnit;
+          const uint64_t load_off = wbase + (uint64_t)j * kWaveLoad;
           uint32_t mm = m;
           while (mm) {
             const uint32_t b = (uint32_t)__ffs((int)mm) - 1u;
             mm &= mm - 1u;
             if (A.m_cap == 0 || r < A.m_cap) {
-              A.m_pos[r] = unit_off + b;
-              A.m_chunk[r] = c;
+              A.m_pos[r] = load_off + (lane * kUnit + b);  // (= this unit's offset in set_tile_masks, + b: keep them equal)
+              A.m_chunk[r] = t.c;
             }
             ++r;
           }
@@ -180,29 +217,22 @@ __global__ __launch_bounds__(kBlock) void k_set_verify(const RxPreArgs A) {
   if (i >= A.n) return;
   const PatternDev P = A.pat;
   const ChunkDev ch = A.chunks[A.c_chunk[i]];
-  SetTable T;
-  T.keys = reinterpret_cast<const uint32_t*>(P.d_pat + P.set_keys);
-  T.first = reinterpret_cast<const uint32_t*>(P.d_pat + P.set_first);
-  T.ent = reinterpret_cast<const uint32_t*>(P.d_pat + P.set_ent);
-  T.bytes = P.d_pat + P.set_bytes;
-  T.ngrams = P.set_ngrams;
-  T.g = P.set_g;
+  const SetTable T = set_table(P);
   const uint64_t p = A.c_pos[i];
   // (the scan reports p only with p + g <= length; a position without that room holds nothing)
   A.c_len[i] = p + T.g <= ch.length ? set_verify_at(T, A.base + ch.offset, p, ch.length, P.icase != 0) : 0u;
 }
 
 // ---- xsg_count_literals: one count per literal, the verify step inside the candidate scan's own pass ---------------------------
-// k_set_scan<false, ICASE>'s tile loop, loads, fold and candidate masks as they are (copied, not factored out: the
-// existing instantiations keep their code byte for byte).  Instead of summing popc, every candidate bit is decided
-// here: set_count_at looks the gram up and compares EVERY literal under it; each one that fits the room and compares
-// equal adds 1 to its word of a workgroup histogram in LDS.  No candidate list, no size leaves the device; behind its
+// k_set_scan's tile stage as it is (set_tile_masks).  Instead of summing popc, every candidate bit is decided here:
+// set_count_at looks the gram up and compares EVERY literal under it; each one that fits the room and compares equal
+// adds 1 to its word of a workgroup histogram in LDS.  No candidate list, no size leaves the device; behind its
 // grid-stride loop the workgroup adds its non-zero words to LitCountArgs::counts with 64-bit atomics.
-//   KEYS_LDS  the sorted keys (at most 16 KiB) are copied into LDS once per workgroup: the binary search, up to 12
-//             dependent loads per candidate, stays out of global memory
-//   COMPACT   a wave's candidates of one wave-load are first packed into a queue in LDS, so that all 64 lanes verify;
-//             otherwise a lane verifies the bits of its own unit as it finds them
-// Dynamic LDS: the histogram (nlits words, at most 16 KiB), then the keys, then the queues.
+//   KEYS     the sorted keys (at most 16 KiB: the launcher refuses more than XSG_MAX_LITERALS grams) are copied into LDS
+//            once per workgroup: the binary search, up to 12 dependent loads per candidate, stays out of global memory
+//   COMPACT  a wave's candidates of one wave-load are first packed into a queue in LDS, so that all 64 lanes verify
+// (Keys read from global memory and a lane verifying the bits of its own unit were built, measured and removed:
+// DESIGN.md 3.5e.)
 // A histogram word cannot wrap: it counts positions at which ITS literal occurs, at most one per position the workgroup
 // looks at, and a workgroup looks at no more than ceil(ntiles / grid) tiles of 16 Ki positions -- the launcher keeps that
 // quotient below 2^18, so a word stays below 2^32.
@@ -210,118 +240,93 @@ constexpr uint32_t kLitQueue = kWaveLoad;  // candidates of one wave-load: 64 la
 
 __host__ __device__ constexpr uint32_t lit_round4(uint32_t n) { return (n + 3u) & ~3u; }
 
-template <bool ICASE, bool KEYS_LDS, bool COMPACT>
+// The dynamic LDS of the two counting kernels, as byte offsets: the histogram (nlits words), the keys (ngrams words), a
+// queue per wave, and for the matrix kernel the touched list and chunks_with's sums.  The sums exist only where they are
+// wanted and the list is short (kLitWithLds).  bytes_count: what k_set_count_literals needs, histogram, keys and queues;
+// bytes: what the matrix kernel needs, all of it.
+struct LitLds {
+  uint32_t hist, keys, queues, bytes_count, touched, with, bytes;
+  bool with_lds;
+};
+__host__ __device__ constexpr LitLds lit_lds(uint32_t nlits, uint32_t ngrams, bool want_with) {
+  LitLds l{};
+  l.hist = 0u;
+  l.keys = l.hist + 4u * lit_round4(nlits);
+  l.queues = l.keys + 4u * lit_round4(ngrams);
+  l.bytes_count = l.queues + 2u * kLitQueue * kWaves;
+  l.touched = l.bytes_count;
+  l.with = l.touched + 2u * kLitTouched;
+  l.with_lds = want_with && nlits <= kLitWithLds;
+  l.bytes = l.with + (l.with_lds ? 4u * lit_round4(nlits) : 0u);
+  return l;
+}
+// the largest list under as many grams: 42 KiB, and no room for chunks_with's sums above kLitWithLds
+static_assert(lit_lds(XSG_MAX_LITERALS, XSG_MAX_LITERALS, false).bytes == 42u * 1024u, "dynamic LDS of the largest list");
+static_assert(!lit_lds(XSG_MAX_LITERALS, XSG_MAX_LITERALS, true).with_lds &&
+                  lit_lds(XSG_MAX_LITERALS, XSG_MAX_LITERALS, true).bytes == 42u * 1024u,
+              "a long list keeps chunks_with out of the LDS");
+static_assert(lit_lds(kLitWithLds, XSG_MAX_LITERALS, true).bytes == lit_lds(kLitWithLds, XSG_MAX_LITERALS, false).bytes + 4u * kLitWithLds,
+              "a short list sums chunks_with in LDS");
+
+// the histogram zeroed and the sorted keys copied into LDS, once per workgroup.  The barrier is the caller's.
+__device__ __forceinline__ void lit_stage(const PatternDev& P, uint32_t nlits, uint32_t* s_hist, uint32_t* s_keys, uint32_t tid) {
+  for (uint32_t k = tid; k < nlits; k += kBlock) s_hist[k] = 0u;
+  const uint32_t* keys = reinterpret_cast<const uint32_t*>(P.d_pat + P.set_keys);
+  for (uint32_t k = tid; k < P.set_ngrams; k += kBlock) s_keys[k] = keys[k];
+}
+
+// The compacted verify of one wave-load: `m` holds this lane's candidate bits of the load that begins at `load_off`.  The
+// wave packs its candidates into its queue, then every lane decides one: set_count_at with the keys in LDS calls hit(listing
+// index) for every literal there (the bytes were just loaded: these reads hit the caches).
+template <bool ICASE, typename Hit>
+__device__ __forceinline__ void set_verify_load(const SetTable& T, const uint32_t* s_keys, uint16_t* s_queue, const SetTile& t,
+                                                uint64_t load_off, uint32_t m, uint32_t lane, Hit& hit) {
+  const uint32_t pc = (uint32_t)__popc(m);
+  const uint32_t incl = wave_incl_scan_u32(pc, lane);
+  const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+  if (total == 0u) return;  // (wave-uniform)
+  uint32_t r = incl - pc;
+  while (m) {
+    const uint32_t b = (uint32_t)__ffs((int)m) - 1u;
+    m &= m - 1u;
+    s_queue[r++] = (uint16_t)(lane * kUnit + b);
+  }
+  // the queue belongs to this wave alone: a wavefront-scope release/acquire orders its lanes' LDS accesses
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  for (uint32_t i = lane; i < total; i += 64u) set_count_at(T, t.cbase, load_off + s_queue[i], t.L, ICASE, hit, s_keys);
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();  // the next wave-load refills the queue
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+template <bool ICASE>
 __global__ __launch_bounds__(kBlock) void k_set_count_literals(const ScanArgs A, const LitCountArgs C) {
   __shared__ __attribute__((aligned(16))) uint32_t s_filter[kSetFilterWords];
-  extern __shared__ __attribute__((aligned(16))) uint32_t s_lit[];
+  extern __shared__ __attribute__((aligned(16))) uint8_t s_lit[];
   const PatternDev P = A.pat;
   const uint32_t tid = threadIdx.x;
   const uint32_t lane = tid & 63u;
   const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  uint32_t* const s_hist = s_lit;
-  uint32_t* const s_keys = s_lit + lit_round4(C.nlits);
-  uint16_t* const s_queue =
-      reinterpret_cast<uint16_t*>(s_keys + (KEYS_LDS ? lit_round4(P.set_ngrams) : 0u)) + (size_t)wave * kLitQueue;
-  {
-    const uint4* src = reinterpret_cast<const uint4*>(P.d_pat);
-    uint4* dst = reinterpret_cast<uint4*>(s_filter);
-    for (uint32_t k = tid; k < kSetFilterBytes / 16u; k += kBlock) dst[k] = src[k];
-    for (uint32_t k = tid; k < C.nlits; k += kBlock) s_hist[k] = 0u;
-    if (KEYS_LDS) {
-      const uint32_t* keys = reinterpret_cast<const uint32_t*>(P.d_pat + P.set_keys);
-      for (uint32_t k = tid; k < P.set_ngrams; k += kBlock) s_keys[k] = keys[k];
-    }
-  }
+  const LitLds lay = lit_lds(C.nlits, P.set_ngrams, false);
+  uint32_t* const s_hist = reinterpret_cast<uint32_t*>(s_lit + lay.hist);
+  uint32_t* const s_keys = reinterpret_cast<uint32_t*>(s_lit + lay.keys);
+  uint16_t* const s_queue = reinterpret_cast<uint16_t*>(s_lit + lay.queues) + (size_t)wave * kLitQueue;
+  set_stage_filter(P, s_filter, tid);
+  lit_stage(P, C.nlits, s_hist, s_keys, tid);
   __syncthreads();
   const uint32_t g = P.set_g;
-  SetTable T;
-  T.keys = reinterpret_cast<const uint32_t*>(P.d_pat + P.set_keys);
-  T.first = reinterpret_cast<const uint32_t*>(P.d_pat + P.set_first);
-  T.ent = reinterpret_cast<const uint32_t*>(P.d_pat + P.set_ent);
-  T.bytes = P.d_pat + P.set_bytes;
-  T.ngrams = P.set_ngrams;
-  T.g = g;
-  T.idx = reinterpret_cast<const uint16_t*>(P.d_pat + C.idx_off);
+  const SetTable T = set_table(P, C.idx_off);
   auto hit = [&](uint32_t i) { atomicAdd(&s_hist[i], 1u); };
 
   for (uint64_t tile = blockIdx.x; tile < A.ntiles; tile += gridDim.x) {
-    const uint32_t c = A.tile_chunk ? A.tile_chunk[tile] : 0u;
-    const ChunkDev ch = A.chunks[c];
-    const uint8_t* cbase = A.base + ch.offset;
-    const uint64_t L = ch.length;
-    const uint64_t Lr = (L + 15u) & ~(uint64_t)15u;
-    // as in k_set_scan: a candidate's whole gram lies inside the chunk, p + g <= L; no bit at or beyond `limit` survives
-    const uint64_t limit = L >= g ? L - g + 1u : 0u;
-    const uint64_t toff = (tile - A.chunk_tile0[c]) * (uint64_t)kSetTile;
-    const uint64_t wbase = toff + (uint64_t)wave * kSetWaveSpan;
-
     uint4 u[kSetLoads];
-#pragma unroll
-    for (int j = 0; j < kSetLoads; ++j) {
-      const uint64_t off = wbase + (uint64_t)j * kWaveLoad + (uint64_t)lane * kUnit;
-      u[j] = off < Lr ? *reinterpret_cast<const uint4*>(cbase + off) : uint4{0u, 0u, 0u, 0u};
-    }
-    const uint64_t behind = wbase + kSetWaveSpan;
-    const uint32_t edge_last = behind < Lr ? *reinterpret_cast<const uint32_t*>(cbase + behind) : 0u;
-
     uint32_t masks[kSetLoads];
+    const SetTile t = set_tile_masks<ICASE>(A, tile, g, s_filter, lane, wave, u, masks);
 #pragma unroll
-    for (int j = 0; j < kSetLoads; ++j) {
-      uint32_t w[5] = {u[j].x, u[j].y, u[j].z, u[j].w, 0u};
-      const uint32_t edge = j + 1 < kSetLoads ? (uint32_t)__builtin_amdgcn_readfirstlane((int)u[j + 1 < kSetLoads ? j + 1 : j].x) : edge_last;
-      w[4] = from_next_lane(w[0], edge, lane);
-      if (ICASE) {
-#pragma unroll
-        for (int q = 0; q < 5; ++q) w[q] = set_fold4(w[q]);
-      }
-      uint32_t m;
-      switch (g) {  // (wave-uniform)
-        case 1: m = set_cand16<1>(w, s_filter); break;
-        case 2: m = set_cand16<2>(w, s_filter); break;
-        case 3: m = set_cand16<3>(w, s_filter); break;
-        default: m = set_cand16<4>(w, s_filter); break;
-      }
-      const uint64_t unit_off = wbase + (uint64_t)j * kWaveLoad + (uint64_t)lane * kUnit;
-      if (unit_off >= limit)
-        m = 0u;
-      else if (unit_off + kUnit > limit)
-        m &= (1u << (uint32_t)(limit - unit_off)) - 1u;
-      masks[j] = m;
-    }
-
-    // ---- verify: every candidate, every literal under its gram (the bytes were just loaded: these reads hit the caches)
-#pragma unroll
-    for (int j = 0; j < kSetLoads; ++j) {
-      uint32_t m = masks[j];
-      const uint64_t load_off = wbase + (uint64_t)j * kWaveLoad;
-      if (!COMPACT) {
-        while (m) {
-          const uint32_t b = (uint32_t)__ffs((int)m) - 1u;
-          m &= m - 1u;
-          set_count_at(T, cbase, load_off + (uint64_t)lane * kUnit + b, L, ICASE, hit, KEYS_LDS ? s_keys : T.keys);
-        }
-      } else {
-        const uint32_t pc = (uint32_t)__popc(m);
-        const uint32_t incl = wave_incl_scan_u32(pc, lane);
-        const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-        if (total == 0u) continue;  // (wave-uniform)
-        uint32_t r = incl - pc;
-        while (m) {
-          const uint32_t b = (uint32_t)__ffs((int)m) - 1u;
-          m &= m - 1u;
-          s_queue[r++] = (uint16_t)(lane * kUnit + b);
-        }
-        // the queue belongs to this wave alone: a wavefront-scope release/acquire orders its lanes' LDS accesses
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        for (uint32_t i = lane; i < total; i += 64u)
-          set_count_at(T, cbase, load_off + s_queue[i], L, ICASE, hit, KEYS_LDS ? s_keys : T.keys);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();  // the next wave-load refills the queue
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-      }
-    }
+    for (int j = 0; j < kSetLoads; ++j)
+      set_verify_load<ICASE>(T, s_keys, s_queue, t, t.wbase + (uint64_t)j * kWaveLoad, masks[j], lane, hit);
   }
   __syncthreads();
   for (uint32_t k = tid; k < C.nlits; k += kBlock) {
@@ -331,8 +336,7 @@ __global__ __launch_bounds__(kBlock) void k_set_count_literals(const ScanArgs A,
 }
 
 // ---- xsg_count_literals_chunks: a count per chunk AND literal -------------------------------------------------------------------
-// k_set_count_literals' tile loop in its default form -- candidates compacted through the per-wave queue -- with the chunk
-// boundaries kept (copied again, not factored out: the instantiations above keep their code).  What differs:
+// k_set_count_literals' stages with the chunk boundaries kept.  What differs:
 //   PARTITION  a workgroup owns a CONTIGUOUS range of tiles (xsg_litmatrix.h), not a grid stride: tiles ascend by chunk, so
 //              the histogram in LDS always belongs to ONE chunk, and the workgroup meets each boundary in its range once.
 //   FLUSH      when the next tile belongs to another chunk, and behind the last tile: barrier, the non-zero words are added
@@ -348,46 +352,30 @@ __global__ __launch_bounds__(kBlock) void k_set_count_literals(const ScanArgs A,
 //              positive, so a word leaves 0 exactly once -- and adds 1 to chunks_with[j]: exact, no second pass.  For a
 //              list of at most kLitWithLds literals the workgroup sums these ones in LDS and adds them behind its last
 //              tile: the few words of a short list, added to by every chunk, serialise in the L2 otherwise.
-// Dynamic LDS: the histogram, the keys (KEYS_LDS), the queues, the touched list, chunks_with's sums (short lists).
-template <bool ICASE, bool KEYS_LDS>
+template <bool ICASE>
 __global__ __launch_bounds__(kBlock) void k_set_count_literals_chunks(const ScanArgs A, const LitMatrixArgs C) {
   __shared__ __attribute__((aligned(16))) uint32_t s_filter[kSetFilterWords];
   __shared__ uint32_t s_ntouched;
-  extern __shared__ __attribute__((aligned(16))) uint32_t s_lit[];
+  extern __shared__ __attribute__((aligned(16))) uint8_t s_lit[];
   const PatternDev P = A.pat;
   const uint32_t tid = threadIdx.x;
   const uint32_t lane = tid & 63u;
   const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  uint32_t* const s_hist = s_lit;
-  uint32_t* const s_keys = s_lit + lit_round4(C.nlits);
-  uint16_t* const s_queues = reinterpret_cast<uint16_t*>(s_keys + (KEYS_LDS ? lit_round4(P.set_ngrams) : 0u));
-  uint16_t* const s_queue = s_queues + (size_t)wave * kLitQueue;
-  uint16_t* const s_touched = s_queues + (size_t)kWaves * kLitQueue;
-  uint32_t* const s_with = reinterpret_cast<uint32_t*>(s_touched + kLitTouched);
-  const bool with_lds = C.chunks_with && C.nlits <= kLitWithLds;  // (the launcher sized the LDS by the same rule)
-  {
-    const uint4* src = reinterpret_cast<const uint4*>(P.d_pat);
-    uint4* dst = reinterpret_cast<uint4*>(s_filter);
-    for (uint32_t k = tid; k < kSetFilterBytes / 16u; k += kBlock) dst[k] = src[k];
-    for (uint32_t k = tid; k < C.nlits; k += kBlock) s_hist[k] = 0u;
-    if (KEYS_LDS) {
-      const uint32_t* keys = reinterpret_cast<const uint32_t*>(P.d_pat + P.set_keys);
-      for (uint32_t k = tid; k < P.set_ngrams; k += kBlock) s_keys[k] = keys[k];
-    }
-    if (with_lds)
-      for (uint32_t k = tid; k < C.nlits; k += kBlock) s_with[k] = 0u;
-    if (tid == 0) s_ntouched = 0u;
-  }
+  const LitLds lay = lit_lds(C.nlits, P.set_ngrams, C.chunks_with != nullptr);
+  uint32_t* const s_hist = reinterpret_cast<uint32_t*>(s_lit + lay.hist);
+  uint32_t* const s_keys = reinterpret_cast<uint32_t*>(s_lit + lay.keys);
+  uint16_t* const s_queue = reinterpret_cast<uint16_t*>(s_lit + lay.queues) + (size_t)wave * kLitQueue;
+  uint16_t* const s_touched = reinterpret_cast<uint16_t*>(s_lit + lay.touched);
+  uint32_t* const s_with = reinterpret_cast<uint32_t*>(s_lit + lay.with);
+  const bool with_lds = lay.with_lds;
+  set_stage_filter(P, s_filter, tid);
+  lit_stage(P, C.nlits, s_hist, s_keys, tid);
+  if (with_lds)
+    for (uint32_t k = tid; k < C.nlits; k += kBlock) s_with[k] = 0u;
+  if (tid == 0) s_ntouched = 0u;
   __syncthreads();
   const uint32_t g = P.set_g;
-  SetTable T;
-  T.keys = reinterpret_cast<const uint32_t*>(P.d_pat + P.set_keys);
-  T.first = reinterpret_cast<const uint32_t*>(P.d_pat + P.set_first);
-  T.ent = reinterpret_cast<const uint32_t*>(P.d_pat + P.set_ent);
-  T.bytes = P.d_pat + P.set_bytes;
-  T.ngrams = P.set_ngrams;
-  T.g = g;
-  T.idx = reinterpret_cast<const uint16_t*>(P.d_pat + C.idx_off);
+  const SetTable T = set_table(P, C.idx_off);
   const bool listed = C.touched != 0u;  // (XSG_LITMATRIX_TOUCHED=0, the A/B switch: every flush sweeps)
   uint32_t t_base = 0u;
   auto hit = [&](uint32_t i) {
@@ -402,77 +390,19 @@ __global__ __launch_bounds__(kBlock) void k_set_count_literals_chunks(const Scan
   const uint64_t per = litmatrix_per(A.ntiles, gridDim.x);
   const uint64_t tile_end = litmatrix_last(blockIdx.x, per, A.ntiles);
   for (uint64_t tile = litmatrix_first(blockIdx.x, per, A.ntiles); tile < tile_end; ++tile) {
-    const uint32_t c = A.tile_chunk ? A.tile_chunk[tile] : 0u;
-    // (workgroup-uniform) the histogram is flushed behind this tile
-    const bool boundary = tile + 1u == tile_end || (A.tile_chunk && A.tile_chunk[tile + 1u] != c);
-    const ChunkDev ch = A.chunks[c];
-    const uint8_t* cbase = A.base + ch.offset;
-    const uint64_t L = ch.length;
-    const uint64_t Lr = (L + 15u) & ~(uint64_t)15u;
-    // as in k_set_scan: a candidate's whole gram lies inside the chunk, p + g <= L; no bit at or beyond `limit` survives
-    const uint64_t limit = L >= g ? L - g + 1u : 0u;
-    const uint64_t toff = (tile - A.chunk_tile0[c]) * (uint64_t)kSetTile;
-    const uint64_t wbase = toff + (uint64_t)wave * kSetWaveSpan;
-
     uint4 u[kSetLoads];
-#pragma unroll
-    for (int j = 0; j < kSetLoads; ++j) {
-      const uint64_t off = wbase + (uint64_t)j * kWaveLoad + (uint64_t)lane * kUnit;
-      u[j] = off < Lr ? *reinterpret_cast<const uint4*>(cbase + off) : uint4{0u, 0u, 0u, 0u};
-    }
-    const uint64_t behind = wbase + kSetWaveSpan;
-    const uint32_t edge_last = behind < Lr ? *reinterpret_cast<const uint32_t*>(cbase + behind) : 0u;
-
     uint32_t masks[kSetLoads];
+    // the next tile's chunk is read in front of this tile's loads, not behind them where it is used: behind them the pass
+    // measured 0.7 % slower on 2^16 chunks of 32 KiB
+    const bool last = tile + 1u == tile_end;
+    const uint32_t c_next = (uint32_t)__builtin_amdgcn_readfirstlane((int)(!last && A.tile_chunk ? A.tile_chunk[tile + 1u] : 0u));  // (workgroup-uniform)
+    const SetTile t = set_tile_masks<ICASE>(A, tile, g, s_filter, lane, wave, u, masks);
+    const uint32_t c = t.c;
+    // (workgroup-uniform) the histogram is flushed behind this tile
+    const bool boundary = last || (A.tile_chunk && c_next != c);
 #pragma unroll
-    for (int j = 0; j < kSetLoads; ++j) {
-      uint32_t w[5] = {u[j].x, u[j].y, u[j].z, u[j].w, 0u};
-      const uint32_t edge = j + 1 < kSetLoads ? (uint32_t)__builtin_amdgcn_readfirstlane((int)u[j + 1 < kSetLoads ? j + 1 : j].x) : edge_last;
-      w[4] = from_next_lane(w[0], edge, lane);
-      if (ICASE) {
-#pragma unroll
-        for (int q = 0; q < 5; ++q) w[q] = set_fold4(w[q]);
-      }
-      uint32_t m;
-      switch (g) {  // (wave-uniform)
-        case 1: m = set_cand16<1>(w, s_filter); break;
-        case 2: m = set_cand16<2>(w, s_filter); break;
-        case 3: m = set_cand16<3>(w, s_filter); break;
-        default: m = set_cand16<4>(w, s_filter); break;
-      }
-      const uint64_t unit_off = wbase + (uint64_t)j * kWaveLoad + (uint64_t)lane * kUnit;
-      if (unit_off >= limit)
-        m = 0u;
-      else if (unit_off + kUnit > limit)
-        m &= (1u << (uint32_t)(limit - unit_off)) - 1u;
-      masks[j] = m;
-    }
-
-    // ---- verify: a wave-load's candidates packed into the wave's queue, then every lane decides one
-#pragma unroll
-    for (int j = 0; j < kSetLoads; ++j) {
-      uint32_t m = masks[j];
-      const uint64_t load_off = wbase + (uint64_t)j * kWaveLoad;
-      const uint32_t pc = (uint32_t)__popc(m);
-      const uint32_t incl = wave_incl_scan_u32(pc, lane);
-      const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-      if (total == 0u) continue;  // (wave-uniform)
-      uint32_t r = incl - pc;
-      while (m) {
-        const uint32_t b = (uint32_t)__ffs((int)m) - 1u;
-        m &= m - 1u;
-        s_queue[r++] = (uint16_t)(lane * kUnit + b);
-      }
-      // the queue belongs to this wave alone: a wavefront-scope release/acquire orders its lanes' LDS accesses
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-      for (uint32_t i = lane; i < total; i += 64u)
-        set_count_at(T, cbase, load_off + s_queue[i], L, ICASE, hit, KEYS_LDS ? s_keys : T.keys);
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();  // the next wave-load refills the queue
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    }
+    for (int j = 0; j < kSetLoads; ++j)
+      set_verify_load<ICASE>(T, s_keys, s_queue, t, t.wbase + (uint64_t)j * kWaveLoad, masks[j], lane, hit);
 
     if (!boundary) continue;
     // ---- flush into row c
@@ -521,25 +451,25 @@ static unsigned set_grid(const ScanArgs& a) {
   return (unsigned)std::min<uint64_t>(a.ntiles, (uint64_t)cus * kSetGridPerCu);
 }
 
+// what every launcher of a scanning kernel asks of its arguments; the counting launchers add their result and the bounds
+// that size the LDS (lit_lds: at most XSG_MAX_LITERALS literals and grams)
+static bool set_args_ok(const ScanArgs& a) { return a.tile_bytes == kSetTile && a.pat.set_g >= 1 && a.pat.set_g <= 4; }
+static bool set_args_ok(const ScanArgs& a, const unsigned long long* counts, uint32_t nlits) {
+  return set_args_ok(a) && counts && nlits != 0 && nlits <= XSG_MAX_LITERALS && a.pat.set_ngrams <= XSG_MAX_LITERALS;
+}
+
 hipError_t launch_set_count(const ScanArgs& a, bool want_nl, hipStream_t s) {
   if (a.ntiles == 0) return hipSuccess;
-  if (a.tile_bytes != kSetTile || a.pat.set_g < 1 || a.pat.set_g > 4) return hipErrorInvalidValue;
-  const dim3 grid(set_grid(a));
-  if (a.pat.icase)
-    hipLaunchKernelGGL((k_set_scan<false, true>), grid, dim3(kBlock), 0, s, a, want_nl ? 1u : 0u);
-  else
-    hipLaunchKernelGGL((k_set_scan<false, false>), grid, dim3(kBlock), 0, s, a, want_nl ? 1u : 0u);
+  if (!set_args_ok(a)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL((a.pat.icase ? k_set_scan<false, true> : k_set_scan<false, false>), dim3(set_grid(a)), dim3(kBlock), 0, s, a,
+                     want_nl ? 1u : 0u);
   return hipGetLastError();
 }
 
 hipError_t launch_set_emit(const ScanArgs& a, hipStream_t s) {
   if (a.ntiles == 0) return hipSuccess;
-  if (a.tile_bytes != kSetTile || a.pat.set_g < 1 || a.pat.set_g > 4) return hipErrorInvalidValue;
-  const dim3 grid(set_grid(a));
-  if (a.pat.icase)
-    hipLaunchKernelGGL((k_set_scan<true, true>), grid, dim3(kBlock), 0, s, a, 0u);
-  else
-    hipLaunchKernelGGL((k_set_scan<true, false>), grid, dim3(kBlock), 0, s, a, 0u);
+  if (!set_args_ok(a)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL((a.pat.icase ? k_set_scan<true, true> : k_set_scan<true, false>), dim3(set_grid(a)), dim3(kBlock), 0, s, a, 0u);
   return hipGetLastError();
 }
 
@@ -548,28 +478,14 @@ hipError_t launch_set_verify(const RxPreArgs& a, hipStream_t s) {
   return hipGetLastError();
 }
 
-template <bool ICASE, bool KEYS_LDS>
-static void launch_lit(const ScanArgs& a, const LitCountArgs& c, dim3 grid, size_t lds, hipStream_t s) {
-  if (c.compact)
-    hipLaunchKernelGGL((k_set_count_literals<ICASE, KEYS_LDS, true>), grid, dim3(kBlock), lds, s, a, c);
-  else
-    hipLaunchKernelGGL((k_set_count_literals<ICASE, KEYS_LDS, false>), grid, dim3(kBlock), lds, s, a, c);
-}
-
 hipError_t launch_set_count_literals(const ScanArgs& a, const LitCountArgs& c, hipStream_t s) {
   if (a.ntiles == 0) return hipSuccess;
-  if (a.tile_bytes != kSetTile || a.pat.set_g < 1 || a.pat.set_g > 4 || !c.counts || c.nlits == 0 || c.nlits > XSG_MAX_LITERALS ||
-      a.pat.set_ngrams > XSG_MAX_LITERALS)
-    return hipErrorInvalidValue;
+  if (!set_args_ok(a, c.counts, c.nlits)) return hipErrorInvalidValue;
   // (a histogram word stays below 2^32: fewer than 2^18 tiles per workgroup, see the kernel)
   const uint64_t per = (1u << 18) - 1u;
   const dim3 grid((unsigned)std::max<uint64_t>(set_grid(a), (a.ntiles + per - 1u) / per));
-  const size_t lds = 4u * (size_t)lit_round4(c.nlits) + (c.keys_lds ? 4u * (size_t)lit_round4(a.pat.set_ngrams) : 0u) +
-                     (c.compact ? 2u * (size_t)kLitQueue * kWaves : 0u);
-  if (a.pat.icase)
-    c.keys_lds ? launch_lit<true, true>(a, c, grid, lds, s) : launch_lit<true, false>(a, c, grid, lds, s);
-  else
-    c.keys_lds ? launch_lit<false, true>(a, c, grid, lds, s) : launch_lit<false, false>(a, c, grid, lds, s);
+  const size_t lds = lit_lds(c.nlits, a.pat.set_ngrams, false).bytes_count;
+  hipLaunchKernelGGL((a.pat.icase ? k_set_count_literals<true> : k_set_count_literals<false>), grid, dim3(kBlock), lds, s, a, c);
   return hipGetLastError();
 }
 
@@ -581,26 +497,13 @@ unsigned set_litmatrix_grid(const ScanArgs& a, uint32_t forced) {
 
 hipError_t launch_set_count_literals_chunks(const ScanArgs& a, const LitMatrixArgs& c, uint32_t forced_grid, hipStream_t s) {
   if (a.ntiles == 0) return hipSuccess;
-  if (a.tile_bytes != kSetTile || a.pat.set_g < 1 || a.pat.set_g > 4 || !c.counts || c.nlits == 0 || c.nlits > XSG_MAX_LITERALS ||
-      a.pat.set_ngrams > XSG_MAX_LITERALS)
-    return hipErrorInvalidValue;
+  if (!set_args_ok(a, c.counts, c.nlits)) return hipErrorInvalidValue;
   const dim3 grid(set_litmatrix_grid(a, forced_grid));
   // (a histogram word stays below 2^32: fewer than 2^18 tiles per workgroup, xsg_litmatrix.h)
   if (litmatrix_per(a.ntiles, grid.x) >= kLitMatrixPerLimit) return hipErrorInvalidValue;
-  const size_t lds = 4u * (size_t)lit_round4(c.nlits) + (c.keys_lds ? 4u * (size_t)lit_round4(a.pat.set_ngrams) : 0u) +
-                     2u * (size_t)kLitQueue * kWaves + 2u * (size_t)kLitTouched +
-                     (c.chunks_with && c.nlits <= kLitWithLds ? 4u * (size_t)lit_round4(c.nlits) : 0u);
-  if (a.pat.icase) {
-    if (c.keys_lds)
-      hipLaunchKernelGGL((k_set_count_literals_chunks<true, true>), grid, dim3(kBlock), lds, s, a, c);
-    else
-      hipLaunchKernelGGL((k_set_count_literals_chunks<true, false>), grid, dim3(kBlock), lds, s, a, c);
-  } else {
-    if (c.keys_lds)
-      hipLaunchKernelGGL((k_set_count_literals_chunks<false, true>), grid, dim3(kBlock), lds, s, a, c);
-    else
-      hipLaunchKernelGGL((k_set_count_literals_chunks<false, false>), grid, dim3(kBlock), lds, s, a, c);
-  }
+  const size_t lds = lit_lds(c.nlits, a.pat.set_ngrams, c.chunks_with != nullptr).bytes;
+  hipLaunchKernelGGL((a.pat.icase ? k_set_count_literals_chunks<true> : k_set_count_literals_chunks<false>), grid, dim3(kBlock), lds,
+                     s, a, c);
   return hipGetLastError();
 }
 
