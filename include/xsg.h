@@ -41,8 +41,9 @@ extern "C" {
  * XSG_FLAG_CONTEXT and xsg_result_context_edges joined; xsg_set_literals, xsg_literals_info, xsg_host_searcher_create_list
  * and xsg_job_opts.pattern_is_list joined (the structure grew: see there for what that asks of a program built before);
  * xsg_count_chunks and xsg_count_chunks_async joined; xsg_count_literals, xsg_count_literals_async and xsg_literal_counter_*
- * joined; xsg_count_literals_chunks, xsg_count_literals_chunks_async and xsg_literals_chunks_touched_capacity joined; no
- * entry point was removed or changed in meaning */
+ * joined; xsg_count_literals_chunks, xsg_count_literals_chunks_async and xsg_literals_chunks_touched_capacity joined;
+ * xsg_count_literals_csr, xsg_result_literals_csr and xsg_count_literals_csr_async joined; no entry point was removed or
+ * changed in meaning */
 #define XSG_ABI_VERSION 4
 
 /* ---- status codes ------------------------------------------------------- */
@@ -509,7 +510,7 @@ int xsg_count_literals_async(xsg_shard* shard, void* stream, uint64_t* d_counts,
  * XSG_ESTATE: the ctx holds no pattern.  XSG_ENOTSUP: the pattern is no list set by xsg_set_literals; XSG_FLAG_INVERT is
  * set; a binding of 2^24 chunks or more.  XSG_EINVAL: counts == NULL, cap_words < n * k, chunks_with != NULL with
  * cap_literals < k.  The CONTEXT bits and XSG_FLAG_EXACT_TAIL are accepted and ignored.
- * The matrix is DENSE: n * k words whatever they hold.  A sparse result (COO / CSR) is not offered.
+ * The matrix is DENSE: n * k words whatever they hold.  The sparse form is xsg_count_literals_csr, below.
  * One launch behind the memsets of both results (k_set_count_literals_chunks): a workgroup owns a contiguous range of
  * tiles, keeps one histogram in LDS and adds it to row c with 64-bit atomics whenever the next tile belongs to another
  * chunk; an add that finds its word 0 is the chunk's first for that literal and counts 1 for chunks_with[j] (exact: every
@@ -525,6 +526,42 @@ int xsg_count_literals_chunks_async(xsg_shard* shard, void* stream, uint64_t* d_
 /* The literals a workgroup of that pass can note between two flushes before a flush sweeps its whole histogram instead
  * of walking the noted ones (results do not depend on it; tests place their lists around it). */
 uint32_t xsg_literals_chunks_touched_capacity(void);
+
+/* The same matrix in CSR form, for bindings of many small chunks under a long list, whose matrix is almost all zeros.
+ * Let D[c][j] be the word xsg_count_literals_chunks would write to counts[c * k + j].  The result is
+ *   row_ptr  n + 1 uint64: row_ptr[0] == 0, row_ptr[c + 1] - row_ptr[c] = the number of j with D[c][j] > 0,
+ *            row_ptr[n] == nnz;
+ *   cols     nnz uint32: within a row the literal indices j ASCEND STRICTLY;
+ *   vals     nnz uint64: vals[e] == D[c][cols[e]], never 0
+ * -- what scipy.sparse.csr_matrix((vals, cols, row_ptr)) and torch.sparse_csr_tensor take.  Duplicates in the list get an
+ * entry each, as they get a column each in the dense form; a chunk of length 0 is an empty row; a binding of 0 chunks is
+ * XSG_OK with row_ptr = {0} and nnz = 0.  The result is a function of the list, the flags and the bound bytes alone:
+ * bit-identical from call to call and across grid sizes, no entry's place is left to scheduling.  chunks_with is not
+ * produced here: it is the bincount of cols.
+ * xsg_count_literals_csr runs the pass, sizes the result exactly and KEEPS it on the shard; *nnz = row_ptr[n].  The kept
+ * result is valid until the next xsg_count_literals_csr, xsg_shard_rebind or xsg_shard_invalidate on the shard (calls to
+ * other entry points in between do not disturb it: it lives in buffers of its own); xsg_result_literals_csr copies it out
+ * and is XSG_ESTATE otherwise -- the xsg_search / xsg_result_u64 pattern.  There: cap_rows >= n + 1 and cap_entries >= nnz;
+ * cols and vals may BOTH be NULL (row_ptr alone); words behind n + 1 / nnz are not touched.
+ * XSG_ESTATE, XSG_ENOTSUP as for xsg_count_literals_chunks (no pattern; no list, XSG_FLAG_INVERT, 2^24 chunks or more).
+ * XSG_EINVAL: nnz == NULL; in xsg_result_literals_csr row_ptr == NULL, cap_rows < n + 1, cap_entries < nnz, exactly one
+ * of cols / vals NULL.  The CONTEXT bits and XSG_FLAG_EXACT_TAIL are accepted and ignored.
+ * A result of more than 2^28 entries is XSG_ENOTSUP in the synchronous form -- the stream-ordered form, whose memory is
+ * the caller's, has no such limit.  There is NO limit on n * k: the scratch is a word per chunk and at most 64 MiB.
+ * Two passes of the dense form's partition around a prefix sum (k_set_count_literals_csr): the first sizes every row, the
+ * second writes its entries at row_ptr[c] + rank in ascending j.  The synchronous form fetches row_ptr[n] between them,
+ * its one extra wait. */
+int xsg_count_literals_csr(xsg_shard* shard, uint64_t* nnz);                                 /* waits; keeps the result */
+int xsg_result_literals_csr(xsg_shard* shard, uint64_t* row_ptr, uint64_t cap_rows, uint32_t* cols, uint64_t* vals,
+                            uint64_t cap_entries);                                           /* host memory */
+/* Stream-ordered form: d_row_ptr (cap_rows >= n + 1 words), d_cols and d_vals (cap_entries entries each) and d_status (one
+ * word) are DEVICE memory of the caller's, all required; nothing waits and nothing is fetched.  nnz <= cap_entries:
+ * *d_status = 0 and everything is written.  Otherwise *d_status = XSG_STATUS_OVERFLOW; d_row_ptr is still complete and
+ * true, so d_row_ptr[n] is the capacity to come back with; every entry with an index below cap_entries is written and
+ * correct; nothing at or behind cap_entries is written.  cap_entries == 0 (non-NULL pointers) is a pure sizing pass.
+ * XSG_EINVAL: a NULL output, cap_rows < n + 1.  The scratch is the shard's: calls on one shard follow one another. */
+int xsg_count_literals_csr_async(xsg_shard* shard, void* stream, uint64_t* d_row_ptr, uint64_t cap_rows,
+                                 uint32_t* d_cols, uint64_t* d_vals, uint64_t cap_entries, uint64_t* d_status);
 
 /* ---- list results (replace byte_offsets_match/_line, line; :136-154,187-207) */
 /* Runs the search for one of the list modes on the ctx stream and waits.

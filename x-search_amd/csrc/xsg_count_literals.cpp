@@ -2,7 +2,8 @@
 // xsg_count_literals_async).  One launch of k_set_count_literals (xsg_set_kernels.hip) behind a memset of the result:
 // no candidate list, no size fetched from the device, none of the list route's scratch read or written.  Behind them the
 // chunks x literals matrix (xsg_count_literals_chunks, xsg_count_literals_chunks_async): the same pass with the chunk
-// boundaries kept, k_set_count_literals_chunks.
+// boundaries kept, k_set_count_literals_chunks.  Behind those the matrix in CSR form (xsg_count_literals_csr,
+// xsg_result_literals_csr, xsg_count_literals_csr_async): a count pass, a prefix sum of the rows' lengths and a fill pass.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -12,12 +13,19 @@
 
 using namespace xsg;
 
-static int count_literals_args(xsg_shard* s, const uint64_t* counts, uint64_t cap_literals) {
+// what every entry point of this file asks of the context: a pattern, a list, no XSG_FLAG_INVERT
+static int count_literals_pattern(xsg_shard* s) {
   XSG_TRY(check_ready(s));
   const xsg_ctx* c = s->ctx;
   if (c->pat.kind != kSet)
     return fail(XSG_ENOTSUP, "counts per literal need a literal list as the pattern: xsg_set_literals (a single pattern: a list of one)");
   if (c->flags & XSG_FLAG_INVERT) return fail(XSG_ENOTSUP, "%s", kInvertMatchMsg);
+  return XSG_OK;
+}
+
+static int count_literals_args(xsg_shard* s, const uint64_t* counts, uint64_t cap_literals) {
+  XSG_TRY(count_literals_pattern(s));
+  const xsg_ctx* c = s->ctx;
   if (!counts) return fail(XSG_EINVAL, "counts is null");
   if (cap_literals < c->set_count)
     return fail(XSG_EINVAL, "room for %llu literals, the list holds %u", (unsigned long long)cap_literals, c->set_count);
@@ -130,3 +138,143 @@ extern "C" int xsg_count_literals_chunks_async(xsg_shard* s, void* stream, uint6
 }
 
 extern "C" uint32_t xsg_literals_chunks_touched_capacity(void) { return kLitTouched; }
+
+// ---- the matrix in CSR form ---------------------------------------------------------------------------------------------------
+// count_literals_args' refusals (its room checks are the sparse form's own, in the callers)
+static int count_literals_csr_args(xsg_shard* s) {
+  XSG_TRY(count_literals_pattern(s));
+  return set_route_serves(s);
+}
+
+namespace {
+struct CsrCall {
+  ScanArgs a;
+  LitCsrArgs l;
+  uint32_t grid;
+};
+}  // namespace
+
+// Steps 1 to 3 of DESIGN.md 3.5g on `st`: the scratch zeroed, the count pass with its seam count, the prefix sum of the
+// rows' lengths into d_row_ptr (n + 1 words).  Every size is the host's: chunks, literals, the grid.
+static int csr_count_rows(xsg_shard* s, hipStream_t st, uint64_t* d_row_ptr, CsrCall* k) {
+  xsg_ctx* c = s->ctx;
+  if (s->table_pending && st != c->stream) HIP_TRY(hipStreamWaitEvent(st, s->table_ev, 0));
+  const uint64_t n = s->chunks.size();
+  k->a = scan_args(s);
+  const char* g = XSG_TOGGLE("XSG_LITMATRIX_GRID");
+  const uint32_t forced = g && atoll(g) > 0 ? (uint32_t)std::min<long long>(atoll(g), 1 << 30) : 0u;
+  k->grid = set_litcsr_grid(k->a, c->set_count, forced);
+  const size_t seam_bytes = 8 * (size_t)k->grid * c->set_count;  // (at most 64 MiB: kLitCsrSeamWords)
+  XSG_TRY(s->d_csr_row_nnz.ensure(4 * (size_t)n));
+  XSG_TRY(s->d_csr_tmp.ensure(8 * (size_t)scan_tmp_elems(n)));
+  XSG_TRY(s->d_csr_seam.ensure(seam_bytes));
+  if (n) HIP_TRY(hipMemsetAsync(s->d_csr_row_nnz.p, 0, 4 * (size_t)n, st));
+  if (seam_bytes) HIP_TRY(hipMemsetAsync(s->d_csr_seam.p, 0, seam_bytes, st));
+  LitCsrArgs& l = k->l;
+  l = LitCsrArgs{};
+  l.row_nnz = s->d_csr_row_nnz.as<uint32_t>();
+  l.seam = s->d_csr_seam.as<unsigned long long>();
+  l.nchunks = n;
+  l.nlits = c->set_count;
+  l.idx_off = c->set_idx_off;
+  // the touched list and its A/B switch, as for the dense form (XSG_LITMATRIX_TOUCHED=0: every flush sweeps the histogram)
+  const char* t = XSG_TOGGLE("XSG_LITMATRIX_TOUCHED");
+  l.touched = !(t && *t == '0');
+  HIP_TRY(launch_set_count_literals_csr(k->a, l, k->grid, false, st));
+  HIP_TRY(launch_exclusive_scan_u32(l.row_nnz, d_row_ptr, n, s->d_csr_tmp.as<uint64_t>(), st));
+  return XSG_OK;
+}
+
+// Steps 4 and 5: the fill pass and the seam rows into d_cols / d_vals, nothing at or behind cap_entries; *d_status
+static int csr_fill_rows(hipStream_t st, CsrCall* k, const uint64_t* d_row_ptr, uint32_t* d_cols, uint64_t* d_vals,
+                         uint64_t cap_entries, uint64_t* d_status) {
+  LitCsrArgs& l = k->l;
+  l.row_ptr = d_row_ptr;
+  l.cols = d_cols;
+  l.vals = reinterpret_cast<unsigned long long*>(d_vals);
+  l.cap_entries = cap_entries;
+  l.status = d_status;
+  HIP_TRY(launch_set_count_literals_csr(k->a, l, k->grid, true, st));
+  return XSG_OK;
+}
+
+int xsg::enqueue_count_literals_csr(xsg_shard* s, hipStream_t st, uint64_t* d_row_ptr, uint32_t* d_cols, uint64_t* d_vals,
+                                    uint64_t cap_entries, uint64_t* d_status) {
+  CsrCall k;
+  XSG_TRY(csr_count_rows(s, st, d_row_ptr, &k));
+  return csr_fill_rows(st, &k, d_row_ptr, d_cols, d_vals, cap_entries, d_status);
+}
+
+extern "C" int xsg_count_literals_csr(xsg_shard* s, uint64_t* nnz) {
+  XSG_TRY(count_literals_csr_args(s));
+  if (!nnz) return fail(XSG_EINVAL, "nnz is null");
+  xsg_ctx* c = s->ctx;
+  HIP_TRY(hipSetDevice(c->device));
+  s->csr_valid = false;
+  const uint64_t n = s->chunks.size();
+  XSG_TRY(s->d_csr_row_ptr.ensure(8 * (size_t)(n + 2)));  // row_ptr, then the status word
+  uint64_t* const d_row_ptr = s->d_csr_row_ptr.as<uint64_t>();
+  CsrCall k;
+  XSG_TRY(csr_count_rows(s, c->stream, d_row_ptr, &k));
+  // the one size this form fetches: it sizes cols, vals and the mirror exactly
+  uint64_t total = 0;
+  HIP_TRY(hipMemcpyAsync(&total, d_row_ptr + n, 8, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  s->table_pending = false;
+  if (total > (1ull << 28))
+    return fail(XSG_ENOTSUP, "a result of %llu entries is more than the synchronous form keeps (2^28 entries): use "
+                "xsg_count_literals_csr_async with device memory of the caller's", (unsigned long long)total);
+  const size_t rp_bytes = 8 * (size_t)(n + 1), val_bytes = 8 * (size_t)total, col_bytes = 4 * (size_t)total;
+  s->h_csr.trim(rp_bytes + val_bytes + col_bytes);  // (what a far larger earlier result left page-locked)
+  XSG_TRY(s->d_csr_cols.ensure(col_bytes));
+  XSG_TRY(s->d_csr_vals.ensure(val_bytes));
+  XSG_TRY(s->h_csr.ensure(rp_bytes + val_bytes + col_bytes));
+  XSG_TRY(csr_fill_rows(c->stream, &k, d_row_ptr, s->d_csr_cols.as<uint32_t>(), s->d_csr_vals.as<uint64_t>(), total, d_row_ptr + n + 1));
+  uint8_t* const h = s->h_csr.as<uint8_t>();
+  HIP_TRY(hipMemcpyAsync(h, d_row_ptr, rp_bytes, hipMemcpyDeviceToHost, c->stream));
+  if (total) {
+    HIP_TRY(hipMemcpyAsync(h + rp_bytes, s->d_csr_vals.p, val_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(h + rp_bytes + val_bytes, s->d_csr_cols.p, col_bytes, hipMemcpyDeviceToHost, c->stream));
+  }
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  s->csr_rows = n;
+  s->csr_nnz = total;
+  s->csr_valid = true;
+  *nnz = total;
+  return XSG_OK;
+}
+
+extern "C" int xsg_result_literals_csr(xsg_shard* s, uint64_t* row_ptr, uint64_t cap_rows, uint32_t* cols, uint64_t* vals,
+                                       uint64_t cap_entries) {
+  if (!s) return fail(XSG_EINVAL, "shard is null");
+  if (!s->csr_valid)
+    return fail(XSG_ESTATE, "no result of xsg_count_literals_csr is kept: none was run on this binding, or a rebind or invalidate dropped it");
+  if (!row_ptr) return fail(XSG_EINVAL, "row_ptr is null");
+  if (cap_rows < s->csr_rows + 1)
+    return fail(XSG_EINVAL, "room for %llu row_ptr words, %llu chunks need %llu", (unsigned long long)cap_rows,
+                (unsigned long long)s->csr_rows, (unsigned long long)s->csr_rows + 1);
+  if ((cols == nullptr) != (vals == nullptr)) return fail(XSG_EINVAL, "cols and vals go together: both, or neither for row_ptr alone");
+  if (cols && cap_entries < s->csr_nnz)
+    return fail(XSG_EINVAL, "room for %llu entries, the result holds %llu", (unsigned long long)cap_entries, (unsigned long long)s->csr_nnz);
+  const size_t rp_bytes = 8 * (size_t)(s->csr_rows + 1), val_bytes = 8 * (size_t)s->csr_nnz;
+  const uint8_t* const h = s->h_csr.as<uint8_t>();
+  memcpy(row_ptr, h, rp_bytes);
+  if (cols && s->csr_nnz) {
+    memcpy(vals, h + rp_bytes, val_bytes);
+    memcpy(cols, h + rp_bytes + val_bytes, 4 * (size_t)s->csr_nnz);
+  }
+  return XSG_OK;
+}
+
+extern "C" int xsg_count_literals_csr_async(xsg_shard* s, void* stream, uint64_t* d_row_ptr, uint64_t cap_rows, uint32_t* d_cols,
+                                            uint64_t* d_vals, uint64_t cap_entries, uint64_t* d_status) {
+  XSG_TRY(count_literals_csr_args(s));
+  if (!d_row_ptr || !d_cols || !d_vals || !d_status) return fail(XSG_EINVAL, "d_row_ptr, d_cols, d_vals or d_status is null");
+  if (cap_rows < (uint64_t)s->chunks.size() + 1)
+    return fail(XSG_EINVAL, "room for %llu row_ptr words, %llu chunks need %llu", (unsigned long long)cap_rows,
+                (unsigned long long)s->chunks.size(), (unsigned long long)s->chunks.size() + 1);
+  xsg_ctx* c = s->ctx;
+  HIP_TRY(hipSetDevice(c->device));
+  return enqueue_count_literals_csr(s, stream ? static_cast<hipStream_t>(stream) : c->stream, d_row_ptr, d_cols, d_vals, cap_entries,
+                                    d_status);
+}

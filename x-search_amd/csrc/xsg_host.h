@@ -36,6 +36,10 @@ int enqueue_count_literals(xsg_shard* s, hipStream_t st, uint64_t* d_counts, boo
 // The pass of xsg_count_literals_chunks on `st`: both results zeroed on the stream, then one launch.  d_counts: chunks x
 // literals words, d_chunks_with: a word per literal or null.
 int enqueue_count_literals_chunks(xsg_shard* s, hipStream_t st, uint64_t* d_counts, uint64_t* d_chunks_with);
+// The passes of xsg_count_literals_csr on `st`: the shard's scratch zeroed, count pass, prefix sum into d_row_ptr (chunks + 1
+// words), fill pass into d_cols / d_vals below cap_entries, *d_status.  No size leaves the device.
+int enqueue_count_literals_csr(xsg_shard* s, hipStream_t st, uint64_t* d_row_ptr, uint32_t* d_cols, uint64_t* d_vals,
+                               uint64_t cap_entries, uint64_t* d_status);
 
 inline const char* const kNonAsciiMsg =
     "the expression uses '.', a negated class or \\D \\W \\S, which match whole code points in RE2; the data holds "

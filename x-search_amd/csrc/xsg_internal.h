@@ -341,6 +341,27 @@ struct LitMatrixArgs {
 };
 hipError_t launch_set_count_literals_chunks(const ScanArgs& a, const LitMatrixArgs& c, uint32_t forced_grid, hipStream_t s);
 unsigned set_litmatrix_grid(const ScanArgs& a, uint32_t forced);  // the workgroups that launch would use
+// k_set_count_literals_csr<ICASE, FILL> and k_set_csr_seam<FILL> (xsg_count_literals_csr*): the matrix in CSR form, in two
+// passes of the same partition around a prefix sum.  The count pass (FILL = false) stores row_nnz[c] for
+// the chunks a workgroup owns alone and sums the others' rows in `seam`, whose non-zeros the seam kernel counts; the fill
+// pass writes cols / vals at row_ptr[c] + rank, every store guarded by cap_entries, and the seam kernel does the same for
+// the seam rows and writes *status.  The caller zeroes row_nnz (nchunks words) and seam (grid x nlits words) on the stream
+// in front of the count pass and scans row_nnz into row_ptr between the passes; `grid` is set_litcsr_grid's for both.
+struct LitCsrArgs {
+  uint32_t* row_nnz;            // device, one word per chunk
+  unsigned long long* seam;     // device, grid x nlits words: row `slot` is the seam chunk's that starts in that range
+  const uint64_t* row_ptr;      // device, nchunks + 1 words (fill pass)
+  uint32_t* cols;               // device, cap_entries words (fill pass)
+  unsigned long long* vals;     // device, cap_entries words (fill pass)
+  uint64_t cap_entries;
+  uint64_t* status;             // device, one word (fill pass): XSG_STATUS_OVERFLOW iff row_ptr[nchunks] > cap_entries
+  uint64_t nchunks;
+  uint32_t nlits;               // literals of the list (SetProgram::count)
+  uint32_t idx_off;             // byte offset of SetTable::idx inside PatternDev::d_pat
+  uint32_t touched;             // the flushes walk the touched list (XSG_LITMATRIX_TOUCHED=0: they always sweep)
+};
+unsigned set_litcsr_grid(const ScanArgs& a, uint32_t nlits, uint32_t forced);  // 0: the binding has no tile
+hipError_t launch_set_count_literals_csr(const ScanArgs& a, const LitCsrArgs& c, uint32_t grid, bool fill, hipStream_t s);
 // "xsg::k_scan<KIND, WANT_NL, WANT_LINES, EMIT, LOADS, ICASE>" + the stagger launch_scan would use, for reports
 // finishing: the caller's pass is a plain match count that takes the finishing form where scan_finishing says so;
 // spans: that form would run with the binding's span locator (GateFinArgs::spans); waves: and as the wave form, taking

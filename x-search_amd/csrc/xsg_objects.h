@@ -268,6 +268,15 @@ struct xsg_shard {
   // them) and its pinned mirror.  Grow-only, sized by the call.
   DevBuf d_lit_matrix;
   PinBuf h_lit_matrix;
+  // xsg_count_literals_csr: the scratch of both forms -- a word per chunk (the rows' lengths), the tmp of their prefix sum
+  // and the seam buffer of grid x literals words (at most 64 MiB: xsg_litmatrix.h) -- all sized from host-known numbers,
+  // none of them by chunks x literals.  Then the synchronous form's result (row_ptr; cols and vals, sized exactly from
+  // row_ptr[n]; the status word behind row_ptr) and its pinned mirror (row_ptr, vals, cols in this order), kept until the
+  // next xsg_count_literals_csr, rebind or invalidate: xsg_result_literals_csr copies from the mirror.
+  DevBuf d_csr_row_nnz, d_csr_tmp, d_csr_seam, d_csr_row_ptr, d_csr_cols, d_csr_vals;
+  PinBuf h_csr;
+  bool csr_valid = false;
+  uint64_t csr_rows = 0, csr_nnz = 0;  // ... n and row_ptr[n] of the kept result
   uint64_t list_entries = 0;  // raw entries (ListArgs::M) the last exact list pass left in d_m_chunk / d_keep_pre
   bool begin_sync_result = false;  // xsg_count_begin had to run synchronously: _end hands out begin_counters
   uint64_t begin_counters[XSG_NUM_COUNTERS] = {0, 0, 0, 0};
@@ -303,13 +312,13 @@ struct xsg_shard {
                      &d_c_pre, &d_tile_mask, &d_tot, &d_hit, &d_scan2, &d_wmask, &d_inv_lo, &d_inv_cnt,
                      &d_inv_off, &d_inv_pos, &d_inv_chunk, &d_m_len, &d_f_len, &d_cx_lo, &d_cx_hi, &d_cx_cnt,
                      &d_cx_slot, &d_cx_pos, &d_cx_chunk, &d_cx_edge, &d_sketch, &d_spans, &d_chunk_counts, &d_lit_counts,
-                     &d_lit_matrix};
+                     &d_lit_matrix, &d_csr_row_nnz, &d_csr_tmp, &d_csr_seam, &d_csr_row_ptr, &d_csr_cols, &d_csr_vals};
     for (DevBuf* b : all) b->release();
     if (h_stage) (void)hipHostFree(h_stage);
     if (h_counters) (void)hipHostFree(h_counters);
     if (h_tot) (void)hipHostFree(h_tot);
     h_tot = nullptr;
-    for (PinBuf* b : {&h_result, &hp_line_len, &hp_line_bytes, &h_chunk_counts, &h_lit_counts, &h_lit_matrix}) b->release();
+    for (PinBuf* b : {&h_result, &hp_line_len, &hp_line_bytes, &h_chunk_counts, &h_lit_counts, &h_lit_matrix, &h_csr}) b->release();
     if (table_ev) (void)hipEventDestroy(table_ev);
     h_stage = nullptr;
     h_counters = nullptr;

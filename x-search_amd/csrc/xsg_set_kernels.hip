@@ -8,7 +8,9 @@
 //   k_set_count_literals     xsg_count_literals: the scan with the verify step inside its own pass, one count per literal
 //   k_set_count_literals_chunks   xsg_count_literals_chunks: the same pass with the chunk boundaries kept, a count per
 //                            chunk and literal and the number of chunks that hold each literal
-// The three scanning kernels share one copy of each stage: set_stage_filter, set_tile_masks (from the chunk lookup to the
+//   k_set_count_literals_csr, k_set_csr_seam   xsg_count_literals_csr: that matrix in CSR form, a count pass and a fill pass
+//                            of the same partition around a prefix sum of the rows' lengths
+// The scanning kernels share one copy of each stage: set_stage_filter, set_tile_masks (from the chunk lookup to the
 // clipped candidate masks), set_verify_load (the compacted verify of one wave-load) and lit_stage (histogram and keys);
 // LitLds is the one layout of the counting kernels' dynamic LDS, for the kernels' pointers and the launchers' byte count.
 #include "xsg_devutil.h"
@@ -441,6 +443,214 @@ __global__ __launch_bounds__(kBlock) void k_set_count_literals_chunks(const Scan
     }
 }
 
+// ---- xsg_count_literals_csr: the same matrix in CSR form ------------------------------------------------------------------------
+// Two passes of k_set_count_literals_chunks' partition around a prefix sum, so that every row has its place before an entry
+// is written and no entry's place depends on scheduling.  What differs from the dense kernel:
+//   WHOLE / SEAM  a chunk whose tiles all lie in the workgroup's range (xsg_litmatrix.h: litcsr_whole) has one owner: the
+//              count pass stores the number of its non-zero words in row_nnz[c], a plain store.  A chunk that crosses a
+//              range boundary is summed in the seam buffer, row litcsr_slot of grid x nlits uint64, with 64-bit atomics;
+//              k_set_csr_seam counts that row's non-zeros behind the pass.
+//   LOOP       the chunk's tile range [t0, t1) decides whole or seam, so it also gives the flush: the workgroup walks
+//              min(t1, its range's end) and flushes there -- no look at the next tile's chunk.
+//   FILL       the second pass skips the tiles of seam chunks (their rows are complete in the seam buffer; workgroup-
+//              uniform) and flushes a whole chunk's non-zero words as (j, word) in ASCENDING j at row_ptr[c] + rank: at
+//              most kLitCsrRank noted literals are ranked by counting the smaller ones among them, anything else is an
+//              ordered compaction of the histogram (csr_compact).  Every store is guarded by cap_entries.
+// Both passes read the same bytes, so the fill pass finds exactly the rows the count pass sized.
+
+// csr_compact's split of a row of k words: wave w takes the words [w * q, (w + 1) * q) (xsg_litmatrix.h)
+__device__ __forceinline__ uint32_t csr_wave_span(uint32_t k) { return litcsr_wave_span(k, kWaves); }
+
+// the non-zero words of this wave's span (wave-uniform); get(j) -> unsigned long long
+template <typename Get>
+__device__ __forceinline__ uint32_t csr_wave_count(uint32_t k, uint32_t lane, uint32_t wave, Get& get) {
+  const uint32_t q = csr_wave_span(k), lo = wave * q, hi = lo + q < k ? lo + q : k;
+  uint32_t n = 0;
+  for (uint32_t j0 = lo; j0 < hi; j0 += 64u) {
+    const uint32_t j = j0 + lane;
+    n += (uint32_t)__popcll(__ballot(j < hi && get(j) != 0ull));
+  }
+  return n;
+}
+
+// The ordered compaction of a row: put(j, word, rank) for every non-zero word, rank = the non-zero words in front of it.
+// A wave counts its span, the counts meet in s_wcnt behind one barrier, then the wave walks its span again with a running
+// base and a ballot / mbcnt rank.  Called by all four waves; the caller's barrier behind it frees s_wcnt.
+template <typename Get, typename Put>
+__device__ __forceinline__ void csr_compact(uint32_t k, uint32_t* s_wcnt, uint32_t lane, uint32_t wave, Get& get, Put& put) {
+  const uint32_t n = csr_wave_count(k, lane, wave, get);
+  if (lane == 0) s_wcnt[wave] = n;
+  __syncthreads();
+  uint32_t rank = 0;
+  for (uint32_t w = 0; w < wave; ++w) rank += s_wcnt[w];
+  const uint32_t q = csr_wave_span(k), lo = wave * q, hi = lo + q < k ? lo + q : k;
+  for (uint32_t j0 = lo; j0 < hi; j0 += 64u) {
+    const uint32_t j = j0 + lane;
+    const unsigned long long v = j < hi ? get(j) : 0ull;
+    const unsigned long long m = __ballot(v != 0ull);
+    if (v != 0ull) put(j, v, rank + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u)));
+    rank += (uint32_t)__popcll(m);
+  }
+}
+
+template <bool ICASE, bool FILL>
+__global__ __launch_bounds__(kBlock) void k_set_count_literals_csr(const ScanArgs A, const LitCsrArgs C) {
+  __shared__ __attribute__((aligned(16))) uint32_t s_filter[kSetFilterWords];
+  __shared__ uint32_t s_ntouched;
+  __shared__ uint32_t s_wcnt[kWaves];
+  extern __shared__ __attribute__((aligned(16))) uint8_t s_lit[];
+  const PatternDev P = A.pat;
+  const uint32_t tid = threadIdx.x;
+  const uint32_t lane = tid & 63u;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const LitLds lay = lit_lds(C.nlits, P.set_ngrams, false);
+  uint32_t* const s_hist = reinterpret_cast<uint32_t*>(s_lit + lay.hist);
+  uint32_t* const s_keys = reinterpret_cast<uint32_t*>(s_lit + lay.keys);
+  uint16_t* const s_queue = reinterpret_cast<uint16_t*>(s_lit + lay.queues) + (size_t)wave * kLitQueue;
+  uint16_t* const s_touched = reinterpret_cast<uint16_t*>(s_lit + lay.touched);
+  set_stage_filter(P, s_filter, tid);
+  lit_stage(P, C.nlits, s_hist, s_keys, tid);
+  if (tid == 0) s_ntouched = 0u;
+  __syncthreads();
+  const uint32_t g = P.set_g;
+  const SetTable T = set_table(P, C.idx_off);
+  const bool listed = C.touched != 0u;
+  uint32_t t_base = 0u;  // (the counter runs on, as in k_set_count_literals_chunks)
+  auto hit = [&](uint32_t i) {
+    if (!listed) {
+      atomicAdd(&s_hist[i], 1u);
+    } else if (atomicAdd(&s_hist[i], 1u) == 0u) {
+      const uint32_t slot = atomicAdd(&s_ntouched, 1u) - t_base;
+      if (slot < kLitTouched) s_touched[slot] = (uint16_t)i;
+    }
+  };
+  auto word = [&](uint32_t j) { return (unsigned long long)s_hist[j]; };
+
+  const uint64_t per = litmatrix_per(A.ntiles, gridDim.x);
+  const uint64_t tile_first = litmatrix_first(blockIdx.x, per, A.ntiles);
+  const uint64_t tile_end = litmatrix_last(blockIdx.x, per, A.ntiles);
+  uint64_t tile = tile_first;
+  while (tile < tile_end) {
+    // (workgroup-uniform) a chunk begins here, or the range does inside one
+    const uint32_t c = (uint32_t)__builtin_amdgcn_readfirstlane((int)(A.tile_chunk ? A.tile_chunk[tile] : 0u));
+    const uint64_t t0 = A.chunk_tile0[c], t1 = A.chunk_tile0[c + 1u];
+    const bool whole = litcsr_whole(t0, t1, tile_first, tile_end);
+    const uint64_t c_end = t1 < tile_end ? t1 : tile_end;
+    if (FILL && !whole) {  // a seam chunk's row is complete in the seam buffer
+      tile = c_end;
+      continue;
+    }
+    for (; tile < c_end; ++tile) {
+      uint4 u[kSetLoads];
+      uint32_t masks[kSetLoads];
+      const SetTile t = set_tile_masks<ICASE>(A, tile, g, s_filter, lane, wave, u, masks);
+#pragma unroll
+      for (int j = 0; j < kSetLoads; ++j)
+        set_verify_load<ICASE>(T, s_keys, s_queue, t, t.wbase + (uint64_t)j * kWaveLoad, masks[j], lane, hit);
+    }
+
+    // ---- flush chunk c
+    __syncthreads();
+    const uint32_t t_now = s_ntouched;
+    const uint32_t nt = t_now - t_base;
+    t_base = t_now;
+    const bool walk = listed && nt <= kLitTouched;
+    if (!FILL) {
+      if (whole) {
+        // the row's length: with the list, the literals noted since the last flush
+        if (walk) {
+          for (uint32_t k = tid; k < nt; k += kBlock) s_hist[s_touched[k]] = 0u;
+          if (tid == 0) C.row_nnz[c] = nt;
+        } else {
+          const uint32_t n = csr_wave_count(C.nlits, lane, wave, word);
+          if (lane == 0) s_wcnt[wave] = n;
+          __syncthreads();  // (every wave has counted its span: the words may go)
+          for (uint32_t k = tid; k < C.nlits; k += kBlock) s_hist[k] = 0u;
+          if (tid == 0) C.row_nnz[c] = s_wcnt[0] + s_wcnt[1] + s_wcnt[2] + s_wcnt[3];
+        }
+      } else {
+        unsigned long long* const row = C.seam + litcsr_slot(t0, per) * C.nlits;
+        if (walk) {
+          for (uint32_t k = tid; k < nt; k += kBlock) {
+            const uint32_t j = s_touched[k];
+            atomicAdd(&row[j], (unsigned long long)s_hist[j]);
+            s_hist[j] = 0u;
+          }
+        } else {
+          for (uint32_t k = tid; k < C.nlits; k += kBlock) {
+            const uint32_t v = s_hist[k];
+            if (v) {
+              atomicAdd(&row[k], (unsigned long long)v);
+              s_hist[k] = 0u;
+            }
+          }
+        }
+      }
+    } else {
+      const uint64_t at = C.row_ptr[c];
+      auto put = [&](uint32_t j, unsigned long long v, uint32_t rank) {
+        s_hist[j] = 0u;
+        const uint64_t e = at + rank;
+        if (e < C.cap_entries) {
+          C.cols[e] = j;
+          C.vals[e] = v;
+        }
+      };
+      if (walk && nt <= kLitCsrRank) {
+        // the noted literals are distinct: a literal's rank is the number of smaller ones among them
+        if (tid < nt) {
+          const uint32_t j = s_touched[tid];
+          uint32_t rank = 0;
+          for (uint32_t i = 0; i < nt; ++i) rank += s_touched[i] < j ? 1u : 0u;
+          put(j, s_hist[j], rank);
+        }
+      } else {
+        csr_compact(C.nlits, s_wcnt, lane, wave, word, put);
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// One workgroup per range of the pass above: the seam chunk that starts in range `blockIdx.x`, if there is one, has its
+// whole row in seam[blockIdx.x * nlits ..).  FILL = false: its non-zero words are counted into row_nnz[c]; FILL = true: they
+// are compacted in order to row_ptr[c], and one lane of the launch writes *status.  nslots: the grid of the pass (the fill
+// launch has one workgroup even for a binding without tiles, for the status word).
+template <bool FILL>
+__global__ __launch_bounds__(kBlock) void k_set_csr_seam(const uint32_t* tile_chunk, const uint64_t* chunk_tile0, uint64_t ntiles,
+                                                          uint32_t nslots, const LitCsrArgs C) {
+  __shared__ uint32_t s_wcnt[kWaves];
+  const uint32_t tid = threadIdx.x;
+  const uint32_t lane = tid & 63u;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  if (FILL && blockIdx.x == 0 && tid == 0)
+    *C.status = C.row_ptr[C.nchunks] > C.cap_entries ? (uint64_t)XSG_STATUS_OVERFLOW : 0ull;
+  if (blockIdx.x >= nslots) return;
+  const uint64_t per = litmatrix_per(ntiles, nslots);
+  const uint64_t first = litmatrix_first(blockIdx.x, per, ntiles), last = litmatrix_last(blockIdx.x, per, ntiles);
+  if (first == last) return;
+  const uint32_t c = tile_chunk ? tile_chunk[last - 1u] : 0u;
+  if (!litcsr_slot_seam(chunk_tile0[c], chunk_tile0[c + 1u], first, last)) return;  // (workgroup-uniform)
+  const unsigned long long* const row = C.seam + (uint64_t)blockIdx.x * C.nlits;
+  auto word = [&](uint32_t j) { return row[j]; };
+  if (!FILL) {
+    const uint32_t n = csr_wave_count(C.nlits, lane, wave, word);
+    if (lane == 0) s_wcnt[wave] = n;
+    __syncthreads();
+    if (tid == 0) C.row_nnz[c] = s_wcnt[0] + s_wcnt[1] + s_wcnt[2] + s_wcnt[3];
+  } else {
+    const uint64_t at = C.row_ptr[c];
+    auto put = [&](uint32_t j, unsigned long long v, uint32_t rank) {
+      const uint64_t e = at + rank;
+      if (e < C.cap_entries) {
+        C.cols[e] = j;
+        C.vals[e] = v;
+      }
+    };
+    csr_compact(C.nlits, s_wcnt, lane, wave, word, put);
+  }
+}
+
 static unsigned set_grid(const ScanArgs& a) {
   static const unsigned cus = [] {
     int dev = 0, n = 0;
@@ -504,6 +714,37 @@ hipError_t launch_set_count_literals_chunks(const ScanArgs& a, const LitMatrixAr
   const size_t lds = lit_lds(c.nlits, a.pat.set_ngrams, c.chunks_with != nullptr).bytes;
   hipLaunchKernelGGL((a.pat.icase ? k_set_count_literals_chunks<true> : k_set_count_literals_chunks<false>), grid, dim3(kBlock), lds,
                      s, a, c);
+  return hipGetLastError();
+}
+
+unsigned set_litcsr_grid(const ScanArgs& a, uint32_t nlits, uint32_t forced) {
+  ScanArgs all{};
+  all.ntiles = ~0ull;
+  const uint64_t want = (uint64_t)set_grid(all) / kSetGridPerCu * kLitMatrixGridPerCu;
+  return (unsigned)litmatrix_grid(a.ntiles, litcsr_grid_cap(want, nlits), forced ? litcsr_grid_cap(forced, nlits) : 0u);
+}
+
+hipError_t launch_set_count_literals_csr(const ScanArgs& a, const LitCsrArgs& c, uint32_t grid, bool fill, hipStream_t s) {
+  if (!c.row_nnz || (fill && (!c.row_ptr || !c.cols || !c.vals || !c.status))) return hipErrorInvalidValue;
+  if (a.ntiles && grid) {
+    if (!set_args_ok(a, c.seam, c.nlits)) return hipErrorInvalidValue;
+    // (the seam buffer's rows, the workgroups without a tile and the histogram's words: xsg_litmatrix.h)
+    if ((uint64_t)grid * c.nlits > kLitCsrSeamWords || grid != litmatrix_grid(a.ntiles, grid, grid) ||
+        litmatrix_per(a.ntiles, grid) >= kLitMatrixPerLimit)
+      return hipErrorInvalidValue;
+    const size_t lds = lit_lds(c.nlits, a.pat.set_ngrams, false).bytes;
+    if (fill) {
+      hipLaunchKernelGGL((a.pat.icase ? k_set_count_literals_csr<true, true> : k_set_count_literals_csr<false, true>), dim3(grid),
+                         dim3(kBlock), lds, s, a, c);
+      hipLaunchKernelGGL(k_set_csr_seam<true>, dim3(grid), dim3(kBlock), 0, s, a.tile_chunk, a.chunk_tile0, a.ntiles, grid, c);
+    } else {
+      hipLaunchKernelGGL((a.pat.icase ? k_set_count_literals_csr<true, false> : k_set_count_literals_csr<false, false>), dim3(grid),
+                         dim3(kBlock), lds, s, a, c);
+      hipLaunchKernelGGL(k_set_csr_seam<false>, dim3(grid), dim3(kBlock), 0, s, a.tile_chunk, a.chunk_tile0, a.ntiles, grid, c);
+    }
+  } else if (fill) {  // no tile: every row is empty, the status word is still due
+    hipLaunchKernelGGL(k_set_csr_seam<true>, dim3(1), dim3(kBlock), 0, s, a.tile_chunk, a.chunk_tile0, (uint64_t)0, 0u, c);
+  }
   return hipGetLastError();
 }
 

@@ -146,6 +146,9 @@ def load():
         "xsg_count_literals_chunks": (ci, [vp, vp, u64, vp, u64]),
         "xsg_count_literals_chunks_async": (ci, [vp, vp, vp, u64, vp, u64]),
         "xsg_literals_chunks_touched_capacity": (u32, []),
+        "xsg_count_literals_csr": (ci, [vp, vp]),
+        "xsg_result_literals_csr": (ci, [vp, vp, u64, vp, vp, u64]),
+        "xsg_count_literals_csr_async": (ci, [vp, vp, vp, u64, vp, vp, u64, vp]),
         "xsg_literal_counter_create": (ci, [ci, C.c_char_p, sz, u32, C.POINTER(vp)]),
         "xsg_literal_counter_add": (ci, [vp, vp, u64]),
         "xsg_literal_counter_get": (ci, [vp, vp, u64, _u64p]),
@@ -221,7 +224,8 @@ EXPORTS = ["xsg_abi_version", "xsg_strerror", "xsg_last_error", "xsg_device_coun
            "xsg_host_searcher_create_list", "xsg_count_chunks", "xsg_count_chunks_async", "xsg_count_literals",
            "xsg_count_literals_async", "xsg_literal_counter_create", "xsg_literal_counter_add", "xsg_literal_counter_get",
            "xsg_literal_counter_destroy", "xsg_count_literals_chunks", "xsg_count_literals_chunks_async",
-           "xsg_literals_chunks_touched_capacity"]
+           "xsg_literals_chunks_touched_capacity", "xsg_count_literals_csr", "xsg_result_literals_csr",
+           "xsg_count_literals_csr_async"]
 
 
 def _check(rc):
@@ -498,6 +502,27 @@ class Shard:
         uint64 words; d_chunks_with 0: not wanted"""
         _check(self._lib.xsg_count_literals_chunks_async(self.h, C.c_void_p(stream), C.c_void_p(d_counts) if d_counts else None, cap_words,
                                                          C.c_void_p(d_chunks_with) if d_chunks_with else None, cap_literals))
+
+    def count_literals_csr(self):
+        """-> (indptr uint64[n + 1], indices uint32[nnz], data uint64[nnz]) (xsg_count_literals_csr, xsg_result_literals_csr):
+        count_literals_chunks()'s matrix in CSR form, what scipy.sparse.csr_matrix((data, indices, indptr)) takes.  Within a
+        row the literal indices ascend; no entry is 0; chunks_with is np.bincount(indices, minlength=k)."""
+        nnz = C.c_uint64(0)
+        _check(self._lib.xsg_count_literals_csr(self.h, C.byref(nnz)))
+        indptr = np.zeros(self.nchunks + 1, dtype=np.uint64)
+        indices = np.zeros(nnz.value, dtype=np.uint32)
+        data = np.zeros(nnz.value, dtype=np.uint64)
+        _check(self._lib.xsg_result_literals_csr(self.h, C.c_void_p(indptr.ctypes.data), indptr.size, C.c_void_p(indices.ctypes.data),
+                                                 C.c_void_p(data.ctypes.data), nnz.value))
+        return indptr, indices, data
+
+    def count_literals_csr_async(self, stream: int, d_row_ptr: int, cap_rows: int, d_cols: int, d_vals: int, cap_entries: int,
+                                 d_status: int):
+        """the stream-ordered form (xsg_count_literals_csr_async): device addresses of cap_rows uint64, cap_entries uint32,
+        cap_entries uint64 and one uint64; *d_status is STATUS_OVERFLOW when cap_entries < d_row_ptr[nchunks]"""
+        p = lambda a: C.c_void_p(a) if a else None
+        _check(self._lib.xsg_count_literals_csr_async(self.h, C.c_void_p(stream), p(d_row_ptr), cap_rows, p(d_cols), p(d_vals),
+                                                      cap_entries, p(d_status)))
 
     def count_begin(self, mode: int):
         _check(self._lib.xsg_count_begin(self.h, mode))
