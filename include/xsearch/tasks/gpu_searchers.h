@@ -14,7 +14,9 @@
 // Context lines (XSG_FLAG_CONTEXT in `flags`) are CHUNK-LOCAL like everything here: the context of the line functors is
 // clipped at the edges of the chunk handed in, and nothing joins consecutive calls (xs::extern_search does, xsg.h).
 //
-// A trailing `literal_list = true` makes `pattern` a list of literals separated by '\n' (xsg.h: xsg_set_literals).
+// A trailing `literal_list = true` makes `pattern` a list of literals separated by '\n' (xsg.h: xsg_set_literals); behind
+// it `list_flags` takes the list's options (XSG_LIST_WHOLE_WORDS: whole words only; the edges of every chunk handed in are
+// word boundaries).
 //
 // DataT: anything with data() -> convertible to const char* and size()
 // (the reference's DefaultDataC, concepts.h:17-22; xs::strtype = std::vector<char>).
@@ -35,8 +37,9 @@ namespace gpu_detail {
 struct Handle {
   xsg_host_searcher* hs = nullptr;
   // literal_list: `pattern` holds several literals separated by '\n' (xsg.h: xsg_set_literals)
-  Handle(const std::string& pattern, int device, int max_slots, uint32_t flags, bool literal_list = false) {
-    const int r = literal_list ? xsg_host_searcher_create_list(device, pattern.data(), pattern.size(), flags, max_slots, &hs)
+  Handle(const std::string& pattern, int device, int max_slots, uint32_t flags, bool literal_list = false, uint32_t list_flags = 0) {
+    if (list_flags && !literal_list) throw std::invalid_argument("xs::Gpu*Searcher: list_flags need literal_list = true");
+    const int r = literal_list ? xsg_host_searcher_create_list_opts(device, pattern.data(), pattern.size(), flags, list_flags, max_slots, &hs)
                                : xsg_host_searcher_create(device, pattern.data(), pattern.size(), flags, max_slots, &hs);
     if (r != XSG_OK)
       throw std::runtime_error(std::string("xs::Gpu*Searcher: ") + xsg_strerror(r) + " (" + xsg_last_error() + ")");
@@ -93,8 +96,8 @@ template <class T = std::vector<char>>
 class GpuIndexSearcher {
  public:
   explicit GpuIndexSearcher(std::string pattern, int device = 0, int max_concurrent = 8, uint32_t flags = 0,
-           bool literal_list = false)
-      : _h(std::make_shared<gpu_detail::Handle>(pattern, device, max_concurrent, flags, literal_list)) {}
+           bool literal_list = false, uint32_t list_flags = 0)
+      : _h(std::make_shared<gpu_detail::Handle>(pattern, device, max_concurrent, flags, literal_list, list_flags)) {}
   std::optional<std::vector<uint64_t>> operator()(const T& data) const {
     return gpu_detail::offsets(*_h, XSG_MATCH_BYTE_OFFSETS, data);
   }
@@ -108,8 +111,8 @@ template <class T = std::vector<char>>
 class GpuLineIndexSearcher {
  public:
   explicit GpuLineIndexSearcher(std::string pattern, int device = 0, int max_concurrent = 8, uint32_t flags = 0,
-           bool literal_list = false)
-      : _h(std::make_shared<gpu_detail::Handle>(pattern, device, max_concurrent, flags, literal_list)) {}
+           bool literal_list = false, uint32_t list_flags = 0)
+      : _h(std::make_shared<gpu_detail::Handle>(pattern, device, max_concurrent, flags, literal_list, list_flags)) {}
   std::optional<std::vector<uint64_t>> operator()(const T& data) const {
     return gpu_detail::offsets(*_h, XSG_LINE_BYTE_OFFSETS, data);
   }
@@ -123,8 +126,8 @@ template <class T = std::vector<char>>
 class GpuLineSearcher {
  public:
   explicit GpuLineSearcher(std::string pattern, int device = 0, int max_concurrent = 8, uint32_t flags = 0,
-           bool literal_list = false)
-      : _h(std::make_shared<gpu_detail::Handle>(pattern, device, max_concurrent, flags, literal_list)) {}
+           bool literal_list = false, uint32_t list_flags = 0)
+      : _h(std::make_shared<gpu_detail::Handle>(pattern, device, max_concurrent, flags, literal_list, list_flags)) {}
   std::optional<std::vector<std::string>> operator()(const T& data) const {
     return gpu_detail::strings(*_h, xsg_host_lines, data);
   }
@@ -138,8 +141,8 @@ template <class T = std::vector<char>>
 class GpuMatchSearcher {
  public:
   explicit GpuMatchSearcher(std::string pattern, int device = 0, int max_concurrent = 8, uint32_t flags = 0,
-           bool literal_list = false)
-      : _h(std::make_shared<gpu_detail::Handle>(pattern, device, max_concurrent, flags, literal_list)) {}
+           bool literal_list = false, uint32_t list_flags = 0)
+      : _h(std::make_shared<gpu_detail::Handle>(pattern, device, max_concurrent, flags, literal_list, list_flags)) {}
   std::optional<std::vector<std::string>> operator()(const T& data) const {
     return gpu_detail::strings(*_h, xsg_host_matches, data);
   }
@@ -153,8 +156,8 @@ template <class T = std::vector<char>>
 class GpuCountSearcher {
  public:
   explicit GpuCountSearcher(std::string pattern, bool skip_to_nl = true, int device = 0, int max_concurrent = 8,
-                            uint32_t flags = 0, bool literal_list = false)
-      : _h(std::make_shared<gpu_detail::Handle>(pattern, device, max_concurrent, flags, literal_list)), _skip(skip_to_nl) {}
+                            uint32_t flags = 0, bool literal_list = false, uint32_t list_flags = 0)
+      : _h(std::make_shared<gpu_detail::Handle>(pattern, device, max_concurrent, flags, literal_list, list_flags)), _skip(skip_to_nl) {}
   std::optional<uint64_t> operator()(const T& data) const {
     uint64_t c = 0;
     const int r = xsg_host_count(_h->hs, data.data(), data.size(), _skip ? 1 : 0, &c);

@@ -38,7 +38,9 @@
 // chunk size without a metafile, default 16 MiB), XS_INVERT_MATCH (1: the lines WITHOUT a match), XS_CONTEXT_BEFORE /
 // XS_CONTEXT_AFTER (context lines of line_byte_offsets, line_indices and lines, grep -B / -A, at most 4095 each; the
 // other tags ignore them; not with several devices), XS_PATTERN_LIST (1: the pattern is a LIST of literals separated by
-// '\n', searched leftmost-first in listing order -- xsg.h: xsg_set_literals; it implies the literal reading).
+// '\n', searched leftmost-first in listing order -- xsg.h: xsg_set_literals; it implies the literal reading),
+// XS_WHOLE_WORDS (1: whole words only, grep -w -- xsg.h: XSG_LIST_WHOLE_WORDS; honoured only together with XS_PATTERN_LIST=1,
+// a single word being a list of one; without a list extern_search throws std::invalid_argument).
 #pragma once
 
 #include <xsg.h>
@@ -182,6 +184,15 @@ inline bool reference_routes_to_regex(const std::string& pattern) {
 
 // XS_PATTERN_LIST=1: the pattern is a list of literals separated by '\n' (xsg.h: xsg_set_literals)
 inline bool pattern_is_list() { return env_u64("XS_PATTERN_LIST", 0) != 0; }
+// XS_WHOLE_WORDS=1: the list_flags of xsg_job_start_list (XSG_LIST_WHOLE_WORDS).  The option belongs to literal lists:
+// without XS_PATTERN_LIST=1 it is refused, never dropped for a substring search.
+inline uint32_t list_flags() {
+  if (env_u64("XS_WHOLE_WORDS", 0) == 0) return 0u;
+  if (!pattern_is_list())
+    throw std::invalid_argument("xs::extern_search: XS_WHOLE_WORDS=1 (whole words, grep -w) is served for literal lists only: "
+                                "set XS_PATTERN_LIST=1 as well (xsgrep: -F), a single word being a list of one");
+  return XSG_LIST_WHOLE_WORDS;
+}
 
 // XSG_FLAG_* for a pattern, routed as the reference routes it; throws std::invalid_argument for a
 // regular expression the GPU matcher does not serve.  XS_INVERT_MATCH=1 adds XSG_FLAG_INVERT (the lines WITHOUT a
@@ -438,6 +449,7 @@ class ExternSearcher {
     xsg_job_opts_init(&o);
     o.pattern_flags = detail::pattern_flags(pattern, ignore_case);
     o.pattern_is_list = detail::pattern_is_list() ? 1u : 0u;
+    _list_flags = detail::list_flags();
     o.mode = detail::traits<Tag>::mode;
     detail::require_line_tag(o.pattern_flags, o.mode);
     const uint32_t context = detail::context_flags(o.mode);
@@ -533,11 +545,13 @@ class ExternSearcher {
  private:
   void start(const std::string& pattern, const std::string& file_path, const char* meta, const xsg_job_opts& o) {
     xsg_job* j = nullptr;
-    const int r = xsg_job_start(pattern.data(), pattern.size(), file_path.c_str(), meta, &o, &j);
+    const int r = _list_flags ? xsg_job_start_list(pattern.data(), pattern.size(), _list_flags, file_path.c_str(), meta, &o, &j)
+                              : xsg_job_start(pattern.data(), pattern.size(), file_path.c_str(), meta, &o, &j);
     if (r != XSG_OK) detail::throw_last("xs::extern_search", r);
     _set.jobs.push_back(j);
   }
   detail::JobSet _set;
+  uint32_t _list_flags = 0;  // XS_WHOLE_WORDS: through xsg_job_start_list
   std::unique_ptr<ResultT> _result;
 };
 

@@ -42,8 +42,9 @@ extern "C" {
  * and xsg_job_opts.pattern_is_list joined (the structure grew: see there for what that asks of a program built before);
  * xsg_count_chunks and xsg_count_chunks_async joined; xsg_count_literals, xsg_count_literals_async and xsg_literal_counter_*
  * joined; xsg_count_literals_chunks, xsg_count_literals_chunks_async and xsg_literals_chunks_touched_capacity joined;
- * xsg_count_literals_csr, xsg_result_literals_csr and xsg_count_literals_csr_async joined; no entry point was removed or
- * changed in meaning */
+ * xsg_count_literals_csr, xsg_result_literals_csr and xsg_count_literals_csr_async joined; XSG_LIST_WHOLE_WORDS with
+ * xsg_set_literals_opts, xsg_host_searcher_create_list_opts, xsg_literal_counter_create_opts and xsg_job_start_list joined;
+ * no entry point was removed or changed in meaning */
 #define XSG_ABI_VERSION 4
 
 /* ---- status codes ------------------------------------------------------- */
@@ -277,6 +278,32 @@ int xsg_set_pattern(xsg_ctx* ctx, const void* pattern, size_t plen, uint32_t fla
  * listing order (k_set_verify), and the walk and the list stages are the ones of every other pattern.  There is no
  * density bail-out: a list that makes most positions candidates ("e", "th") is slow but exact. */
 int xsg_set_literals(xsg_ctx* ctx, const void* list, size_t n, uint32_t flags);
+/* WHOLE WORDS (grep -w -F): options of a literal list, given in `list_flags` -- the pattern flags have no free bit.  The
+ * _opts entry points take them; list_flags == 0 is the call without _opts, result for result, and every bit but
+ * XSG_LIST_WHOLE_WORDS is XSG_EINVAL.  Single patterns (xsg_set_pattern, literal or expression) have no such option: a
+ * single word goes in as a list of one.
+ * A WORD BYTE is one of 0-9 A-Z a-z _ (63 values).  Every other byte is none, '\n' and every byte >= 0x80 included (GNU
+ * grep in the C locale); XSG_FLAG_IGNORE_CASE does not change the set.  With XSG_LIST_WHOLE_WORDS an occurrence of
+ * literal l at position p of a chunk of length L is ADMISSIBLE iff
+ *   p == 0           or chunk[p - 1]      is no word byte, and
+ *   p + len(l) == L  or chunk[p + len(l)] is no word byte.
+ * A chunk's edges are word boundaries: no byte in front of the chunk's first or at or beyond L is read for this test or
+ * decides anything.  The test looks at the NEIGHBOURS whatever the literal's own edge bytes are, as grep -w does: "-x-" in
+ * "a-x-b" is not admissible.
+ *   list tags   xsg_count, xsg_count_begin / _end, xsg_search on all seven tags, xsg_count_chunks, with XSG_FLAG_INVERT,
+ *               XSG_FLAG_CONTEXT and XSG_MATCHES: the search xsg_set_literals defines, restricted to admissible
+ *               occurrences.  At the leftmost position where any literal occurs ADMISSIBLY, the first-listed literal that
+ *               does so is the match, and the walk resumes at its end: ("ab","abc") on "abc ab abcd" matches "abc" at 0
+ *               and "ab" at 4.  This is what a backtracking leftmost-first engine computes for
+ *               (?<![0-9A-Za-z_])(?:l1|l2|...)(?![0-9A-Za-z_]); the set of matching lines is grep -w -F's.
+ *   counts      xsg_count_literals, xsg_count_literals_chunks, xsg_count_literals_csr (and their _async forms),
+ *               xsg_literal_counter_*: counts[j] is the number of admissible occurrences of l_j -- per literal,
+ *               independent of the rest of the list; duplicates get the same number each; the matrix's column sums still
+ *               equal xsg_count_literals, and the CSR form the dense one.
+ * The option is a property of the pattern: any later xsg_set_pattern, xsg_set_literals or failed set call clears it.
+ * xsg_scan_kernel_name of such a list ends in " whole words". */
+#define XSG_LIST_WHOLE_WORDS 0x1u /* list_flags; every other bit: XSG_EINVAL */
+int xsg_set_literals_opts(xsg_ctx* ctx, const void* list, size_t n, uint32_t flags, uint32_t list_flags);
 /* Would xsg_set_literals accept this list, and what does it compile to?  Host only, needs no device (like
  * xsg_regex_check).  XSG_OK or XSG_EINVAL with the reason in xsg_last_error().  `info` (optional) receives the numbers,
  * `filter` (optional, XSG_LITERAL_FILTER_BYTES) the filter image: bit h of the little-endian uint32 words is set <=> some
@@ -670,6 +697,12 @@ void xsg_job_opts_init(xsg_job_opts* opts);
  * job's own threads. */
 int xsg_job_start(const void* pattern, size_t plen, const char* file_path, const char* meta_file_path,
                   const xsg_job_opts* opts, xsg_job** out);
+/* xsg_job_start for a literal list with list options (xsg_set_literals_opts: XSG_LIST_WHOLE_WORDS) -- an entry point of
+ * its own because xsg_job_opts does not grow again.  It behaves as xsg_job_start with pattern_is_list forced on, whatever
+ * `opts` says there; struct_size is read as xsg_job_start reads it.  XSG_FLAG_REGEX in opts->pattern_flags is XSG_EINVAL,
+ * as for any list; an unknown bit of list_flags too.  list_flags == 0: xsg_job_start with pattern_is_list = 1. */
+int xsg_job_start_list(const void* list, size_t n, uint32_t list_flags, const char* file_path,
+                       const char* meta_file_path, const xsg_job_opts* opts, xsg_job** out);
 /* Blocks until every worker has finished; returns the first worker error. */
 int xsg_job_join(xsg_job* job);
 /* Joins, then frees the job and everything it returned pointers into. */
@@ -705,6 +738,9 @@ int xsg_host_searcher_create(int device, const void* pattern, size_t plen, uint3
 /* The same for a literal list (xsg_set_literals); every xsg_host_* call then works on it. */
 int xsg_host_searcher_create_list(int device, const void* list, size_t n, uint32_t flags, int max_slots,
                                   xsg_host_searcher** out);
+/* ... with list options (xsg_set_literals_opts); list_flags == 0 is the call above. */
+int xsg_host_searcher_create_list_opts(int device, const void* list, size_t n, uint32_t flags, uint32_t list_flags,
+                                       int max_slots, xsg_host_searcher** out);
 void xsg_host_searcher_destroy(xsg_host_searcher* hs);
 /* search::count(data, pattern, skip_to_nl)  (search_wrappers.h:163-185) */
 int xsg_host_count(xsg_host_searcher* hs, const void* data, uint64_t len, int skip_to_nl, uint64_t* count);
@@ -730,6 +766,10 @@ int xsg_host_matches(xsg_host_searcher* hs, const void* data, uint64_t len, uint
  * from one thread at a time. */
 typedef struct xsg_literal_counter xsg_literal_counter;
 int xsg_literal_counter_create(int device, const void* list, size_t n, uint32_t flags, xsg_literal_counter** out);
+/* ... with list options (xsg_set_literals_opts: under XSG_LIST_WHOLE_WORDS the edges of every chunk that is added are word
+ * boundaries); list_flags == 0 is the call above. */
+int xsg_literal_counter_create_opts(int device, const void* list, size_t n, uint32_t flags, uint32_t list_flags,
+                                    xsg_literal_counter** out);
 int xsg_literal_counter_add(xsg_literal_counter* lc, const void* data, uint64_t len);
 int xsg_literal_counter_get(xsg_literal_counter* lc, uint64_t* counts, uint64_t cap_literals, uint64_t* bytes);
 void xsg_literal_counter_destroy(xsg_literal_counter* lc);

@@ -1,14 +1,15 @@
 """A literal list next to the regex route that stood in for it: whole synchronous calls on a resident shard built as
 bench.py builds its corpus (16 MiB chunks replicated from seeded corpus.py templates).
 
-    python scripts/bench_literal_set.py [--gib 2] [--templates 16] [--regex-only] [--label NAME] [--out FILE]
+    python scripts/bench_literal_set.py [--gib 2] [--templates 16] [--regex-only] [--list-flags N] [--label NAME] [--out FILE]
 
 For (Sherlock, Holmes), an 8-word list and a 300-word list it times xsg_count(XSG_COUNT_LINES) and an XSG_LINES search
 through xsg_set_literals; for the first two also the same search through XSG_FLAG_REGEX with E(S) = l1|l2|...  One warm-up
 call, then 5 repetitions: the median, the minimum and the maximum in ms.  `kernel_ms` is the candidate count pass alone
 (xsg_time_scan_kernel) and `kernel_share` its part of the median count call.  One JSON line per (list, route, tag), appended
 to --out if given.  --regex-only times the regex route alone: run it with XSG_LIB pointing at a build of the parent commit
-for the yardstick (that library has no xsg_set_literals)."""
+for the yardstick (that library has no xsg_set_literals).  --list-flags N sets the lists through xsg_set_literals_opts(..., N)
+(1: XSG_LIST_WHOLE_WORDS; the regex route has no such option and is left out); every row says which it ran with."""
 import argparse
 import json
 import statistics
@@ -50,6 +51,7 @@ def main():
     ap.add_argument("--templates", type=int, default=16)
     ap.add_argument("--seed", type=int, default=0x5EED)
     ap.add_argument("--regex-only", action="store_true")
+    ap.add_argument("--list-flags", type=int, default=0)
     ap.add_argument("--label", default="")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
@@ -76,7 +78,7 @@ def main():
         med = statistics.median(ms)
         row = {"label": args.label, "list": name, "route": route, "tag": tag, "result": int(result), "median_ms": round(med, 3),
                "min_ms": round(min(ms), 3), "max_ms": round(max(ms), 3), "gbs": round(total / med / 1e6, 1),
-               "gib": round(total / 2**30, 2), "reps": REPS}
+               "gib": round(total / 2**30, 2), "reps": REPS, "list_flags": args.list_flags}
         row.update(extra)
         line = json.dumps(row)
         print(line, flush=True)
@@ -87,8 +89,8 @@ def main():
     for name, lits in lists():
         routes = []
         if not args.regex_only:
-            routes.append(("list", lambda lits=lits: ctx.set_literals(xsg.literal_list(lits))))
-        if len(lits) <= 8:
+            routes.append(("list", lambda lits=lits: ctx.set_literals(xsg.literal_list(lits), 0, args.list_flags)))
+        if len(lits) <= 8 and not args.list_flags:
             routes.append(("regex", lambda lits=lits: ctx.set_pattern(b"|".join(lits), xsg.FLAG_REGEX)))
         for route, set_it in routes:
             set_it()

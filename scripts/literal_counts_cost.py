@@ -15,7 +15,13 @@ line per (list, call) with every run's median, the ratio to the parent's xsg_cou
 max / min spread, for this build's calls the parent's run medians of the same call, the ratio to it (`ratio_to_same`)
 and the parent's spread of it (the runs alternate between the listed order and its reverse, so that neither build always
 runs behind the other), and the share of positions that are candidates (from the filter image, on one 16 MiB template).  The two builds'
-results are compared word for word before anything is timed."""
+results are compared word for word before anything is timed.
+
+--list-flags N (XSG_LIST_WHOLE_WORDS = 1; profiles/literal_words_ab.jsonl) adds a third side: this
+build with the same list set through xsg_set_literals_opts(..., N), on a context and a binding of its own over the same
+memory.  Its calls, `xsg_count opts` and `count_literals opts`, run interleaved with the others; their `same` is this
+build's call WITHOUT the option, so `ratio_to_same` is the option's cost, and `occurrences_opts` / `list_matches_opts` say
+how much it leaves standing.  The parent and this build without the option are compared as before."""
 import argparse
 import importlib.util
 import json
@@ -93,6 +99,7 @@ def main():
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--calls", type=int, default=10)
     ap.add_argument("--warm", type=int, default=2)
+    ap.add_argument("--list-flags", type=int, default=0, help="also time this build with these list_flags (1: whole words)")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     import torch
@@ -113,7 +120,7 @@ def main():
     del dev_t
     total = int(ln.sum())
     sides = {}
-    for label, mod in (("parent", parent), ("new", new)):
+    for label, mod in (("parent", parent), ("new", new), ("opts", new if a.list_flags else None)):
         if mod is None:
             continue
         ctx = mod.Context(0)
@@ -123,8 +130,11 @@ def main():
 
     for name, lits in lists():
         lst = new.literal_list(lits)
-        for _, ctx, _ in sides.values():
-            ctx.set_literals(lst, 0)
+        for label, (_, ctx, _) in sides.items():
+            if label == "opts":
+                ctx.set_literals(lst, 0, a.list_flags)
+            else:
+                ctx.set_literals(lst, 0)
         ns = sides["new"][2]
         rate, g = candidate_rate(new, blocks[0], lits)
         calls = {}
@@ -135,6 +145,10 @@ def main():
         if parent and hasattr(ps, "count_literals"):
             calls["parent count_literals"] = lambda ps=ps: ps.count_literals()
         calls["count_literals"] = lambda: ns.count_literals()
+        if "opts" in sides:
+            os_ = sides["opts"][2]
+            calls["xsg_count opts"] = lambda os_=os_: os_.count(new.COUNT_MATCHES)
+            calls["count_literals opts"] = lambda os_=os_: os_.count_literals()
         ref = calls["count_literals"]().tolist()
         # parity: the two builds agree word for word, call by call
         for k in [k for k in calls if k.startswith("parent ")]:
@@ -151,12 +165,17 @@ def main():
         for k, v in med.items():
             m = float(np.median(v))
             same = "parent " + k.replace("new ", "")  # the parent's same call, for this build's
+            if k.endswith(" opts"):  # ... and this build's call without the option, for the option's
+                same = "new xsg_count" if k.startswith("xsg_count") else "count_literals"
             row = {"what": "literal_counts", "list": name, "literals": len(lits), "gram": g, "candidate_rate": round(rate, 5),
                    "call": k, "bytes": total, "chunks": int(len(ln)), "list_matches": matches, "occurrences": int(sum(ref)),
                    "literals_that_occur": int(np.count_nonzero(ref)), "runs": a.runs, "calls_per_run": a.calls,
                    "run_median_ms": [round(x, 4) for x in v], "ms": round(m, 4), "ratio_to": base_key,
                    "ratio": round(m / base, 4), "max_over_min": round(max(v) / min(v), 4), "scan_ms": round(scan_ms, 4),
                    "ratio_to_scan": round(m / scan_ms, 3)}
+            if k.endswith(" opts"):
+                row.update({"list_flags": a.list_flags, "same": same, "list_matches_opts": int(calls["xsg_count opts"]()[new.CTR_MATCHES]),
+                            "occurrences_opts": int(sum(calls["count_literals opts"]().tolist()))})
             if same in med and same != k:
                 row.update({"same_run_median_ms": [round(x, 4) for x in med[same]], "same_ms": round(float(np.median(med[same])), 4), "ratio_to_same": round(m / float(np.median(med[same])), 4),
                             "same_max_over_min": round(max(med[same]) / min(med[same]), 4)})

@@ -2,8 +2,8 @@
 // on the MI355X engine, without boost::program_options.
 //
 //   xsgrep [-c] [-i] [-o] [-v] [-E|-F] [-x] [-A N] [-B N] [-C N] [-j THREADS] [-m METAFILE] PATTERN FILE|-
-//   xsgrep -F [-c] [-i] [-o] [-v] [-A N] [-B N] [-C N] [-j THREADS] [-m METAFILE] (-e PATTERN)... [-f FILE]... FILE|-
-//   xsgrep -F [-i] --count-each (-e PATTERN)... [-f FILE]... FILE|-
+//   xsgrep -F [-c] [-i] [-o] [-v] [-w] [-A N] [-B N] [-C N] [-j THREADS] [-m METAFILE] (-e PATTERN)... [-f FILE]... FILE|-
+//   xsgrep -F [-i] [-w] --count-each (-e PATTERN)... [-f FILE]... FILE|-
 //
 // -c  print only a count of matching lines   (grep.cpp:45-46 -> xs::count_lines)
 // -i  ignore ASCII case                      (grep.cpp:47-48)
@@ -32,7 +32,12 @@
 //     however many literals there are.  Requires -F; a single -e or the positional PATTERN is a list of one.  Excludes
 //     -c -o -v -x -A -B -C -m: it prints no lines and counts no lines.  The input is read in newline-aligned chunks, FILE
 //     and stdin alike; a literal holds no newline, so no occurrence straddles a cut and the sums are the input's.
-// The one-letter options without an argument may be bundled (-vc, -ci, -oi).
+// -w  whole words only (grep -w; XS_WHOLE_WORDS -> XSG_LIST_WHOLE_WORDS): an occurrence counts only between two bytes that
+//     are no word bytes (0-9 A-Z a-z _), the ends of the input's chunks counting as such.  Served with -F only -- the
+//     literals go as a list, a single PATTERN as a list of one -- and never dropped: without -F it is an error.  Combines
+//     with -c -i -o -v -A -B -C -e -f and --count-each, on FILE and on `-`; excludes -x.  As everywhere with a list, the
+//     FIRST-listed literal that stands as a whole word at a position is the match.
+// The one-letter options without an argument may be bundled (-vc, -ci, -oi, -wc).
 // otherwise print the matching lines, live, as they are found (grep.cpp:74-79).
 #include <xsearch/tasks/gpu_searchers.h>
 #include <xsearch/xsearch.h>
@@ -49,14 +54,16 @@
 
 static const char kUsage[] =
     "usage: %s [-c] [-i] [-o] [-v] [-E|-F] [-x] [-A N] [-B N] [-C N] [-j THREADS] [-m METAFILE] PATTERN FILE|-\n"
-    "       %s -F [-c] [-i] [-o] [-v] [-A N] [-B N] [-C N] [-j THREADS] [-m METAFILE] (-e PATTERN)... [-f FILE]... FILE|-\n"
-    "       %s -F [-i] --count-each (-e PATTERN)... [-f FILE]... FILE|-\n"
+    "       %s -F [-c] [-i] [-o] [-v] [-w] [-A N] [-B N] [-C N] [-j THREADS] [-m METAFILE] (-e PATTERN)... [-f FILE]... FILE|-\n"
+    "       %s -F [-i] [-w] --count-each (-e PATTERN)... [-f FILE]... FILE|-\n"
     "  -e PATTERN, -f FILE (one literal per line) search for any of several literals; both may repeat, need -F and exclude -x\n"
     "     when they give more than one pattern; -o then prints the FIRST-listed literal that occurs at a position (GNU grep: the longest)\n"
     "  -A N, -B N, -C N also print N lines after / before / around every selected line (N <= 4095), each line once and\n"
     "     without group separators; nothing changes under -c and -o; not with FILE = -\n"
     "  -o, --only-matching prints only the matched text, every match on its own line (not with -v)\n"
     "  -v, --invert-match selects the lines WITHOUT a match (with -c: counts them)\n"
+    "  -w, --word-regexp whole words only: an occurrence counts only between bytes that are none of 0-9 A-Z a-z _ (or at the\n"
+    "     ends of the input); needs -F (a single PATTERN goes as a list of one), excludes -x; works with --count-each too\n"
     "  -x searches (?m)^(?:PATTERN)$; PATTERN must not be empty\n"
     "  --count-each prints COUNT<TAB>LITERAL for every literal in listing order: its occurrences in the input, overlapping\n"
     "     ones and those inside another literal's included; needs -F, excludes -c -o -v -x -A -B -C -m\n";
@@ -127,7 +134,7 @@ static void for_each_aligned_chunk(std::FILE* in, F&& f) {
 }
 
 // --count-each: the table of xsg_literal_counter_* over the input's chunks; -> the exit status
-static int count_each(const std::vector<std::string>& lits, bool icase, const std::string& file) {
+static int count_each(const std::vector<std::string>& lits, bool icase, bool words, const std::string& file) {
   std::string list;
   for (const std::string& l : lits) list += (list.empty() ? "" : "\n") + l;
   std::FILE* in = file == "-" ? stdin : std::fopen(file.c_str(), "rb");
@@ -136,7 +143,8 @@ static int count_each(const std::vector<std::string>& lits, bool icase, const st
     return 2;
   }
   xsg_literal_counter* lc = nullptr;
-  int rc = xsg_literal_counter_create(0, list.data(), list.size(), icase ? XSG_FLAG_IGNORE_CASE : 0u, &lc);
+  int rc = xsg_literal_counter_create_opts(0, list.data(), list.size(), icase ? XSG_FLAG_IGNORE_CASE : 0u,
+                                           words ? XSG_LIST_WHOLE_WORDS : 0u, &lc);
   if (rc == XSG_OK)
     for_each_aligned_chunk(in, [&](const std::vector<char>& chunk) {
       if (rc == XSG_OK) rc = xsg_literal_counter_add(lc, chunk.data(), chunk.size());
@@ -154,7 +162,7 @@ static int count_each(const std::vector<std::string>& lits, bool icase, const st
 
 int main(int argc, char** argv) {
   bool count = false, icase = false, fixed = false, extended = false, whole_lines = false, invert = false, only = false;
-  bool each = false, context_given = false;
+  bool each = false, context_given = false, words = false;
   int threads = 2;  // grep.cpp:21
   long before = 0, after = 0;
   std::string meta, pattern, file;
@@ -164,7 +172,7 @@ int main(int argc, char** argv) {
   std::vector<std::string> args;
   for (int i = 1; i < argc; ++i) {  // -vc -> -v -c (only letters that take no argument; anything else stays one word)
     const std::string a = argv[i];
-    if (a.size() > 2 && a[0] == '-' && a[1] != '-' && a.find_first_not_of("ciEFxvo", 1) == std::string::npos) {
+    if (a.size() > 2 && a[0] == '-' && a[1] != '-' && a.find_first_not_of("ciEFxvow", 1) == std::string::npos) {
       for (size_t k = 1; k < a.size(); ++k) args.push_back(std::string("-") + a[k]);
     } else {
       args.push_back(a);
@@ -177,6 +185,8 @@ int main(int argc, char** argv) {
       invert = true;
     } else if (a == "-o" || a == "--only-matching") {
       only = true;
+    } else if (a == "-w" || a == "--word-regexp") {
+      words = true;
     } else if (a == "--count-each") {
       each = true;
     } else if (a == "-c" || a == "--count") {
@@ -250,6 +260,10 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, kUsage, argv[0], argv[0], argv[0]);
     return 2;
   }
+  if (words && (!fixed || whole_lines)) {  // never a silent substring search
+    std::fprintf(stderr, "xsgrep: -w (whole words) is served for literals only: it needs -F and excludes -x\n");
+    return 2;
+  }
   if (each) {  // a keyword table: no lines are selected, printed or counted
     const char* clash = !fixed ? "needs -F: it counts literals" : count ? "excludes -c (it counts occurrences per literal, not lines)"
                         : only ? "excludes -o (it prints counts, not matched text)" : invert ? "excludes -v (an occurrence count has no inverted form)"
@@ -270,7 +284,7 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "xsgrep: --count-each: an empty pattern (or one with a newline) is not served\n");
         return 2;
       }
-    const int rc = count_each(patterns, icase, file);
+    const int rc = count_each(patterns, icase, words, file);
     std::fflush(stdout);
     std::_Exit(rc);  // (as at the end of main: the runtime's teardown is left to the kernel)
   }
@@ -301,6 +315,13 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "xsgrep: -E and -F exclude each other\n");
     return 2;
   }
+  if (words && !list) {  // a single PATTERN under -F -w: a list of one
+    if (pattern.empty() || pattern.find('\n') != std::string::npos) {
+      std::fprintf(stderr, "xsgrep: -w: an empty pattern (or one with a newline) is not served\n");
+      return 2;
+    }
+    list = true;
+  }
   if (only && invert) {
     std::fprintf(stderr, "xsgrep: -o and -v exclude each other (a line without a match has no matched text)\n");
     return 2;
@@ -324,6 +345,8 @@ int main(int argc, char** argv) {
     extended = true, fixed = false;
   }
   if (list) setenv("XS_PATTERN_LIST", "1", 1);
+  if (words) setenv("XS_WHOLE_WORDS", "1", 1);
+  const uint32_t list_flags = words ? XSG_LIST_WHOLE_WORDS : 0u;
   if (fixed) setenv("XS_FORCE_LITERAL", "1", 1);
   if (extended) setenv("XS_FORCE_REGEX", "1", 1);
   if (invert) setenv("XS_INVERT_MATCH", "1", 1);
@@ -336,9 +359,9 @@ int main(int argc, char** argv) {
       // read newline-aligned chunks here and hand each to the reference-style searcher functors
       // (include/xsearch/tasks/gpu_searchers.h), like Searcher::run_thread does with a reader.
       const uint32_t flags = xs::detail::pattern_flags(pattern, icase);
-      xs::GpuLineSearcher<std::vector<char>> lines(pattern, 0, 1, flags, list);
-      xs::GpuMatchSearcher<std::vector<char>> matches(pattern, 0, 1, flags, list);
-      xs::GpuCountSearcher<std::vector<char>> counter(pattern, true, 0, 1, flags, list);
+      xs::GpuLineSearcher<std::vector<char>> lines(pattern, 0, 1, flags, list, list_flags);
+      xs::GpuMatchSearcher<std::vector<char>> matches(pattern, 0, 1, flags, list, list_flags);
+      xs::GpuCountSearcher<std::vector<char>> counter(pattern, true, 0, 1, flags, list, list_flags);
       uint64_t total = 0;
       for_each_aligned_chunk(stdin, [&](const std::vector<char>& chunk) {
         if (count) {

@@ -471,14 +471,17 @@ struct Partial {
 // then refused at its start.
 extern "C" int xsg_result_context_edges(xsg_shard* shard, xsg_context_edge* out, uint64_t cap_chunks) __attribute__((weak));
 // ... and of a literal list (xsg_job_opts.pattern_is_list, xsg_host_searcher_create_list), the same way
-extern "C" int xsg_set_literals(xsg_ctx* ctx, const void* list, size_t n, uint32_t flags) __attribute__((weak));
+extern "C" int xsg_set_literals_opts(xsg_ctx* ctx, const void* list, size_t n, uint32_t flags, uint32_t list_flags) __attribute__((weak));
 extern "C" int xsg_literals_info(const void* list, size_t n, uint32_t flags, xsg_literal_list* info, uint8_t* filter) __attribute__((weak));
 static const char kNoListMsg[] = "this build holds no device side for literal lists";
-// the pattern of a worker or a slot: a literal list where the caller said so
-static int set_job_pattern(xsg_ctx* ctx, const std::vector<uint8_t>& pattern, uint32_t flags, bool is_list) {
+// the pattern of a worker or a slot: a literal list where the caller said so, with its list flags (XSG_LIST_WHOLE_WORDS)
+static int set_job_pattern(xsg_ctx* ctx, const std::vector<uint8_t>& pattern, uint32_t flags, bool is_list, uint32_t list_flags) {
   if (!is_list) return xsg_set_pattern(ctx, pattern.data(), pattern.size(), flags);
-  if (!xsg_set_literals) return xsg::fail(XSG_ENOTSUP, "%s", kNoListMsg);
-  return xsg_set_literals(ctx, pattern.data(), pattern.size(), flags);
+  if (!xsg_set_literals_opts) return xsg::fail(XSG_ENOTSUP, "%s", kNoListMsg);
+  return xsg_set_literals_opts(ctx, pattern.data(), pattern.size(), flags, list_flags);
+}
+static int check_list_flags(uint32_t list_flags) {
+  return (list_flags & ~XSG_LIST_WHOLE_WORDS) ? xsg::fail(XSG_EINVAL, "unknown list flags 0x%x", list_flags) : XSG_OK;
 }
 static bool context_flags(uint32_t flags) { return XSG_CONTEXT_BEFORE(flags) != 0 || XSG_CONTEXT_AFTER(flags) != 0; }
 // the tags whose list context widens (every other tag ignores the bits)
@@ -491,6 +494,7 @@ struct xsg_job {
   const uint64_t serial = ++g_job_serial;
   xsg_job_opts opts{};
   std::vector<uint8_t> pattern;
+  uint32_t list_flags = 0;  // xsg_job_start_list
   int fd = -1;
   int32_t compression = XSG_COMPRESSION_NONE;
   std::vector<xsg_file_chunk> plan;
@@ -704,7 +708,7 @@ static int lane_prepare(xsg_job* j, Slot& s, int k) {
     XSG_TRY(xsg_shard_create(l.ctx, nullptr, 0, nullptr, 0, &l.shard));
     XSG_TRACE("slot: lane %d ctx + shard created", k);
   }
-  XSG_TRY(set_job_pattern(l.ctx, j->pattern, j->opts.pattern_flags, j->opts.pattern_is_list != 0));
+  XSG_TRY(set_job_pattern(l.ctx, j->pattern, j->opts.pattern_flags, j->opts.pattern_is_list != 0, j->list_flags));
   if (need > l.cap) {
     if (l.dev) (void)hipFree(l.dev);
     l.dev = nullptr;
@@ -1223,13 +1227,14 @@ extern "C" void xsg_job_opts_init(xsg_job_opts* o) {
   o->chunk_bytes = 16u << 20;
 }
 
+// force_list: xsg_job_start_list -- the pattern is a list whatever pattern_is_list says, with `list_flags`
 static int job_start_impl(const void* pattern, size_t plen, const char* file_path, const char* meta_file_path,
-                          const xsg_job_opts* opts, xsg_job** out);
+                          const xsg_job_opts* opts, bool force_list, uint32_t list_flags, xsg_job** out);
 
-extern "C" int xsg_job_start(const void* pattern, size_t plen, const char* file_path, const char* meta_file_path,
-                             const xsg_job_opts* opts, xsg_job** out) {
+static int job_start_guarded(const void* pattern, size_t plen, const char* file_path, const char* meta_file_path,
+                             const xsg_job_opts* opts, bool force_list, uint32_t list_flags, xsg_job** out) {
   try {
-    return job_start_impl(pattern, plen, file_path, meta_file_path, opts, out);
+    return job_start_impl(pattern, plen, file_path, meta_file_path, opts, force_list, list_flags, out);
   } catch (const std::bad_alloc&) {  // e.g. a plan with millions of records
     return fail(XSG_ENOMEM, "host allocation failed while setting up the job");
   } catch (const std::exception& e) {
@@ -1237,8 +1242,18 @@ extern "C" int xsg_job_start(const void* pattern, size_t plen, const char* file_
   }
 }
 
+extern "C" int xsg_job_start(const void* pattern, size_t plen, const char* file_path, const char* meta_file_path,
+                             const xsg_job_opts* opts, xsg_job** out) {
+  return job_start_guarded(pattern, plen, file_path, meta_file_path, opts, false, 0u, out);
+}
+
+extern "C" int xsg_job_start_list(const void* list, size_t n, uint32_t list_flags, const char* file_path,
+                                  const char* meta_file_path, const xsg_job_opts* opts, xsg_job** out) {
+  return job_start_guarded(list, n, file_path, meta_file_path, opts, true, list_flags, out);
+}
+
 static int job_start_impl(const void* pattern, size_t plen, const char* file_path, const char* meta_file_path,
-                          const xsg_job_opts* opts, xsg_job** out) {
+                          const xsg_job_opts* opts, bool force_list, uint32_t list_flags, xsg_job** out) {
   XSG_TRACE("job: start");
   if (!out) return fail(XSG_EINVAL, "out is null");
   *out = nullptr;
@@ -1251,6 +1266,8 @@ static int job_start_impl(const void* pattern, size_t plen, const char* file_pat
   memset(&known, 0, sizeof known);
   memcpy(&known, opts, opts->struct_size);
   opts = &known;
+  if (force_list) known.pattern_is_list = 1u;
+  XSG_TRY(check_list_flags(list_flags));
   const bool is_list = known.pattern_is_list != 0;
   if (is_list) {  // refuse a bad list here, not in a worker
     if (!xsg_literals_info) return fail(XSG_ENOTSUP, "%s", kNoListMsg);
@@ -1293,6 +1310,7 @@ static int job_start_impl(const void* pattern, size_t plen, const char* file_pat
   j->opts = *opts;
   if (!j->opts.chunk_bytes) j->opts.chunk_bytes = 16u << 20;
   j->pattern.assign((const uint8_t*)pattern, (const uint8_t*)pattern + plen);
+  j->list_flags = list_flags;
   uint64_t fsize = 0;
   XSG_TRY(open_ro(file_path, &j->fd, &fsize));
   int r = XSG_OK;
@@ -1575,6 +1593,7 @@ struct xsg_host_searcher {
   std::vector<uint8_t> pattern;
   uint32_t flags = 0;
   bool is_list = false;  // xsg_host_searcher_create_list
+  uint32_t list_flags = 0;  // xsg_host_searcher_create_list_opts
   int max_slots = 1;
   std::mutex mu;
   std::condition_variable cv;
@@ -1595,7 +1614,7 @@ static int host_slot_acquire(xsg_host_searcher* hs, HostSlot** out) {
       HostSlot* s = hs->all.back().get();
       lk.unlock();
       int r = xsg_ctx_create(hs->device, &s->ctx);
-      if (r == XSG_OK) r = set_job_pattern(s->ctx, hs->pattern, hs->flags, hs->is_list);
+      if (r == XSG_OK) r = set_job_pattern(s->ctx, hs->pattern, hs->flags, hs->is_list, hs->list_flags);
       if (r == XSG_OK) r = xsg_shard_create(s->ctx, nullptr, 0, nullptr, 0, &s->shard);
       if (r != XSG_OK) {
         // give the place back, or later callers would wait for a slot that never comes
@@ -1650,10 +1669,11 @@ static int host_stage(HostSlot* s, const void* data, uint64_t len) {
   return xsg_shard_rebind(s->shard, s->dev, s->cap, &ch, 1);
 }
 
-static int host_searcher_create(int device, const void* pattern, size_t plen, uint32_t flags, bool is_list, int max_slots,
-                                xsg_host_searcher** out) {
+static int host_searcher_create(int device, const void* pattern, size_t plen, uint32_t flags, bool is_list, uint32_t list_flags,
+                                int max_slots, xsg_host_searcher** out) {
   if (!out) return fail(XSG_EINVAL, "out is null");
   *out = nullptr;
+  XSG_TRY(check_list_flags(list_flags));
   if (!pattern || plen == 0 || plen > XSG_MAX_PATTERN) return fail(XSG_EINVAL, "pattern must be 1..%u bytes",
                                                                   XSG_MAX_PATTERN);
   if (is_list) {
@@ -1671,6 +1691,7 @@ static int host_searcher_create(int device, const void* pattern, size_t plen, ui
   hs->pattern.assign((const uint8_t*)pattern, (const uint8_t*)pattern + plen);
   hs->flags = flags;
   hs->is_list = is_list;
+  hs->list_flags = list_flags;
   hs->max_slots = max_slots < 1 ? 1 : max_slots;
   // build the first slot now so that a bad pattern / missing GPU fails here, not in the first search
   HostSlot* s = nullptr;
@@ -1682,12 +1703,17 @@ static int host_searcher_create(int device, const void* pattern, size_t plen, ui
 
 extern "C" int xsg_host_searcher_create(int device, const void* pattern, size_t plen, uint32_t flags, int max_slots,
                                         xsg_host_searcher** out) {
-  return host_searcher_create(device, pattern, plen, flags, false, max_slots, out);
+  return host_searcher_create(device, pattern, plen, flags, false, 0u, max_slots, out);
 }
 
 extern "C" int xsg_host_searcher_create_list(int device, const void* list, size_t n, uint32_t flags, int max_slots,
                                              xsg_host_searcher** out) {
-  return host_searcher_create(device, list, n, flags, true, max_slots, out);
+  return xsg_host_searcher_create_list_opts(device, list, n, flags, 0u, max_slots, out);
+}
+
+extern "C" int xsg_host_searcher_create_list_opts(int device, const void* list, size_t n, uint32_t flags, uint32_t list_flags,
+                                                  int max_slots, xsg_host_searcher** out) {
+  return host_searcher_create(device, list, n, flags, true, list_flags, max_slots, out);
 }
 
 extern "C" void xsg_host_searcher_destroy(xsg_host_searcher* hs) { delete hs; }

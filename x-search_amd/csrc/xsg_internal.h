@@ -58,6 +58,9 @@ struct PatternDev {
   uint32_t p0, m0, p1, m1;  // the 8 pattern bytes of the filter window (pattern[koff..koff+8)) as dwords + byte masks
   uint32_t q0, q1;          // ignore_case hot filter: (p0 | 0x20202020) & m0, (p1 | 0x20202020) & m1 (k_scan, LAZY)
   uint32_t koff;            // kLong, kClass: offset of the 8-byte filter window inside the pattern (0 for the other kinds)
+  uint32_t set_words;       // kSet: XSG_LIST_WHOLE_WORDS (SetTable::words).  It lies HERE, in the four bytes that padded d_pat to
+                            // its alignment: the structure keeps its size and every other field its offset, so no other
+                            // kernel's arguments change (profiles/literal_words_registers.txt)
   const uint8_t* d_pat;     // device copy of the pattern
   uint32_t exact_tail;      // XSG_FLAG_EXACT_TAIL
   uint32_t nl_first;        // literal whose FIRST byte is '\n': the reference's line start of a match then lies one byte behind the
@@ -341,7 +344,7 @@ struct LitMatrixArgs {
 };
 hipError_t launch_set_count_literals_chunks(const ScanArgs& a, const LitMatrixArgs& c, uint32_t forced_grid, hipStream_t s);
 unsigned set_litmatrix_grid(const ScanArgs& a, uint32_t forced);  // the workgroups that launch would use
-// k_set_count_literals_csr<ICASE, FILL> and k_set_csr_seam<FILL> (xsg_count_literals_csr*): the matrix in CSR form, in two
+// k_set_count_literals_csr<ICASE, FILL, WORDS> and k_set_csr_seam<FILL> (xsg_count_literals_csr*): the matrix in CSR form, in two
 // passes of the same partition around a prefix sum.  The count pass (FILL = false) stores row_nnz[c] for
 // the chunks a workgroup owns alone and sums the others' rows in `seam`, whose non-zeros the seam kernel counts; the fill
 // pass writes cols / vals at row_ptr[c] + rank, every store guarded by cap_entries, and the seam kernel does the same for

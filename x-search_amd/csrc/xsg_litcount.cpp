@@ -44,14 +44,20 @@ struct xsg_literal_counter {
 };
 
 extern "C" int xsg_literal_counter_create(int device, const void* list, size_t n, uint32_t flags, xsg_literal_counter** out) {
+  return xsg_literal_counter_create_opts(device, list, n, flags, 0u, out);
+}
+
+extern "C" int xsg_literal_counter_create_opts(int device, const void* list, size_t n, uint32_t flags, uint32_t list_flags,
+                                               xsg_literal_counter** out) {
   if (!out) return fail(XSG_EINVAL, "out is null");
   *out = nullptr;
+  if (list_flags & ~XSG_LIST_WHOLE_WORDS) return fail(XSG_EINVAL, "unknown list flags 0x%x", list_flags);
   if (flags & XSG_FLAG_INVERT) return fail(XSG_ENOTSUP, "%s", kInvertMatchMsg);
   XSG_TRY(xsg_literals_info(list, n, flags, nullptr, nullptr));  // a bad list fails before a device is touched
   std::unique_ptr<xsg_literal_counter> lc(new (std::nothrow) xsg_literal_counter());
   if (!lc) return fail(XSG_ENOMEM, "host allocation failed");
   XSG_TRY(xsg_ctx_create(device, &lc->ctx));
-  XSG_TRY(xsg_set_literals(lc->ctx, list, n, flags));
+  XSG_TRY(xsg_set_literals_opts(lc->ctx, list, n, flags, list_flags));
   HIP_TRY(hipSetDevice(lc->ctx->device));
   for (LitSlot& s : lc->slot) {
     HIP_TRY(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));

@@ -537,8 +537,15 @@ extern "C" int xsg_literals_info(const void* list, size_t n, uint32_t flags, xsg
 }
 
 extern "C" int xsg_set_literals(xsg_ctx* c, const void* list, size_t n, uint32_t flags) {
+  return xsg_set_literals_opts(c, list, n, flags, 0u);
+}
+
+// XSG_LIST_WHOLE_WORDS is a property of the compiled pattern: it lives in PatternDev::set_words, which every set call
+// rewrites (P = PatternDev{}), and nowhere else -- nothing of it can outlive the pattern.
+extern "C" int xsg_set_literals_opts(xsg_ctx* c, const void* list, size_t n, uint32_t flags, uint32_t list_flags) {
+  if (c) c->pattern.clear();  // a failed call leaves the context without a pattern
+  if (list_flags & ~XSG_LIST_WHOLE_WORDS) return fail(XSG_EINVAL, "unknown list flags 0x%x", list_flags);
   if (!c) return fail(XSG_EINVAL, "ctx is null");
-  c->pattern.clear();  // a failed call leaves the context without a pattern
   xsg::SetProgram prog;
   XSG_TRY(compile_list(list, n, flags, &prog));
   HIP_TRY(hipSetDevice(c->device));
@@ -562,6 +569,7 @@ extern "C" int xsg_set_literals(xsg_ctx* c, const void* list, size_t n, uint32_t
   P.exact_tail = 1u;
   P.icase = prog.icase ? 1u : 0u;
   P.set_g = prog.g;
+  P.set_words = (list_flags & XSG_LIST_WHOLE_WORDS) ? 1u : 0u;
   P.set_ngrams = (uint32_t)prog.keys.size();
   P.set_keys = off[0], P.set_first = off[1], P.set_ent = off[2], P.set_bytes = off[3];
   c->set_count = prog.count;

@@ -51,6 +51,8 @@ XSG_SET_HD bool set_filter_has(const uint32_t* filter, uint32_t v, uint32_t g) {
 //   bytes              the literals back to back (folded under ignore-case)
 //   idx[nlits]         the LISTING index of every entry of `ent`, uint16 (xsg_count_literals: set_count_at; the search
 //                      routes never read it, and a table built without it leaves it null)
+// words: XSG_LIST_WHOLE_WORDS (include/xsg.h) -- an occurrence stands only between two bytes that are no word bytes, the
+// chunk's edges counting as such (set_entry_at).
 struct SetTable {
   const uint32_t* keys;
   const uint32_t* first;
@@ -59,12 +61,20 @@ struct SetTable {
   uint32_t ngrams;
   uint32_t g;
   const uint16_t* idx = nullptr;
+  uint32_t words = 0;
 };
+
+// A word byte: 0-9 A-Z a-z _ (63 values; GNU grep -w in the C locale).  Ignore-case does not change the set.
+XSG_SET_HD bool set_word_byte(uint8_t b) {
+  return (uint8_t)((b | 0x20u) - 'a') < 26u || (uint8_t)(b - '0') < 10u || b == '_';
+}
 
 // The two steps of a verify.  set_gram_find: is gram v one of the sorted keys[0 .. ngrams)?  *k receives the index of
 // the first key >= v (binary search), the gram's own when it is found.  set_entry_at: do the bytes of entry e's literal
 // fit the `room` left in the chunk at `at` and equal the chunk's there (folded under icase)?  *len receives the literal's
-// length; no byte at or beyond at + room is read.
+// length; no byte at or beyond at + room is read.  `p`: the bytes of the chunk in front of `at`.  Under T.words a literal that
+// compared equal still has to stand between two bytes that are no word bytes: at[-1] is read only if p > 0, at[n] only if
+// n < room -- the chunk's edges are word boundaries, and no byte outside the chunk decides anything.
 XSG_SET_HD bool set_gram_find(const uint32_t* keys, uint32_t ngrams, uint32_t v, uint32_t* k) {
   uint32_t lo = 0, hi = ngrams;
   while (lo < hi) {  // first key >= v
@@ -77,36 +87,43 @@ XSG_SET_HD bool set_gram_find(const uint32_t* keys, uint32_t ngrams, uint32_t v,
   *k = lo;
   return lo != ngrams && keys[lo] == v;
 }
-XSG_SET_HD bool set_entry_at(const SetTable& T, uint32_t e, const uint8_t* at, uint64_t room, bool icase, uint32_t* len) {
+XSG_SET_HD bool set_entry_at(const SetTable& T, uint32_t e, const uint8_t* at, uint64_t p, uint64_t room, bool icase,
+                             uint32_t* len) {
   const uint32_t n = *len = T.ent[e] & 0xffu;
   if (n > room) return false;
   const uint8_t* lit = T.bytes + (T.ent[e] >> 8);
   uint32_t k = T.g;  // (the gram is the literal's start: already compared)
   while (k < n && set_fold(at[k], icase) == lit[k]) ++k;
-  return k == n;
+  if (k != n) return false;
+  if (T.words) {  // (the same for every lane; behind a compare that succeeded)
+    if (p > 0u && set_word_byte(at[-1])) return false;
+    if (n < room && set_word_byte(at[n])) return false;
+  }
+  return true;
 }
 
-// Length of the first-listed literal that occurs at d[p] of a chunk of L bytes, or 0.  p + g <= L is the caller's to
-// ensure (the scan reports no other position); nothing at or beyond L is read.
+// Length of the first-listed literal that occurs (under T.words: admissibly) at d[p] of a chunk of L bytes, or 0.
+// p + g <= L is the caller's to ensure (the scan reports no other position); nothing at or beyond L is read.
 XSG_SET_HD uint32_t set_verify_at(const SetTable& T, const uint8_t* d, uint64_t p, uint64_t L, bool icase) {
   uint32_t k, len;
   if (!set_gram_find(T.keys, T.ngrams, set_gram_at(d + p, T.g, icase), &k)) return 0u;
   for (uint32_t e = T.first[k]; e < T.first[k + 1u]; ++e)
-    if (set_entry_at(T, e, d + p, L - p, icase, &len)) return len;
+    if (set_entry_at(T, e, d + p, p, L - p, icase, &len)) return len;
   return 0u;
 }
 
-// EVERY literal that occurs at d[p] of a chunk of L bytes: visit(listing index) once per literal whose len bytes fit the
-// room L - p and equal the chunk's (folded under icase) -- prefixes, infixes and duplicates of one another included, which
-// is what xsg_count_literals counts.  p + g <= L is the caller's to ensure, as for set_verify_at; nothing at or beyond L is
-// read.  `keys`: T.keys, or a copy of them that is cheaper to reach (the kernel's lies in LDS).
+// EVERY literal that occurs (under T.words: admissibly) at d[p] of a chunk of L bytes: visit(listing index) once per
+// literal whose len bytes fit the room L - p and equal the chunk's (folded under icase) -- prefixes, infixes and
+// duplicates of one another included, which is what xsg_count_literals counts.  p + g <= L is the caller's to ensure, as
+// for set_verify_at; nothing at or beyond L is read.  `keys`: T.keys, or a copy of them that is cheaper to reach (the
+// kernel's lies in LDS).
 template <typename Visit>
 XSG_SET_HD void set_count_at(const SetTable& T, const uint8_t* d, uint64_t p, uint64_t L, bool icase, Visit&& visit,
                              const uint32_t* keys) {
   uint32_t k, len;
   if (!set_gram_find(keys, T.ngrams, set_gram_at(d + p, T.g, icase), &k)) return;
   for (uint32_t e = T.first[k]; e < T.first[k + 1u]; ++e)
-    if (set_entry_at(T, e, d + p, L - p, icase, &len)) visit((uint32_t)T.idx[e]);
+    if (set_entry_at(T, e, d + p, p, L - p, icase, &len)) visit((uint32_t)T.idx[e]);
 }
 
 template <typename Visit>

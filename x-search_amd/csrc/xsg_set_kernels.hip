@@ -13,6 +13,11 @@
 // The scanning kernels share one copy of each stage: set_stage_filter, set_tile_masks (from the chunk lookup to the
 // clipped candidate masks), set_verify_load (the compacted verify of one wave-load) and lit_stage (histogram and keys);
 // LitLds is the one layout of the counting kernels' dynamic LDS, for the kernels' pointers and the launchers' byte count.
+// XSG_LIST_WHOLE_WORDS (PatternDev::set_words) is tested in set_entry_at alone, behind a compare that succeeded; the candidate
+// scan and the filter do not know it.  k_set_verify reads it at run time through set_table().  The counting kernels take it as
+// the template argument WORDS, chosen by their launchers: as a run-time flag it cost them 2 to 3 VGPRs, and three of them a
+// wave per SIMD, whether the option was on or not (profiles/literal_words_registers.txt) -- with WORDS = false they are the
+// kernels they were.
 #include "xsg_devutil.h"
 #include "xsg_litmatrix.h"
 #include "xsg_set.h"
@@ -56,11 +61,14 @@ __device__ __forceinline__ SetTable set_table(const PatternDev& P) {
   T.bytes = P.d_pat + P.set_bytes;
   T.ngrams = P.set_ngrams;
   T.g = P.set_g;
+  T.words = P.set_words;  // (wave-uniform; read only behind a compare that succeeded: set_entry_at)
   return T;
 }
+template <bool WORDS>
 __device__ __forceinline__ SetTable set_table(const PatternDev& P, uint32_t idx_off) {
   SetTable T = set_table(P);
   T.idx = reinterpret_cast<const uint16_t*>(P.d_pat + idx_off);
+  T.words = WORDS ? 1u : 0u;  // (a constant of the instantiation; the launcher picked it from P.set_words)
   return T;
 }
 
@@ -303,7 +311,7 @@ __device__ __forceinline__ void set_verify_load(const SetTable& T, const uint32_
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-template <bool ICASE>
+template <bool ICASE, bool WORDS>
 __global__ __launch_bounds__(kBlock) void k_set_count_literals(const ScanArgs A, const LitCountArgs C) {
   __shared__ __attribute__((aligned(16))) uint32_t s_filter[kSetFilterWords];
   extern __shared__ __attribute__((aligned(16))) uint8_t s_lit[];
@@ -319,7 +327,7 @@ __global__ __launch_bounds__(kBlock) void k_set_count_literals(const ScanArgs A,
   lit_stage(P, C.nlits, s_hist, s_keys, tid);
   __syncthreads();
   const uint32_t g = P.set_g;
-  const SetTable T = set_table(P, C.idx_off);
+  const SetTable T = set_table<WORDS>(P, C.idx_off);
   auto hit = [&](uint32_t i) { atomicAdd(&s_hist[i], 1u); };
 
   for (uint64_t tile = blockIdx.x; tile < A.ntiles; tile += gridDim.x) {
@@ -354,7 +362,7 @@ __global__ __launch_bounds__(kBlock) void k_set_count_literals(const ScanArgs A,
 //              positive, so a word leaves 0 exactly once -- and adds 1 to chunks_with[j]: exact, no second pass.  For a
 //              list of at most kLitWithLds literals the workgroup sums these ones in LDS and adds them behind its last
 //              tile: the few words of a short list, added to by every chunk, serialise in the L2 otherwise.
-template <bool ICASE>
+template <bool ICASE, bool WORDS>
 __global__ __launch_bounds__(kBlock) void k_set_count_literals_chunks(const ScanArgs A, const LitMatrixArgs C) {
   __shared__ __attribute__((aligned(16))) uint32_t s_filter[kSetFilterWords];
   __shared__ uint32_t s_ntouched;
@@ -377,7 +385,7 @@ __global__ __launch_bounds__(kBlock) void k_set_count_literals_chunks(const Scan
   if (tid == 0) s_ntouched = 0u;
   __syncthreads();
   const uint32_t g = P.set_g;
-  const SetTable T = set_table(P, C.idx_off);
+  const SetTable T = set_table<WORDS>(P, C.idx_off);
   const bool listed = C.touched != 0u;  // (XSG_LITMATRIX_TOUCHED=0, the A/B switch: every flush sweeps)
   uint32_t t_base = 0u;
   auto hit = [&](uint32_t i) {
@@ -493,7 +501,7 @@ __device__ __forceinline__ void csr_compact(uint32_t k, uint32_t* s_wcnt, uint32
   }
 }
 
-template <bool ICASE, bool FILL>
+template <bool ICASE, bool FILL, bool WORDS>
 __global__ __launch_bounds__(kBlock) void k_set_count_literals_csr(const ScanArgs A, const LitCsrArgs C) {
   __shared__ __attribute__((aligned(16))) uint32_t s_filter[kSetFilterWords];
   __shared__ uint32_t s_ntouched;
@@ -513,7 +521,7 @@ __global__ __launch_bounds__(kBlock) void k_set_count_literals_csr(const ScanArg
   if (tid == 0) s_ntouched = 0u;
   __syncthreads();
   const uint32_t g = P.set_g;
-  const SetTable T = set_table(P, C.idx_off);
+  const SetTable T = set_table<WORDS>(P, C.idx_off);
   const bool listed = C.touched != 0u;
   uint32_t t_base = 0u;  // (the counter runs on, as in k_set_count_literals_chunks)
   auto hit = [&](uint32_t i) {
@@ -667,6 +675,11 @@ static bool set_args_ok(const ScanArgs& a) { return a.tile_bytes == kSetTile && 
 static bool set_args_ok(const ScanArgs& a, const unsigned long long* counts, uint32_t nlits) {
   return set_args_ok(a) && counts && nlits != 0 && nlits <= XSG_MAX_LITERALS && a.pat.set_ngrams <= XSG_MAX_LITERALS;
 }
+// a counting kernel's instantiation for this pattern: [ignore-case][whole words]
+template <typename K>
+static K lit_kernel(const K (&k)[2][2], const PatternDev& p) {
+  return k[p.icase ? 1 : 0][p.set_words ? 1 : 0];
+}
 
 hipError_t launch_set_count(const ScanArgs& a, bool want_nl, hipStream_t s) {
   if (a.ntiles == 0) return hipSuccess;
@@ -695,7 +708,10 @@ hipError_t launch_set_count_literals(const ScanArgs& a, const LitCountArgs& c, h
   const uint64_t per = (1u << 18) - 1u;
   const dim3 grid((unsigned)std::max<uint64_t>(set_grid(a), (a.ntiles + per - 1u) / per));
   const size_t lds = lit_lds(c.nlits, a.pat.set_ngrams, false).bytes_count;
-  hipLaunchKernelGGL((a.pat.icase ? k_set_count_literals<true> : k_set_count_literals<false>), grid, dim3(kBlock), lds, s, a, c);
+  using K = void (*)(const ScanArgs, const LitCountArgs);
+  static const K k[2][2] = {{k_set_count_literals<false, false>, k_set_count_literals<false, true>},
+                            {k_set_count_literals<true, false>, k_set_count_literals<true, true>}};
+  hipLaunchKernelGGL(lit_kernel(k, a.pat), grid, dim3(kBlock), lds, s, a, c);
   return hipGetLastError();
 }
 
@@ -712,8 +728,10 @@ hipError_t launch_set_count_literals_chunks(const ScanArgs& a, const LitMatrixAr
   // (a histogram word stays below 2^32: fewer than 2^18 tiles per workgroup, xsg_litmatrix.h)
   if (litmatrix_per(a.ntiles, grid.x) >= kLitMatrixPerLimit) return hipErrorInvalidValue;
   const size_t lds = lit_lds(c.nlits, a.pat.set_ngrams, c.chunks_with != nullptr).bytes;
-  hipLaunchKernelGGL((a.pat.icase ? k_set_count_literals_chunks<true> : k_set_count_literals_chunks<false>), grid, dim3(kBlock), lds,
-                     s, a, c);
+  using K = void (*)(const ScanArgs, const LitMatrixArgs);
+  static const K k[2][2] = {{k_set_count_literals_chunks<false, false>, k_set_count_literals_chunks<false, true>},
+                            {k_set_count_literals_chunks<true, false>, k_set_count_literals_chunks<true, true>}};
+  hipLaunchKernelGGL(lit_kernel(k, a.pat), grid, dim3(kBlock), lds, s, a, c);
   return hipGetLastError();
 }
 
@@ -733,13 +751,16 @@ hipError_t launch_set_count_literals_csr(const ScanArgs& a, const LitCsrArgs& c,
         litmatrix_per(a.ntiles, grid) >= kLitMatrixPerLimit)
       return hipErrorInvalidValue;
     const size_t lds = lit_lds(c.nlits, a.pat.set_ngrams, false).bytes;
+    using K = void (*)(const ScanArgs, const LitCsrArgs);
+    static const K k_count[2][2] = {{k_set_count_literals_csr<false, false, false>, k_set_count_literals_csr<false, false, true>},
+                                    {k_set_count_literals_csr<true, false, false>, k_set_count_literals_csr<true, false, true>}};
+    static const K k_fill[2][2] = {{k_set_count_literals_csr<false, true, false>, k_set_count_literals_csr<false, true, true>},
+                                   {k_set_count_literals_csr<true, true, false>, k_set_count_literals_csr<true, true, true>}};
     if (fill) {
-      hipLaunchKernelGGL((a.pat.icase ? k_set_count_literals_csr<true, true> : k_set_count_literals_csr<false, true>), dim3(grid),
-                         dim3(kBlock), lds, s, a, c);
+      hipLaunchKernelGGL(lit_kernel(k_fill, a.pat), dim3(grid), dim3(kBlock), lds, s, a, c);
       hipLaunchKernelGGL(k_set_csr_seam<true>, dim3(grid), dim3(kBlock), 0, s, a.tile_chunk, a.chunk_tile0, a.ntiles, grid, c);
     } else {
-      hipLaunchKernelGGL((a.pat.icase ? k_set_count_literals_csr<true, false> : k_set_count_literals_csr<false, false>), dim3(grid),
-                         dim3(kBlock), lds, s, a, c);
+      hipLaunchKernelGGL(lit_kernel(k_count, a.pat), dim3(grid), dim3(kBlock), lds, s, a, c);
       hipLaunchKernelGGL(k_set_csr_seam<false>, dim3(grid), dim3(kBlock), 0, s, a.tile_chunk, a.chunk_tile0, a.ntiles, grid, c);
     }
   } else if (fill) {  // no tile: every row is empty, the status word is still due
@@ -749,8 +770,8 @@ hipError_t launch_set_count_literals_csr(const ScanArgs& a, const LitCsrArgs& c,
 }
 
 void describe_set_scan(const ScanArgs& a, bool emit, char* out, size_t cap) {
-  snprintf(out, cap, "xsg::k_set_scan<%s, %s> g=%u + xsg::k_set_verify", emit ? "true" : "false", a.pat.icase ? "true" : "false",
-           a.pat.set_g);
+  snprintf(out, cap, "xsg::k_set_scan<%s, %s> g=%u + xsg::k_set_verify%s", emit ? "true" : "false", a.pat.icase ? "true" : "false",
+           a.pat.set_g, a.pat.set_words ? " whole words" : "");
 }
 
 __global__ void k_warm_set() {}

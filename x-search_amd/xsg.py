@@ -34,6 +34,7 @@ MAX_REGEX = 1024
 MAX_LITERALS = 4096  # a literal list (xsg_set_literals): literals, bytes per literal, bytes of its filter image
 MAX_LITERAL_BYTES = 255
 LITERAL_FILTER_BYTES = 8192
+LIST_WHOLE_WORDS = 0x1  # list_flags of the _opts entry points: grep -w on a literal list (xsg.h: XSG_LIST_WHOLE_WORDS)
 STATUS_OK, STATUS_OVERFLOW, STATUS_NONASCII = 0, 1, 2
 TILE = 16384
 
@@ -126,6 +127,10 @@ def load():
         "xsg_set_literals": (ci, [vp, C.c_char_p, sz, u32]),
         "xsg_literals_info": (ci, [C.c_char_p, sz, u32, C.POINTER(LiteralList), vp]),
         "xsg_host_searcher_create_list": (ci, [ci, C.c_char_p, sz, u32, ci, C.POINTER(vp)]),
+        "xsg_set_literals_opts": (ci, [vp, C.c_char_p, sz, u32, u32]),
+        "xsg_host_searcher_create_list_opts": (ci, [ci, C.c_char_p, sz, u32, u32, ci, C.POINTER(vp)]),
+        "xsg_literal_counter_create_opts": (ci, [ci, C.c_char_p, sz, u32, u32, C.POINTER(vp)]),
+        "xsg_job_start_list": (ci, [C.c_char_p, sz, u32, C.c_char_p, C.c_char_p, C.POINTER(JobOpts), C.POINTER(vp)]),
         "xsg_regex_check": (ci, [C.c_char_p, sz, u32, C.POINTER(u32), C.POINTER(u32)]),
         "xsg_regex_info": (ci, [C.c_char_p, sz, u32, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)]),
         "xsg_regex_factor": (ci, [C.c_char_p, sz, u32, C.POINTER(u32), C.POINTER(u32)]),
@@ -225,7 +230,8 @@ EXPORTS = ["xsg_abi_version", "xsg_strerror", "xsg_last_error", "xsg_device_coun
            "xsg_count_literals_async", "xsg_literal_counter_create", "xsg_literal_counter_add", "xsg_literal_counter_get",
            "xsg_literal_counter_destroy", "xsg_count_literals_chunks", "xsg_count_literals_chunks_async",
            "xsg_literals_chunks_touched_capacity", "xsg_count_literals_csr", "xsg_result_literals_csr",
-           "xsg_count_literals_csr_async"]
+           "xsg_count_literals_csr_async", "xsg_set_literals_opts", "xsg_host_searcher_create_list_opts",
+           "xsg_literal_counter_create_opts", "xsg_job_start_list"]
 
 
 def _check(rc):
@@ -385,10 +391,11 @@ class Context:
         self.nliterals = 0
         _check(self._lib.xsg_set_pattern(self.h, pattern, len(pattern), flags))
 
-    def set_literals(self, lst: bytes, flags: int = 0):
-        """a list of literals separated by '\\n' as the pattern (xsg_set_literals; literal_list() joins one)"""
+    def set_literals(self, lst: bytes, flags: int = 0, list_flags: int = 0):
+        """a list of literals separated by '\\n' as the pattern (xsg_set_literals_opts; literal_list() joins one);
+        list_flags: LIST_WHOLE_WORDS"""
         self.nliterals = 0
-        _check(self._lib.xsg_set_literals(self.h, lst, len(lst), flags))
+        _check(self._lib.xsg_set_literals_opts(self.h, lst, len(lst), flags, list_flags))
         self.nliterals = literals_info(lst, flags)["count"]  # what Shard.count_literals sizes its result by
 
     def info(self):
@@ -617,12 +624,12 @@ class LiteralCounter:
     """Counts per literal over chunks in host memory, accumulated (xsg_literal_counter_*): add() the newline-aligned
     chunks of a file, get() its table."""
 
-    def __init__(self, device: int, lst: bytes, flags: int = 0):
+    def __init__(self, device: int, lst: bytes, flags: int = 0, list_flags: int = 0):
         self._lib = load()
         self.h = None
         self.k = literals_info(lst, flags)["count"]
         h = C.c_void_p()
-        _check(self._lib.xsg_literal_counter_create(device, lst, len(lst), flags, C.byref(h)))
+        _check(self._lib.xsg_literal_counter_create_opts(device, lst, len(lst), flags, list_flags, C.byref(h)))
         self.h = h
 
     def add(self, data):
@@ -785,7 +792,7 @@ class Job:
 
     def __init__(self, pattern: bytes, path: str, mode: int, meta_path: str | None = None, device: int = 0,
                  num_threads: int = 1, num_max_readers: int = 1, chunk_bytes: int = 16 << 20, flags: int = 0,
-                 chunk_range: tuple[int, int] | None = None, pattern_is_list: bool = False):
+                 chunk_range: tuple[int, int] | None = None, pattern_is_list: bool = False, list_flags: int = 0):
         self._lib = load()
         o = JobOpts()
         self._lib.xsg_job_opts_init(C.byref(o))
@@ -795,8 +802,11 @@ class Job:
             o.chunk_begin, o.chunk_end = chunk_range
         o.pattern_is_list = 1 if pattern_is_list else 0
         h = C.c_void_p()
-        _check(self._lib.xsg_job_start(pattern, len(pattern), os.fsencode(path),
-                                       os.fsencode(meta_path) if meta_path else None, C.byref(o), C.byref(h)))
+        meta = os.fsencode(meta_path) if meta_path else None
+        if list_flags:  # (xsg_job_start_list: the pattern is a list whatever pattern_is_list says)
+            _check(self._lib.xsg_job_start_list(pattern, len(pattern), list_flags, os.fsencode(path), meta, C.byref(o), C.byref(h)))
+        else:
+            _check(self._lib.xsg_job_start(pattern, len(pattern), os.fsencode(path), meta, C.byref(o), C.byref(h)))
         self.h = h
         self.mode = mode
 
