@@ -44,6 +44,7 @@ extern "C" {
  * joined; xsg_count_literals_chunks, xsg_count_literals_chunks_async and xsg_literals_chunks_touched_capacity joined;
  * xsg_count_literals_csr, xsg_result_literals_csr and xsg_count_literals_csr_async joined; XSG_LIST_WHOLE_WORDS with
  * xsg_set_literals_opts, xsg_host_searcher_create_list_opts, xsg_literal_counter_create_opts and xsg_job_start_list joined;
+ * xsg_find_literals, xsg_result_literal_hits, xsg_find_literals_async and xsg_literal_finder_* joined;
  * no entry point was removed or changed in meaning */
 #define XSG_ABI_VERSION 4
 
@@ -590,6 +591,52 @@ int xsg_result_literals_csr(xsg_shard* shard, uint64_t* row_ptr, uint64_t cap_ro
 int xsg_count_literals_csr_async(xsg_shard* shard, void* stream, uint64_t* d_row_ptr, uint64_t cap_rows,
                                  uint32_t* d_cols, uint64_t* d_vals, uint64_t cap_entries, uint64_t* d_status);
 
+/* ---- occurrences per literal ------------------------------------------------- */
+/* Where, and which literal: every occurrence of every literal of the list with its identity, in text order -- what
+ * dictionary tagging, positional postings and highlighting need, and the "all matches" output of an Aho-Corasick matcher.
+ * (The list tags, xsg_search with XSG_MATCH_BYTE_OFFSETS / XSG_MATCHES, report the winners of the leftmost-first walk only
+ * and not which literal won.)  Let l_0 .. l_{k-1} be the list as xsg_set_literals[_opts] parsed it and n the number of
+ * bound chunks.  An OCCURRENCE is a triple (c, p, j) with p + len(l_j) <= length(c) and the chunk bytes [p, p + len(l_j))
+ * equal to l_j; under XSG_FLAG_IGNORE_CASE both sides are ASCII-lowered first; under XSG_LIST_WHOLE_WORDS only admissible
+ * occurrences count.  This is the definition xsg_count_literals uses: overlapping occurrences (`aa` in `aaaa`: 3), covered
+ * ones (`ab`, `abc` on `abc`: both, at one position) and duplicates of the list (an entry each) are all included.  No byte
+ * at or beyond a chunk's end decides anything.
+ * The result is the list of ALL occurrences sorted ascending by (c, p, j), in three arrays:
+ *   chunk_ptr  n + 1 uint64: chunk_ptr[0] == 0, the entries [chunk_ptr[c], chunk_ptr[c + 1]) are chunk c's,
+ *              chunk_ptr[n] == total;
+ *   pos        total uint64: global_offset(c) + p, like every reported byte offset;
+ *   lit        total uint32: the listing index j.
+ * A chunk of length 0 is an empty range; a binding of 0 chunks is XSG_OK with chunk_ptr = {0} and total = 0.  The result
+ * is a function of the list, the flags and the bound bytes alone: bit-identical from call to call and across grid sizes,
+ * no entry's place is left to scheduling.  Relations: bincount(lit) == xsg_count_literals' counts; the bincount of chunk
+ * c's range == row c of xsg_count_literals_chunks; for a list of one literal without a border, pos equals the
+ * XSG_MATCH_BYTE_OFFSETS list under XSG_FLAG_EXACT_TAIL.
+ * xsg_find_literals runs the passes, sizes the result exactly and KEEPS it on the shard in buffers of its own (device
+ * memory and a pinned mirror); *total = chunk_ptr[n].  The kept result is valid until the next xsg_find_literals,
+ * xsg_shard_rebind or xsg_shard_invalidate on the shard; calls to other entry points in between do not disturb it.
+ * xsg_result_literal_hits copies it out and is XSG_ESTATE without one.  There: cap_rows >= n + 1; pos and lit are either
+ * both given (cap_entries >= total) or both NULL (chunk_ptr alone); words behind n + 1 / total are not touched.
+ * XSG_ESTATE: the ctx holds no pattern.  XSG_ENOTSUP: the pattern is no list set by xsg_set_literals, XSG_FLAG_INVERT is
+ * set, a binding of 2^24 chunks or more -- the refusals of xsg_count_literals_csr.  XSG_EINVAL: total == NULL; in
+ * xsg_result_literal_hits chunk_ptr == NULL, cap_rows < n + 1, cap_entries < total, exactly one of pos / lit NULL.  The
+ * CONTEXT bits and XSG_FLAG_EXACT_TAIL are accepted and ignored.  A result of more than 2^28 entries is XSG_ENOTSUP in the
+ * synchronous form -- the stream-ordered form, whose memory is the caller's, has no such limit.
+ * Two passes of the candidate scan around a prefix sum (k_set_find_literals): the first stores one word per 4 KiB wave
+ * span, its occurrences; the second skips the spans without one and stores the others' entries at the span's offset plus
+ * their rank.  The scratch is the shard's, 12 bytes per span (0.3 % of the text).  The synchronous form fetches
+ * chunk_ptr[n] between the passes, its one extra wait. */
+int xsg_find_literals(xsg_shard* shard, uint64_t* total);                                    /* waits; keeps the result */
+int xsg_result_literal_hits(xsg_shard* shard, uint64_t* chunk_ptr, uint64_t cap_rows, uint64_t* pos, uint32_t* lit,
+                            uint64_t cap_entries);                                           /* host memory */
+/* Stream-ordered form: d_chunk_ptr (cap_rows >= n + 1 words), d_pos and d_lit (cap_entries entries each) and d_status (one
+ * word) are DEVICE memory of the caller's, all required; nothing waits and nothing is fetched.  total <= cap_entries:
+ * *d_status = 0 and everything is written.  Otherwise *d_status = XSG_STATUS_OVERFLOW; d_chunk_ptr is still complete and
+ * true, so d_chunk_ptr[n] is the capacity to come back with; every entry with an index below cap_entries is written and
+ * correct; nothing at or behind cap_entries is written.  cap_entries == 0 (non-NULL pointers) is a pure sizing pass.
+ * XSG_EINVAL: a NULL output, cap_rows < n + 1.  The scratch is the shard's: calls on one shard follow one another. */
+int xsg_find_literals_async(xsg_shard* shard, void* stream, uint64_t* d_chunk_ptr, uint64_t cap_rows, uint64_t* d_pos,
+                            uint32_t* d_lit, uint64_t cap_entries, uint64_t* d_status);
+
 /* ---- list results (replace byte_offsets_match/_line, line; :136-154,187-207) */
 /* Runs the search for one of the list modes on the ctx stream and waits.
  * *n_results = number of elements (offsets / indices / lines).  Results stay
@@ -773,6 +820,19 @@ int xsg_literal_counter_create_opts(int device, const void* list, size_t n, uint
 int xsg_literal_counter_add(xsg_literal_counter* lc, const void* data, uint64_t len);
 int xsg_literal_counter_get(xsg_literal_counter* lc, uint64_t* counts, uint64_t cap_literals, uint64_t* bytes);
 void xsg_literal_counter_destroy(xsg_literal_counter* lc);
+
+/* Occurrences per literal (xsg_find_literals) of ONE chunk in host memory, synchronous: *pos and *lit receive malloc'ed
+ * arrays of *n entries (xsg_free each; never NULL on XSG_OK), sorted by (position, listing index), pos[i] = base + p -- a
+ * reader loop passes the chunk's offset in its file as `base` and gets file offsets.  len == 0 yields n = 0.  The finder
+ * owns a context with the list, a pinned staging block and a device buffer.  `flags`, `list_flags`: those of
+ * xsg_set_literals_opts; XSG_FLAG_INVERT is XSG_ENOTSUP; under XSG_LIST_WHOLE_WORDS the chunk's edges are word boundaries.
+ * One finder is used from one thread at a time. */
+typedef struct xsg_literal_finder xsg_literal_finder;
+int xsg_literal_finder_create_opts(int device, const void* list, size_t n, uint32_t flags, uint32_t list_flags,
+                                   xsg_literal_finder** out);
+int xsg_literal_finder_find(xsg_literal_finder* lf, const void* data, uint64_t len, uint64_t base, uint64_t** pos,
+                            uint32_t** lit, uint64_t* n);
+void xsg_literal_finder_destroy(xsg_literal_finder* lf);
 
 /* ---- chunk plans and metafiles (host only: usable without a GPU) ------------- */
 /* One record of the reference's metafile (decoded from test/files/ *.meta,

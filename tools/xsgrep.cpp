@@ -4,6 +4,7 @@
 //   xsgrep [-c] [-i] [-o] [-v] [-E|-F] [-x] [-A N] [-B N] [-C N] [-j THREADS] [-m METAFILE] PATTERN FILE|-
 //   xsgrep -F [-c] [-i] [-o] [-v] [-w] [-A N] [-B N] [-C N] [-j THREADS] [-m METAFILE] (-e PATTERN)... [-f FILE]... FILE|-
 //   xsgrep -F [-i] [-w] --count-each (-e PATTERN)... [-f FILE]... FILE|-
+//   xsgrep -F [-i] [-w] --find-each (-e PATTERN)... [-f FILE]... FILE|-
 //
 // -c  print only a count of matching lines   (grep.cpp:45-46 -> xs::count_lines)
 // -i  ignore ASCII case                      (grep.cpp:47-48)
@@ -32,6 +33,11 @@
 //     however many literals there are.  Requires -F; a single -e or the positional PATTERN is a list of one.  Excludes
 //     -c -o -v -x -A -B -C -m: it prints no lines and counts no lines.  The input is read in newline-aligned chunks, FILE
 //     and stdin alike; a literal holds no newline, so no occurrence straddles a cut and the sums are the input's.
+// --find-each  every occurrence with its identity: one line per occurrence, OFFSET:LITERAL -- the shape of grep -b -o -- in
+//     file order and, at one offset, in listing order (xsg_literal_finder_* -> xsg_find_literals).  These are the occurrences
+//     --count-each counts: overlapping ones, covered ones and duplicates of the list all appear.  OFFSET is the byte offset
+//     in the input; LITERAL is printed as listed, not in the text's case.  Requires -F; reads the input in the same
+//     newline-aligned chunks; excludes what --count-each excludes, and --count-each itself.
 // -w  whole words only (grep -w; XS_WHOLE_WORDS -> XSG_LIST_WHOLE_WORDS): an occurrence counts only between two bytes that
 //     are no word bytes (0-9 A-Z a-z _), the ends of the input's chunks counting as such.  Served with -F only -- the
 //     literals go as a list, a single PATTERN as a list of one -- and never dropped: without -F it is an error.  Combines
@@ -56,6 +62,7 @@ static const char kUsage[] =
     "usage: %s [-c] [-i] [-o] [-v] [-E|-F] [-x] [-A N] [-B N] [-C N] [-j THREADS] [-m METAFILE] PATTERN FILE|-\n"
     "       %s -F [-c] [-i] [-o] [-v] [-w] [-A N] [-B N] [-C N] [-j THREADS] [-m METAFILE] (-e PATTERN)... [-f FILE]... FILE|-\n"
     "       %s -F [-i] [-w] --count-each (-e PATTERN)... [-f FILE]... FILE|-\n"
+    "       %s -F [-i] [-w] --find-each (-e PATTERN)... [-f FILE]... FILE|-\n"
     "  -e PATTERN, -f FILE (one literal per line) search for any of several literals; both may repeat, need -F and exclude -x\n"
     "     when they give more than one pattern; -o then prints the FIRST-listed literal that occurs at a position (GNU grep: the longest)\n"
     "  -A N, -B N, -C N also print N lines after / before / around every selected line (N <= 4095), each line once and\n"
@@ -66,7 +73,10 @@ static const char kUsage[] =
     "     ends of the input); needs -F (a single PATTERN goes as a list of one), excludes -x; works with --count-each too\n"
     "  -x searches (?m)^(?:PATTERN)$; PATTERN must not be empty\n"
     "  --count-each prints COUNT<TAB>LITERAL for every literal in listing order: its occurrences in the input, overlapping\n"
-    "     ones and those inside another literal's included; needs -F, excludes -c -o -v -x -A -B -C -m\n";
+    "     ones and those inside another literal's included; needs -F, excludes -c -o -v -x -A -B -C -m\n"
+    "  --find-each prints OFFSET:LITERAL for every occurrence of every literal, in file order and then listing order (the shape\n"
+    "     of grep -b -o, with overlapping and covered occurrences); the literal as listed; needs -F, excludes what --count-each\n"
+    "     excludes and --count-each itself\n";
 
 // PATTERN without a leading `^` and a trailing unescaped `$`: under -x they say what the wrap says already
 static std::string strip_edge_anchors(std::string p) {
@@ -160,9 +170,44 @@ static int count_each(const std::vector<std::string>& lits, bool icase, bool wor
   return 0;
 }
 
+// --find-each: OFFSET:LITERAL for every occurrence (xsg_literal_finder_*), chunk after chunk; -> the exit status
+static int find_each(const std::vector<std::string>& lits, bool icase, bool words, const std::string& file) {
+  std::string list;
+  for (const std::string& l : lits) list += (list.empty() ? "" : "\n") + l;
+  std::FILE* in = file == "-" ? stdin : std::fopen(file.c_str(), "rb");
+  if (!in) {
+    std::fprintf(stderr, "xsgrep: cannot read '%s'\n", file.c_str());
+    return 2;
+  }
+  xsg_literal_finder* lf = nullptr;
+  int rc = xsg_literal_finder_create_opts(0, list.data(), list.size(), icase ? XSG_FLAG_IGNORE_CASE : 0u,
+                                          words ? XSG_LIST_WHOLE_WORDS : 0u, &lf);
+  uint64_t base = 0;  // the chunk's offset in the input
+  if (rc == XSG_OK)
+    for_each_aligned_chunk(in, [&](const std::vector<char>& chunk) {
+      if (rc != XSG_OK) return;
+      uint64_t* pos = nullptr;
+      uint32_t* lit = nullptr;
+      uint64_t n = 0;
+      rc = xsg_literal_finder_find(lf, chunk.data(), chunk.size(), base, &pos, &lit, &n);
+      if (rc == XSG_OK) {
+        for (uint64_t i = 0; i < n; ++i) std::cout << pos[i] << ':' << lits[lit[i]] << '\n';
+        xsg_free(pos);
+        xsg_free(lit);
+      }
+      base += chunk.size();
+    });
+  if (rc != XSG_OK) {
+    std::fprintf(stderr, "xsgrep: %s\n", xsg_last_error());
+    return rc == XSG_EINVAL ? 2 : 1;
+  }
+  std::cout.flush();
+  return 0;
+}
+
 int main(int argc, char** argv) {
   bool count = false, icase = false, fixed = false, extended = false, whole_lines = false, invert = false, only = false;
-  bool each = false, context_given = false, words = false;
+  bool each = false, find = false, context_given = false, words = false;
   int threads = 2;  // grep.cpp:21
   long before = 0, after = 0;
   std::string meta, pattern, file;
@@ -189,6 +234,8 @@ int main(int argc, char** argv) {
       words = true;
     } else if (a == "--count-each") {
       each = true;
+    } else if (a == "--find-each") {
+      find = true;
     } else if (a == "-c" || a == "--count") {
       count = true;
     } else if (a == "-i" || a == "--ignore-case") {
@@ -234,7 +281,7 @@ int main(int argc, char** argv) {
       }
       have_patterns = true;
     } else if (a == "-h" || a == "--help") {
-      std::printf(kUsage, argv[0], argv[0], argv[0]);
+      std::printf(kUsage, argv[0], argv[0], argv[0], argv[0]);
       return 0;
     } else if (pos == 0 && !have_patterns) {
       pattern = a;
@@ -257,12 +304,38 @@ int main(int argc, char** argv) {
     pos = 2;
   }
   if (pos != 2) {
-    std::fprintf(stderr, kUsage, argv[0], argv[0], argv[0]);
+    std::fprintf(stderr, kUsage, argv[0], argv[0], argv[0], argv[0]);
     return 2;
   }
   if (words && (!fixed || whole_lines)) {  // never a silent substring search
     std::fprintf(stderr, "xsgrep: -w (whole words) is served for literals only: it needs -F and excludes -x\n");
     return 2;
+  }
+  if (find) {  // every occurrence with its literal: no lines are selected, printed or counted
+    const char* clash = !fixed ? "needs -F: it finds literals" : each ? "excludes --count-each (one prints occurrences, the other their number)"
+                        : count ? "excludes -c (it prints occurrences, it counts no lines)"
+                        : only ? "excludes -o (it prints every occurrence, not the matches of the leftmost-first walk)"
+                        : invert ? "excludes -v (an occurrence has no inverted form)"
+                        : whole_lines ? "excludes -x (it finds occurrences, not whole lines)"
+                        : context_given ? "excludes -A, -B and -C (it prints no lines)"
+                        : !meta.empty() ? "excludes -m (it reads the input in chunks of its own)" : extended ? "excludes -E" : nullptr;
+    if (clash) {
+      std::fprintf(stderr, "xsgrep: --find-each %s\n", clash);
+      return 2;
+    }
+    if (!have_patterns) patterns.push_back(pattern);
+    if (patterns.empty()) {
+      std::fprintf(stderr, "xsgrep: -f: the pattern file holds no pattern\n");
+      return 2;
+    }
+    for (const std::string& p : patterns)
+      if (p.empty() || p.find('\n') != std::string::npos) {
+        std::fprintf(stderr, "xsgrep: --find-each: an empty pattern (or one with a newline) is not served\n");
+        return 2;
+      }
+    const int rc = find_each(patterns, icase, words, file);
+    std::fflush(stdout);
+    std::_Exit(rc);  // (as at the end of main: the runtime's teardown is left to the kernel)
   }
   if (each) {  // a keyword table: no lines are selected, printed or counted
     const char* clash = !fixed ? "needs -F: it counts literals" : count ? "excludes -c (it counts occurrences per literal, not lines)"

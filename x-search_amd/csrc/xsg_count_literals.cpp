@@ -4,11 +4,14 @@
 // chunks x literals matrix (xsg_count_literals_chunks, xsg_count_literals_chunks_async): the same pass with the chunk
 // boundaries kept, k_set_count_literals_chunks.  Behind those the matrix in CSR form (xsg_count_literals_csr,
 // xsg_result_literals_csr, xsg_count_literals_csr_async): a count pass, a prefix sum of the rows' lengths and a fill pass.
+// Last the occurrences themselves (xsg_find_literals, xsg_result_literal_hits, xsg_find_literals_async): a count pass per
+// 4 KiB wave span, a prefix sum over the spans and a fill pass of (position, literal) entries.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
 
 #include "xsg_host.h"
+#include "xsg_litfind.h"
 #include "xsg_litmatrix.h"
 
 using namespace xsg;
@@ -277,4 +280,128 @@ extern "C" int xsg_count_literals_csr_async(xsg_shard* s, void* stream, uint64_t
   HIP_TRY(hipSetDevice(c->device));
   return enqueue_count_literals_csr(s, stream ? static_cast<hipStream_t>(stream) : c->stream, d_row_ptr, d_cols, d_vals, cap_entries,
                                     d_status);
+}
+
+// ---- every occurrence with its identity: xsg_find_literals -------------------------------------------------------------------------
+namespace {
+struct FindCall {
+  ScanArgs a;
+  LitFindArgs f;
+  uint32_t forced;
+};
+}  // namespace
+
+// Steps 1 and 2 of DESIGN.md 3.5i on `st`: the count pass into a word per wave span, their prefix sum, and d_chunk_ptr
+// (n + 1 words) with *d_status (optional) gathered from it.  Every size is the host's: tiles and chunks.
+static int find_count_spans(xsg_shard* s, hipStream_t st, uint64_t* d_chunk_ptr, uint64_t cap_entries, uint64_t* d_status, FindCall* k) {
+  xsg_ctx* c = s->ctx;
+  if (s->table_pending && st != c->stream) HIP_TRY(hipStreamWaitEvent(st, s->table_ev, 0));
+  k->a = scan_args(s);
+  const uint64_t words = litfind_words(k->a.ntiles);
+  XSG_TRY(s->d_find_occ.ensure(4 * (size_t)words));
+  XSG_TRY(s->d_find_off.ensure(8 * (size_t)(words + 1)));
+  XSG_TRY(s->d_find_tmp.ensure(8 * (size_t)scan_tmp_elems(words)));
+  // tests: a grid of a few workgroups on a dozen tiles (never more workgroups than tiles: set_litfind_grid)
+  const char* g = XSG_TOGGLE("XSG_LITFIND_GRID");
+  k->forced = g && atoll(g) > 0 ? (uint32_t)std::min<long long>(atoll(g), 1 << 30) : 0u;
+  LitFindArgs& f = k->f;
+  f = LitFindArgs{};
+  f.wave_occ = s->d_find_occ.as<uint32_t>();
+  f.idx_off = c->set_idx_off;
+  HIP_TRY(launch_set_find_literals(k->a, f, k->forced, false, st));
+  HIP_TRY(launch_exclusive_scan_u32(f.wave_occ, s->d_find_off.as<uint64_t>(), words, s->d_find_tmp.as<uint64_t>(), st));
+  HIP_TRY(launch_set_find_chunk_ptr(k->a, s->d_find_off.as<uint64_t>(), d_chunk_ptr, cap_entries, d_status, st));
+  return XSG_OK;
+}
+
+// Step 3: the fill pass into d_pos / d_lit, nothing at or behind cap_entries
+static int find_fill_spans(xsg_shard* s, hipStream_t st, FindCall* k, uint64_t* d_pos, uint32_t* d_lit, uint64_t cap_entries) {
+  LitFindArgs& f = k->f;
+  f.wave_off = s->d_find_off.as<uint64_t>();
+  f.pos = d_pos;
+  f.lit = d_lit;
+  f.cap_entries = cap_entries;
+  HIP_TRY(launch_set_find_literals(k->a, f, k->forced, true, st));
+  return XSG_OK;
+}
+
+int xsg::enqueue_find_literals(xsg_shard* s, hipStream_t st, uint64_t* d_chunk_ptr, uint64_t* d_pos, uint32_t* d_lit,
+                               uint64_t cap_entries, uint64_t* d_status) {
+  FindCall k;
+  XSG_TRY(find_count_spans(s, st, d_chunk_ptr, cap_entries, d_status, &k));
+  if (cap_entries == 0) return XSG_OK;  // a sizing pass: no entry has a place
+  return find_fill_spans(s, st, &k, d_pos, d_lit, cap_entries);
+}
+
+extern "C" int xsg_find_literals(xsg_shard* s, uint64_t* total_out) {
+  XSG_TRY(count_literals_csr_args(s));
+  if (!total_out) return fail(XSG_EINVAL, "total is null");
+  xsg_ctx* c = s->ctx;
+  HIP_TRY(hipSetDevice(c->device));
+  s->find_valid = false;
+  const uint64_t n = s->chunks.size();
+  XSG_TRY(s->d_find_ptr.ensure(8 * (size_t)(n + 1)));
+  uint64_t* const d_chunk_ptr = s->d_find_ptr.as<uint64_t>();
+  FindCall k;
+  XSG_TRY(find_count_spans(s, c->stream, d_chunk_ptr, 0, nullptr, &k));
+  // the one size this form fetches: it sizes pos, lit and the mirror exactly
+  uint64_t total = 0;
+  HIP_TRY(hipMemcpyAsync(&total, d_chunk_ptr + n, 8, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  s->table_pending = false;
+  if (total > (1ull << 28))
+    return fail(XSG_ENOTSUP, "a result of %llu entries is more than the synchronous form keeps (2^28 entries): use "
+                "xsg_find_literals_async with device memory of the caller's", (unsigned long long)total);
+  const size_t cp_bytes = 8 * (size_t)(n + 1), pos_bytes = 8 * (size_t)total, lit_bytes = 4 * (size_t)total;
+  s->h_find.trim(cp_bytes + pos_bytes + lit_bytes);  // (what a far larger earlier result left page-locked)
+  XSG_TRY(s->d_find_pos.ensure(pos_bytes));
+  XSG_TRY(s->d_find_lit.ensure(lit_bytes));
+  XSG_TRY(s->h_find.ensure(cp_bytes + pos_bytes + lit_bytes));
+  uint8_t* const h = s->h_find.as<uint8_t>();
+  HIP_TRY(hipMemcpyAsync(h, d_chunk_ptr, cp_bytes, hipMemcpyDeviceToHost, c->stream));
+  if (total) {
+    XSG_TRY(find_fill_spans(s, c->stream, &k, s->d_find_pos.as<uint64_t>(), s->d_find_lit.as<uint32_t>(), total));
+    HIP_TRY(hipMemcpyAsync(h + cp_bytes, s->d_find_pos.p, pos_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(h + cp_bytes + pos_bytes, s->d_find_lit.p, lit_bytes, hipMemcpyDeviceToHost, c->stream));
+  }
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  s->find_rows = n;
+  s->find_total = total;
+  s->find_valid = true;
+  *total_out = total;
+  return XSG_OK;
+}
+
+extern "C" int xsg_result_literal_hits(xsg_shard* s, uint64_t* chunk_ptr, uint64_t cap_rows, uint64_t* pos, uint32_t* lit,
+                                       uint64_t cap_entries) {
+  if (!s) return fail(XSG_EINVAL, "shard is null");
+  if (!s->find_valid)
+    return fail(XSG_ESTATE, "no result of xsg_find_literals is kept: none was run on this binding, or a rebind or invalidate dropped it");
+  if (!chunk_ptr) return fail(XSG_EINVAL, "chunk_ptr is null");
+  if (cap_rows < s->find_rows + 1)
+    return fail(XSG_EINVAL, "room for %llu chunk_ptr words, %llu chunks need %llu", (unsigned long long)cap_rows,
+                (unsigned long long)s->find_rows, (unsigned long long)s->find_rows + 1);
+  if ((pos == nullptr) != (lit == nullptr)) return fail(XSG_EINVAL, "pos and lit go together: both, or neither for chunk_ptr alone");
+  if (pos && cap_entries < s->find_total)
+    return fail(XSG_EINVAL, "room for %llu entries, the result holds %llu", (unsigned long long)cap_entries, (unsigned long long)s->find_total);
+  const size_t cp_bytes = 8 * (size_t)(s->find_rows + 1), pos_bytes = 8 * (size_t)s->find_total;
+  const uint8_t* const h = s->h_find.as<uint8_t>();
+  memcpy(chunk_ptr, h, cp_bytes);
+  if (pos && s->find_total) {
+    memcpy(pos, h + cp_bytes, pos_bytes);
+    memcpy(lit, h + cp_bytes + pos_bytes, 4 * (size_t)s->find_total);
+  }
+  return XSG_OK;
+}
+
+extern "C" int xsg_find_literals_async(xsg_shard* s, void* stream, uint64_t* d_chunk_ptr, uint64_t cap_rows, uint64_t* d_pos,
+                                       uint32_t* d_lit, uint64_t cap_entries, uint64_t* d_status) {
+  XSG_TRY(count_literals_csr_args(s));
+  if (!d_chunk_ptr || !d_pos || !d_lit || !d_status) return fail(XSG_EINVAL, "d_chunk_ptr, d_pos, d_lit or d_status is null");
+  if (cap_rows < (uint64_t)s->chunks.size() + 1)
+    return fail(XSG_EINVAL, "room for %llu chunk_ptr words, %llu chunks need %llu", (unsigned long long)cap_rows,
+                (unsigned long long)s->chunks.size(), (unsigned long long)s->chunks.size() + 1);
+  xsg_ctx* c = s->ctx;
+  HIP_TRY(hipSetDevice(c->device));
+  return enqueue_find_literals(s, stream ? static_cast<hipStream_t>(stream) : c->stream, d_chunk_ptr, d_pos, d_lit, cap_entries, d_status);
 }

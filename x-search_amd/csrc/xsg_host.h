@@ -41,6 +41,12 @@ int enqueue_count_literals_chunks(xsg_shard* s, hipStream_t st, uint64_t* d_coun
 int enqueue_count_literals_csr(xsg_shard* s, hipStream_t st, uint64_t* d_row_ptr, uint32_t* d_cols, uint64_t* d_vals,
                                uint64_t cap_entries, uint64_t* d_status);
 
+// The passes of xsg_find_literals on `st`: count pass into the shard's scratch, prefix sum over the wave spans, d_chunk_ptr
+// (chunks + 1 words) and *d_status gathered from it, fill pass into d_pos / d_lit below cap_entries (none for a capacity of
+// 0).  No size leaves the device and nothing is zeroed.
+int enqueue_find_literals(xsg_shard* s, hipStream_t st, uint64_t* d_chunk_ptr, uint64_t* d_pos, uint32_t* d_lit,
+                          uint64_t cap_entries, uint64_t* d_status);
+
 inline const char* const kNonAsciiMsg =
     "the expression uses '.', a negated class or \\D \\W \\S, which match whole code points in RE2; the data holds "
     "bytes >= 0x80, where one byte per position is not the same thing: refused, not approximated";

@@ -365,6 +365,25 @@ struct LitCsrArgs {
 };
 unsigned set_litcsr_grid(const ScanArgs& a, uint32_t nlits, uint32_t forced);  // 0: the binding has no tile
 hipError_t launch_set_count_literals_csr(const ScanArgs& a, const LitCsrArgs& c, uint32_t grid, bool fill, hipStream_t s);
+// k_set_find_literals<ICASE, FILL, WORDS> and k_set_find_chunk_ptr (xsg_find_literals*): every occurrence of every literal as
+// (position, listing index), sorted by (chunk, position, listing index), in two passes of one grid-stride loop around a
+// prefix sum (xsg_litfind.h).  The count pass (FILL = false) writes wave_occ[4 * tile + wave], every word;
+// the caller scans them into wave_off (4 * ntiles + 1 words), launch_set_find_chunk_ptr gathers chunk_ptr from it and
+// writes *status, and the fill pass stores pos / lit below cap_entries.  Nothing needs a memset.
+struct LitFindArgs {
+  uint32_t* wave_occ;        // device, 4 * ntiles words: the occurrences of every wave span
+  const uint64_t* wave_off;  // device, 4 * ntiles + 1 words: their exclusive prefix (fill pass)
+  uint64_t* pos;             // device, cap_entries words: global_offset(c) + p (fill pass)
+  uint32_t* lit;             // device, cap_entries words: the listing index (fill pass)
+  uint64_t cap_entries;
+  uint32_t idx_off;          // byte offset of SetTable::idx inside PatternDev::d_pat
+};
+unsigned set_litfind_grid(const ScanArgs& a, uint32_t forced);  // forced: XSG_LITFIND_GRID, 0 when unset; 0 tiles: 0
+hipError_t launch_set_find_literals(const ScanArgs& a, const LitFindArgs& f, uint32_t forced_grid, bool fill, hipStream_t s);
+// chunk_ptr[c] = wave_off[4 * chunk_tile0[c]] for c in [0, nchunks]; *status (optional) = XSG_STATUS_OVERFLOW iff
+// chunk_ptr[nchunks] > cap_entries
+hipError_t launch_set_find_chunk_ptr(const ScanArgs& a, const uint64_t* wave_off, uint64_t* chunk_ptr, uint64_t cap_entries,
+                                     uint64_t* status, hipStream_t s);
 // "xsg::k_scan<KIND, WANT_NL, WANT_LINES, EMIT, LOADS, ICASE>" + the stagger launch_scan would use, for reports
 // finishing: the caller's pass is a plain match count that takes the finishing form where scan_finishing says so;
 // spans: that form would run with the binding's span locator (GateFinArgs::spans); waves: and as the wave form, taking

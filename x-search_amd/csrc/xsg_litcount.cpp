@@ -2,7 +2,9 @@
 // reader loop hands in chunk after chunk of a file; the counter stages each through one of two pinned slots, runs the pass
 // of xsg_count_literals over it on the slot's stream and keeps the running sums on the device.  The copy of chunk i + 1
 // overlaps the pass over chunk i.  (Its own file: xsg_file.cpp links against tests/cpp/device_double.cpp alone and must
-// not reference a chunk-level entry point that double does not have.)
+// not reference a chunk-level entry point that double does not have.)  Beside it xsg_literal_finder_*, the same seam of
+// xsg_find_literals: one chunk per call, its occurrences handed back in malloc'ed arrays.
+#include <cstdlib>
 #include <cstring>
 #include <memory>
 #include <new>
@@ -118,3 +120,92 @@ extern "C" int xsg_literal_counter_get(xsg_literal_counter* lc, uint64_t* counts
 }
 
 extern "C" void xsg_literal_counter_destroy(xsg_literal_counter* lc) { delete lc; }
+
+// ---- xsg_literal_finder_*: the host-memory seam of xsg_find_literals --------------------------------------------------------------
+// One chunk per call, synchronous: the chunk goes up through a pinned block, is bound as the shard's only chunk with
+// global_offset = base, and the kept result of xsg_find_literals comes back in malloc'ed arrays.
+struct xsg_literal_finder {
+  xsg_ctx* ctx = nullptr;
+  xsg_shard* shard = nullptr;
+  void* pinned = nullptr;
+  void* dev = nullptr;
+  uint64_t cap = 0;
+  ~xsg_literal_finder() {
+    if (ctx) (void)hipSetDevice(ctx->device);
+    if (ctx && ctx->stream) (void)hipStreamSynchronize(ctx->stream);
+    if (shard) xsg_shard_destroy(shard);
+    if (pinned) (void)hipHostFree(pinned);
+    if (dev) (void)hipFree(dev);
+    if (ctx) xsg_ctx_destroy(ctx);
+  }
+};
+
+extern "C" int xsg_literal_finder_create_opts(int device, const void* list, size_t n, uint32_t flags, uint32_t list_flags,
+                                              xsg_literal_finder** out) {
+  if (!out) return fail(XSG_EINVAL, "out is null");
+  *out = nullptr;
+  if (list_flags & ~XSG_LIST_WHOLE_WORDS) return fail(XSG_EINVAL, "unknown list flags 0x%x", list_flags);
+  if (flags & XSG_FLAG_INVERT) return fail(XSG_ENOTSUP, "%s", kInvertMatchMsg);
+  XSG_TRY(xsg_literals_info(list, n, flags, nullptr, nullptr));  // a bad list fails before a device is touched
+  std::unique_ptr<xsg_literal_finder> lf(new (std::nothrow) xsg_literal_finder());
+  if (!lf) return fail(XSG_ENOMEM, "host allocation failed");
+  XSG_TRY(xsg_ctx_create(device, &lf->ctx));
+  XSG_TRY(xsg_set_literals_opts(lf->ctx, list, n, flags, list_flags));
+  XSG_TRY(xsg_shard_create(lf->ctx, nullptr, 0, nullptr, 0, &lf->shard));
+  *out = lf.release();
+  return XSG_OK;
+}
+
+extern "C" int xsg_literal_finder_find(xsg_literal_finder* lf, const void* data, uint64_t len, uint64_t base, uint64_t** pos,
+                                       uint32_t** lit, uint64_t* n) {
+  if (!lf || !pos || !lit || !n || (!data && len)) return fail(XSG_EINVAL, "null argument");
+  *pos = nullptr;
+  *lit = nullptr;
+  *n = 0;
+  if (len >= (1ull << 40)) return fail(XSG_EINVAL, "chunk too large");
+  xsg_ctx* c = lf->ctx;
+  HIP_TRY(hipSetDevice(c->device));
+  uint64_t total = 0;
+  if (len) {
+    const uint64_t need = ((len + 15u) & ~(uint64_t)15u) + 256u;
+    if (need > lf->cap) {
+      if (lf->pinned) (void)hipHostFree(lf->pinned);
+      if (lf->dev) (void)hipFree(lf->dev);
+      lf->pinned = lf->dev = nullptr;
+      lf->cap = 0;
+      const uint64_t cap = std::max<uint64_t>(need, 1u << 20);
+      HIP_TRY(hipHostMalloc(&lf->pinned, cap, hipHostMallocDefault));
+      HIP_TRY(hipMalloc(&lf->dev, cap));
+      lf->cap = cap;
+    }
+    memcpy(lf->pinned, data, len);
+    HIP_TRY(hipMemcpyAsync(lf->dev, lf->pinned, len, hipMemcpyHostToDevice, c->stream));
+    xsg_chunk ch{};
+    ch.length = len;
+    ch.global_offset = base;
+    XSG_TRY(xsg_shard_rebind(lf->shard, lf->dev, lf->cap, &ch, 1));
+    XSG_TRY(xsg_find_literals(lf->shard, &total));  // (waits on the context's stream, behind the copy)
+  }
+  uint64_t* p = static_cast<uint64_t*>(malloc(8 * std::max<uint64_t>(total, 1)));
+  uint32_t* l = static_cast<uint32_t*>(malloc(4 * std::max<uint64_t>(total, 1)));
+  if (!p || !l) {
+    free(p);
+    free(l);
+    return fail(XSG_ENOMEM, "host allocation failed");
+  }
+  if (total) {
+    uint64_t chunk_ptr[2];
+    const int r = xsg_result_literal_hits(lf->shard, chunk_ptr, 2, p, l, total);
+    if (r != XSG_OK) {
+      free(p);
+      free(l);
+      return r;
+    }
+  }
+  *pos = p;
+  *lit = l;
+  *n = total;
+  return XSG_OK;
+}
+
+extern "C" void xsg_literal_finder_destroy(xsg_literal_finder* lf) { delete lf; }

@@ -277,6 +277,14 @@ struct xsg_shard {
   PinBuf h_csr;
   bool csr_valid = false;
   uint64_t csr_rows = 0, csr_nnz = 0;  // ... n and row_ptr[n] of the kept result
+  // xsg_find_literals: the scratch of both forms -- a word per 4 KiB wave span (its occurrences), their prefix sum (uint64)
+  // and its tmp: 12 bytes per span, 0.3 % of the text.  Then the synchronous form's result (chunk_ptr and the status word
+  // behind it; pos and lit, sized exactly from chunk_ptr[n]) and its pinned mirror (chunk_ptr, pos, lit in this order), kept
+  // until the next xsg_find_literals, rebind or invalidate: xsg_result_literal_hits copies from the mirror.
+  DevBuf d_find_occ, d_find_off, d_find_tmp, d_find_ptr, d_find_pos, d_find_lit;
+  PinBuf h_find;
+  bool find_valid = false;
+  uint64_t find_rows = 0, find_total = 0;  // ... n and chunk_ptr[n] of the kept result
   uint64_t list_entries = 0;  // raw entries (ListArgs::M) the last exact list pass left in d_m_chunk / d_keep_pre
   bool begin_sync_result = false;  // xsg_count_begin had to run synchronously: _end hands out begin_counters
   uint64_t begin_counters[XSG_NUM_COUNTERS] = {0, 0, 0, 0};
@@ -312,13 +320,14 @@ struct xsg_shard {
                      &d_c_pre, &d_tile_mask, &d_tot, &d_hit, &d_scan2, &d_wmask, &d_inv_lo, &d_inv_cnt,
                      &d_inv_off, &d_inv_pos, &d_inv_chunk, &d_m_len, &d_f_len, &d_cx_lo, &d_cx_hi, &d_cx_cnt,
                      &d_cx_slot, &d_cx_pos, &d_cx_chunk, &d_cx_edge, &d_sketch, &d_spans, &d_chunk_counts, &d_lit_counts,
-                     &d_lit_matrix, &d_csr_row_nnz, &d_csr_tmp, &d_csr_seam, &d_csr_row_ptr, &d_csr_cols, &d_csr_vals};
+                     &d_lit_matrix, &d_csr_row_nnz, &d_csr_tmp, &d_csr_seam, &d_csr_row_ptr, &d_csr_cols, &d_csr_vals,
+                     &d_find_occ, &d_find_off, &d_find_tmp, &d_find_ptr, &d_find_pos, &d_find_lit};
     for (DevBuf* b : all) b->release();
     if (h_stage) (void)hipHostFree(h_stage);
     if (h_counters) (void)hipHostFree(h_counters);
     if (h_tot) (void)hipHostFree(h_tot);
     h_tot = nullptr;
-    for (PinBuf* b : {&h_result, &hp_line_len, &hp_line_bytes, &h_chunk_counts, &h_lit_counts, &h_lit_matrix, &h_csr}) b->release();
+    for (PinBuf* b : {&h_result, &hp_line_len, &hp_line_bytes, &h_chunk_counts, &h_lit_counts, &h_lit_matrix, &h_csr, &h_find}) b->release();
     if (table_ev) (void)hipEventDestroy(table_ev);
     h_stage = nullptr;
     h_counters = nullptr;

@@ -154,6 +154,12 @@ def load():
         "xsg_count_literals_csr": (ci, [vp, vp]),
         "xsg_result_literals_csr": (ci, [vp, vp, u64, vp, vp, u64]),
         "xsg_count_literals_csr_async": (ci, [vp, vp, vp, u64, vp, vp, u64, vp]),
+        "xsg_find_literals": (ci, [vp, vp]),
+        "xsg_result_literal_hits": (ci, [vp, vp, u64, vp, vp, u64]),
+        "xsg_find_literals_async": (ci, [vp, vp, vp, u64, vp, vp, u64, vp]),
+        "xsg_literal_finder_create_opts": (ci, [ci, C.c_char_p, sz, u32, u32, C.POINTER(vp)]),
+        "xsg_literal_finder_find": (ci, [vp, vp, u64, u64, C.POINTER(vp), C.POINTER(vp), _u64p]),
+        "xsg_literal_finder_destroy": (None, [vp]),
         "xsg_literal_counter_create": (ci, [ci, C.c_char_p, sz, u32, C.POINTER(vp)]),
         "xsg_literal_counter_add": (ci, [vp, vp, u64]),
         "xsg_literal_counter_get": (ci, [vp, vp, u64, _u64p]),
@@ -231,7 +237,9 @@ EXPORTS = ["xsg_abi_version", "xsg_strerror", "xsg_last_error", "xsg_device_coun
            "xsg_literal_counter_destroy", "xsg_count_literals_chunks", "xsg_count_literals_chunks_async",
            "xsg_literals_chunks_touched_capacity", "xsg_count_literals_csr", "xsg_result_literals_csr",
            "xsg_count_literals_csr_async", "xsg_set_literals_opts", "xsg_host_searcher_create_list_opts",
-           "xsg_literal_counter_create_opts", "xsg_job_start_list"]
+           "xsg_literal_counter_create_opts", "xsg_job_start_list", "xsg_find_literals", "xsg_result_literal_hits",
+           "xsg_find_literals_async", "xsg_literal_finder_create_opts", "xsg_literal_finder_find",
+           "xsg_literal_finder_destroy"]
 
 
 def _check(rc):
@@ -531,6 +539,27 @@ class Shard:
         _check(self._lib.xsg_count_literals_csr_async(self.h, C.c_void_p(stream), p(d_row_ptr), cap_rows, p(d_cols), p(d_vals),
                                                       cap_entries, p(d_status)))
 
+    def find_literals(self):
+        """-> (chunk_ptr uint64[n + 1], pos uint64[total], lit uint32[total]) (xsg_find_literals, xsg_result_literal_hits):
+        every occurrence of every literal of the context's list, sorted by (chunk, position, listing index); the entries
+        [chunk_ptr[c], chunk_ptr[c + 1]) are chunk c's, pos holds global byte offsets, lit listing indices.
+        np.bincount(lit, minlength=k) is count_literals()."""
+        total = C.c_uint64(0)
+        _check(self._lib.xsg_find_literals(self.h, C.byref(total)))
+        chunk_ptr = np.zeros(self.nchunks + 1, dtype=np.uint64)
+        pos = np.zeros(total.value, dtype=np.uint64)
+        lit = np.zeros(total.value, dtype=np.uint32)
+        _check(self._lib.xsg_result_literal_hits(self.h, C.c_void_p(chunk_ptr.ctypes.data), chunk_ptr.size, C.c_void_p(pos.ctypes.data),
+                                                 C.c_void_p(lit.ctypes.data), total.value))
+        return chunk_ptr, pos, lit
+
+    def find_literals_async(self, stream: int, d_chunk_ptr: int, cap_rows: int, d_pos: int, d_lit: int, cap_entries: int, d_status: int):
+        """the stream-ordered form (xsg_find_literals_async): device addresses of cap_rows uint64, cap_entries uint64,
+        cap_entries uint32 and one uint64; *d_status is STATUS_OVERFLOW when cap_entries < d_chunk_ptr[nchunks]"""
+        p = lambda a: C.c_void_p(a) if a else None
+        _check(self._lib.xsg_find_literals_async(self.h, C.c_void_p(stream), p(d_chunk_ptr), cap_rows, p(d_pos), p(d_lit), cap_entries,
+                                                 p(d_status)))
+
     def count_begin(self, mode: int):
         _check(self._lib.xsg_count_begin(self.h, mode))
 
@@ -647,6 +676,44 @@ class LiteralCounter:
     def close(self):
         if self.h:
             self._lib.xsg_literal_counter_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class LiteralFinder:
+    """Occurrences per literal of chunks in host memory (xsg_literal_finder_*): find() one chunk, get its (pos, lit)."""
+
+    def __init__(self, device: int, lst: bytes, flags: int = 0, list_flags: int = 0):
+        self._lib = load()
+        self.h = None
+        h = C.c_void_p()
+        _check(self._lib.xsg_literal_finder_create_opts(device, lst, len(lst), flags, list_flags, C.byref(h)))
+        self.h = h
+
+    def find(self, data, base: int = 0):
+        """one chunk (bytes, or a contiguous uint8 array) -> (pos uint64[n], lit uint32[n]) sorted by (position, listing
+        index); pos = base + the position in the chunk"""
+        a = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, dtype=np.uint8)
+        pos, lit, n = C.c_void_p(), C.c_void_p(), C.c_uint64(0)
+        _check(self._lib.xsg_literal_finder_find(self.h, C.c_void_p(a.ctypes.data) if a.size else None, a.size, base, C.byref(pos),
+                                                 C.byref(lit), C.byref(n)))
+        try:
+            if n.value == 0:
+                return np.zeros(0, dtype=np.uint64), np.zeros(0, dtype=np.uint32)
+            return (np.ctypeslib.as_array(C.cast(pos, _u64p), shape=(n.value,)).copy(),
+                    np.ctypeslib.as_array(C.cast(lit, C.POINTER(C.c_uint32)), shape=(n.value,)).copy())
+        finally:
+            self._lib.xsg_free(pos)
+            self._lib.xsg_free(lit)
+
+    def close(self):
+        if self.h:
+            self._lib.xsg_literal_finder_destroy(self.h)
             self.h = None
 
     def __del__(self):
