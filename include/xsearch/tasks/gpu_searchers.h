@@ -16,7 +16,9 @@
 //
 // A trailing `literal_list = true` makes `pattern` a list of literals separated by '\n' (xsg.h: xsg_set_literals); behind
 // it `list_flags` takes the list's options (XSG_LIST_WHOLE_WORDS: whole words only; the edges of every chunk handed in are
-// word boundaries).
+// word boundaries; XSG_LIST_ALL_OF: the line functors and GpuCountSearcher(skip_to_nl = true) select the lines of the chunk
+// that hold every literal, and the match functors -- GpuIndexSearcher, GpuMatchSearcher, GpuCountSearcher(skip_to_nl =
+// false) -- throw std::runtime_error on every call, with XSG_ENOTSUP's message, which names XSG_LIST_ALL_OF).
 //
 // DataT: anything with data() -> convertible to const char* and size()
 // (the reference's DefaultDataC, concepts.h:17-22; xs::strtype = std::vector<char>).

@@ -40,7 +40,10 @@
 // other tags ignore them; not with several devices), XS_PATTERN_LIST (1: the pattern is a LIST of literals separated by
 // '\n', searched leftmost-first in listing order -- xsg.h: xsg_set_literals; it implies the literal reading),
 // XS_WHOLE_WORDS (1: whole words only, grep -w -- xsg.h: XSG_LIST_WHOLE_WORDS; honoured only together with XS_PATTERN_LIST=1,
-// a single word being a list of one; without a list extern_search throws std::invalid_argument).
+// a single word being a list of one; without a list extern_search throws std::invalid_argument), XS_ALL_OF (1: the lines
+// that hold EVERY literal of the list, grep -F a | grep -F b -- xsg.h: XSG_LIST_ALL_OF; honoured only together with
+// XS_PATTERN_LIST=1 like XS_WHOLE_WORDS, at most 64 literals, the line tags only: count_matches, match_byte_offsets and
+// matches throw std::invalid_argument).
 #pragma once
 
 #include <xsg.h>
@@ -186,12 +189,22 @@ inline bool reference_routes_to_regex(const std::string& pattern) {
 inline bool pattern_is_list() { return env_u64("XS_PATTERN_LIST", 0) != 0; }
 // XS_WHOLE_WORDS=1: the list_flags of xsg_job_start_list (XSG_LIST_WHOLE_WORDS).  The option belongs to literal lists:
 // without XS_PATTERN_LIST=1 it is refused, never dropped for a substring search.
+// XS_ALL_OF=1: XSG_LIST_ALL_OF beside it, under the same rule.
 inline uint32_t list_flags() {
-  if (env_u64("XS_WHOLE_WORDS", 0) == 0) return 0u;
-  if (!pattern_is_list())
+  const bool words = env_u64("XS_WHOLE_WORDS", 0) != 0, all_of = env_u64("XS_ALL_OF", 0) != 0;
+  if (words && !pattern_is_list())
     throw std::invalid_argument("xs::extern_search: XS_WHOLE_WORDS=1 (whole words, grep -w) is served for literal lists only: "
                                 "set XS_PATTERN_LIST=1 as well (xsgrep: -F), a single word being a list of one");
-  return XSG_LIST_WHOLE_WORDS;
+  if (all_of && !pattern_is_list())
+    throw std::invalid_argument("xs::extern_search: XS_ALL_OF=1 (the lines that hold every literal) is served for literal lists "
+                                "only: set XS_PATTERN_LIST=1 as well (xsgrep: -F), a single pattern being a list of one");
+  return (words ? XSG_LIST_WHOLE_WORDS : 0u) | (all_of ? XSG_LIST_ALL_OF : 0u);
+}
+// XS_ALL_OF=1 selects lines: the match tags have nothing to report for a conjunction
+inline void require_line_tag_all_of(uint32_t list_flags, uint32_t mode) {
+  if ((list_flags & XSG_LIST_ALL_OF) && (mode == XSG_COUNT_MATCHES || mode == XSG_MATCH_BYTE_OFFSETS || mode == XSG_MATCHES))
+    throw std::invalid_argument("xs::extern_search: XS_ALL_OF (all of the list's literals in one line) serves the line tags "
+                                "only: count_lines, line_byte_offsets, line_indices, lines");
 }
 
 // XSG_FLAG_* for a pattern, routed as the reference routes it; throws std::invalid_argument for a
@@ -452,6 +465,7 @@ class ExternSearcher {
     _list_flags = detail::list_flags();
     o.mode = detail::traits<Tag>::mode;
     detail::require_line_tag(o.pattern_flags, o.mode);
+    detail::require_line_tag_all_of(_list_flags, o.mode);
     const uint32_t context = detail::context_flags(o.mode);
     o.pattern_flags |= context;
     o.num_threads = num_threads < 1 ? 1 : num_threads;
@@ -551,7 +565,7 @@ class ExternSearcher {
     _set.jobs.push_back(j);
   }
   detail::JobSet _set;
-  uint32_t _list_flags = 0;  // XS_WHOLE_WORDS: through xsg_job_start_list
+  uint32_t _list_flags = 0;  // XS_WHOLE_WORDS, XS_ALL_OF: through xsg_job_start_list
   std::unique_ptr<ResultT> _result;
 };
 

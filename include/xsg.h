@@ -45,6 +45,7 @@ extern "C" {
  * xsg_count_literals_csr, xsg_result_literals_csr and xsg_count_literals_csr_async joined; XSG_LIST_WHOLE_WORDS with
  * xsg_set_literals_opts, xsg_host_searcher_create_list_opts, xsg_literal_counter_create_opts and xsg_job_start_list joined;
  * xsg_find_literals, xsg_result_literal_hits, xsg_find_literals_async and xsg_literal_finder_* joined;
+ * XSG_LIST_ALL_OF joined the list_flags of xsg_set_literals_opts, xsg_host_searcher_create_list_opts and xsg_job_start_list;
  * no entry point was removed or changed in meaning */
 #define XSG_ABI_VERSION 4
 
@@ -281,7 +282,7 @@ int xsg_set_pattern(xsg_ctx* ctx, const void* pattern, size_t plen, uint32_t fla
 int xsg_set_literals(xsg_ctx* ctx, const void* list, size_t n, uint32_t flags);
 /* WHOLE WORDS (grep -w -F): options of a literal list, given in `list_flags` -- the pattern flags have no free bit.  The
  * _opts entry points take them; list_flags == 0 is the call without _opts, result for result, and every bit but
- * XSG_LIST_WHOLE_WORDS is XSG_EINVAL.  Single patterns (xsg_set_pattern, literal or expression) have no such option: a
+ * XSG_LIST_WHOLE_WORDS and XSG_LIST_ALL_OF (below) is XSG_EINVAL.  Single patterns (xsg_set_pattern, literal or expression) have no such option: a
  * single word goes in as a list of one.
  * A WORD BYTE is one of 0-9 A-Z a-z _ (63 values).  Every other byte is none, '\n' and every byte >= 0x80 included (GNU
  * grep in the C locale); XSG_FLAG_IGNORE_CASE does not change the set.  With XSG_LIST_WHOLE_WORDS an occurrence of
@@ -303,7 +304,36 @@ int xsg_set_literals(xsg_ctx* ctx, const void* list, size_t n, uint32_t flags);
  *               equal xsg_count_literals, and the CSR form the dense one.
  * The option is a property of the pattern: any later xsg_set_pattern, xsg_set_literals or failed set call clears it.
  * xsg_scan_kernel_name of such a list ends in " whole words". */
-#define XSG_LIST_WHOLE_WORDS 0x1u /* list_flags; every other bit: XSG_EINVAL */
+#define XSG_LIST_WHOLE_WORDS 0x1u /* list_flags */
+/* ALL OF (grep -F a | grep -F b | ...): a bit of list_flags, accepted wherever XSG_LIST_WHOLE_WORDS is and combinable with
+ * it.  Let l_0 .. l_{k-1} be the list as parsed.  The lines of a chunk are those defined under XSG_FLAG_INVERT.  An
+ * occurrence is what xsg_count_literals counts: both sides folded under XSG_FLAG_IGNORE_CASE, and under
+ * XSG_LIST_WHOLE_WORDS only admissible occurrences count.  A literal holds no '\n', so an occurrence lies in exactly one
+ * line.  With the bit set, the set R of selected lines of a chunk is
+ *     R = { lines in which, for EVERY j, at least one occurrence of l_j starts }
+ * which equals the intersection over j of the set XSG_LINE_BYTE_OFFSETS reports for the list (l_j) alone, under the same
+ * flags and the same XSG_LIST_WHOLE_WORDS bit.  Overlapping occurrences may serve different literals, and so may covered
+ * ones ("ab" and "abc" on "abc"); duplicates in the list are one requirement; a list of one is the plain list search; a
+ * chunk's edges are line edges, and no byte at or beyond a chunk's end decides anything.
+ *   served    with R in place of the plain list's line set: XSG_COUNT_LINES through xsg_count, xsg_count_begin / _end and
+ *             xsg_count_chunks; XSG_LINE_BYTE_OFFSETS, XSG_LINE_INDICES and XSG_LINES through xsg_search and every
+ *             accessor; XSG_FLAG_INVERT (the lines that lack at least one literal); XSG_FLAG_CONTEXT and
+ *             xsg_result_context_edges; xsg_job_start_list; xsg_host_searcher_create_list_opts with
+ *             xsg_host_count(skip_to_nl = 1), xsg_host_offsets in the two line modes and xsg_host_lines.
+ *   refused   never approximated: XSG_COUNT_MATCHES, XSG_MATCH_BYTE_OFFSETS and XSG_MATCHES are XSG_ENOTSUP from the count,
+ *             search, job or host call, xsg_host_count(skip_to_nl = 0) and xsg_host_matches too -- a conjunction has no
+ *             single match.  More than XSG_MAX_ALL_OF_LITERALS literals under the bit is XSG_EINVAL from the set call, and
+ *             the context then holds no pattern.  xsg_literal_counter_create_opts and xsg_literal_finder_create_opts
+ *             refuse the bit with XSG_EINVAL: it means nothing for a count per literal.
+ *   unchanged xsg_count_literals, _chunks, _csr, xsg_find_literals and their stream-ordered forms answer per literal on a
+ *             context whose list carries the bit, as they do without it; xsg_count_async / _status stay XSG_ENOTSUP as for
+ *             every list.
+ * xsg_scan_kernel_name of such a list ends in " all of", behind " whole words" if both are set.  list_flags == 0 and
+ * list_flags == XSG_LIST_WHOLE_WORDS stay, result for result, what they are without this bit.  Like whole words, the option
+ * is a property of the pattern: any later set call clears it. */
+#define XSG_LIST_ALL_OF 0x4u /* list_flags; every bit but these two, 0x2 among them, stays XSG_EINVAL: 0x2 was refused as an
+                                * unknown flag by every build so far, and callers that probe with it keep their answer */
+#define XSG_MAX_ALL_OF_LITERALS 64u
 int xsg_set_literals_opts(xsg_ctx* ctx, const void* list, size_t n, uint32_t flags, uint32_t list_flags);
 /* Would xsg_set_literals accept this list, and what does it compile to?  Host only, needs no device (like
  * xsg_regex_check).  XSG_OK or XSG_EINVAL with the reason in xsg_last_error().  `info` (optional) receives the numbers,

@@ -3,6 +3,7 @@
 //
 //   xsgrep [-c] [-i] [-o] [-v] [-E|-F] [-x] [-A N] [-B N] [-C N] [-j THREADS] [-m METAFILE] PATTERN FILE|-
 //   xsgrep -F [-c] [-i] [-o] [-v] [-w] [-A N] [-B N] [-C N] [-j THREADS] [-m METAFILE] (-e PATTERN)... [-f FILE]... FILE|-
+//   xsgrep -F --all-of [-c] [-i] [-v] [-w] [-A N] [-B N] [-C N] [-j THREADS] [-m METAFILE] (-e PATTERN)... [-f FILE]... FILE|-
 //   xsgrep -F [-i] [-w] --count-each (-e PATTERN)... [-f FILE]... FILE|-
 //   xsgrep -F [-i] [-w] --find-each (-e PATTERN)... [-f FILE]... FILE|-
 //
@@ -43,6 +44,11 @@
 //     literals go as a list, a single PATTERN as a list of one -- and never dropped: without -F it is an error.  Combines
 //     with -c -i -o -v -A -B -C -e -f and --count-each, on FILE and on `-`; excludes -x.  As everywhere with a list, the
 //     FIRST-listed literal that stands as a whole word at a position is the match.
+// --all-of  the lines that hold EVERY pattern of the list (grep -F a | grep -F b | ...; XS_ALL_OF -> XSG_LIST_ALL_OF), in one
+//     pass over the input.  Occurrences may overlap or cover one another (-e ab -e abc selects `abc`), duplicates are one
+//     requirement, and under -w only whole-word occurrences count.  Requires -F; at most 64 patterns; a single PATTERN is a
+//     list of one.  Combines with -c -i -v -w -A -B -C -e -f -j -m, on FILE and on `-`; with -v it selects the lines that
+//     lack at least one pattern.  Excludes -o (a conjunction has no single matched text), -x, --count-each and --find-each.
 // The one-letter options without an argument may be bundled (-vc, -ci, -oi, -wc).
 // otherwise print the matching lines, live, as they are found (grep.cpp:74-79).
 #include <xsearch/tasks/gpu_searchers.h>
@@ -61,6 +67,7 @@
 static const char kUsage[] =
     "usage: %s [-c] [-i] [-o] [-v] [-E|-F] [-x] [-A N] [-B N] [-C N] [-j THREADS] [-m METAFILE] PATTERN FILE|-\n"
     "       %s -F [-c] [-i] [-o] [-v] [-w] [-A N] [-B N] [-C N] [-j THREADS] [-m METAFILE] (-e PATTERN)... [-f FILE]... FILE|-\n"
+    "       %s -F --all-of [-c] [-i] [-v] [-w] [-A N] [-B N] [-C N] [-j THREADS] [-m METAFILE] (-e PATTERN)... [-f FILE]... FILE|-\n"
     "       %s -F [-i] [-w] --count-each (-e PATTERN)... [-f FILE]... FILE|-\n"
     "       %s -F [-i] [-w] --find-each (-e PATTERN)... [-f FILE]... FILE|-\n"
     "  -e PATTERN, -f FILE (one literal per line) search for any of several literals; both may repeat, need -F and exclude -x\n"
@@ -71,6 +78,8 @@ static const char kUsage[] =
     "  -v, --invert-match selects the lines WITHOUT a match (with -c: counts them)\n"
     "  -w, --word-regexp whole words only: an occurrence counts only between bytes that are none of 0-9 A-Z a-z _ (or at the\n"
     "     ends of the input); needs -F (a single PATTERN goes as a list of one), excludes -x; works with --count-each too\n"
+    "  --all-of selects the lines that hold EVERY pattern of the list (grep -F a | grep -F b), in one pass; needs -F, at most 64\n"
+    "     patterns, a single PATTERN is a list of one; with -v the lines that lack at least one; excludes -o -x --count-each --find-each\n"
     "  -x searches (?m)^(?:PATTERN)$; PATTERN must not be empty\n"
     "  --count-each prints COUNT<TAB>LITERAL for every literal in listing order: its occurrences in the input, overlapping\n"
     "     ones and those inside another literal's included; needs -F, excludes -c -o -v -x -A -B -C -m\n"
@@ -207,7 +216,7 @@ static int find_each(const std::vector<std::string>& lits, bool icase, bool word
 
 int main(int argc, char** argv) {
   bool count = false, icase = false, fixed = false, extended = false, whole_lines = false, invert = false, only = false;
-  bool each = false, find = false, context_given = false, words = false;
+  bool each = false, find = false, context_given = false, words = false, all_of = false;
   int threads = 2;  // grep.cpp:21
   long before = 0, after = 0;
   std::string meta, pattern, file;
@@ -232,6 +241,8 @@ int main(int argc, char** argv) {
       only = true;
     } else if (a == "-w" || a == "--word-regexp") {
       words = true;
+    } else if (a == "--all-of") {
+      all_of = true;
     } else if (a == "--count-each") {
       each = true;
     } else if (a == "--find-each") {
@@ -281,7 +292,7 @@ int main(int argc, char** argv) {
       }
       have_patterns = true;
     } else if (a == "-h" || a == "--help") {
-      std::printf(kUsage, argv[0], argv[0], argv[0], argv[0]);
+      std::printf(kUsage, argv[0], argv[0], argv[0], argv[0], argv[0]);
       return 0;
     } else if (pos == 0 && !have_patterns) {
       pattern = a;
@@ -304,12 +315,26 @@ int main(int argc, char** argv) {
     pos = 2;
   }
   if (pos != 2) {
-    std::fprintf(stderr, kUsage, argv[0], argv[0], argv[0], argv[0]);
+    std::fprintf(stderr, kUsage, argv[0], argv[0], argv[0], argv[0], argv[0]);
     return 2;
   }
   if (words && (!fixed || whole_lines)) {  // never a silent substring search
     std::fprintf(stderr, "xsgrep: -w (whole words) is served for literals only: it needs -F and excludes -x\n");
     return 2;
+  }
+  if (all_of) {  // never a silent any-of search
+    const char* clash = !fixed ? "needs -F: it selects the lines that hold every one of a list of literals"
+                        : only ? "excludes -o (a conjunction has no single matched text)"
+                        : whole_lines ? "excludes -x" : each ? "excludes --count-each (that counts per literal, it selects no lines)"
+                        : find ? "excludes --find-each (that prints occurrences, it selects no lines)" : extended ? "excludes -E" : nullptr;
+    if (clash) {
+      std::fprintf(stderr, "xsgrep: --all-of %s\n", clash);
+      return 2;
+    }
+    if (have_patterns && patterns.size() > XSG_MAX_ALL_OF_LITERALS) {
+      std::fprintf(stderr, "xsgrep: --all-of: %zu patterns, at most %u are served\n", patterns.size(), (unsigned)XSG_MAX_ALL_OF_LITERALS);
+      return 2;
+    }
   }
   if (find) {  // every occurrence with its literal: no lines are selected, printed or counted
     const char* clash = !fixed ? "needs -F: it finds literals" : each ? "excludes --count-each (one prints occurrences, the other their number)"
@@ -388,9 +413,9 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "xsgrep: -E and -F exclude each other\n");
     return 2;
   }
-  if (words && !list) {  // a single PATTERN under -F -w: a list of one
+  if ((words || all_of) && !list) {  // a single PATTERN under -F -w or -F --all-of: a list of one
     if (pattern.empty() || pattern.find('\n') != std::string::npos) {
-      std::fprintf(stderr, "xsgrep: -w: an empty pattern (or one with a newline) is not served\n");
+      std::fprintf(stderr, "xsgrep: %s: an empty pattern (or one with a newline) is not served\n", words ? "-w" : "--all-of");
       return 2;
     }
     list = true;
@@ -419,7 +444,8 @@ int main(int argc, char** argv) {
   }
   if (list) setenv("XS_PATTERN_LIST", "1", 1);
   if (words) setenv("XS_WHOLE_WORDS", "1", 1);
-  const uint32_t list_flags = words ? XSG_LIST_WHOLE_WORDS : 0u;
+  if (all_of) setenv("XS_ALL_OF", "1", 1);
+  const uint32_t list_flags = (words ? XSG_LIST_WHOLE_WORDS : 0u) | (all_of ? XSG_LIST_ALL_OF : 0u);
   if (fixed) setenv("XS_FORCE_LITERAL", "1", 1);
   if (extended) setenv("XS_FORCE_REGEX", "1", 1);
   if (invert) setenv("XS_INVERT_MATCH", "1", 1);

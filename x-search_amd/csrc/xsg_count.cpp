@@ -643,6 +643,7 @@ static int count_async_impl(xsg_shard* s, uint32_t mode, void* stream, uint64_t*
   if (c->pat.kind == kSet)  // (no sketch, no hot-filter probe, no one-pass count either: candidates are verified from a fetched size)
     return fail(XSG_ENOTSUP, "a literal list fetches sizes from the device: the stream-ordered counts do not serve it, xsg_count() does");
   if (m == XSG_COUNT_MATCHES && inverted(c)) return fail(XSG_ENOTSUP, "%s", kInvertMatchMsg);
+  if (m == XSG_COUNT_MATCHES && all_of_list(c)) return fail(XSG_ENOTSUP, "%s", kAllOfMatchMsg);
   if (m == XSG_COUNT_MATCHES) {
     if (c->bordered && !overlap_free_known(s)) {  // (known from an earlier synchronous call: this entry point may not wait)
       if (want_nl)
@@ -695,6 +696,7 @@ extern "C" int xsg_count(xsg_shard* s, uint32_t mode, uint64_t counters[XSG_NUM_
   bool want_nl = false;
   XSG_TRY(parse_count_mode(mode, &m, &want_nl));
   if (m == XSG_COUNT_MATCHES && inverted(c)) return fail(XSG_ENOTSUP, "%s", kInvertMatchMsg);
+  if (m == XSG_COUNT_MATCHES && all_of_list(c)) return fail(XSG_ENOTSUP, "%s", kAllOfMatchMsg);
   const bool inv = inverted(c);  // (XSG_COUNT_LINES from here on: the pass below also counts newlines)
   XSG_TRY(ensure_factor_mask(s));
   if (use_prefilter(s, false) && s->pre_dense_serial != c->pattern_serial) {  // (not again where the candidates were found dense)
@@ -799,6 +801,7 @@ static int count_chunks_args(xsg_shard* s, uint32_t mode, const uint64_t* counts
     return fail(XSG_EINVAL, "room for %llu chunks, the binding holds %llu", (unsigned long long)cap_chunks,
                 (unsigned long long)s->chunks.size());
   if (*m == XSG_COUNT_MATCHES && inverted(s->ctx)) return fail(XSG_ENOTSUP, "%s", kInvertMatchMsg);
+  if (*m == XSG_COUNT_MATCHES && all_of_list(s->ctx)) return fail(XSG_ENOTSUP, "%s", kAllOfMatchMsg);
   return XSG_OK;
 }
 
@@ -911,6 +914,7 @@ extern "C" int xsg_count_begin(xsg_shard* s, uint32_t mode) {
   bool want_nl = false;
   XSG_TRY(parse_count_mode(mode, &m, &want_nl));
   if (m == XSG_COUNT_MATCHES && inverted(c)) return fail(XSG_ENOTSUP, "%s", kInvertMatchMsg);
+  if (m == XSG_COUNT_MATCHES && all_of_list(c)) return fail(XSG_ENOTSUP, "%s", kAllOfMatchMsg);
   const bool inv = inverted(c);
   s->begin_sync_result = false;
   XSG_TRY(ensure_factor_mask(s));

@@ -481,7 +481,7 @@ static int set_job_pattern(xsg_ctx* ctx, const std::vector<uint8_t>& pattern, ui
   return xsg_set_literals_opts(ctx, pattern.data(), pattern.size(), flags, list_flags);
 }
 static int check_list_flags(uint32_t list_flags) {
-  return (list_flags & ~XSG_LIST_WHOLE_WORDS) ? xsg::fail(XSG_EINVAL, "unknown list flags 0x%x", list_flags) : XSG_OK;
+  return (list_flags & ~(XSG_LIST_WHOLE_WORDS | XSG_LIST_ALL_OF)) ? xsg::fail(XSG_EINVAL, "unknown list flags 0x%x", list_flags) : XSG_OK;
 }
 static bool context_flags(uint32_t flags) { return XSG_CONTEXT_BEFORE(flags) != 0 || XSG_CONTEXT_AFTER(flags) != 0; }
 // the tags whose list context widens (every other tag ignores the bits)
@@ -1271,7 +1271,14 @@ static int job_start_impl(const void* pattern, size_t plen, const char* file_pat
   const bool is_list = known.pattern_is_list != 0;
   if (is_list) {  // refuse a bad list here, not in a worker
     if (!xsg_literals_info) return fail(XSG_ENOTSUP, "%s", kNoListMsg);
-    XSG_TRY(xsg_literals_info(pattern, plen, opts->pattern_flags, nullptr, nullptr));
+    xsg_literal_list info;
+    XSG_TRY(xsg_literals_info(pattern, plen, opts->pattern_flags, &info, nullptr));
+    if (list_flags & XSG_LIST_ALL_OF) {  // (xsg.h: XSG_LIST_ALL_OF -- what the set call and the searches would refuse, here)
+      if (info.count > XSG_MAX_ALL_OF_LITERALS)
+        return fail(XSG_EINVAL, "XSG_LIST_ALL_OF: %u literals, at most %u are served", info.count, XSG_MAX_ALL_OF_LITERALS);
+      if (opts->mode == XSG_COUNT_MATCHES || opts->mode == XSG_MATCH_BYTE_OFFSETS || opts->mode == XSG_MATCHES)
+        return fail(XSG_ENOTSUP, "XSG_LIST_ALL_OF: a conjunction selects lines; it has no single match, and the match tags are not served for it");
+    }
   }
   if (!pattern || plen == 0 || plen > XSG_MAX_PATTERN) return fail(XSG_EINVAL, "pattern must be 1..%u bytes",
                                                                   XSG_MAX_PATTERN);
@@ -1678,7 +1685,10 @@ static int host_searcher_create(int device, const void* pattern, size_t plen, ui
                                                                   XSG_MAX_PATTERN);
   if (is_list) {
     if (!xsg_literals_info) return fail(XSG_ENOTSUP, "%s", kNoListMsg);
-    XSG_TRY(xsg_literals_info(pattern, plen, flags, nullptr, nullptr));
+    xsg_literal_list info;
+    XSG_TRY(xsg_literals_info(pattern, plen, flags, &info, nullptr));
+    if ((list_flags & XSG_LIST_ALL_OF) && info.count > XSG_MAX_ALL_OF_LITERALS)
+      return fail(XSG_EINVAL, "XSG_LIST_ALL_OF: %u literals, at most %u are served", info.count, XSG_MAX_ALL_OF_LITERALS);
   } else if (flags & XSG_FLAG_REGEX) {
     XSG_TRY(xsg_regex_check(pattern, plen, flags & XSG_FLAG_IGNORE_CASE, nullptr, nullptr));
   }

@@ -52,6 +52,8 @@ inline const char* const kNonAsciiMsg =
     "bytes >= 0x80, where one byte per position is not the same thing: refused, not approximated";
 inline const char* const kInvertMatchMsg =
     "XSG_FLAG_INVERT: an inverted search reports lines without a match; the match tags have no inverted form";
+inline const char* const kAllOfMatchMsg =
+    "XSG_LIST_ALL_OF: a conjunction selects lines; it has no single match, and the match tags are not served for it";
 inline const char* const kNewlineExprMsg = "line modes do not accept an expression that can match '\\n'";
 
 // ---- xsg_list.cpp ------------------------------------------------------------------------------------------------
@@ -59,6 +61,7 @@ inline const char* const kNewlineExprMsg = "line modes do not accept an expressi
 // route.  (An EXPRESSION that can match '\n' keeps being refused by the line tags: RE2's walk over a re-sliced input is
 // not restated for it.)
 bool newline_literal(const xsg_ctx* c);
+bool all_of_list(const xsg_ctx* c);  // a literal list set with XSG_LIST_ALL_OF (PatternDev::set_all_of)
 int ensure_factor_mask(xsg_shard* s);
 // `pre_off`: the caller must not take the prefilter route (run_list: its candidates were dense or outran their budget)
 bool use_prefilter(const xsg_shard* s, bool pre_off);

@@ -58,9 +58,12 @@ struct PatternDev {
   uint32_t p0, m0, p1, m1;  // the 8 pattern bytes of the filter window (pattern[koff..koff+8)) as dwords + byte masks
   uint32_t q0, q1;          // ignore_case hot filter: (p0 | 0x20202020) & m0, (p1 | 0x20202020) & m1 (k_scan, LAZY)
   uint32_t koff;            // kLong, kClass: offset of the 8-byte filter window inside the pattern (0 for the other kinds)
-  uint32_t set_words;       // kSet: XSG_LIST_WHOLE_WORDS (SetTable::words).  It lies HERE, in the four bytes that padded d_pat to
+  uint16_t set_words;       // kSet: XSG_LIST_WHOLE_WORDS (SetTable::words).  It lies HERE, in the four bytes that padded d_pat to
                             // its alignment: the structure keeps its size and every other field its offset, so no other
                             // kernel's arguments change (profiles/literal_words_registers.txt)
+  uint16_t set_all_of;      // kSet: XSG_LIST_ALL_OF, in the upper half of those four bytes.  No kernel reads it: the host picks
+                            // the all-of stages by it (xsg_list.cpp), and 0 / 1 in the lower half reads as it did
+                            // (profiles/all_of_registers.txt)
   const uint8_t* d_pat;     // device copy of the pattern
   uint32_t exact_tail;      // XSG_FLAG_EXACT_TAIL
   uint32_t nl_first;        // literal whose FIRST byte is '\n': the reference's line start of a match then lies one byte behind the
@@ -322,6 +325,41 @@ hipError_t launch_set_count(const ScanArgs& a, bool want_nl, hipStream_t s);
 hipError_t launch_set_emit(const ScanArgs& a, hipStream_t s);
 hipError_t launch_set_verify(const RxPreArgs& a, hipStream_t s);
 void describe_set_scan(const ScanArgs& a, bool emit, char* out, size_t cap);
+// XSG_LIST_ALL_OF (xsg_list.cpp: prefilter_candidates, decide_keep).  k_set_verify_all in k_set_verify's place: c_mask[i] =
+// the listing indices of EVERY literal that occurs at candidate i, as bits, c_keep[i] = c_mask[i] != 0; k_set_compact_all packs
+// the kept candidates with their masks at the ranks c_pre.  The arguments are their own, so that RxPreArgs and every kernel
+// that takes it stay what they are.
+struct SetAllArgs {
+  const uint8_t* base;
+  const ChunkDev* chunks;
+  PatternDev pat;
+  uint32_t idx_off;          // byte offset of SetTable::idx inside PatternDev::d_pat (SetProgram::idx_offset)
+  uint64_t n;                // candidates
+  const uint64_t* c_pos;
+  const uint32_t* c_chunk;
+  uint64_t* c_mask;          // one word per candidate
+  uint32_t* c_keep;
+  const uint64_t* c_pre;     // exclusive prefix of c_keep (compact)
+  uint64_t* m_pos;           // the entries, packed (compact)
+  uint32_t* m_chunk;
+  uint64_t* m_mask;          // one word per entry
+};
+hipError_t launch_set_verify_all(const SetAllArgs& a, hipStream_t s);
+hipError_t launch_set_compact_all(const SetAllArgs& a, hipStream_t s);
+// k_all_of_or / k_all_of_keep (xsg_list_kernels.hip), behind k_line_starts_keep and the exclusive prefix of its keep column:
+// entry i lies in the line of ordinal keep_pre[i] + keep[i] - 1.  or: line_mask[ordinal] |= m_mask[i], one atomic per run
+// of equal ordinals inside a wave; line_mask must be zero on entry (one word per kept entry at most: M words always do).
+// keep: keep[i] &= line_mask[ordinal] == full.  The caller scans keep again behind it.
+struct AllOfArgs {
+  uint64_t M;                     // entries
+  uint32_t* keep;                 // first entry of its line (k_line_starts_keep)
+  const uint64_t* keep_pre;       // exclusive prefix of keep
+  const uint64_t* m_mask;         // the literals that occur at entry i
+  unsigned long long* line_mask;  // one word per line that holds an entry
+  uint64_t full;                  // the mask of a line that holds every literal of the list
+};
+hipError_t launch_all_of_or(const AllOfArgs& a, hipStream_t s);
+hipError_t launch_all_of_keep(const AllOfArgs& a, hipStream_t s);
 // k_set_count_literals (xsg_count_literals*): k_set_scan's pass with the verify step inside it, one count per literal.  What
 // it needs beyond ScanArgs travels as a second kernel parameter, so that every other kernel keeps its argument block.  The
 // kernel ADDS to counts[0 .. nlits): the caller zeroes them on the stream in front of the launch, or accumulates.  One

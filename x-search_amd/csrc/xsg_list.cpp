@@ -19,6 +19,9 @@ static int d2h_u64(xsg_ctx* c, const uint64_t* d, uint64_t* h) {
 // XSG_FLAG_CONTEXT with a non-zero count (the line-list tags widen their list; every other tag ignores the bits)
 static bool context_on(const xsg_ctx* c) { return XSG_CONTEXT_BEFORE(c->flags) != 0 || XSG_CONTEXT_AFTER(c->flags) != 0; }
 
+// XSG_LIST_ALL_OF: the context's pattern is a literal list whose lines must hold every literal
+bool xsg::all_of_list(const xsg_ctx* c) { return c->pat.kind == kSet && c->pat.set_all_of != 0; }
+
 bool xsg::newline_literal(const xsg_ctx* c) { return c->pat.has_newline && c->pat.kind != kClass && c->pat.kind != kDfa && c->pat.kind != kSet; }
 
 // ---------------------------------------------------------------------------
@@ -461,6 +464,37 @@ static int prefilter_candidates(xsg_shard* s, bool outputs, bool want_len, ScanA
   a.m_pos = s->d_c_pos.as<uint64_t>();
   a.m_chunk = s->d_c_chunk.as<uint32_t>();
   if (Mc) HIP_TRY(launch_scan_emit(a, st));
+  if (all_of_list(c)) {
+    // XSG_LIST_ALL_OF: every literal at every candidate (k_set_verify_all: a mask per candidate), and EVERY position with
+    // an occurrence becomes an entry -- no leftmost-first walk, a covered occurrence still serves its literal -- packed
+    // with its mask.  One size from the device, as on the plain list's pass.
+    XSG_TRY(s->d_c_mask.ensure(8 * std::max<uint64_t>(Mc, 1)));
+    SetAllArgs v{};
+    v.base = s->base;
+    v.chunks = a.chunks;
+    v.pat = c->pat;
+    v.idx_off = c->set_idx_off;
+    v.n = Mc;
+    v.c_pos = a.m_pos;
+    v.c_chunk = a.m_chunk;
+    v.c_mask = s->d_c_mask.as<uint64_t>();
+    v.c_keep = s->d_c_keep.as<uint32_t>();
+    v.c_pre = s->d_c_pre.as<uint64_t>();
+    HIP_TRY(launch_set_verify_all(v, st));
+    HIP_TRY(launch_exclusive_scan_u32(v.c_keep, s->d_c_pre.as<uint64_t>(), Mc, s->d_scan_tmp.as<uint64_t>(), st));
+    XSG_TRY(d2h_u64(c, s->d_c_pre.as<uint64_t>() + Mc, M));
+    XSG_TRY(s->d_m_pos.ensure(8 * std::max<uint64_t>(*M, 1)));
+    XSG_TRY(s->d_m_chunk.ensure(4 * std::max<uint64_t>(*M, 1)));
+    XSG_TRY(s->d_m_mask.ensure(8 * std::max<uint64_t>(*M, 1)));
+    v.m_pos = s->d_m_pos.as<uint64_t>();
+    v.m_chunk = s->d_m_chunk.as<uint32_t>();
+    v.m_mask = s->d_m_mask.as<uint64_t>();
+    HIP_TRY(launch_set_compact_all(v, st));
+    a.m_pos = v.m_pos;
+    a.m_chunk = v.m_chunk;
+    a.m_len = nullptr;
+    return XSG_OK;
+  }
   RxPreArgs r{};
   r.base = s->base;
   r.chunks = a.chunks;
@@ -535,6 +569,22 @@ static int decide_keep(xsg_shard* s, ListArgs& l, bool chain_lines) {
     }
   } else if (l.line_mode) {
     HIP_TRY(launch_line_starts_keep(l, st));
+    if (all_of_list(c) && M) {
+      // XSG_LIST_ALL_OF: keep marks the first entry of every line; its prefix numbers the lines, one OR per line of the
+      // entries' masks (k_all_of_or), and keep stays only where the line's mask is full.  The prefix below is taken again.
+      HIP_TRY(launch_exclusive_scan_u32(l.keep, s->d_keep_pre.as<uint64_t>(), M, s->d_scan_tmp.as<uint64_t>(), st));
+      XSG_TRY(s->d_line_mask.ensure(8 * M));
+      HIP_TRY(hipMemsetAsync(s->d_line_mask.p, 0, 8 * M, st));
+      AllOfArgs o{};
+      o.M = M;
+      o.keep = l.keep;
+      o.keep_pre = s->d_keep_pre.as<uint64_t>();
+      o.m_mask = s->d_m_mask.as<uint64_t>();
+      o.line_mask = s->d_line_mask.as<unsigned long long>();
+      o.full = c->set_count >= 64u ? ~0ull : (1ull << c->set_count) - 1ull;  // (never 1 << 64)
+      HIP_TRY(launch_all_of_or(o, st));
+      HIP_TRY(launch_all_of_keep(o, st));
+    }
   } else if (c->bordered && !overlap_free_known(s)) {
     // chain heads walk their chains (a few entries at text densities); a chain over the budget -- a long run of one
     // byte searched for `aa` is ONE chain per chunk -- raises a flag and is finished by pointer jumping, log2(length)
@@ -567,7 +617,10 @@ static int tails_and_total(xsg_shard* s, const ScanArgs& a, const ListArgs& l, b
   xsg_ctx* c = s->ctx;
   hipStream_t st = c->stream;
   const uint64_t ntiles = s->ntiles;
-  HIP_TRY(launch_chunk_shift0(l, st));
+  // (k_chunk_shift0 looks backwards from a chunk's last entry for a kept one, one lane per chunk: under XSG_LIST_ALL_OF
+  // kept entries can be arbitrarily rare and the loop would run over the chunk's whole column.  A list has no tail zone
+  // -- exact_tail: k_tail_list reads no chunk_shift0 and writes 0 -- so the kernel is not launched for such a list.)
+  if (!all_of_list(c)) HIP_TRY(launch_chunk_shift0(l, st));
   HIP_TRY(launch_tail_list(l, st));
   HIP_TRY(launch_exclusive_scan_u32(l.tail_cnt, s->d_tail_pre.as<uint64_t>(), l.nchunks, s->d_scan_tmp.as<uint64_t>(), st));
   uint64_t kept = 0, tails = 0;
@@ -860,6 +913,7 @@ int xsg::run_list(xsg_shard* s, uint32_t mode, bool outputs, bool want_nl_total,
       if (ch.length >= (1ull << 32)) return fail(XSG_ENOTSUP, "XSG_MATCHES with an expression of variable length needs chunks shorter than 4 GiB");
   if (line_mode && c->pat.has_newline && !newline_literal(c)) return fail(XSG_ENOTSUP, "%s", kNewlineExprMsg);
   const bool chain_lines = line_mode && newline_literal(c);
+  if (match_mode && all_of_list(c)) return fail(XSG_ENOTSUP, "%s", kAllOfMatchMsg);  // (before any launch)
 
   s->last_mode = -1;
   s->context_edges_valid = false;
@@ -963,6 +1017,7 @@ extern "C" int xsg_search(xsg_shard* s, uint32_t mode, uint64_t* n_results) {
       mode != XSG_LINES && mode != XSG_MATCHES)
     return fail(XSG_EINVAL, "xsg_search: mode %u is not a list mode", mode);
   if ((mode == XSG_MATCH_BYTE_OFFSETS || mode == XSG_MATCHES) && (s->ctx->flags & XSG_FLAG_INVERT)) return fail(XSG_ENOTSUP, "%s", kInvertMatchMsg);
+  if ((mode == XSG_MATCH_BYTE_OFFSETS || mode == XSG_MATCHES) && all_of_list(s->ctx)) return fail(XSG_ENOTSUP, "%s", kAllOfMatchMsg);
   HIP_TRY(hipSetDevice(s->ctx->device));
   XSG_TRY(run_list(s, mode, true));
   if (!s->fast_result) trim_pinned(s, 8 * (size_t)s->total, 8 * (size_t)s->total, (size_t)s->line_bytes);  // (an exact-route result is still on the device)

@@ -470,6 +470,58 @@ __global__ __launch_bounds__(kBlock) void k_line_starts_keep(const ListArgs A) {
   }
 }
 
+// ---- XSG_LIST_ALL_OF: one OR per line -------------------------------------------------------------------------------------------
+// Behind k_line_starts_keep and the exclusive prefix of keep, entry i lies in the line of ordinal keep_pre[i] + keep[i] - 1
+// (entry 0 is the first of its chunk, so kept: no ordinal is negative), and ordinals do not decrease with i.  A wave holds
+// 64 consecutive entries, so equal ordinals are contiguous in it: a segmented inclusive OR over the lanes (six shuffle
+// steps on the two halves of the word, no LDS; a lane takes its neighbour's value only from inside its own segment, whose
+// first lane it knows from one ballot), and the LAST lane of every segment adds the segment's OR to line_mask[ordinal]
+// with one 64-bit atomic.  A line of n entries costs at most n / 64 + 1 atomics and no lane walks a line's entries: a line
+// of a million occurrences is handled like any other.  line_mask is zero on entry.
+__global__ __launch_bounds__(kBlock) void k_all_of_or(const AllOfArgs A) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+  const bool live = i < A.M;  // (no early return: every lane of the wave takes part in the shuffles)
+  // a lane without an entry: an ordinal no entry has, a segment of its own, nothing to add
+  const uint64_t ord = live ? A.keep_pre[i] + A.keep[i] - 1u : UINT64_MAX;
+  const uint64_t m = live ? A.m_mask[i] : 0ull;
+  uint32_t lo = (uint32_t)m, hi = (uint32_t)(m >> 32);
+  const uint32_t p_lo = (uint32_t)__shfl_up((int)(uint32_t)ord, 1), p_hi = (uint32_t)__shfl_up((int)(uint32_t)(ord >> 32), 1);
+  const bool first = lane == 0u || (((uint64_t)p_hi << 32) | p_lo) != ord;
+  const unsigned long long firsts = __ballot(first);  // bit l: lane l opens a segment (bit 0 is always set)
+  // the lane that opens this lane's segment: the highest set bit at or below `lane`
+  const uint32_t head = 63u - (uint32_t)__clzll((long long)(firsts & (~0ull >> (63u - lane))));
+#pragma unroll
+  for (uint32_t s = 1; s < 64u; s <<= 1) {
+    const uint32_t o_lo = (uint32_t)__shfl_up((int)lo, s), o_hi = (uint32_t)__shfl_up((int)hi, s);
+    if (lane >= head + s) lo |= o_lo, hi |= o_hi;
+  }
+  const bool last = lane == 63u || ((firsts >> (lane + 1u)) & 1ull) != 0ull;
+  const uint64_t v = ((uint64_t)hi << 32) | lo;
+  if (live && last && v != 0ull && ord < A.M) atomicOr(&A.line_mask[ord], (unsigned long long)v);
+}
+
+// keep[i] &= "the line of entry i holds every literal".  The exclusive prefix of keep is taken again behind this kernel;
+// from there the list pipeline runs as for any list.
+__global__ void k_all_of_keep(const AllOfArgs A) {
+  const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= A.M || !A.keep[i]) return;
+  if (A.line_mask[A.keep_pre[i]] != A.full) A.keep[i] = 0u;  // (a kept entry's ordinal is keep_pre[i])
+}
+
+hipError_t launch_all_of_or(const AllOfArgs& a, hipStream_t s) {
+  if (!a.M) return hipSuccess;
+  if (!a.keep || !a.keep_pre || !a.m_mask || !a.line_mask) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_all_of_or, grid_for(a.M), dim3(kBlock), 0, s, a);
+  return hipGetLastError();
+}
+hipError_t launch_all_of_keep(const AllOfArgs& a, hipStream_t s) {
+  if (!a.M) return hipSuccess;
+  if (!a.keep || !a.keep_pre || !a.line_mask) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_all_of_keep, grid_for(a.M), dim3(kBlock), 0, s, a);
+  return hipGetLastError();
+}
+
 // per chunk: where the walk enters the tail zone, from the last kept bulk match
 __global__ __launch_bounds__(kBlock) void k_chunk_shift0(const ListArgs A) {
   const uint64_t c = (uint64_t)blockIdx.x * kBlock + threadIdx.x;

@@ -223,6 +223,9 @@ struct xsg_shard {
   std::vector<xsg_context_edge> context_edges;  // ... the edges of the last search with context, one per chunk
   bool context_edges_valid = false;             // ... which was the last search on this shard (xsg_result_context_edges)
   DevBuf d_c_pos, d_c_chunk, d_c_len, d_c_keep, d_c_pre;  // prefilter route of kDfa: the candidates
+  // XSG_LIST_ALL_OF: the literals at every candidate, at every entry, and in every line that holds an entry, as masks
+  // (8 bytes each; the line masks are sized by the entries, their upper bound: the lines' number is not fetched for them)
+  DevBuf d_c_mask, d_m_mask, d_line_mask;
   // The 4-gram sketch of the bound bytes (xsg_sketch.h): 512 B per tile, pattern-independent, built once per binding by
   // xsg_shard_tune or before the second eligible pass of a synchronous entry point (xsg_count.cpp: sketch_before_pass)
   DevBuf d_sketch;
@@ -321,7 +324,8 @@ struct xsg_shard {
                      &d_inv_off, &d_inv_pos, &d_inv_chunk, &d_m_len, &d_f_len, &d_cx_lo, &d_cx_hi, &d_cx_cnt,
                      &d_cx_slot, &d_cx_pos, &d_cx_chunk, &d_cx_edge, &d_sketch, &d_spans, &d_chunk_counts, &d_lit_counts,
                      &d_lit_matrix, &d_csr_row_nnz, &d_csr_tmp, &d_csr_seam, &d_csr_row_ptr, &d_csr_cols, &d_csr_vals,
-                     &d_find_occ, &d_find_off, &d_find_tmp, &d_find_ptr, &d_find_pos, &d_find_lit};
+                     &d_find_occ, &d_find_off, &d_find_tmp, &d_find_ptr, &d_find_pos, &d_find_lit, &d_c_mask, &d_m_mask,
+                     &d_line_mask};
     for (DevBuf* b : all) b->release();
     if (h_stage) (void)hipHostFree(h_stage);
     if (h_counters) (void)hipHostFree(h_counters);

@@ -540,14 +540,17 @@ extern "C" int xsg_set_literals(xsg_ctx* c, const void* list, size_t n, uint32_t
   return xsg_set_literals_opts(c, list, n, flags, 0u);
 }
 
-// XSG_LIST_WHOLE_WORDS is a property of the compiled pattern: it lives in PatternDev::set_words, which every set call
-// rewrites (P = PatternDev{}), and nowhere else -- nothing of it can outlive the pattern.
+// XSG_LIST_WHOLE_WORDS and XSG_LIST_ALL_OF are properties of the compiled pattern: they live in PatternDev::set_words and
+// PatternDev::set_all_of, which every set call rewrites (P = PatternDev{}), and nowhere else -- nothing of them can outlive
+// the pattern.  Under XSG_LIST_ALL_OF a line's literals are one 64-bit mask: a longer list is refused here.
 extern "C" int xsg_set_literals_opts(xsg_ctx* c, const void* list, size_t n, uint32_t flags, uint32_t list_flags) {
   if (c) c->pattern.clear();  // a failed call leaves the context without a pattern
-  if (list_flags & ~XSG_LIST_WHOLE_WORDS) return fail(XSG_EINVAL, "unknown list flags 0x%x", list_flags);
+  if (list_flags & ~(XSG_LIST_WHOLE_WORDS | XSG_LIST_ALL_OF)) return fail(XSG_EINVAL, "unknown list flags 0x%x", list_flags);
   if (!c) return fail(XSG_EINVAL, "ctx is null");
   xsg::SetProgram prog;
   XSG_TRY(compile_list(list, n, flags, &prog));
+  if ((list_flags & XSG_LIST_ALL_OF) && prog.count > XSG_MAX_ALL_OF_LITERALS)
+    return fail(XSG_EINVAL, "XSG_LIST_ALL_OF: %u literals, at most %u are served", prog.count, XSG_MAX_ALL_OF_LITERALS);
   HIP_TRY(hipSetDevice(c->device));
   uint32_t off[4];
   const std::vector<uint8_t> blob = prog.blob(off);
@@ -570,6 +573,7 @@ extern "C" int xsg_set_literals_opts(xsg_ctx* c, const void* list, size_t n, uin
   P.icase = prog.icase ? 1u : 0u;
   P.set_g = prog.g;
   P.set_words = (list_flags & XSG_LIST_WHOLE_WORDS) ? 1u : 0u;
+  P.set_all_of = (list_flags & XSG_LIST_ALL_OF) ? 1u : 0u;
   P.set_ngrams = (uint32_t)prog.keys.size();
   P.set_keys = off[0], P.set_first = off[1], P.set_ent = off[2], P.set_bytes = off[3];
   c->set_count = prog.count;

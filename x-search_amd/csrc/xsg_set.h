@@ -49,8 +49,9 @@ XSG_SET_HD bool set_filter_has(const uint32_t* filter, uint32_t v, uint32_t g) {
 //   first[ngrams + 1]  entries of gram k: ent[first[k] .. first[k + 1])
 //   ent[nlits]         (offset of the literal's bytes in `bytes`) << 8 | its length, listing order inside a gram
 //   bytes              the literals back to back (folded under ignore-case)
-//   idx[nlits]         the LISTING index of every entry of `ent`, uint16 (xsg_count_literals: set_count_at; the search
-//                      routes never read it, and a table built without it leaves it null)
+//   idx[nlits]         the LISTING index of every entry of `ent`, uint16 (xsg_count_literals: set_count_at; an all-of
+//                      list: set_mask_at; the other search routes never read it, and a table built without it leaves
+//                      it null)
 // words: XSG_LIST_WHOLE_WORDS (include/xsg.h) -- an occurrence stands only between two bytes that are no word bytes, the
 // chunk's edges counting as such (set_entry_at).
 struct SetTable {
@@ -129,6 +130,15 @@ XSG_SET_HD void set_count_at(const SetTable& T, const uint8_t* d, uint64_t p, ui
 template <typename Visit>
 XSG_SET_HD void set_count_at(const SetTable& T, const uint8_t* d, uint64_t p, uint64_t L, bool icase, Visit&& visit) {
   set_count_at(T, d, p, L, icase, visit, T.keys);
+}
+
+// XSG_LIST_ALL_OF: set_count_at's visit as a mask -- bit j set <=> the literal of listing index j occurs (under T.words:
+// admissibly) at d[p].  The list holds at most 64 literals (xsg_set_literals_opts refuses more under the option), so j < 64.
+// Same contract: p + g <= L is the caller's to ensure, nothing at or beyond L is read, and T.idx must be set.
+XSG_SET_HD uint64_t set_mask_at(const SetTable& T, const uint8_t* d, uint64_t p, uint64_t L, bool icase) {
+  uint64_t mask = 0;
+  set_count_at(T, d, p, L, icase, [&](uint32_t j) { mask |= 1ull << (j & 63u); });
+  return mask;
 }
 
 // What the host compiles a list into.

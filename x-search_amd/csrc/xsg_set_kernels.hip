@@ -5,6 +5,8 @@
 //   k_set_verify             one lane per candidate: the literals that start with its gram, in listing order, against the
 //                            chunk bytes -> c_len, in k_rx_verify's place; k_rx_heads / k_rx_chains / k_rx_compact and
 //                            the shared list pipeline take over from there (xsg_list.cpp: prefilter_candidates).
+//   k_set_verify_all, k_set_compact_all   XSG_LIST_ALL_OF: every literal at a candidate as a mask of listing indices, and
+//                            the candidates that hold one packed with their masks (k_all_of_or, xsg_list_kernels.hip, follows)
 //   k_set_count_literals     xsg_count_literals: the scan with the verify step inside its own pass, one count per literal
 //   k_set_count_literals_chunks   xsg_count_literals_chunks: the same pass with the chunk boundaries kept, a count per
 //                            chunk and literal and the number of chunks that hold each literal
@@ -55,7 +57,8 @@ __device__ __forceinline__ void set_stage_filter(const PatternDev& P, uint32_t* 
   for (uint32_t k = tid; k < kSetFilterBytes / 16u; k += kBlock) dst[k] = src[k];
 }
 
-// the verify table inside the pattern's blob; the counting kernels pass the offset of SetTable::idx, the search leaves it null
+// the verify table inside the pattern's blob; the counting kernels and k_set_verify_all pass the offset of SetTable::idx, the
+// plain search leaves it null
 __device__ __forceinline__ SetTable set_table(const PatternDev& P) {
   SetTable T;
   T.keys = reinterpret_cast<const uint32_t*>(P.d_pat + P.set_keys);
@@ -234,6 +237,36 @@ __global__ __launch_bounds__(kBlock) void k_set_verify(const RxPreArgs A) {
   const uint64_t p = A.c_pos[i];
   // (the scan reports p only with p + g <= length; a position without that room holds nothing)
   A.c_len[i] = p + T.g <= ch.length ? set_verify_at(T, A.base + ch.offset, p, ch.length, P.icase != 0) : 0u;
+}
+
+// ---- XSG_LIST_ALL_OF: which literals occur at every candidate ----------------------------------------------------------------------
+// k_set_verify's place on the all-of route (xsg_list.cpp: prefilter_candidates): one lane per candidate, EVERY literal under
+// the candidate's gram compared (set_mask_at), c_mask[i] = the listing indices of those that occur there as bits, c_keep[i] =
+// "some literal occurs here".  No leftmost-first walk follows: an occurrence another one covers still serves its literal, so
+// every position with an occurrence becomes an entry (k_rx_heads / k_rx_chains do not run), and k_set_compact_all packs the
+// mask beside position and chunk.  A kernel of its own, not a branch of k_set_verify, and WORDS is a template argument as in
+// the counting kernels: what a run-time flag costs those is in profiles/literal_words_registers.txt.
+template <bool WORDS>
+__global__ __launch_bounds__(kBlock) void k_set_verify_all(const SetAllArgs A) {
+  const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= A.n) return;
+  const PatternDev P = A.pat;
+  const ChunkDev ch = A.chunks[A.c_chunk[i]];
+  const SetTable T = set_table<WORDS>(P, A.idx_off);
+  const uint64_t p = A.c_pos[i];
+  // (the scan reports p only with p + g <= length; a position without that room holds nothing)
+  const uint64_t mask = p + T.g <= ch.length ? set_mask_at(T, A.base + ch.offset, p, ch.length, P.icase != 0) : 0ull;
+  A.c_mask[i] = mask;
+  A.c_keep[i] = mask != 0ull ? 1u : 0u;
+}
+
+__global__ __launch_bounds__(kBlock) void k_set_compact_all(const SetAllArgs A) {
+  const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= A.n || !A.c_keep[i]) return;
+  const uint64_t dst = A.c_pre[i];
+  A.m_pos[dst] = A.c_pos[i];
+  A.m_chunk[dst] = A.c_chunk[i];
+  A.m_mask[dst] = A.c_mask[i];
 }
 
 // ---- xsg_count_literals: one count per literal, the verify step inside the candidate scan's own pass ---------------------------
@@ -831,6 +864,21 @@ hipError_t launch_set_verify(const RxPreArgs& a, hipStream_t s) {
   return hipGetLastError();
 }
 
+hipError_t launch_set_verify_all(const SetAllArgs& a, hipStream_t s) {
+  if (!a.n) return hipSuccess;
+  if (!a.c_pos || !a.c_chunk || !a.c_mask || !a.c_keep || a.pat.set_g < 1 || a.pat.set_g > 4) return hipErrorInvalidValue;
+  hipLaunchKernelGGL((a.pat.set_words ? k_set_verify_all<true> : k_set_verify_all<false>), dim3((unsigned)((a.n + kBlock - 1) / kBlock)),
+                     dim3(kBlock), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_set_compact_all(const SetAllArgs& a, hipStream_t s) {
+  if (!a.n) return hipSuccess;
+  if (!a.c_pre || !a.m_pos || !a.m_chunk || !a.m_mask) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_set_compact_all, dim3((unsigned)((a.n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, a);
+  return hipGetLastError();
+}
+
 hipError_t launch_set_count_literals(const ScanArgs& a, const LitCountArgs& c, hipStream_t s) {
   if (a.ntiles == 0) return hipSuccess;
   if (!set_args_ok(a, c.counts, c.nlits)) return hipErrorInvalidValue;
@@ -928,8 +976,9 @@ hipError_t launch_set_find_chunk_ptr(const ScanArgs& a, const uint64_t* wave_off
 }
 
 void describe_set_scan(const ScanArgs& a, bool emit, char* out, size_t cap) {
-  snprintf(out, cap, "xsg::k_set_scan<%s, %s> g=%u + xsg::k_set_verify%s", emit ? "true" : "false", a.pat.icase ? "true" : "false",
-           a.pat.set_g, a.pat.set_words ? " whole words" : "");
+  snprintf(out, cap, "xsg::k_set_scan<%s, %s> g=%u + xsg::k_set_verify%s%s%s", emit ? "true" : "false", a.pat.icase ? "true" : "false",
+           a.pat.set_g, a.pat.set_all_of ? "_all + xsg::k_all_of_or" : "", a.pat.set_words ? " whole words" : "",
+           a.pat.set_all_of ? " all of" : "");
 }
 
 __global__ void k_warm_set() {}

@@ -35,6 +35,8 @@ MAX_LITERALS = 4096  # a literal list (xsg_set_literals): literals, bytes per li
 MAX_LITERAL_BYTES = 255
 LITERAL_FILTER_BYTES = 8192
 LIST_WHOLE_WORDS = 0x1  # list_flags of the _opts entry points: grep -w on a literal list (xsg.h: XSG_LIST_WHOLE_WORDS)
+LIST_ALL_OF = 0x4  # ... the lines that hold EVERY literal of the list, grep -F a | grep -F b (xsg.h: XSG_LIST_ALL_OF)
+MAX_ALL_OF_LITERALS = 64
 STATUS_OK, STATUS_OVERFLOW, STATUS_NONASCII = 0, 1, 2
 TILE = 16384
 
@@ -401,7 +403,8 @@ class Context:
 
     def set_literals(self, lst: bytes, flags: int = 0, list_flags: int = 0):
         """a list of literals separated by '\\n' as the pattern (xsg_set_literals_opts; literal_list() joins one);
-        list_flags: LIST_WHOLE_WORDS"""
+        list_flags: LIST_WHOLE_WORDS, LIST_ALL_OF (at most MAX_ALL_OF_LITERALS literals; the line tags and
+        COUNT_LINES then select the lines that hold every literal, the match tags are XSG_ENOTSUP)"""
         self.nliterals = 0
         _check(self._lib.xsg_set_literals_opts(self.h, lst, len(lst), flags, list_flags))
         self.nliterals = literals_info(lst, flags)["count"]  # what Shard.count_literals sizes its result by
@@ -855,7 +858,8 @@ def meta_write(path: str, meta_out: str, data_out: str | None = None, compressio
 
 
 class Job:
-    """A file search (what xs::extern_search returns a handle to)."""
+    """A file search (what xs::extern_search returns a handle to).  list_flags: those of Context.set_literals
+    (LIST_WHOLE_WORDS, LIST_ALL_OF -- the latter with the line tags and COUNT_LINES only)."""
 
     def __init__(self, pattern: bytes, path: str, mode: int, meta_path: str | None = None, device: int = 0,
                  num_threads: int = 1, num_max_readers: int = 1, chunk_bytes: int = 16 << 20, flags: int = 0,
