@@ -46,6 +46,7 @@ extern "C" {
  * xsg_set_literals_opts, xsg_host_searcher_create_list_opts, xsg_literal_counter_create_opts and xsg_job_start_list joined;
  * xsg_find_literals, xsg_result_literal_hits, xsg_find_literals_async and xsg_literal_finder_* joined;
  * XSG_LIST_ALL_OF joined the list_flags of xsg_set_literals_opts, xsg_host_searcher_create_list_opts and xsg_job_start_list;
+ * xsg_result_chunk_ptr and xsg_fileset_* joined;
  * no entry point was removed or changed in meaning */
 #define XSG_ABI_VERSION 4
 
@@ -711,6 +712,23 @@ typedef struct xsg_context_edge {
 } xsg_context_edge;
 int xsg_result_context_edges(xsg_shard* shard, xsg_context_edge* out, uint64_t cap_chunks);
 
+/* The rows of a list result: which of its entries belong to which bound chunk -- what a caller that binds many documents
+ * as the chunks of one buffer needs to hand every document its own list (the per-chunk counts of xsg_count_chunks are
+ * the rows' lengths).  Valid after a successful xsg_search in any of the five list modes, until the next search, rebind
+ * or invalidate on the shard; XSG_ESTATE otherwise, also after a search that failed -- the xsg_result_u64 pattern.
+ * With n chunks bound, chunk_ptr receives n + 1 words: chunk_ptr[0] == 0, the entries [chunk_ptr[c], chunk_ptr[c + 1])
+ * of the result as xsg_result_u64[_view] and xsg_result_lines[_view] hand it out (for XSG_LINES: after the unterminated
+ * last lines were dropped) are chunk c's, and chunk_ptr[n] == *n_results.  Under XSG_FLAG_INVERT the rows are those of
+ * I, under XSG_FLAG_CONTEXT those of C, as defined per chunk above; a chunk of length 0 has an empty row, a binding of 0
+ * chunks yields {0}.  byte_ptr is optional and allowed only after XSG_LINES / XSG_MATCHES (XSG_EINVAL after a uint64
+ * mode): n + 1 words, byte_ptr[c] the sum of the lengths of the entries in front of chunk_ptr[c] -- where chunk c's
+ * bytes begin in `bytes` --, byte_ptr[n] == total_bytes.  XSG_EINVAL: chunk_ptr NULL, cap_rows < n + 1.
+ * The rows come from the chunk number the device keeps with every entry, never from the reported values: they hold for
+ * any global_offset / line_base the chunks were bound with.  A search pays nothing for them: they are computed by this
+ * call (a small kernel, one copy of the words, one wait), which leaves the result as it is -- every other accessor works
+ * before and after it, and it may be called again. */
+int xsg_result_chunk_ptr(xsg_shard* shard, uint64_t* chunk_ptr, uint64_t cap_rows, uint64_t* byte_ptr);
+
 /* ======================================================================== */
 /* File searches: the host pipeline behind xs::extern_search                 */
 /* ======================================================================== */
@@ -796,6 +814,66 @@ int xsg_job_get_u64(xsg_job* job, uint64_t first, uint64_t n, uint64_t* out);
 /* XSG_LINES: line `index`, XSG_MATCHES: match `index`; *data stays valid until xsg_job_destroy. */
 int xsg_job_get_line(xsg_job* job, uint64_t index, const char** data, uint64_t* len);
 int xsg_job_stats_get(xsg_job* job, xsg_job_stats* stats);
+
+/* ======================================================================== */
+/* File sets: a LIST of files searched in a few bindings                     */
+/* ======================================================================== */
+/* The sibling of the job API for many files: a source tree of 20 000 small files is 20 000 jobs there, each with its own
+ * transfer, binding, launches and wait; here the files are the CHUNKS of a few bindings.  xsg_fileset_start returns at once,
+ * the search runs in the set's own threads, and results are published per file in path order.
+ * File f's result is what a search of that file ALONE reports: byte offsets relative to the file, line indices from 0,
+ * context clipped at the file's edges, the default lossy end-of-chunk behaviour applied per chunk of the file's own plan.
+ *   - A file of at most chunk_bytes is ONE chunk.  Readers pread it into a pinned batch buffer at the next multiple of 16; a
+ *     batch closes when the next file would not fit batch_bytes, or at 2^20 files; it is uploaded, bound by xsg_shard_rebind
+ *     (global_offset = 0, line_base = 0 per chunk) and searched with ONE xsg_count_chunks (the two count tags) or ONE
+ *     xsg_search + xsg_result_chunk_ptr (the five list tags).  Two batch buffers: reading batch k + 1 overlaps the transfer
+ *     and search of batch k; readers never run further ahead.
+ *   - A file larger than chunk_bytes goes through xsg_job_start[_list] on the same device with the same chunk_bytes --
+ *     that pipeline and its seam stitcher as they are -- and its result is spliced in at the file's place.
+ *   - A path that cannot be read, a directory, or a file whose size changes under the read has the status XSG_EIO and an
+ *     empty row; the rest are searched.  Only pattern, option and device errors fail xsg_fileset_start or _join.
+ *   - xsg_count_chunks / xsg_search refuse a WHOLE binding that holds a byte >= 0x80 under an ASCII-only expression.  The
+ *     set then searches that batch again one file per binding, and only the files that hold such a byte get XSG_ENOTSUP.
+ *   - Results are a function of pattern, flags and file bytes only: identical for every batch_bytes, num_readers and cut.
+ *   - Paths may repeat, each mention is a file; npaths == 0 is XSG_OK with nothing to report.
+ * XSG_EINVAL from xsg_fileset_start: NULL paths (or a NULL path), a struct_size that is not sizeof(xsg_fileset_opts), a
+ * mode that is no tag, batch_bytes < chunk_bytes, an empty or oversized pattern, unknown list_flags, list_flags without
+ * pattern_is_list, num_readers < 0.  Patterns and flags the searches would refuse (xsg_set_pattern, xsg_set_literals_opts,
+ * XSG_FLAG_INVERT or XSG_LIST_ALL_OF with a match tag, a pattern that can match '\n' with a line tag) are refused there
+ * too, with the code the search would give. */
+typedef struct xsg_fileset xsg_fileset;
+typedef struct xsg_fileset_opts {
+  uint32_t struct_size;     /* sizeof(xsg_fileset_opts) */
+  uint32_t mode;            /* enum xsg_mode: any of the seven tags */
+  uint32_t pattern_flags;   /* XSG_FLAG_* */
+  uint32_t pattern_is_list; /* != 0: `pattern` is a literal list (xsg_set_literals) */
+  uint32_t list_flags;      /* XSG_LIST_* (with pattern_is_list) */
+  int32_t device;           /* HIP device index */
+  int32_t num_readers;      /* 0: auto, never more than 16 */
+  uint64_t batch_bytes;     /* 0: 256 MiB */
+  uint64_t chunk_bytes;     /* 0: 16 MiB */
+} xsg_fileset_opts;
+void xsg_fileset_opts_init(xsg_fileset_opts* opts);  /* clears, stamps struct_size, mode = XSG_COUNT_LINES */
+int xsg_fileset_start(const void* pattern, size_t plen, const char* const* paths, uint64_t npaths,
+                      const xsg_fileset_opts* opts, xsg_fileset** out);
+/* Blocks until file `file_index` is published or the set has finished; *files_done = files published so far (they publish
+ * in path order, so the files [0, *files_done) have their results), *finished = 1 once no more will come. */
+int xsg_fileset_wait(xsg_fileset* set, uint64_t file_index, uint64_t* files_done, int* finished);
+/* Blocks until the set has finished; returns its error (never a single file's: see xsg_fileset_status). */
+int xsg_fileset_join(xsg_fileset* set);
+/* Per file: XSG_OK or its XSG_E* (cap >= npaths); files not yet published read XSG_OK. */
+int xsg_fileset_status(xsg_fileset* set, int32_t* status, uint64_t cap);
+/* Per file: the count (count tags) or the number of its entries (list tags); cap >= npaths; not yet published: 0. */
+int xsg_fileset_counts(xsg_fileset* set, uint64_t* counts, uint64_t cap);
+/* List tags: npaths + 1 words, the entries [file_ptr[f], file_ptr[f + 1]) of the set's flat result are file f's (files
+ * not yet published have empty rows at the current end).  XSG_ESTATE for a count tag. */
+int xsg_fileset_file_ptr(xsg_fileset* set, uint64_t* file_ptr, uint64_t cap_rows);
+/* The flat result, as far as it is published: uint64 tags / XSG_LINES and XSG_MATCHES (*data stays valid until
+ * xsg_fileset_destroy). */
+int xsg_fileset_get_u64(xsg_fileset* set, uint64_t first, uint64_t n, uint64_t* out);
+int xsg_fileset_get_line(xsg_fileset* set, uint64_t index, const char** data, uint64_t* len);
+/* Stops what is still running, joins, frees the set and everything it returned pointers into. */
+void xsg_fileset_destroy(xsg_fileset* set);
 
 /* ======================================================================== */
 /* The lower seam: one chunk held in HOST memory                             */

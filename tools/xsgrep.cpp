@@ -6,6 +6,7 @@
 //   xsgrep -F --all-of [-c] [-i] [-v] [-w] [-A N] [-B N] [-C N] [-j THREADS] [-m METAFILE] (-e PATTERN)... [-f FILE]... FILE|-
 //   xsgrep -F [-i] [-w] --count-each (-e PATTERN)... [-f FILE]... FILE|-
 //   xsgrep -F [-i] [-w] --find-each (-e PATTERN)... [-f FILE]... FILE|-
+//   xsgrep [the options of the first three forms but -m] [-r] [-l|-L] [-H|--no-filename] PATTERN FILE FILE...
 //
 // -c  print only a count of matching lines   (grep.cpp:45-46 -> xs::count_lines)
 // -i  ignore ASCII case                      (grep.cpp:47-48)
@@ -49,10 +50,28 @@
 //     requirement, and under -w only whole-word occurrences count.  Requires -F; at most 64 patterns; a single PATTERN is a
 //     list of one.  Combines with -c -i -v -w -A -B -C -e -f -j -m, on FILE and on `-`; with -v it selects the lines that
 //     lack at least one pattern.  Excludes -o (a conjunction has no single matched text), -x, --count-each and --find-each.
-// The one-letter options without an argument may be bundled (-vc, -ci, -oi, -wc).
+// FILE FILE..., -r / --recursive  several files in one run (xsg_fileset_*: the files are the chunks of a few bindings, not
+//     one job each).  -r walks directories depth-first, entries in byte-wise sorted order, regular files only; symbolic links
+//     met during the walk are not followed.  Every file's result is what a search of that file alone gives.
+// -l / --files-with-matches, -L / --files-without-match  print only the names of the files with / without a selected line
+//     (a count of lines through the file set; no line is printed).  -c prints PATH:COUNT per file.
+// -H / --with-filename, --no-filename  the prefix PATH: on every printed line; on by default with more than one FILE operand
+//     or -r, off otherwise (-h stays help).  Under -A/-B/-C EVERY printed line carries PATH: -- GNU grep marks context lines
+//     with PATH- instead, a deviation like the missing `--` separators.
+//     Several FILE operands go with the positional PATTERN; with -e / -f there is one FILE operand, as before this mode
+//     existed (a second one stays "unexpected argument"): a list of patterns reaches many files through -r DIR.
+//     This mode combines with -i -v -o -w -x -E -F -e -f --all-of -A -B -C -j; it refuses `-` among the files, -m,
+//     --count-each and --find-each (exit 2, before a device is touched).  Its exit status is grep's: 0 if something was
+//     selected (under -L: listed), 1 if nothing was, 2 if a file failed -- `xsgrep: PATH: reason` on stderr, the other files
+//     are still printed.  Output comes per published file, in operand / walk order.  A single FILE without any of -r -l -L
+//     -H --no-filename takes the single-file path above, output and exit status unchanged.
+// The one-letter options without an argument may be bundled (-vc, -ci, -oi, -wc, -rl).
 // otherwise print the matching lines, live, as they are found (grep.cpp:74-79).
 #include <xsearch/tasks/gpu_searchers.h>
 #include <xsearch/xsearch.h>
+
+#include <dirent.h>
+#include <sys/stat.h>
 
 #include <algorithm>
 #include <cstdio>
@@ -70,6 +89,12 @@ static const char kUsage[] =
     "       %s -F --all-of [-c] [-i] [-v] [-w] [-A N] [-B N] [-C N] [-j THREADS] [-m METAFILE] (-e PATTERN)... [-f FILE]... FILE|-\n"
     "       %s -F [-i] [-w] --count-each (-e PATTERN)... [-f FILE]... FILE|-\n"
     "       %s -F [-i] [-w] --find-each (-e PATTERN)... [-f FILE]... FILE|-\n"
+    "       %s [options of the first three forms but -m] [-r] [-l|-L] [-H|--no-filename] PATTERN FILE FILE...\n"
+    "  FILE FILE..., -r / --recursive search several files in one run (directories depth-first, sorted byte-wise, regular files\n"
+    "     only, links met on the walk not followed); -l / -L print only the names of files with / without a selected line;\n"
+    "     -c prints PATH:COUNT; -H / --no-filename force the PATH: prefix on / off (default: on with several FILEs or -r;\n"
+    "     context lines carry PATH: too, where GNU grep prints PATH-); exit status 0 selected, 1 nothing, 2 a file failed;\n"
+    "     not with FILE = -, -m, --count-each, --find-each; with -e / -f one FILE operand only (use -r DIR)\n"
     "  -e PATTERN, -f FILE (one literal per line) search for any of several literals; both may repeat, need -F and exclude -x\n"
     "     when they give more than one pattern; -o then prints the FIRST-listed literal that occurs at a position (GNU grep: the longest)\n"
     "  -A N, -B N, -C N also print N lines after / before / around every selected line (N <= 4095), each line once and\n"
@@ -214,9 +239,115 @@ static int find_each(const std::vector<std::string>& lits, bool icase, bool word
   return 0;
 }
 
+// -r: the regular files under `dir`, depth-first, entries in byte-wise sorted order; links are not followed
+static void walk(const std::string& dir, std::vector<std::string>& out) {
+  std::vector<std::string> names;
+  if (DIR* d = opendir(dir.c_str())) {
+    while (const dirent* e = readdir(d)) {
+      const std::string n = e->d_name;
+      if (n != "." && n != "..") names.push_back(n);
+    }
+    closedir(d);
+  } else {
+    out.push_back(dir);  // (unreadable: the file set reports it)
+    return;
+  }
+  std::sort(names.begin(), names.end());
+  for (const std::string& n : names) {
+    const std::string path = dir.empty() || dir.back() == '/' ? dir + n : dir + "/" + n;
+    struct stat st;
+    if (lstat(path.c_str(), &st) != 0) continue;
+    if (S_ISDIR(st.st_mode)) walk(path, out);
+    else if (S_ISREG(st.st_mode)) out.push_back(path);
+  }
+}
+
+struct FileSetRun {
+  bool count = false, only = false, list_with = false, list_without = false, prefix = false, is_list = false;
+  uint32_t list_flags = 0;
+  int threads = 2;
+};
+
+// several files (xsg_fileset_*): prints per published file; -> grep's exit status
+static int search_files(const std::string& pattern, bool icase, const std::vector<std::string>& files, const FileSetRun& run) {
+  xsg_fileset_opts o;
+  xsg_fileset_opts_init(&o);
+  const bool counting = run.count || run.list_with || run.list_without;
+  o.mode = counting ? XSG_COUNT_LINES : run.only ? XSG_MATCHES : XSG_LINES;
+  o.pattern_flags = xs::detail::pattern_flags(pattern, icase) | xs::detail::context_flags(o.mode);
+  o.pattern_is_list = run.is_list ? 1u : 0u;
+  o.list_flags = run.list_flags;
+  o.device = (int32_t)xs::detail::env_u64("XS_DEVICE", 0);
+  o.num_readers = run.threads > 2 ? std::min(run.threads, 16) : 0;  // (-j beyond its default asks for that many readers)
+  o.chunk_bytes = xs::detail::env_u64("XS_CHUNK_BYTES", 0);
+  o.batch_bytes = xs::detail::env_u64("XS_BATCH_BYTES", 0);
+  std::vector<const char*> paths;
+  for (const std::string& f : files) paths.push_back(f.c_str());
+  xsg_fileset* set = nullptr;
+  if (xsg_fileset_start(pattern.data(), pattern.size(), paths.data(), paths.size(), &o, &set) != XSG_OK) {
+    std::fprintf(stderr, "xsgrep: %s\n", xsg_last_error());
+    return 2;
+  }
+  const uint64_t n = files.size();
+  std::vector<int32_t> status(n);
+  std::vector<uint64_t> counts(n), file_ptr(n + 1);
+  bool selected = false, failed = false;
+  uint64_t next = 0;
+  while (next < n) {
+    uint64_t done = 0;
+    int fin = 0;
+    if (xsg_fileset_wait(set, next, &done, &fin) != XSG_OK) break;  // (the set failed: reported by the join below)
+    if (done == next) break;
+    xsg_fileset_status(set, status.data(), n);
+    xsg_fileset_counts(set, counts.data(), n);
+    if (!counting) xsg_fileset_file_ptr(set, file_ptr.data(), n + 1);
+    for (uint64_t f = next; f < done; ++f) {
+      const std::string& path = files[f];
+      if (status[f] != XSG_OK) {
+        std::cout.flush();
+        std::fprintf(stderr, "xsgrep: %s: %s\n", path.c_str(),
+                     status[f] == XSG_ENOTSUP ? "not searched: it holds bytes this expression does not accept (>= 0x80), or context that crosses a whole chunk"
+                                              : "cannot be read (missing, unreadable, no regular file, or changed while it was read)");
+        failed = true;
+        continue;
+      }
+      if (run.list_with || run.list_without) {
+        if ((counts[f] != 0) == run.list_with) {
+          std::cout << path << '\n';
+          selected = true;
+        }
+      } else if (run.count) {
+        if (run.prefix) std::cout << path << ':';
+        std::cout << counts[f] << '\n';
+        selected |= counts[f] != 0;
+      } else {
+        for (uint64_t k = file_ptr[f]; k < file_ptr[f + 1]; ++k) {
+          const char* d = nullptr;
+          uint64_t len = 0;
+          if (xsg_fileset_get_line(set, k, &d, &len) != XSG_OK) break;
+          if (run.prefix) std::cout << path << ':';
+          std::cout.write(d, (std::streamsize)len);
+          std::cout << '\n';
+        }
+        selected |= file_ptr[f + 1] != file_ptr[f];
+      }
+    }
+    std::cout.flush();
+    next = done;
+  }
+  if (xsg_fileset_join(set) != XSG_OK) {
+    std::cout.flush();
+    std::fprintf(stderr, "xsgrep: %s\n", xsg_last_error());
+    return 2;
+  }
+  return failed ? 2 : selected ? 0 : 1;
+}
+
 int main(int argc, char** argv) {
   bool count = false, icase = false, fixed = false, extended = false, whole_lines = false, invert = false, only = false;
   bool each = false, find = false, context_given = false, words = false, all_of = false;
+  bool recursive = false, list_with = false, list_without = false, with_filename = false, no_filename = false;
+  std::vector<std::string> files;  // every FILE operand (`file` is the first)
   int threads = 2;  // grep.cpp:21
   long before = 0, after = 0;
   std::string meta, pattern, file;
@@ -226,7 +357,7 @@ int main(int argc, char** argv) {
   std::vector<std::string> args;
   for (int i = 1; i < argc; ++i) {  // -vc -> -v -c (only letters that take no argument; anything else stays one word)
     const std::string a = argv[i];
-    if (a.size() > 2 && a[0] == '-' && a[1] != '-' && a.find_first_not_of("ciEFxvow", 1) == std::string::npos) {
+    if (a.size() > 2 && a[0] == '-' && a[1] != '-' && a.find_first_not_of("ciEFxvowlLrH", 1) == std::string::npos) {
       for (size_t k = 1; k < a.size(); ++k) args.push_back(std::string("-") + a[k]);
     } else {
       args.push_back(a);
@@ -243,6 +374,16 @@ int main(int argc, char** argv) {
       words = true;
     } else if (a == "--all-of") {
       all_of = true;
+    } else if (a == "-r" || a == "--recursive") {
+      recursive = true;
+    } else if (a == "-l" || a == "--files-with-matches") {
+      list_with = true;
+    } else if (a == "-L" || a == "--files-without-match") {
+      list_without = true;
+    } else if (a == "-H" || a == "--with-filename") {
+      with_filename = true;
+    } else if (a == "--no-filename") {
+      no_filename = true;
     } else if (a == "--count-each") {
       each = true;
     } else if (a == "--find-each") {
@@ -292,31 +433,43 @@ int main(int argc, char** argv) {
       }
       have_patterns = true;
     } else if (a == "-h" || a == "--help") {
-      std::printf(kUsage, argv[0], argv[0], argv[0], argv[0], argv[0]);
+      std::printf(kUsage, argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
       return 0;
     } else if (pos == 0 && !have_patterns) {
       pattern = a;
       ++pos;
-    } else if (pos <= 1 && file.empty()) {
-      file = a;
-      pos = 2;
     } else {
-      std::fprintf(stderr, "unexpected argument '%s'\n", a.c_str());
-      return 2;
+      files.push_back(a);
+      pos = 2;
     }
   }
-  if (have_patterns && !pattern.empty()) {  // (PATTERN was read before the first -e / -f: it is the FILE)
-    if (!file.empty()) {
-      std::fprintf(stderr, "unexpected argument '%s'\n", file.c_str());
-      return 2;
-    }
-    file = pattern;
+  if (have_patterns && !pattern.empty()) {  // (PATTERN was read before the first -e / -f: it is the first FILE)
+    files.insert(files.begin(), pattern);
     pattern.clear();
     pos = 2;
   }
-  if (pos != 2) {
-    std::fprintf(stderr, kUsage, argv[0], argv[0], argv[0], argv[0], argv[0]);
+  if (have_patterns && files.size() > 1) {  // with -e / -f there is ONE FILE operand, as there always was (under -r: a directory)
+    std::fprintf(stderr, "unexpected argument '%s'\n", files[1].c_str());
     return 2;
+  }
+  if (pos != 2) {
+    std::fprintf(stderr, kUsage, argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
+    return 2;
+  }
+  file = files[0];
+  // several files, or an option that only the file-set mode knows; a single FILE without them goes the way it always went
+  const bool multi = files.size() > 1 || recursive || list_with || list_without || with_filename || no_filename;
+  if (multi) {
+    const char* clash = std::find(files.begin(), files.end(), "-") != files.end() ? "`-` (stdin) is not served among several files or with -r -l -L -H --no-filename"
+                        : !meta.empty() ? "-m METAFILE belongs to one FILE: it is not served with several files or -r -l -L -H --no-filename"
+                        : each ? "--count-each reads one input: it is not served with several files or -r -l -L -H --no-filename"
+                        : find ? "--find-each reads one input: it is not served with several files or -r -l -L -H --no-filename"
+                        : list_with && list_without ? "-l and -L exclude each other"
+                        : with_filename && no_filename ? "-H and --no-filename exclude each other" : nullptr;
+    if (clash) {
+      std::fprintf(stderr, "xsgrep: %s\n", clash);
+      return 2;
+    }
   }
   if (words && (!fixed || whole_lines)) {  // never a silent substring search
     std::fprintf(stderr, "xsgrep: -w (whole words) is served for literals only: it needs -F and excludes -x\n");
@@ -453,6 +606,22 @@ int main(int argc, char** argv) {
   setenv("XS_CONTEXT_AFTER", context ? std::to_string(after).c_str() : "0", 1);
   try {
     std::ios::sync_with_stdio(false);
+    if (multi) {
+      std::vector<std::string> paths;
+      for (const std::string& f : files) {
+        struct stat st;
+        if (recursive && stat(f.c_str(), &st) == 0 && S_ISDIR(st.st_mode)) walk(f, paths);
+        else paths.push_back(f);
+      }
+      FileSetRun run;
+      run.count = count, run.only = only, run.list_with = list_with, run.list_without = list_without;
+      run.prefix = with_filename || (!no_filename && (files.size() > 1 || recursive));
+      run.is_list = list, run.list_flags = list_flags, run.threads = threads;
+      const int rc = search_files(pattern, icase, paths, run);
+      std::cout.flush();
+      std::fflush(stdout);
+      std::_Exit(rc);  // (as at the end of main: the runtime's teardown is left to the kernel)
+    }
     if (file == "-") {
       // stdin (grep.cpp:37: "input file, stdin if '-' or empty"): no file to plan chunks on, so
       // read newline-aligned chunks here and hand each to the reference-style searcher functors

@@ -22,6 +22,7 @@
 #include <thread>
 
 #include "xsg_context.h"
+#include "xsg_fileio.h"
 #include "xsg_lz4.h"
 #include "xsg_objects.h"
 
@@ -49,39 +50,7 @@ static int guarded(const char* what, F&& f) {
 // ---------------------------------------------------------------------------
 // file helpers
 // ---------------------------------------------------------------------------
-static int pread_full(int fd, void* buf, uint64_t n, uint64_t off) {
-  uint8_t* p = static_cast<uint8_t*>(buf);
-  while (n) {
-    const ssize_t r = pread(fd, p, n > (1u << 30) ? (1u << 30) : n, (off_t)off);
-    if (r < 0) {
-      if (errno == EINTR) continue;
-      return fail(XSG_EIO, "pread failed: %s", strerror(errno));
-    }
-    if (r == 0) return fail(XSG_EIO, "unexpected end of file at offset %llu", (unsigned long long)off);
-    p += r;
-    off += (uint64_t)r;
-    n -= (uint64_t)r;
-  }
-  return XSG_OK;
-}
-
-static int open_ro(const char* path, int* fd, uint64_t* size) {
-  if (!path || !*path) return fail(XSG_EINVAL, "empty file path");
-  const int f = open(path, O_RDONLY | O_CLOEXEC);
-  if (f < 0) return fail(XSG_EIO, "cannot open '%s': %s", path, strerror(errno));
-  struct stat st;
-  if (fstat(f, &st) != 0) {
-    close(f);
-    return fail(XSG_EIO, "cannot stat '%s': %s", path, strerror(errno));
-  }
-  if (!S_ISREG(st.st_mode)) {
-    close(f);
-    return fail(XSG_EIO, "'%s' is not a regular file", path);
-  }
-  *fd = f;
-  *size = (uint64_t)st.st_size;
-  return XSG_OK;
-}
+// (open_ro, pread_full and cpu_budget live in xsg_fileio.h: xsg_fileset.cpp reads files too)
 
 // ---------------------------------------------------------------------------
 // chunk plan of a plain file: >= target bytes, extended to just past the next '\n'
@@ -854,22 +823,6 @@ extern "C" int xsg_device_numa(int device, int* node, char* cpulist, size_t cap)
   return XSG_OK;
 }
 
-// CPUs this process may use: its affinity mask, capped by the cgroup's CPU quota (cpu.max)
-static int cpu_budget() {
-  int n = 1;
-  cpu_set_t set;
-  if (sched_getaffinity(0, sizeof set, &set) == 0) n = std::max(1, CPU_COUNT(&set));
-  if (FILE* f = fopen("/sys/fs/cgroup/cpu.max", "r")) {
-    char q[32] = "";
-    long long period = 0;
-    if (fscanf(f, "%31s %lld", q, &period) == 2 && strcmp(q, "max") != 0 && period > 0) {
-      const long long quota = atoll(q);
-      if (quota > 0) n = (int)std::min<long long>(n, std::max<long long>(1, quota / period));
-    }
-    fclose(f);
-  }
-  return n;
-}
 static uint64_t env_u64(const char* name, uint64_t dflt) {
   const char* v = getenv(name);
   return v && *v ? strtoull(v, nullptr, 0) : dflt;

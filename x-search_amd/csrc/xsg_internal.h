@@ -288,6 +288,31 @@ struct ListChunkArgs {
   uint32_t invert;              // counts[c] = lines of chunk c - counts[c] (needs tile_nl_off)
 };
 hipError_t launch_list_chunk_counts(const ListChunkArgs& a, hipStream_t s);
+// xsg_result_chunk_ptr (xsg_list_kernels.hip: k_chunk_rows): the rows of a finished list result, computed when asked for
+// from what the search left on the device.  One lane per word of the nchunks + 1, a binary search each:
+//   f_chunk != null   the chunk column of the `total` final entries (the exact route behind launch_assemble, invert_list
+//                     or context_list; the one-sync route's line-index and line tags): rows[c] = first entry of chunk c.
+//                     With line_len (XSG_LINES that dropped unterminated lines, UINT64_MAX in line_len: a chunk's last
+//                     entries) the lane writes the row's LENGTH without them to lens[c]; their prefix sum is the rows.
+//   f_chunk == null   the one-sync route's two offset tags, which write no such column: rows[c] = what the walk kept of
+//                     the raw entries in front of chunk c (keep_pre; null: all of them) + the tail entries of the chunks
+//                     in front of it (tail_pre) -- where k_list_out put chunk c's first entry.
+// byte_rows (optional, with f_chunk): line_off at the row's first entry, line_bytes behind the last.
+struct ChunkRowsArgs {
+  uint64_t nchunks;
+  uint64_t total;             // entries of f_chunk, or raw entries of m_chunk
+  const uint32_t* f_chunk;
+  const uint32_t* m_chunk;
+  const uint64_t* keep_pre;   // total + 1 entries
+  const uint64_t* tail_pre;   // nchunks + 1 entries
+  const uint64_t* line_len;   // `total` entries
+  const uint64_t* line_off;   // exclusive prefix of line_len (dropped: 0), `total` entries
+  uint64_t line_bytes;
+  uint64_t* rows;             // nchunks + 1
+  uint64_t* lens;             // nchunks (with line_len)
+  uint64_t* byte_rows;        // nchunks + 1, or null
+};
+hipError_t launch_chunk_rows(const ChunkRowsArgs& a, hipStream_t s);
 
 // ---- launchers (xsg_kernels.hip) --------------------------------------------
 hipError_t launch_scan_count(const ScanArgs& a, bool want_nl, bool want_lines, hipStream_t s);

@@ -415,6 +415,10 @@ static int run_list_fast(xsg_shard* s, uint32_t mode) {
   const uint64_t total = s->h_tot[kTotFinal];
   s->total = total;
   s->fast_result = true;
+  // xsg_result_chunk_ptr: k_list_out wrote the chunk column for two of the tags; the other two keep what it placed them by
+  s->rows_chunk = want_f ? l.f_chunk : nullptr;
+  s->rows_entries = want_f ? total : s->h_tot[kTotRaw];
+  s->rows_keep_all = !line_mode;
   if (want_nl) s->last_newlines = s->nl_total;
   if (mode == XSG_LINES) {
     // lines without a terminating '\n' are not reported (search_wrappers.h:199-202)
@@ -894,6 +898,8 @@ static int list_outputs(xsg_shard* s, uint32_t mode, const ScanArgs& a, ListArgs
   if (mode == XSG_LINES) s->total = total - s->h_dropped;  // lines without a terminating '\n' are not reported (search_wrappers.h:199-202)
   s->last_mode = (int)mode;
   s->context_edges_valid = context;
+  s->rows_chunk = l.f_chunk;  // (xsg_result_chunk_ptr: the column behind the last of assemble, invert and context)
+  s->rows_entries = total;
   return XSG_OK;
 }
 
@@ -1012,6 +1018,7 @@ int xsg::run_list(xsg_shard* s, uint32_t mode, bool outputs, bool want_nl_total,
 }
 
 extern "C" int xsg_search(xsg_shard* s, uint32_t mode, uint64_t* n_results) {
+  if (s) s->rows_valid = false;  // (xsg_result_chunk_ptr: a search that is refused here leaves no rows either)
   XSG_TRY(check_ready(s));
   if (mode != XSG_MATCH_BYTE_OFFSETS && mode != XSG_LINE_BYTE_OFFSETS && mode != XSG_LINE_INDICES &&
       mode != XSG_LINES && mode != XSG_MATCHES)
@@ -1022,6 +1029,7 @@ extern "C" int xsg_search(xsg_shard* s, uint32_t mode, uint64_t* n_results) {
   XSG_TRY(run_list(s, mode, true));
   if (!s->fast_result) trim_pinned(s, 8 * (size_t)s->total, 8 * (size_t)s->total, (size_t)s->line_bytes);  // (an exact-route result is still on the device)
   if (n_results) *n_results = s->total;
+  s->rows_valid = true;
   return XSG_OK;
 }
 
@@ -1089,6 +1097,68 @@ extern "C" int xsg_result_context_edges(xsg_shard* s, xsg_context_edge* out, uin
   if (cap_chunks < n) return fail(XSG_EINVAL, "cap_chunks %llu < %llu chunks", (unsigned long long)cap_chunks, (unsigned long long)n);
   if (n && !out) return fail(XSG_EINVAL, "out is null");
   if (n) memcpy(out, s->context_edges.data(), sizeof(xsg_context_edge) * n);
+  return XSG_OK;
+}
+
+// The rows of the pending list result: which of its entries are whose chunk's.  Computed here, when asked for, from the
+// chunk bookkeeping the search left on the device (xsg_shard::rows_chunk) -- one launch (three more where XSG_LINES
+// dropped a line: the prefix sum of the shortened rows), one copy of the words, one sync; the search itself does
+// nothing for it.  The result and its other accessors are not touched: the words have buffers of their own.
+extern "C" int xsg_result_chunk_ptr(xsg_shard* s, uint64_t* chunk_ptr, uint64_t cap_rows, uint64_t* byte_ptr) {
+  if (!s) return fail(XSG_EINVAL, "shard is null");
+  const int m = s->last_mode;
+  const bool packed = m == XSG_LINES || m == XSG_MATCHES;
+  if (!s->rows_valid || (!packed && m != XSG_MATCH_BYTE_OFFSETS && m != XSG_LINE_BYTE_OFFSETS && m != XSG_LINE_INDICES))
+    return fail(XSG_ESTATE, "no list result of a successful xsg_search is pending on this shard");
+  const uint64_t n = s->chunks.size();
+  if (!chunk_ptr) return fail(XSG_EINVAL, "chunk_ptr is null");
+  if (cap_rows < n + 1) return fail(XSG_EINVAL, "room for %llu rows' words, the binding needs %llu", (unsigned long long)cap_rows,
+                                    (unsigned long long)(n + 1));
+  if (byte_ptr && !packed) return fail(XSG_EINVAL, "byte_ptr belongs to an XSG_LINES or XSG_MATCHES result: the pending one holds uint64 values");
+  if (n == 0) {
+    chunk_ptr[0] = 0;
+    if (byte_ptr) byte_ptr[0] = 0;
+    return XSG_OK;
+  }
+  xsg_ctx* c = s->ctx;
+  hipStream_t st = c->stream;
+  HIP_TRY(hipSetDevice(c->device));
+  const uint64_t words = (n + 1) * (byte_ptr ? 2 : 1);
+  XSG_TRY(s->d_rows.ensure(8 * (3 * n + 2)));
+  XSG_TRY(s->h_rows.ensure(8 * (size_t)(2 * n + 2)));
+  const bool dropped = m == XSG_LINES && s->total != s->rows_entries;
+  ChunkRowsArgs a{};
+  a.nchunks = n;
+  a.total = s->rows_entries;
+  a.f_chunk = s->rows_chunk;
+  a.rows = s->d_rows.as<uint64_t>();
+  if (a.f_chunk) {
+    if (dropped) {
+      a.line_len = s->d_line_len.as<uint64_t>();
+      a.lens = a.rows + 2 * (n + 1);
+    }
+    if (byte_ptr) {
+      a.line_off = s->d_line_off.as<uint64_t>();
+      a.line_bytes = s->line_bytes;
+      a.byte_rows = a.rows + (n + 1);
+    }
+  } else {
+    a.m_chunk = s->d_m_chunk.as<uint32_t>();
+    a.keep_pre = s->rows_keep_all ? nullptr : s->d_keep_pre.as<uint64_t>();
+    a.tail_pre = s->d_tail_pre.as<uint64_t>();
+  }
+  HIP_TRY(launch_chunk_rows(a, st));
+  if (a.lens) {
+    XSG_TRY(s->d_scan_tmp.ensure(8 * scan_tmp_elems(n + 1)));
+    HIP_TRY(launch_exclusive_scan_u64(a.lens, a.rows, n, s->d_scan_tmp.as<uint64_t>(), st));
+  }
+  uint64_t* h = s->h_rows.as<uint64_t>();
+  HIP_TRY(hipMemcpyAsync(h, a.rows, 8 * words, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (h[n] != s->total) return fail(XSG_ESTATE, "the rows end at %llu, the result holds %llu entries: a call since the search took its bookkeeping",
+                                    (unsigned long long)h[n], (unsigned long long)s->total);
+  memcpy(chunk_ptr, h, 8 * (n + 1));
+  if (byte_ptr) memcpy(byte_ptr, h + n + 1, 8 * (n + 1));
   return XSG_OK;
 }
 

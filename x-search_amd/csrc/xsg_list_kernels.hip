@@ -1454,6 +1454,35 @@ hipError_t launch_list_chunk_counts(const ListChunkArgs& a, hipStream_t s) {
   return hipGetLastError();
 }
 
+// xsg_result_chunk_ptr (ChunkRowsArgs, xsg_internal.h): one lane per word of the rows, c = 0 .. nchunks.  No entry names
+// a chunk >= nchunks, so the search for c == nchunks ends at `total`: the last word needs no case of its own.
+__global__ __launch_bounds__(kBlock) void k_chunk_rows(const ChunkRowsArgs A) {
+  const uint64_t c = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (c > A.nchunks) return;
+  if (!A.f_chunk) {
+    const uint64_t i = first_entry_of_chunk(A.m_chunk, A.total, c);
+    A.rows[c] = (A.keep_pre ? A.keep_pre[i] : i) + A.tail_pre[c];
+    return;
+  }
+  const uint64_t lo = first_entry_of_chunk(A.f_chunk, A.total, c);
+  if (A.byte_rows) A.byte_rows[c] = lo < A.total ? A.line_off[lo] : A.line_bytes;
+  if (!A.line_len) {
+    A.rows[c] = lo;
+    return;
+  }
+  if (c == A.nchunks) return;
+  // a line without its '\n' is a chunk's last: the dropped entries end the row
+  uint64_t n = first_entry_of_chunk(A.f_chunk, A.total, c + 1) - lo;
+  while (n && A.line_len[lo + n - 1] == UINT64_MAX) --n;
+  A.lens[c] = n;
+}
+hipError_t launch_chunk_rows(const ChunkRowsArgs& a, hipStream_t s) {
+  if (a.f_chunk ? (a.byte_rows && !a.line_off) || (a.line_len && !a.lens) : !a.m_chunk || !a.tail_pre || a.byte_rows != nullptr)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_chunk_rows, grid_for(a.nchunks + 1), dim3(kBlock), 0, s, a);
+  return hipGetLastError();
+}
+
 
 // ---------------------------------------------------------------------------
 // XSG_FLAG_CONTEXT: the lines around the reported ones (ContextArgs, xsg_internal.h)

@@ -289,6 +289,16 @@ struct xsg_shard {
   bool find_valid = false;
   uint64_t find_rows = 0, find_total = 0;  // ... n and chunk_ptr[n] of the kept result
   uint64_t list_entries = 0;  // raw entries (ListArgs::M) the last exact list pass left in d_m_chunk / d_keep_pre
+  // xsg_result_chunk_ptr: where the pending list result (last_mode) left its chunk bookkeeping -- noted by the search on
+  // the host, nothing is launched or fetched for it until the accessor is called.  rows_chunk: the chunk column of the
+  // final list (d_f_chunk, d_inv_chunk or d_cx_chunk) and rows_entries its length before XSG_LINES drops a line; null:
+  // the one-sync route's offset tags, rows_entries raw entries in d_m_chunk, kept as d_keep_pre says (rows_keep_all: all).
+  bool rows_valid = false;  // the last xsg_search on this shard succeeded (last_mode says whether its result still stands)
+  const uint32_t* rows_chunk = nullptr;
+  uint64_t rows_entries = 0;
+  bool rows_keep_all = false;
+  DevBuf d_rows;  // chunk_ptr, byte_ptr (nchunks + 1 words each), the rows' lengths (nchunks); grow-only
+  PinBuf h_rows;  // ... the pinned mirror of the first two
   bool begin_sync_result = false;  // xsg_count_begin had to run synchronously: _end hands out begin_counters
   uint64_t begin_counters[XSG_NUM_COUNTERS] = {0, 0, 0, 0};
 
@@ -325,13 +335,13 @@ struct xsg_shard {
                      &d_cx_slot, &d_cx_pos, &d_cx_chunk, &d_cx_edge, &d_sketch, &d_spans, &d_chunk_counts, &d_lit_counts,
                      &d_lit_matrix, &d_csr_row_nnz, &d_csr_tmp, &d_csr_seam, &d_csr_row_ptr, &d_csr_cols, &d_csr_vals,
                      &d_find_occ, &d_find_off, &d_find_tmp, &d_find_ptr, &d_find_pos, &d_find_lit, &d_c_mask, &d_m_mask,
-                     &d_line_mask};
+                     &d_line_mask, &d_rows};
     for (DevBuf* b : all) b->release();
     if (h_stage) (void)hipHostFree(h_stage);
     if (h_counters) (void)hipHostFree(h_counters);
     if (h_tot) (void)hipHostFree(h_tot);
     h_tot = nullptr;
-    for (PinBuf* b : {&h_result, &hp_line_len, &hp_line_bytes, &h_chunk_counts, &h_lit_counts, &h_lit_matrix, &h_csr, &h_find}) b->release();
+    for (PinBuf* b : {&h_result, &hp_line_len, &hp_line_bytes, &h_chunk_counts, &h_lit_counts, &h_lit_matrix, &h_csr, &h_find, &h_rows}) b->release();
     if (table_ev) (void)hipEventDestroy(table_ev);
     h_stage = nullptr;
     h_counters = nullptr;

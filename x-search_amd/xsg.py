@@ -59,6 +59,12 @@ class JobOpts(C.Structure):
                 ("pattern_is_list", C.c_uint32)]
 
 
+class FileSetOpts(C.Structure):  # xsg_fileset_opts
+    _fields_ = [("struct_size", C.c_uint32), ("mode", C.c_uint32), ("pattern_flags", C.c_uint32),
+                ("pattern_is_list", C.c_uint32), ("list_flags", C.c_uint32), ("device", C.c_int32),
+                ("num_readers", C.c_int32), ("batch_bytes", C.c_uint64), ("chunk_bytes", C.c_uint64)]
+
+
 class LiteralList(C.Structure):  # xsg_literal_list
     _fields_ = [("count", C.c_uint32), ("min_len", C.c_uint32), ("max_len", C.c_uint32), ("gram", C.c_uint32),
                 ("filter_bits_set", C.c_uint32)]
@@ -176,6 +182,17 @@ def load():
         "xsg_result_lines_view": (ci, [vp, C.POINTER(_u64p), C.POINTER(C.c_char_p), C.POINTER(_u64p), _u64p, _u64p]),
         "xsg_result_newlines": (ci, [vp, _u64p]),
         "xsg_result_context_edges": (ci, [vp, vp, u64]),
+        "xsg_result_chunk_ptr": (ci, [vp, vp, u64, vp]),
+        "xsg_fileset_opts_init": (None, [C.POINTER(FileSetOpts)]),
+        "xsg_fileset_start": (ci, [C.c_char_p, sz, C.POINTER(C.c_char_p), u64, C.POINTER(FileSetOpts), C.POINTER(vp)]),
+        "xsg_fileset_wait": (ci, [vp, u64, _u64p, C.POINTER(ci)]),
+        "xsg_fileset_join": (ci, [vp]),
+        "xsg_fileset_status": (ci, [vp, vp, u64]),
+        "xsg_fileset_counts": (ci, [vp, vp, u64]),
+        "xsg_fileset_file_ptr": (ci, [vp, vp, u64]),
+        "xsg_fileset_get_u64": (ci, [vp, u64, u64, _u64p]),
+        "xsg_fileset_get_line": (ci, [vp, u64, C.POINTER(C.c_char_p), _u64p]),
+        "xsg_fileset_destroy": (None, [vp]),
         "xsg_job_opts_init": (None, [C.POINTER(JobOpts)]),
         "xsg_job_start": (ci, [C.c_char_p, sz, C.c_char_p, C.c_char_p, C.POINTER(JobOpts), C.POINTER(vp)]),
         "xsg_job_join": (ci, [vp]),
@@ -241,7 +258,9 @@ EXPORTS = ["xsg_abi_version", "xsg_strerror", "xsg_last_error", "xsg_device_coun
            "xsg_count_literals_csr_async", "xsg_set_literals_opts", "xsg_host_searcher_create_list_opts",
            "xsg_literal_counter_create_opts", "xsg_job_start_list", "xsg_find_literals", "xsg_result_literal_hits",
            "xsg_find_literals_async", "xsg_literal_finder_create_opts", "xsg_literal_finder_find",
-           "xsg_literal_finder_destroy"]
+           "xsg_literal_finder_destroy", "xsg_result_chunk_ptr", "xsg_fileset_opts_init", "xsg_fileset_start",
+           "xsg_fileset_wait", "xsg_fileset_join", "xsg_fileset_status", "xsg_fileset_counts", "xsg_fileset_file_ptr",
+           "xsg_fileset_get_u64", "xsg_fileset_get_line", "xsg_fileset_destroy"]
 
 
 def _check(rc):
@@ -584,6 +603,16 @@ class Shard:
         _check(self._lib.xsg_result_context_edges(self.h, out.ctypes.data, self.nchunks))
         return out
 
+    def result_chunk_ptr(self, with_bytes: bool = False):
+        """after a list search: chunk_ptr uint64[nchunks + 1] (xsg_result_chunk_ptr) -- the entries
+        [chunk_ptr[c], chunk_ptr[c + 1]) of the result are chunk c's.  with_bytes (after LINES / MATCHES):
+        (chunk_ptr, byte_ptr), byte_ptr[c] where chunk c's bytes begin in the packed bytes."""
+        chunk_ptr = np.zeros(self.nchunks + 1, dtype=np.uint64)
+        byte_ptr = np.zeros(self.nchunks + 1, dtype=np.uint64) if with_bytes else None
+        _check(self._lib.xsg_result_chunk_ptr(self.h, C.c_void_p(chunk_ptr.ctypes.data), chunk_ptr.size,
+                                              C.c_void_p(byte_ptr.ctypes.data) if with_bytes else None))
+        return (chunk_ptr, byte_ptr) if with_bytes else chunk_ptr
+
     def search_u64_view(self, mode: int) -> np.ndarray:
         """like search_u64, but the array is a VIEW of the shard's pinned result buffer: valid until the next search"""
         n = C.c_uint64(0)
@@ -855,6 +884,93 @@ def meta_write(path: str, meta_out: str, data_out: str | None = None, compressio
                chunk_bytes: int = 16 << 20, mapping_gap: int = 500, hc: bool = False):
     _check(load().xsg_meta_write(os.fsencode(path), os.fsencode(meta_out), os.fsencode(data_out) if data_out else None,
                                  compression, chunk_bytes, mapping_gap, 1 if hc else 0))
+
+
+class FileSet:
+    """A LIST of files searched as the chunks of a few bindings (xsg_fileset_*): file f's result is what a search of
+    that file alone reports.  Returns at once; results are published per file in path order.  Iterating yields
+    (path, status, result) per file as it is published."""
+
+    def __init__(self, pattern: bytes, paths, mode: int, flags: int = 0, device: int = 0, num_readers: int = 0,
+                 batch_bytes: int = 0, chunk_bytes: int = 0, pattern_is_list: bool = False, list_flags: int = 0):
+        self._lib = load()
+        self.h = None
+        self.mode = mode
+        self.paths = [os.fsencode(p) for p in paths]
+        o = FileSetOpts()
+        self._lib.xsg_fileset_opts_init(C.byref(o))
+        o.mode, o.pattern_flags, o.device, o.num_readers = mode, flags, device, num_readers
+        o.batch_bytes, o.chunk_bytes = batch_bytes, chunk_bytes
+        o.pattern_is_list, o.list_flags = (1 if pattern_is_list or list_flags else 0), list_flags
+        arr = (C.c_char_p * max(len(self.paths), 1))(*self.paths)
+        h = C.c_void_p()
+        _check(self._lib.xsg_fileset_start(pattern, len(pattern), arr, len(self.paths), C.byref(o), C.byref(h)))
+        self.h = h
+
+    def __len__(self):
+        return len(self.paths)
+
+    def wait(self, file_index: int):
+        """blocks until file `file_index` is published or the set has finished -> (files published, finished)"""
+        done, fin = C.c_uint64(0), C.c_int(0)
+        _check(self._lib.xsg_fileset_wait(self.h, file_index, C.byref(done), C.byref(fin)))
+        return int(done.value), bool(fin.value)
+
+    def join(self):
+        _check(self._lib.xsg_fileset_join(self.h))
+        return self
+
+    def status(self) -> np.ndarray:
+        out = np.zeros(len(self.paths), dtype=np.int32)
+        _check(self._lib.xsg_fileset_status(self.h, C.c_void_p(out.ctypes.data), out.size))
+        return out
+
+    def counts(self) -> np.ndarray:
+        """per file: the count (count tags) or the number of its entries (list tags)"""
+        out = np.zeros(len(self.paths), dtype=np.uint64)
+        _check(self._lib.xsg_fileset_counts(self.h, C.c_void_p(out.ctypes.data), out.size))
+        return out
+
+    def file_ptr(self) -> np.ndarray:
+        out = np.zeros(len(self.paths) + 1, dtype=np.uint64)
+        _check(self._lib.xsg_fileset_file_ptr(self.h, C.c_void_p(out.ctypes.data), out.size))
+        return out
+
+    def _entries(self, lo: int, hi: int):
+        if self.mode in (LINES, MATCHES):
+            out, d, n = [], C.c_char_p(), C.c_uint64(0)
+            for k in range(lo, hi):
+                _check(self._lib.xsg_fileset_get_line(self.h, k, C.byref(d), C.byref(n)))
+                out.append(C.string_at(d, n.value))
+            return out
+        out = np.zeros(hi - lo, dtype=np.uint64)
+        _check(self._lib.xsg_fileset_get_u64(self.h, lo, hi - lo, out.ctypes.data_as(_u64p)))
+        return out
+
+    def result(self, file_index: int):
+        """file `file_index`'s result (waits for it): an int for the count tags, a uint64 array for the uint64 list tags,
+        a list of bytes for LINES / MATCHES"""
+        self.wait(file_index)
+        if self.mode in (COUNT_MATCHES, COUNT_LINES):
+            return int(self.counts()[file_index])
+        fp = self.file_ptr()
+        return self._entries(int(fp[file_index]), int(fp[file_index + 1]))
+
+    def __iter__(self):
+        for f in range(len(self.paths)):
+            self.wait(f)
+            yield os.fsdecode(self.paths[f]), int(self.status()[f]), self.result(f)
+
+    def close(self):
+        if self.h:
+            self._lib.xsg_fileset_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class Job:
