@@ -1,10 +1,10 @@
 // device_double.cpp -- TEST INFRASTRUCTURE ONLY (never linked into the product).
 //
-// A stand-in for the GPU below x-search_amd/csrc/xsg_file.cpp so that the HOST pipeline -- reader threads, the pinned
+// A stand-in for the GPU below x-search_amd/csrc/xsg_job.cpp and xsg_hostsearch.cpp so that the HOST pipeline -- reader threads, the pinned
 // buffer queue, device workers, ordered publication, the blocking result cursor (what replaces the reference's
 // include/xsearch/Searcher.h:100-120 and ResultTypes.h:48-60) -- runs under ThreadSanitizer and AddressSanitizer on a
 // box without a GPU (the reference keeps such builds: Makefile:30-38).  It provides
-//   * the handful of HIP runtime entry points xsg_file.cpp calls, over plain host memory ("device" = malloc,
+//   * the handful of HIP runtime entry points those files call, over plain host memory ("device" = malloc,
 //     hipMemcpyAsync = memcpy, streams are synchronous), and
 //   * the chunk-level C ABI of xsg_ctx / xsg_pattern / xsg_shard / xsg_count / xsg_list.cpp (xsg_ctx_*, xsg_shard_*, xsg_count*, xsg_search, xsg_result_*), answered by
 //     the CPU oracle (oracle/xs_oracle.c, linked from tests/ only).

@@ -1,5 +1,6 @@
-// pipeline_sanitize.cpp -- the host pipeline (x-search_amd/csrc/xsg_file.cpp: readers -> pinned queue -> device
-// workers -> ordered publication) and the blocking result iterator of include/xsearch/xsearch.h under ThreadSanitizer /
+// pipeline_sanitize.cpp -- the host pipeline (x-search_amd/csrc/xsg_job.cpp: readers -> pinned queue -> device
+// workers -> ordered publication; xsg_meta.cpp: plans, metafiles, codecs), the host-memory seam (xsg_hostsearch.cpp over
+// xsg_stage.h) and the blocking result iterator of include/xsearch/xsearch.h under ThreadSanitizer /
 // AddressSanitizer, on a box without a GPU: the device is tests/cpp/device_double.cpp (oracle-backed; test
 // infrastructure).  The reference keeps such builds for its own pipeline (Makefile:30-38; the iterator they would
 // exercise is include/xsearch/ResultTypes.h:48-60, the worker loop include/xsearch/Searcher.h:100-120).
@@ -7,9 +8,11 @@
 // Cases: (1) every tag, join + live iteration, 1..4 workers x 1..4 readers, results equal to a single-threaded pass;
 // (2) several jobs at once on the shared slot / buffer pools; (3) handles destroyed while the search is running and
 // while a consumer thread is blocked in the iterator's wait; (4) a consumer that stops early; (5) a metafile job with the
-// built-in LZ4 codec; (6) the XS_DEVICES fan-out with the host-side sum.
+// built-in LZ4 codec; (6) the XS_DEVICES fan-out with the host-side sum; (7) the host-memory seam: four threads on a
+// searcher of two slots, chunks that fit the staging block, grow it twice and reuse it, results equal to case (1)'s.
 #include <xsearch/xsearch.h>
 
+#include <algorithm>
 #include <atomic>
 #include <cstdio>
 #include <cstdlib>
@@ -70,7 +73,7 @@ int main(int argc, char** argv) {
   const std::string file = dir + "/xsg_sanitize_corpus.txt";
   // small chunks so that a few MB make dozens of them: the queues turn over many times
   setenv("XS_CHUNK_BYTES", "65536", 1);
-  make_corpus(file, 3u << 20, 1234);
+  const std::string text = make_corpus(file, 3u << 20, 1234);
   const std::string pat = "Sherlock";
 
   // ---- (1) every tag against the single-threaded pass
@@ -161,6 +164,69 @@ int main(int argc, char** argv) {
     CHECK(h->num_devices() == 2 && !h->reduced_over_rccl());
     CHECK(sorted(joined<xs::match_byte_offsets>(pat, file, 2, 2)) == m1);
     unsetenv("XS_DEVICES");
+  }
+
+  // ---- (7) the host-memory seam: prefixes of the corpus through xsg_host_*, against case (1) restricted to the prefix
+  {
+    const long live_before = xsg_double_live_allocations();
+    xsg_host_searcher* hs = nullptr;
+    CHECK(xsg_host_searcher_create(0, pat.data(), pat.size(), 0, 2, &hs) == XSG_OK);
+    // 0 .. 17: around the 16-byte rounding of the block's size, too short to hold a match (so that where they cut a line
+    // decides nothing); then prefixes cut at a line start: the largest that fits the first block of 1 MiB, the first that
+    // does not (the block grows), the whole corpus (it grows again), and 17 again (the block is reused, never shrunk)
+    CHECK(!m1.empty() && m1[0] >= 32);
+    const uint64_t fits = (1u << 20) - 256;
+    uint64_t below = fits, above = fits;
+    while (below > 0 && text[below - 1] != '\n') --below;
+    while (text[above] != '\n') ++above;  // (the corpus ends in '\n')
+    ++above;
+    CHECK(below > 17 && below <= fits && above > fits && above < text.size());
+    const uint64_t lens[] = {0, 1, 15, 16, 17, below, above, text.size(), 17};
+    std::atomic<int> wrong{0};
+    auto run = [&] {
+      for (const uint64_t len : lens) {
+        const uint64_t nm = (uint64_t)(std::lower_bound(m1.begin(), m1.end(), len) - m1.begin());  // matches that start in the prefix
+        const uint64_t nl = (uint64_t)(std::lower_bound(l1.begin(), l1.end(), len) - l1.begin());  // ... and matching lines
+        for (int skip = 0; skip < 2; ++skip) {
+          uint64_t cnt = ~0ull;
+          wrong += xsg_host_count(hs, text.data(), len, skip, &cnt) != XSG_OK || cnt != (skip ? nl : nm);
+        }
+        const uint32_t modes[] = {XSG_MATCH_BYTE_OFFSETS, XSG_LINE_BYTE_OFFSETS, XSG_LINE_INDICES};
+        const uint64_t* const wants[] = {m1.data(), l1.data(), i1.data()};
+        for (int k = 0; k < 3; ++k) {
+          uint64_t* out = nullptr;
+          uint64_t n = ~0ull;
+          if (xsg_host_offsets(hs, modes[k], text.data(), len, &out, &n) != XSG_OK) {
+            ++wrong;
+            continue;
+          }
+          wrong += n != (k ? nl : nm) || (n && std::memcmp(out, wants[k], 8 * n) != 0);
+          xsg_free(out);
+        }
+        uint64_t* lengths = nullptr;
+        char* bytes = nullptr;
+        uint64_t n = ~0ull, nbytes = 0;
+        if (xsg_host_lines(hs, text.data(), len, &lengths, &bytes, &n, &nbytes) != XSG_OK) {
+          ++wrong;
+          continue;
+        }
+        bool same = n == nl;
+        uint64_t at = 0;
+        for (uint64_t i = 0; same && i < n; ++i) {
+          same = at + lengths[i] <= nbytes && s1[i] == std::string(bytes + at, lengths[i]);
+          at += lengths[i];
+        }
+        wrong += !same || at != nbytes;
+        xsg_free(lengths);
+        xsg_free(bytes);
+      }
+    };
+    std::vector<std::thread> ts;
+    for (int t = 0; t < 4; ++t) ts.emplace_back(run);
+    for (auto& t : ts) t.join();
+    CHECK(wrong == 0);
+    xsg_host_searcher_destroy(hs);
+    CHECK(xsg_double_live_allocations() == live_before);
   }
   std::remove(file.c_str());
   if (g_fail) {

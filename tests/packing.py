@@ -320,8 +320,8 @@ def hostility(oracle, kind, packed: Packed, blocks, max_len=5000) -> dict:
     return out
 
 
-# ---- the pipeline: one device buffer reused from chunk to chunk (x-search_amd/csrc/xsg_file.cpp: the device workers
-# and host_stage copy exactly `length` bytes and bind capacity = round_up16(length) + 256)
+# ---- the pipeline: one device buffer reused from chunk to chunk (x-search_amd/csrc/xsg_job.cpp: the device workers,
+# and xsg_stage.h: stage, copy exactly `length` bytes and bind capacity = round_up16(length) + 256)
 PIPELINE_PATTERNS = [(b"street\nthe", 0, False), (b"that", 0, True), (b"colou?r", RX, True), (b"t.e", RX, True)]  # (.., line tags)
 PIPELINE_CHUNK = 4096
 PIPELINE_LONG = [12013, 12010, 12007, 12004]  # each ends inside the pad of the next: its '\n' stays behind the next one's end

@@ -128,7 +128,7 @@ def _meta_bytes(ctype, records):
 ])
 def test_job_start_refuses_a_malformed_metafile(tmp_path, name, ctype, records, data_len):
     """Every metafile record is validated before a buffer is sized from it or a byte is read through it
-    (x-search_amd/csrc/xsg_file.cpp, job_start_impl); the file checks run before the device check, so this holds
+    (x-search_amd/csrc/xsg_job.cpp, job_start_impl); the file checks run before the device check, so this holds
     on a host without a GPU too."""
     data = tmp_path / f"{name}.txt"
     data.write_bytes(b"a line of text\n" * (data_len // 15 + 1))

@@ -1,5 +1,6 @@
 """The threaded host code under ThreadSanitizer and AddressSanitizer (the reference keeps such builds for its pipeline:
-Makefile:30-38).  x-search_amd/csrc/xsg_file.cpp (reader -> pinned queue -> device worker -> ordered publication) and
+Makefile:30-38).  x-search_amd/csrc/xsg_job.cpp (reader -> pinned queue -> device worker -> ordered publication; with
+xsg_meta.cpp and the host-memory seam of xsg_hostsearch.cpp) and
 the blocking iterator of include/xsearch/xsearch.h (reference: include/xsearch/ResultTypes.h:48-60) are compiled with
 g++ -fsanitize=... against tests/cpp/device_double.cpp, an oracle-backed stand-in for the GPU (test infrastructure;
 the product library has no CPU path), and run the concurrent-jobs / early-destroy / live-iteration cases of

@@ -1,4 +1,4 @@
-// xsg_context.h -- XSG_FLAG_CONTEXT across the chunks of one text: what the file pipeline (xsg_file.cpp) needs to make a
+// xsg_context.h -- XSG_FLAG_CONTEXT across the chunks of one text: what the file pipeline (xsg_job.cpp) needs to make a
 // job's result the context of the whole searched range, however the chunker cut it.  Host only, no HIP, no library:
 // tests/cpp/context_stitch.cpp drives it alone.
 //

@@ -78,8 +78,7 @@ void xsg::sketch_fields(const xsg_shard* s, ScanArgs* a) {
   }
   a->sk_n = used;
   a->sketch = s->d_sketch.as<uint32_t>();
-  const char* g = XSG_TOGGLE("XSG_GATE_GRID");
-  a->gate_grid = g && atoll(g) > 0 ? (uint32_t)std::min<long long>(atoll(g), 1 << 30) : 0u;
+  a->gate_grid = XSG_TOGGLE_GRID("XSG_GATE_GRID");
   a->sk_pat = a->pat.d_pat;
   a->sk_koff = first;
 }

@@ -6,8 +6,6 @@
 // xsg_result_literals_csr, xsg_count_literals_csr_async): a count pass, a prefix sum of the rows' lengths and a fill pass.
 // Last the occurrences themselves (xsg_find_literals, xsg_result_literal_hits, xsg_find_literals_async): a count pass per
 // 4 KiB wave span, a prefix sum over the spans and a fill pass of (position, literal) entries.
-#include <algorithm>
-#include <cstdlib>
 #include <cstring>
 
 #include "xsg_host.h"
@@ -72,6 +70,13 @@ extern "C" int xsg_count_literals_async(xsg_shard* s, void* stream, uint64_t* d_
 }
 
 // ---- the chunks x literals matrix -------------------------------------------------------------------------------------------
+// the touched list of DESIGN.md 3.5f and its A/B switch (XSG_LITMATRIX_TOUCHED=0: every flush sweeps the histogram), of the
+// dense form and the CSR form alike
+static bool litmatrix_touched() {
+  const char* t = XSG_TOGGLE("XSG_LITMATRIX_TOUCHED");
+  return !(t && *t == '0');
+}
+
 static int count_literals_chunks_args(xsg_shard* s, const uint64_t* counts, uint64_t cap_words, const uint64_t* chunks_with,
                                       uint64_t cap_literals) {
   // (count_literals_args' refusals; its room check is the matrix's own here)
@@ -98,13 +103,9 @@ int xsg::enqueue_count_literals_chunks(xsg_shard* s, hipStream_t st, uint64_t* d
   l.chunks_with = reinterpret_cast<unsigned long long*>(d_chunks_with);
   l.nlits = c->set_count;
   l.idx_off = c->set_idx_off;
-  // the touched list of DESIGN.md 3.5f and its A/B switch (XSG_LITMATRIX_TOUCHED=0: every flush sweeps the histogram)
-  const char* t = XSG_TOGGLE("XSG_LITMATRIX_TOUCHED");
-  l.touched = !(t && *t == '0');
+  l.touched = litmatrix_touched();
   // tests: a grid of a few workgroups on a dozen tiles (never more workgroups than tiles: litmatrix_grid)
-  const char* g = XSG_TOGGLE("XSG_LITMATRIX_GRID");
-  const uint32_t forced = g && atoll(g) > 0 ? (uint32_t)std::min<long long>(atoll(g), 1 << 30) : 0u;
-  HIP_TRY(launch_set_count_literals_chunks(a, l, forced, st));
+  HIP_TRY(launch_set_count_literals_chunks(a, l, XSG_TOGGLE_GRID("XSG_LITMATRIX_GRID"), st));
   return XSG_OK;
 }
 
@@ -142,6 +143,58 @@ extern "C" int xsg_count_literals_chunks_async(xsg_shard* s, void* stream, uint6
 
 extern "C" uint32_t xsg_literals_chunks_touched_capacity(void) { return kLitTouched; }
 
+// ---- a kept ragged result (xsg_objects.h: KeptRagged): what the synchronous CSR and occurrence forms share -----------------------
+// The one size such a form fetches, ptr[n]: it sizes the two entry arrays and the mirror exactly.  `async_call`: where the refusal sends the caller.
+static int kept_size(xsg_shard* s, KeptRagged& k, const uint64_t* d_ptr, uint64_t n, const char* async_call, DevBuf& d_words8, DevBuf& d_words4) {
+  xsg_ctx* c = s->ctx;
+  uint64_t total = 0;
+  HIP_TRY(hipMemcpyAsync(&total, d_ptr + n, 8, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  s->table_pending = false;
+  if (total > (1ull << 28))
+    return fail(XSG_ENOTSUP, "a result of %llu entries is more than the synchronous form keeps (2^28 entries): use "
+                "%s with device memory of the caller's", (unsigned long long)total, async_call);
+  const size_t bytes = 8 * (size_t)(n + 1) + 12 * (size_t)total;
+  k.h.trim(bytes);  // (what a far larger earlier result left page-locked)
+  XSG_TRY(d_words8.ensure(8 * (size_t)total));
+  XSG_TRY(d_words4.ensure(4 * (size_t)total));
+  XSG_TRY(k.h.ensure(bytes));
+  k.rows = n;
+  k.total = total;
+  return XSG_OK;
+}
+// the copies into the mirror on `st`: the pointer words (d_ptr, or null), the entries (both arrays, or null)
+static int kept_mirror(const KeptRagged& k, hipStream_t st, const uint64_t* d_ptr, const void* d_words8, const void* d_words4) {
+  uint8_t* const h = k.h.as<uint8_t>();
+  const size_t ptr_bytes = 8 * (size_t)(k.rows + 1), bytes8 = 8 * (size_t)k.total;
+  if (d_ptr) HIP_TRY(hipMemcpyAsync(h, d_ptr, ptr_bytes, hipMemcpyDeviceToHost, st));
+  if (d_words8) HIP_TRY(hipMemcpyAsync(h + ptr_bytes, d_words8, bytes8, hipMemcpyDeviceToHost, st));
+  if (d_words8) HIP_TRY(hipMemcpyAsync(h + ptr_bytes + bytes8, d_words4, 4 * (size_t)k.total, hipMemcpyDeviceToHost, st));
+  return XSG_OK;
+}
+
+// The read-out of a kept result.  `call` produced it; `ptr_name` its pointer array, `pair_name` its two entry arrays.
+static int kept_read(const KeptRagged& k, const char* call, const char* ptr_name, const char* pair_name, uint64_t* ptr, uint64_t cap_rows,
+                     void* words8, void* words4, uint64_t cap_entries) {
+  if (!k.valid)
+    return fail(XSG_ESTATE, "no result of %s is kept: none was run on this binding, or a rebind or invalidate dropped it", call);
+  if (!ptr) return fail(XSG_EINVAL, "%s is null", ptr_name);
+  if (cap_rows < k.rows + 1)
+    return fail(XSG_EINVAL, "room for %llu %s words, %llu chunks need %llu", (unsigned long long)cap_rows, ptr_name,
+                (unsigned long long)k.rows, (unsigned long long)k.rows + 1);
+  if ((words8 == nullptr) != (words4 == nullptr)) return fail(XSG_EINVAL, "%s go together: both, or neither for %s alone", pair_name, ptr_name);
+  if (words8 && cap_entries < k.total)
+    return fail(XSG_EINVAL, "room for %llu entries, the result holds %llu", (unsigned long long)cap_entries, (unsigned long long)k.total);
+  const size_t ptr_bytes = 8 * (size_t)(k.rows + 1), bytes8 = 8 * (size_t)k.total;
+  const uint8_t* const h = k.h.as<uint8_t>();
+  memcpy(ptr, h, ptr_bytes);
+  if (words8 && k.total) {
+    memcpy(words8, h + ptr_bytes, bytes8);
+    memcpy(words4, h + ptr_bytes + bytes8, 4 * (size_t)k.total);
+  }
+  return XSG_OK;
+}
+
 // ---- the matrix in CSR form ---------------------------------------------------------------------------------------------------
 // count_literals_args' refusals (its room checks are the sparse form's own, in the callers)
 static int count_literals_csr_args(xsg_shard* s) {
@@ -164,9 +217,7 @@ static int csr_count_rows(xsg_shard* s, hipStream_t st, uint64_t* d_row_ptr, Csr
   if (s->table_pending && st != c->stream) HIP_TRY(hipStreamWaitEvent(st, s->table_ev, 0));
   const uint64_t n = s->chunks.size();
   k->a = scan_args(s);
-  const char* g = XSG_TOGGLE("XSG_LITMATRIX_GRID");
-  const uint32_t forced = g && atoll(g) > 0 ? (uint32_t)std::min<long long>(atoll(g), 1 << 30) : 0u;
-  k->grid = set_litcsr_grid(k->a, c->set_count, forced);
+  k->grid = set_litcsr_grid(k->a, c->set_count, XSG_TOGGLE_GRID("XSG_LITMATRIX_GRID"));
   const size_t seam_bytes = 8 * (size_t)k->grid * c->set_count;  // (at most 64 MiB: kLitCsrSeamWords)
   XSG_TRY(s->d_csr_row_nnz.ensure(4 * (size_t)n));
   XSG_TRY(s->d_csr_tmp.ensure(8 * (size_t)scan_tmp_elems(n)));
@@ -180,9 +231,7 @@ static int csr_count_rows(xsg_shard* s, hipStream_t st, uint64_t* d_row_ptr, Csr
   l.nchunks = n;
   l.nlits = c->set_count;
   l.idx_off = c->set_idx_off;
-  // the touched list and its A/B switch, as for the dense form (XSG_LITMATRIX_TOUCHED=0: every flush sweeps the histogram)
-  const char* t = XSG_TOGGLE("XSG_LITMATRIX_TOUCHED");
-  l.touched = !(t && *t == '0');
+  l.touched = litmatrix_touched();
   HIP_TRY(launch_set_count_literals_csr(k->a, l, k->grid, false, st));
   HIP_TRY(launch_exclusive_scan_u32(l.row_nnz, d_row_ptr, n, s->d_csr_tmp.as<uint64_t>(), st));
   return XSG_OK;
@@ -213,60 +262,26 @@ extern "C" int xsg_count_literals_csr(xsg_shard* s, uint64_t* nnz) {
   if (!nnz) return fail(XSG_EINVAL, "nnz is null");
   xsg_ctx* c = s->ctx;
   HIP_TRY(hipSetDevice(c->device));
-  s->csr_valid = false;
+  KeptRagged& kept = s->kept_csr;
+  kept.valid = false;
   const uint64_t n = s->chunks.size();
   XSG_TRY(s->d_csr_row_ptr.ensure(8 * (size_t)(n + 2)));  // row_ptr, then the status word
   uint64_t* const d_row_ptr = s->d_csr_row_ptr.as<uint64_t>();
   CsrCall k;
   XSG_TRY(csr_count_rows(s, c->stream, d_row_ptr, &k));
-  // the one size this form fetches: it sizes cols, vals and the mirror exactly
-  uint64_t total = 0;
-  HIP_TRY(hipMemcpyAsync(&total, d_row_ptr + n, 8, hipMemcpyDeviceToHost, c->stream));
+  XSG_TRY(kept_size(s, kept, d_row_ptr, n, "xsg_count_literals_csr_async", s->d_csr_vals, s->d_csr_cols));
+  XSG_TRY(csr_fill_rows(c->stream, &k, d_row_ptr, s->d_csr_cols.as<uint32_t>(), s->d_csr_vals.as<uint64_t>(), kept.total, d_row_ptr + n + 1));
+  XSG_TRY(kept_mirror(kept, c->stream, d_row_ptr, kept.total ? s->d_csr_vals.p : nullptr, s->d_csr_cols.p));
   HIP_TRY(hipStreamSynchronize(c->stream));
-  s->table_pending = false;
-  if (total > (1ull << 28))
-    return fail(XSG_ENOTSUP, "a result of %llu entries is more than the synchronous form keeps (2^28 entries): use "
-                "xsg_count_literals_csr_async with device memory of the caller's", (unsigned long long)total);
-  const size_t rp_bytes = 8 * (size_t)(n + 1), val_bytes = 8 * (size_t)total, col_bytes = 4 * (size_t)total;
-  s->h_csr.trim(rp_bytes + val_bytes + col_bytes);  // (what a far larger earlier result left page-locked)
-  XSG_TRY(s->d_csr_cols.ensure(col_bytes));
-  XSG_TRY(s->d_csr_vals.ensure(val_bytes));
-  XSG_TRY(s->h_csr.ensure(rp_bytes + val_bytes + col_bytes));
-  XSG_TRY(csr_fill_rows(c->stream, &k, d_row_ptr, s->d_csr_cols.as<uint32_t>(), s->d_csr_vals.as<uint64_t>(), total, d_row_ptr + n + 1));
-  uint8_t* const h = s->h_csr.as<uint8_t>();
-  HIP_TRY(hipMemcpyAsync(h, d_row_ptr, rp_bytes, hipMemcpyDeviceToHost, c->stream));
-  if (total) {
-    HIP_TRY(hipMemcpyAsync(h + rp_bytes, s->d_csr_vals.p, val_bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(h + rp_bytes + val_bytes, s->d_csr_cols.p, col_bytes, hipMemcpyDeviceToHost, c->stream));
-  }
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  s->csr_rows = n;
-  s->csr_nnz = total;
-  s->csr_valid = true;
-  *nnz = total;
+  kept.valid = true;
+  *nnz = kept.total;
   return XSG_OK;
 }
 
 extern "C" int xsg_result_literals_csr(xsg_shard* s, uint64_t* row_ptr, uint64_t cap_rows, uint32_t* cols, uint64_t* vals,
                                        uint64_t cap_entries) {
   if (!s) return fail(XSG_EINVAL, "shard is null");
-  if (!s->csr_valid)
-    return fail(XSG_ESTATE, "no result of xsg_count_literals_csr is kept: none was run on this binding, or a rebind or invalidate dropped it");
-  if (!row_ptr) return fail(XSG_EINVAL, "row_ptr is null");
-  if (cap_rows < s->csr_rows + 1)
-    return fail(XSG_EINVAL, "room for %llu row_ptr words, %llu chunks need %llu", (unsigned long long)cap_rows,
-                (unsigned long long)s->csr_rows, (unsigned long long)s->csr_rows + 1);
-  if ((cols == nullptr) != (vals == nullptr)) return fail(XSG_EINVAL, "cols and vals go together: both, or neither for row_ptr alone");
-  if (cols && cap_entries < s->csr_nnz)
-    return fail(XSG_EINVAL, "room for %llu entries, the result holds %llu", (unsigned long long)cap_entries, (unsigned long long)s->csr_nnz);
-  const size_t rp_bytes = 8 * (size_t)(s->csr_rows + 1), val_bytes = 8 * (size_t)s->csr_nnz;
-  const uint8_t* const h = s->h_csr.as<uint8_t>();
-  memcpy(row_ptr, h, rp_bytes);
-  if (cols && s->csr_nnz) {
-    memcpy(vals, h + rp_bytes, val_bytes);
-    memcpy(cols, h + rp_bytes + val_bytes, 4 * (size_t)s->csr_nnz);
-  }
-  return XSG_OK;
+  return kept_read(s->kept_csr, "xsg_count_literals_csr", "row_ptr", "cols and vals", row_ptr, cap_rows, vals, cols, cap_entries);
 }
 
 extern "C" int xsg_count_literals_csr_async(xsg_shard* s, void* stream, uint64_t* d_row_ptr, uint64_t cap_rows, uint32_t* d_cols,
@@ -302,8 +317,7 @@ static int find_count_spans(xsg_shard* s, hipStream_t st, uint64_t* d_chunk_ptr,
   XSG_TRY(s->d_find_off.ensure(8 * (size_t)(words + 1)));
   XSG_TRY(s->d_find_tmp.ensure(8 * (size_t)scan_tmp_elems(words)));
   // tests: a grid of a few workgroups on a dozen tiles (never more workgroups than tiles: set_litfind_grid)
-  const char* g = XSG_TOGGLE("XSG_LITFIND_GRID");
-  k->forced = g && atoll(g) > 0 ? (uint32_t)std::min<long long>(atoll(g), 1 << 30) : 0u;
+  k->forced = XSG_TOGGLE_GRID("XSG_LITFIND_GRID");
   LitFindArgs& f = k->f;
   f = LitFindArgs{};
   f.wave_occ = s->d_find_occ.as<uint32_t>();
@@ -338,60 +352,29 @@ extern "C" int xsg_find_literals(xsg_shard* s, uint64_t* total_out) {
   if (!total_out) return fail(XSG_EINVAL, "total is null");
   xsg_ctx* c = s->ctx;
   HIP_TRY(hipSetDevice(c->device));
-  s->find_valid = false;
+  KeptRagged& kept = s->kept_find;
+  kept.valid = false;
   const uint64_t n = s->chunks.size();
   XSG_TRY(s->d_find_ptr.ensure(8 * (size_t)(n + 1)));
   uint64_t* const d_chunk_ptr = s->d_find_ptr.as<uint64_t>();
   FindCall k;
   XSG_TRY(find_count_spans(s, c->stream, d_chunk_ptr, 0, nullptr, &k));
-  // the one size this form fetches: it sizes pos, lit and the mirror exactly
-  uint64_t total = 0;
-  HIP_TRY(hipMemcpyAsync(&total, d_chunk_ptr + n, 8, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  s->table_pending = false;
-  if (total > (1ull << 28))
-    return fail(XSG_ENOTSUP, "a result of %llu entries is more than the synchronous form keeps (2^28 entries): use "
-                "xsg_find_literals_async with device memory of the caller's", (unsigned long long)total);
-  const size_t cp_bytes = 8 * (size_t)(n + 1), pos_bytes = 8 * (size_t)total, lit_bytes = 4 * (size_t)total;
-  s->h_find.trim(cp_bytes + pos_bytes + lit_bytes);  // (what a far larger earlier result left page-locked)
-  XSG_TRY(s->d_find_pos.ensure(pos_bytes));
-  XSG_TRY(s->d_find_lit.ensure(lit_bytes));
-  XSG_TRY(s->h_find.ensure(cp_bytes + pos_bytes + lit_bytes));
-  uint8_t* const h = s->h_find.as<uint8_t>();
-  HIP_TRY(hipMemcpyAsync(h, d_chunk_ptr, cp_bytes, hipMemcpyDeviceToHost, c->stream));
-  if (total) {
-    XSG_TRY(find_fill_spans(s, c->stream, &k, s->d_find_pos.as<uint64_t>(), s->d_find_lit.as<uint32_t>(), total));
-    HIP_TRY(hipMemcpyAsync(h + cp_bytes, s->d_find_pos.p, pos_bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(h + cp_bytes + pos_bytes, s->d_find_lit.p, lit_bytes, hipMemcpyDeviceToHost, c->stream));
+  XSG_TRY(kept_size(s, kept, d_chunk_ptr, n, "xsg_find_literals_async", s->d_find_pos, s->d_find_lit));
+  XSG_TRY(kept_mirror(kept, c->stream, d_chunk_ptr, nullptr, nullptr));
+  if (kept.total) {
+    XSG_TRY(find_fill_spans(s, c->stream, &k, s->d_find_pos.as<uint64_t>(), s->d_find_lit.as<uint32_t>(), kept.total));
+    XSG_TRY(kept_mirror(kept, c->stream, nullptr, s->d_find_pos.p, s->d_find_lit.p));
   }
   HIP_TRY(hipStreamSynchronize(c->stream));
-  s->find_rows = n;
-  s->find_total = total;
-  s->find_valid = true;
-  *total_out = total;
+  kept.valid = true;
+  *total_out = kept.total;
   return XSG_OK;
 }
 
 extern "C" int xsg_result_literal_hits(xsg_shard* s, uint64_t* chunk_ptr, uint64_t cap_rows, uint64_t* pos, uint32_t* lit,
                                        uint64_t cap_entries) {
   if (!s) return fail(XSG_EINVAL, "shard is null");
-  if (!s->find_valid)
-    return fail(XSG_ESTATE, "no result of xsg_find_literals is kept: none was run on this binding, or a rebind or invalidate dropped it");
-  if (!chunk_ptr) return fail(XSG_EINVAL, "chunk_ptr is null");
-  if (cap_rows < s->find_rows + 1)
-    return fail(XSG_EINVAL, "room for %llu chunk_ptr words, %llu chunks need %llu", (unsigned long long)cap_rows,
-                (unsigned long long)s->find_rows, (unsigned long long)s->find_rows + 1);
-  if ((pos == nullptr) != (lit == nullptr)) return fail(XSG_EINVAL, "pos and lit go together: both, or neither for chunk_ptr alone");
-  if (pos && cap_entries < s->find_total)
-    return fail(XSG_EINVAL, "room for %llu entries, the result holds %llu", (unsigned long long)cap_entries, (unsigned long long)s->find_total);
-  const size_t cp_bytes = 8 * (size_t)(s->find_rows + 1), pos_bytes = 8 * (size_t)s->find_total;
-  const uint8_t* const h = s->h_find.as<uint8_t>();
-  memcpy(chunk_ptr, h, cp_bytes);
-  if (pos && s->find_total) {
-    memcpy(pos, h + cp_bytes, pos_bytes);
-    memcpy(lit, h + cp_bytes + pos_bytes, 4 * (size_t)s->find_total);
-  }
-  return XSG_OK;
+  return kept_read(s->kept_find, "xsg_find_literals", "chunk_ptr", "pos and lit", chunk_ptr, cap_rows, pos, lit, cap_entries);
 }
 
 extern "C" int xsg_find_literals_async(xsg_shard* s, void* stream, uint64_t* d_chunk_ptr, uint64_t cap_rows, uint64_t* d_pos,

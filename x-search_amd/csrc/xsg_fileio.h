@@ -1,4 +1,4 @@
-// xsg_fileio.h -- the file helpers shared by the host pipelines (xsg_file.cpp: one file per job; xsg_fileset.cpp: a list
+// xsg_fileio.h -- the file helpers shared by the host pipelines (xsg_meta.cpp, xsg_job.cpp: one file per job; xsg_fileset.cpp: a list
 // of files per set): open a regular file read-only, read exactly n bytes, and the CPUs the process may use.  Not installed.
 #pragma once
 #include <errno.h>

@@ -1,5 +1,5 @@
 // xsg_fileset.cpp -- a LIST of files searched as the chunks of a few bindings (include/xsg.h: xsg_fileset_*), the sibling
-// of the job pipeline of xsg_file.cpp, which searches ONE file as many chunks.  Host glue only: the plan of batches is
+// of the job pipeline of xsg_job.cpp, which searches ONE file as many chunks.  Host glue only: the plan of batches is
 // xsg_fileset.h's, the searches are xsg_count_chunks and xsg_search + xsg_result_chunk_ptr on one shard, and a file larger
 // than chunk_bytes goes through xsg_job_start[_list] unchanged.  No CPU search path.
 //
@@ -17,14 +17,10 @@
 
 #include "xsg_fileio.h"
 #include "xsg_fileset.h"
-#include "xsg_objects.h"
+#include "xsg_pipeline.h"
 
 using namespace xsg;
 namespace fsp = xsg_fileset_plan;
-
-static bool fs_string_mode(uint32_t m) { return m == XSG_LINES || m == XSG_MATCHES; }
-static bool fs_count_mode(uint32_t m) { return m == XSG_COUNT_MATCHES || m == XSG_COUNT_LINES; }
-static bool fs_match_mode(uint32_t m) { return m == XSG_COUNT_MATCHES || m == XSG_MATCH_BYTE_OFFSETS || m == XSG_MATCHES; }
 
 struct xsg_fileset {
   xsg_fileset_opts opts{};
@@ -153,11 +149,6 @@ static void stop_readers(xsg_fileset* fs) {
 }
 
 // ---- the device side ------------------------------------------------------------------------------------------------------
-static int set_pattern(xsg_fileset* fs) {
-  if (!fs->opts.pattern_is_list) return xsg_set_pattern(fs->ctx, fs->pattern.data(), fs->pattern.size(), fs->opts.pattern_flags);
-  return xsg_set_literals_opts(fs->ctx, fs->pattern.data(), fs->pattern.size(), fs->opts.pattern_flags, fs->opts.list_flags);
-}
-
 static int bind(xsg_fileset* fs, const xsg_chunk* chunks, uint64_t n) {
   if (!fs->shard) return xsg_shard_create(fs->ctx, fs->d_buf, fs->d_cap, chunks, n, &fs->shard);
   return xsg_shard_rebind(fs->shard, fs->d_buf, fs->d_cap, chunks, n);
@@ -166,7 +157,7 @@ static int bind(xsg_fileset* fs, const xsg_chunk* chunks, uint64_t n) {
 // one search of what is bound (n chunks), appended to `out`: its rows continue where out's rows stand
 static int search_bound(xsg_fileset* fs, uint64_t n, BatchResult& out) {
   const uint32_t mode = fs->opts.mode;
-  if (fs_count_mode(mode)) {
+  if (count_mode(mode)) {
     const size_t at = out.counts.size();
     out.counts.resize(at + n);
     const int r = xsg_count_chunks(fs->shard, mode, out.counts.data() + at, nullptr, n, nullptr);
@@ -175,12 +166,12 @@ static int search_bound(xsg_fileset* fs, uint64_t n, BatchResult& out) {
   }
   uint64_t total = 0;
   XSG_TRY(xsg_search(fs->shard, mode, &total));
-  std::vector<uint64_t> rows(n + 1), byte_rows(fs_string_mode(mode) ? n + 1 : 0);
+  std::vector<uint64_t> rows(n + 1), byte_rows(string_mode(mode) ? n + 1 : 0);
   XSG_TRY(xsg_result_chunk_ptr(fs->shard, rows.data(), n + 1, byte_rows.empty() ? nullptr : byte_rows.data()));
   const uint64_t row0 = out.rows.empty() ? 0 : out.rows.back();
   if (out.rows.empty()) out.rows.push_back(0);
   for (uint64_t i = 1; i <= n; ++i) out.rows.push_back(row0 + rows[i]);
-  if (!fs_string_mode(mode)) {
+  if (!string_mode(mode)) {
     const uint64_t* v = nullptr;
     uint64_t cnt = 0;
     XSG_TRY(xsg_result_u64_view(fs->shard, &v, &cnt));
@@ -220,12 +211,12 @@ static int search_batch(xsg_fileset* fs, const fsp::Batch& b, const uint8_t* hos
     if (r == XSG_OK) continue;
     if (r != XSG_ENOTSUP) return r;
     fs->status[fs->plan.items[b.first_item + i].file] = XSG_ENOTSUP;
-    if (fs_count_mode(fs->opts.mode)) {
+    if (count_mode(fs->opts.mode)) {
       out.counts.push_back(0);
     } else {  // an empty row
       if (out.rows.empty()) out.rows.push_back(0);
       out.rows.push_back(out.rows.back());
-      if (fs_string_mode(fs->opts.mode)) {
+      if (string_mode(fs->opts.mode)) {
         if (out.byte_rows.empty()) out.byte_rows.push_back(0);
         out.byte_rows.push_back(out.byte_rows.back());
       }
@@ -247,13 +238,13 @@ static void publish_empty(xsg_fileset* fs, uint64_t f) {
 static void publish_item(xsg_fileset* fs, uint64_t f, const BatchResult& r, uint64_t i, uint64_t rows) {
   const uint32_t mode = fs->opts.mode;
   std::lock_guard<std::mutex> g(fs->mu);
-  if (fs_count_mode(mode)) {
+  if (count_mode(mode)) {
     fs->counts[f] = r.counts[i];
     fs->file_ptr[f + 1] = fs->file_ptr[f];
   } else {
     const uint64_t lo = r.rows[i], hi = lo + rows;
     fs->counts[f] = hi - lo;
-    if (fs_string_mode(mode)) {
+    if (string_mode(mode)) {
       uint64_t at = r.byte_rows[i];
       for (uint64_t k = lo; k < hi; ++k) {
         fs->lines.emplace_back(r.bytes.data() + at, r.lens[k]);
@@ -296,28 +287,28 @@ static int run_large(xsg_fileset* fs, uint64_t f) {
   }
   uint64_t n = 0;
   int fin = 0;
-  if (fs_count_mode(mode)) {
+  if (count_mode(mode)) {
     r = xsg_job_total(j, &n);
   } else {
     r = xsg_job_poll(j, &n, &fin);
   }
   std::vector<uint64_t> vals;
-  if (r == XSG_OK && !fs_count_mode(mode) && !fs_string_mode(mode)) {
+  if (r == XSG_OK && !count_mode(mode) && !string_mode(mode)) {
     vals.resize(n);
     r = xsg_job_get_u64(j, 0, n, vals.data());
   }
   if (r == XSG_OK) {
     std::lock_guard<std::mutex> g(fs->mu);
     fs->counts[f] = n;
-    fs->file_ptr[f + 1] = fs->file_ptr[f] + (fs_count_mode(mode) ? 0 : n);
-    if (fs_string_mode(mode)) {
+    fs->file_ptr[f + 1] = fs->file_ptr[f] + (count_mode(mode) ? 0 : n);
+    if (string_mode(mode)) {
       for (uint64_t k = 0; k < n && r == XSG_OK; ++k) {
         const char* d = nullptr;
         uint64_t len = 0;
         r = xsg_job_get_line(j, k, &d, &len);
         if (r == XSG_OK) fs->lines.emplace_back(d, len);
       }
-    } else if (!fs_count_mode(mode)) {
+    } else if (!count_mode(mode)) {
       fs->values.insert(fs->values.end(), vals.begin(), vals.end());
     }
     if (r == XSG_OK) {
@@ -349,7 +340,7 @@ static int driver_body(xsg_fileset* fs) {
   HIP_TRY(hipSetDevice(fs->opts.device));
   if (!fs->plan.items.empty()) {  // (a set of large files only is its jobs: no context, no buffers of its own)
     XSG_TRY(xsg_ctx_create(fs->opts.device, &fs->ctx));
-    XSG_TRY(set_pattern(fs));
+    XSG_TRY(set_job_pattern(fs->ctx, fs->pattern, fs->opts.pattern_flags, fs->opts.pattern_is_list != 0, fs->opts.list_flags));
     // (a margin behind the last chunk: the scan reads whole 16-byte units, and an empty last file still needs an address)
     fs->d_cap = max_bytes + 256;
     if (hipMalloc(&fs->d_buf, fs->d_cap) != hipSuccess) return fail(XSG_ENOMEM, "hipMalloc(%llu) failed", (unsigned long long)fs->d_cap);
@@ -428,8 +419,8 @@ extern "C" void xsg_fileset_opts_init(xsg_fileset_opts* o) {
 
 static int check_pattern(const void* pattern, size_t plen, const xsg_fileset_opts& o) {
   const uint32_t flags = o.pattern_flags;
-  const bool line_mode = !fs_match_mode(o.mode);
-  const bool context = XSG_CONTEXT_BEFORE(flags) != 0 || XSG_CONTEXT_AFTER(flags) != 0;
+  const bool line_mode = !match_mode(o.mode);
+  const bool context = context_flags(flags);
   if (o.pattern_is_list) {
     xsg_literal_list info;
     XSG_TRY(xsg_literals_info(pattern, plen, flags, &info, nullptr));
@@ -478,7 +469,7 @@ extern "C" int xsg_fileset_start(const void* pattern, size_t plen, const char* c
   if (o.batch_bytes >= (1ull << 40)) return fail(XSG_EINVAL, "batch_bytes too large");
   if (o.num_readers < 0) return fail(XSG_EINVAL, "num_readers < 0");
   if (!pattern || plen == 0 || plen > XSG_MAX_PATTERN) return fail(XSG_EINVAL, "pattern must be 1..%u bytes", XSG_MAX_PATTERN);
-  if (o.list_flags & ~(XSG_LIST_WHOLE_WORDS | XSG_LIST_ALL_OF)) return fail(XSG_EINVAL, "unknown list flags 0x%x", o.list_flags);
+  XSG_TRY(check_list_flags(o.list_flags));
   if (o.list_flags && !o.pattern_is_list) return fail(XSG_EINVAL, "list_flags without pattern_is_list");
   XSG_TRY(check_pattern(pattern, plen, o));
   int ndev = 0;
@@ -550,7 +541,7 @@ extern "C" int xsg_fileset_counts(xsg_fileset* fs, uint64_t* counts, uint64_t ca
 
 extern "C" int xsg_fileset_file_ptr(xsg_fileset* fs, uint64_t* file_ptr, uint64_t cap_rows) {
   if (!fs) return fail(XSG_EINVAL, "file set is null");
-  if (fs_count_mode(fs->opts.mode)) return fail(XSG_ESTATE, "a count tag has no list: xsg_fileset_counts holds its results");
+  if (count_mode(fs->opts.mode)) return fail(XSG_ESTATE, "a count tag has no list: xsg_fileset_counts holds its results");
   const uint64_t n = fs->paths.size();
   if (cap_rows < n + 1 || !file_ptr) return fail(XSG_EINVAL, "room for %llu words, the set needs %llu", (unsigned long long)cap_rows, (unsigned long long)(n + 1));
   std::lock_guard<std::mutex> g(fs->mu);
@@ -560,7 +551,7 @@ extern "C" int xsg_fileset_file_ptr(xsg_fileset* fs, uint64_t* file_ptr, uint64_
 
 extern "C" int xsg_fileset_get_u64(xsg_fileset* fs, uint64_t first, uint64_t n, uint64_t* out) {
   if (!fs || (!out && n)) return fail(XSG_EINVAL, "null argument");
-  if (fs_count_mode(fs->opts.mode) || fs_string_mode(fs->opts.mode)) return fail(XSG_ESTATE, "not a uint64 list tag");
+  if (count_mode(fs->opts.mode) || string_mode(fs->opts.mode)) return fail(XSG_ESTATE, "not a uint64 list tag");
   std::lock_guard<std::mutex> g(fs->mu);
   if (first + n > fs->values.size() || first + n < first) return fail(XSG_EINVAL, "range beyond the available results");
   if (n) memcpy(out, fs->values.data() + first, 8 * n);
@@ -569,7 +560,7 @@ extern "C" int xsg_fileset_get_u64(xsg_fileset* fs, uint64_t first, uint64_t n, 
 
 extern "C" int xsg_fileset_get_line(xsg_fileset* fs, uint64_t index, const char** data, uint64_t* len) {
   if (!fs || !data || !len) return fail(XSG_EINVAL, "null argument");
-  if (!fs_string_mode(fs->opts.mode)) return fail(XSG_ESTATE, "not an XSG_LINES or XSG_MATCHES file set");
+  if (!string_mode(fs->opts.mode)) return fail(XSG_ESTATE, "not an XSG_LINES or XSG_MATCHES file set");
   std::lock_guard<std::mutex> g(fs->mu);
   if (index >= fs->lines.size()) return fail(XSG_EINVAL, "index beyond the available results");
   const std::string& s = fs->lines[index];

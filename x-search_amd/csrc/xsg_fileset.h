@@ -5,7 +5,7 @@
 // A file set searches a LIST of files in path order.  A file of at most chunk_bytes is ONE chunk of a batch: the batch is
 // one pinned buffer, the files lie in it at multiples of 16 bytes in path order, and the whole batch is bound and searched
 // as one shard.  A batch closes when the next small file would not fit batch_bytes or it holds kMaxBatchFiles files.  A
-// file larger than chunk_bytes is set aside (the job pipeline of xsg_file.cpp searches it); a file that cannot be read
+// file larger than chunk_bytes is set aside (the job pipeline of xsg_job.cpp searches it); a file that cannot be read
 // has no place at all.  Neither closes a batch: results are published per file in path order, whatever the cut.
 #pragma once
 #include <cstdint>

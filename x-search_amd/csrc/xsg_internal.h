@@ -1,5 +1,5 @@
 // xsg_internal.h -- shared between the HIP kernels (xsg_kernels.hip, xsg_list_kernels.hip, xsg_rx_kernels.hip) and the
-// C-ABI host code (through xsg_objects.h: xsg_ctx / xsg_pattern / xsg_shard / xsg_count / xsg_list.cpp, xsg_file.cpp).
+// C-ABI host code (through xsg_objects.h: xsg_ctx / xsg_pattern / xsg_shard / xsg_count / xsg_list.cpp, xsg_job.cpp).
 // Not part of the public boundary.
 #pragma once
 #include <hip/hip_runtime.h>

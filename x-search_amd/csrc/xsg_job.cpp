@@ -1,15 +1,11 @@
-// xsg_file.cpp -- the host pipeline behind xs::extern_search: chunk plans,
-// metafiles, reader/feeder threads, ordered result store.  C++ on the host (the
-// reference's pipeline is C++: include/xsearch/Searcher.h, tasks/readers.h,
-// ResultTypes.h); the scan itself always runs on the GPU through the shard API
-// of xsg_count.cpp / xsg_list.cpp -- there is no CPU search path in here.
+// xsg_job.cpp -- the host pipeline behind xs::extern_search (include/xsg.h: xsg_job_*): ONE file searched as the chunks of
+// its plan (xsg_meta.cpp).  Reader threads fill pinned buffers, device workers copy and scan them, an ordered store
+// publishes the chunks' results, with the context of XSG_FLAG_CONTEXT stitched across their seams.  C++ on the host (the
+// reference's pipeline is C++: include/xsearch/Searcher.h, tasks/readers.h, ResultTypes.h); the scan itself always runs on
+// the GPU through the shard API of xsg_count.cpp / xsg_list.cpp -- there is no CPU search path in here.  Last the sum over
+// the jobs of several devices (xsg_jobs_reduce_total): it reads a job's device, so it stays beside the struct.
 #include <ctype.h>
-#include <dlfcn.h>
-#include <fcntl.h>
 #include <pthread.h>
-#include <sched.h>
-#include <sys/stat.h>
-#include <unistd.h>
 
 #include <atomic>
 #include <chrono>
@@ -23,8 +19,9 @@
 
 #include "xsg_context.h"
 #include "xsg_fileio.h"
-#include "xsg_lz4.h"
-#include "xsg_objects.h"
+#include "xsg_meta.h"
+#include "xsg_pipeline.h"
+#include "xsg_stage.h"
 
 using namespace xsg;
 using Clock = std::chrono::steady_clock;
@@ -33,394 +30,7 @@ static double seconds_since(Clock::time_point t0) {
   return std::chrono::duration<double>(Clock::now() - t0).count();
 }
 
-extern "C" void xsg_free(void* p) { free(p); }
-
-// No C++ exception may cross the C ABI: host-side containers sized from file contents can throw.
-template <typename F>
-static int guarded(const char* what, F&& f) {
-  try {
-    return f();
-  } catch (const std::bad_alloc&) {
-    return fail(XSG_ENOMEM, "%s: host allocation failed", what);
-  } catch (const std::exception& e) {
-    return fail(XSG_EIO, "%s: %s", what, e.what());
-  }
-}
-
-// ---------------------------------------------------------------------------
-// file helpers
-// ---------------------------------------------------------------------------
-// (open_ro, pread_full and cpu_budget live in xsg_fileio.h: xsg_fileset.cpp reads files too)
-
-// ---------------------------------------------------------------------------
-// chunk plan of a plain file: >= target bytes, extended to just past the next '\n'
-// (the layout of the reference's fixtures: SURVEY 5.1)
-// ---------------------------------------------------------------------------
-static int plan_plain(int fd, uint64_t size, uint64_t target, std::vector<xsg_file_chunk>& out) {
-  if (target < 1) target = 1;
-  uint64_t pos = 0;
-  std::vector<uint8_t> probe(1 << 16);
-  while (pos < size) {
-    uint64_t end = pos + target;
-    if (end >= size) {
-      end = size;
-    } else {
-      // first '\n' at or after end-1
-      uint64_t q = end - 1;
-      bool found = false;
-      while (q < size) {
-        const uint64_t n = std::min<uint64_t>(probe.size(), size - q);
-        XSG_TRY(pread_full(fd, probe.data(), n, q));
-        const void* hit = memchr(probe.data(), '\n', n);
-        if (hit) {
-          end = q + (uint64_t)((const uint8_t*)hit - probe.data()) + 1;
-          found = true;
-          break;
-        }
-        q += n;
-      }
-      if (!found) end = size;
-    }
-    xsg_file_chunk c{};
-    c.original_offset = pos;
-    c.actual_offset = pos;
-    c.original_size = end - pos;
-    c.actual_size = end - pos;
-    c.first_line = XSG_LINE_BASE_AUTO;
-    c.n_mappings = 0;
-    out.push_back(c);
-    pos = end;
-  }
-  return XSG_OK;
-}
-
-static int to_malloc(const std::vector<xsg_file_chunk>& v, xsg_file_chunk** chunks, uint64_t* n) {
-  *n = v.size();
-  *chunks = static_cast<xsg_file_chunk*>(malloc(sizeof(xsg_file_chunk) * std::max<size_t>(v.size(), 1)));
-  if (!*chunks) return fail(XSG_ENOMEM, "host allocation failed");
-  if (!v.empty()) memcpy(*chunks, v.data(), sizeof(xsg_file_chunk) * v.size());
-  return XSG_OK;
-}
-
-extern "C" int xsg_plan_chunks(const char* file_path, uint64_t target_bytes, xsg_file_chunk** chunks, uint64_t* n) {
-  if (!chunks || !n) return fail(XSG_EINVAL, "null output");
-  int fd;
-  uint64_t size;
-  XSG_TRY(open_ro(file_path, &fd, &size));
-  return guarded("xsg_plan_chunks", [&]() -> int {
-    std::vector<xsg_file_chunk> v;
-    int r;
-    try {
-      r = plan_plain(fd, size, target_bytes ? target_bytes : (16u << 20), v);
-    } catch (...) {
-      close(fd);
-      throw;
-    }
-    close(fd);
-    if (r != XSG_OK) return r;
-    return to_malloc(v, chunks, n);
-  });
-}
-
-// ---------------------------------------------------------------------------
-// metafile (little-endian, packed):
-//   int32 compression_type, then per chunk
-//   u64 original_offset, actual_offset, original_size, actual_size, n, n x {u64 byte offset, u64 line index}
-// ---------------------------------------------------------------------------
-static int read_meta(const char* path, int32_t* compression, std::vector<xsg_file_chunk>& chunks,
-                     std::vector<uint64_t>* mappings) {
-  // The mapping tables are ~3 % of the corpus size (one entry per >= 500 bytes): a
-  // search only needs the 40-byte record headers and each chunk's first entry, so
-  // the file is walked with small preads and the tables are read only on request.
-  int fd;
-  uint64_t size;
-  XSG_TRY(open_ro(path, &fd, &size));
-  struct Closer {
-    int fd;
-    ~Closer() { close(fd); }
-  } closer{fd};
-  if (size < 4) return fail(XSG_EIO, "metafile '%s' is too short", path);
-  int32_t ct;
-  XSG_TRY(pread_full(fd, &ct, 4, 0));
-  if (ct != XSG_COMPRESSION_NONE && ct != XSG_COMPRESSION_ZSTD && ct != XSG_COMPRESSION_LZ4)
-    return fail(XSG_EIO, "metafile '%s': unknown compression type %d", path, ct);
-  *compression = ct;
-  uint64_t pos = 4;
-  uint64_t expect_orig = 0;
-  while (pos < size) {
-    if (size - pos < 40) return fail(XSG_EIO, "metafile '%s': truncated chunk record at byte %llu", path,
-                                     (unsigned long long)pos);
-    uint64_t f[7] = {0, 0, 0, 0, 0, 0, 0};  // 5 header words + the first mapping entry
-    const uint64_t want = std::min<uint64_t>(56, size - pos);
-    XSG_TRY(pread_full(fd, f, want, pos));
-    pos += 40;
-    const uint64_t n = f[4];
-    if (n > (size - pos) / 16) return fail(XSG_EIO, "metafile '%s': mapping table of chunk %zu overruns the file", path,
-                                           chunks.size());
-    xsg_file_chunk c{};
-    c.original_offset = f[0];
-    c.actual_offset = f[1];
-    c.original_size = f[2];
-    c.actual_size = f[3];
-    c.n_mappings = n;
-    c.first_line = XSG_LINE_BASE_AUTO;
-    if (c.original_offset != expect_orig)
-      return fail(XSG_EIO, "metafile '%s': chunk %zu does not start where its predecessor ends", path, chunks.size());
-    if (c.original_size >= (1ull << 40) || c.actual_size >= (1ull << 40))
-      return fail(XSG_EIO, "metafile '%s': chunk %zu has an implausible size", path, chunks.size());
-    expect_orig += c.original_size;  // < 2^40 each and at most size/40 records: no wrap
-    if (n) {
-      // the first mapping entry of a chunk is the chunk start
-      if (f[5] == c.original_offset) c.first_line = f[6];
-      if (mappings) {
-        const size_t at = mappings->size();
-        mappings->resize(at + 2 * n);
-        XSG_TRY(pread_full(fd, mappings->data() + at, 16 * n, pos));
-      }
-    }
-    pos += 16 * n;
-    chunks.push_back(c);
-  }
-  return XSG_OK;
-}
-
-extern "C" int xsg_meta_read(const char* meta_path, int32_t* compression, xsg_file_chunk** chunks, uint64_t* n,
-                             uint64_t** mappings, uint64_t* n_mapping_pairs) {
-  if (!compression || !chunks || !n) return fail(XSG_EINVAL, "null output");
-  return guarded("xsg_meta_read", [&]() -> int {
-    std::vector<xsg_file_chunk> v;
-    std::vector<uint64_t> maps;
-    XSG_TRY(read_meta(meta_path, compression, v, mappings ? &maps : nullptr));
-    XSG_TRY(to_malloc(v, chunks, n));
-    if (mappings) {
-      *mappings = static_cast<uint64_t*>(malloc(8 * std::max<size_t>(maps.size(), 1)));
-      if (!*mappings) return fail(XSG_ENOMEM, "host allocation failed");
-      if (!maps.empty()) memcpy(*mappings, maps.data(), 8 * maps.size());
-      if (n_mapping_pairs) *n_mapping_pairs = maps.size() / 2;
-    }
-    return XSG_OK;
-  });
-}
-
-// ---------------------------------------------------------------------------
-// LZ4 / ZSTD through the system libraries (the reference links liblz4 / libzstd,
-// Dockerfile:8).  Loaded on demand so that plain-text searches need neither.
-// ---------------------------------------------------------------------------
-struct Codecs {
-  void* lz4 = nullptr;
-  void* zstd = nullptr;
-  int (*LZ4_decompress_safe)(const char*, char*, int, int) = nullptr;
-  int (*LZ4_compress_default)(const char*, char*, int, int) = nullptr;
-  int (*LZ4_compress_HC)(const char*, char*, int, int, int) = nullptr;
-  int (*LZ4_compressBound)(int) = nullptr;
-  size_t (*ZSTD_decompress)(void*, size_t, const void*, size_t) = nullptr;
-  size_t (*ZSTD_compress)(void*, size_t, const void*, size_t, int) = nullptr;
-  size_t (*ZSTD_compressBound)(size_t) = nullptr;
-  unsigned (*ZSTD_isError)(size_t) = nullptr;
-};
-
-static Codecs& codecs() {
-  static Codecs c;
-  return c;
-}
-static std::mutex g_codec_mu;
-
-static void* open_any(const char* const* names) {
-  for (; *names; ++names) {
-    void* h = dlopen(*names, RTLD_NOW | RTLD_LOCAL);
-    if (h) return h;
-  }
-  return nullptr;
-}
-
-// the built-in block codec (xsg_lz4.h) behind liblz4's signatures
-static int builtin_lz4_decompress_safe(const char* src, char* dst, int src_n, int dst_cap) {
-  if (src_n < 0 || dst_cap < 0) return -1;
-  const int64_t r = xsg::lz4_block_decode((const uint8_t*)src, (size_t)src_n, (uint8_t*)dst, (size_t)dst_cap);
-  return r < 0 ? -1 : (int)r;
-}
-static int builtin_lz4_compress_default(const char* src, char* dst, int src_n, int dst_cap) {
-  return xsg::lz4_block_encode((const uint8_t*)src, src_n, (uint8_t*)dst, dst_cap);
-}
-static int builtin_lz4_compress_bound(int n) { return xsg::lz4_compress_bound(n); }
-static char g_builtin_lz4_token;  // non-null marker for Codecs::lz4 when the built-in codec is in use
-
-// liblz4 if the host has one, else the built-in codec (XSG_NO_LIBLZ4=1 forces the built-in one: tests)
-static int need_lz4() {
-  std::lock_guard<std::mutex> g(g_codec_mu);
-  Codecs& c = codecs();
-  if (c.lz4) return XSG_OK;
-  static const char* names[] = {"liblz4.so.1", "liblz4.so", "/opt/conda/lib/liblz4.so.1", nullptr};
-  const char* no = getenv("XSG_NO_LIBLZ4");
-  void* h = (no && *no && *no != '0') ? nullptr : open_any(names);
-  if (h) {
-    c.LZ4_decompress_safe = (int (*)(const char*, char*, int, int))dlsym(h, "LZ4_decompress_safe");
-    c.LZ4_compress_default = (int (*)(const char*, char*, int, int))dlsym(h, "LZ4_compress_default");
-    c.LZ4_compress_HC = (int (*)(const char*, char*, int, int, int))dlsym(h, "LZ4_compress_HC");
-    c.LZ4_compressBound = (int (*)(int))dlsym(h, "LZ4_compressBound");
-    if (c.LZ4_decompress_safe && c.LZ4_compress_default && c.LZ4_compressBound) {
-      c.lz4 = h;
-      return XSG_OK;
-    }
-  }
-  c.LZ4_decompress_safe = builtin_lz4_decompress_safe;
-  c.LZ4_compress_default = builtin_lz4_compress_default;
-  c.LZ4_compress_HC = nullptr;
-  c.LZ4_compressBound = builtin_lz4_compress_bound;
-  c.lz4 = &g_builtin_lz4_token;
-  return XSG_OK;
-}
-
-static int need_zstd() {
-  std::lock_guard<std::mutex> g(g_codec_mu);
-  Codecs& c = codecs();
-  if (c.zstd) return XSG_OK;
-  static const char* names[] = {"libzstd.so.1", "libzstd.so", "/opt/conda/lib/libzstd.so.1", nullptr};
-  void* h = open_any(names);
-  if (!h) return fail(XSG_ENOTSUP, "libzstd not found on this host (needed for ZSTD metafiles)");
-  c.ZSTD_decompress = (size_t(*)(void*, size_t, const void*, size_t))dlsym(h, "ZSTD_decompress");
-  c.ZSTD_compress = (size_t(*)(void*, size_t, const void*, size_t, int))dlsym(h, "ZSTD_compress");
-  c.ZSTD_compressBound = (size_t(*)(size_t))dlsym(h, "ZSTD_compressBound");
-  c.ZSTD_isError = (unsigned (*)(size_t))dlsym(h, "ZSTD_isError");
-  if (!c.ZSTD_decompress || !c.ZSTD_compress || !c.ZSTD_compressBound || !c.ZSTD_isError)
-    return fail(XSG_ENOTSUP, "libzstd lacks the expected symbols");
-  c.zstd = h;
-  return XSG_OK;
-}
-
-extern "C" const char* xsg_codec_name(int32_t compression) {
-  if (compression == XSG_COMPRESSION_NONE) return "none";
-  if (compression == XSG_COMPRESSION_LZ4) {
-    if (need_lz4() != XSG_OK) return "";
-    return codecs().lz4 == &g_builtin_lz4_token ? "built-in LZ4 block codec" : "liblz4";
-  }
-  if (compression == XSG_COMPRESSION_ZSTD) return need_zstd() == XSG_OK ? "libzstd" : "";
-  return "";
-}
-
-static int decompress_chunk(int32_t type, const uint8_t* src, uint64_t src_n, uint8_t* dst, uint64_t dst_n) {
-  if (type == XSG_COMPRESSION_LZ4) {
-    // raw LZ4 block per chunk, decoded to exactly original_size bytes
-    if (src_n > INT32_MAX || dst_n > INT32_MAX) return fail(XSG_EIO, "LZ4 chunk too large");
-    const int r = codecs().LZ4_decompress_safe((const char*)src, (char*)dst, (int)src_n, (int)dst_n);
-    if (r < 0 || (uint64_t)r != dst_n) return fail(XSG_EIO, "LZ4 chunk does not decode to its recorded size");
-    return XSG_OK;
-  }
-  if (type == XSG_COMPRESSION_ZSTD) {
-    const size_t r = codecs().ZSTD_decompress(dst, dst_n, src, src_n);
-    if (codecs().ZSTD_isError(r) || r != dst_n) return fail(XSG_EIO, "ZSTD chunk does not decode to its recorded size");
-    return XSG_OK;
-  }
-  return fail(XSG_EINVAL, "bad compression type %d", type);
-}
-
-// ---------------------------------------------------------------------------
-// metafile writer / preprocessor
-// ---------------------------------------------------------------------------
-static int meta_write_impl(const char* file_path, const char* meta_out_path, const char* data_out_path,
-                           int32_t compression, uint64_t chunk_bytes, uint64_t mapping_gap, int hc);
-extern "C" int xsg_meta_write(const char* file_path, const char* meta_out_path, const char* data_out_path,
-                              int32_t compression, uint64_t chunk_bytes, uint64_t mapping_gap, int hc) {
-  return guarded("xsg_meta_write", [&]() -> int {
-    return meta_write_impl(file_path, meta_out_path, data_out_path, compression, chunk_bytes, mapping_gap, hc);
-  });
-}
-static int meta_write_impl(const char* file_path, const char* meta_out_path, const char* data_out_path,
-                           int32_t compression, uint64_t chunk_bytes, uint64_t mapping_gap, int hc) {
-  if (!meta_out_path) return fail(XSG_EINVAL, "meta_out_path is null");
-  if (compression != XSG_COMPRESSION_NONE && compression != XSG_COMPRESSION_ZSTD && compression != XSG_COMPRESSION_LZ4)
-    return fail(XSG_EINVAL, "bad compression type %d", compression);
-  if (compression != XSG_COMPRESSION_NONE && !data_out_path) return fail(XSG_EINVAL, "data_out_path is null");
-  if (compression == XSG_COMPRESSION_LZ4) XSG_TRY(need_lz4());
-  if (compression == XSG_COMPRESSION_ZSTD) XSG_TRY(need_zstd());
-  if (!chunk_bytes) chunk_bytes = 16u << 20;
-  if (!mapping_gap) mapping_gap = 500;
-  int fd;
-  uint64_t size;
-  XSG_TRY(open_ro(file_path, &fd, &size));
-  std::vector<xsg_file_chunk> plan;
-  int r = plan_plain(fd, size, chunk_bytes, plan);
-  if (r != XSG_OK) {
-    close(fd);
-    return r;
-  }
-  FILE* mf = fopen(meta_out_path, "wb");
-  FILE* df = compression != XSG_COMPRESSION_NONE ? fopen(data_out_path, "wb") : nullptr;
-  if (!mf || (compression != XSG_COMPRESSION_NONE && !df)) {
-    if (mf) fclose(mf);
-    if (df) fclose(df);
-    close(fd);
-    return fail(XSG_EIO, "cannot create output files: %s", strerror(errno));
-  }
-  fwrite(&compression, 4, 1, mf);
-  std::vector<uint8_t> raw, packed;
-  std::vector<uint64_t> maps;
-  uint64_t line = 0, actual_off = 0;
-  for (const xsg_file_chunk& pc : plan) {
-    raw.resize(pc.original_size);
-    r = pread_full(fd, raw.data(), pc.original_size, pc.original_offset);
-    if (r != XSG_OK) break;
-    // mapping: the chunk start, then the first line start >= previous entry + gap
-    maps.clear();
-    maps.push_back(pc.original_offset);
-    maps.push_back(line);
-    uint64_t last_entry = 0;
-    for (uint64_t i = 0; i < pc.original_size; ++i) {
-      if (raw[i] == '\n') {
-        ++line;
-        const uint64_t ls = i + 1;
-        if (ls < pc.original_size && ls >= last_entry + mapping_gap) {
-          maps.push_back(pc.original_offset + ls);
-          maps.push_back(line);
-          last_entry = ls;
-        }
-      }
-    }
-    uint64_t actual_size = pc.original_size;
-    if (compression == XSG_COMPRESSION_LZ4) {
-      if (pc.original_size > INT32_MAX) {
-        r = fail(XSG_EINVAL, "chunk too large for an LZ4 block");
-        break;
-      }
-      packed.resize((size_t)codecs().LZ4_compressBound((int)pc.original_size));
-      const int n = hc && codecs().LZ4_compress_HC
-                        ? codecs().LZ4_compress_HC((const char*)raw.data(), (char*)packed.data(), (int)raw.size(),
-                                                   (int)packed.size(), 9)
-                        : codecs().LZ4_compress_default((const char*)raw.data(), (char*)packed.data(), (int)raw.size(),
-                                                        (int)packed.size());
-      if (n <= 0 && pc.original_size) {
-        r = fail(XSG_EIO, "LZ4 compression failed");
-        break;
-      }
-      actual_size = (uint64_t)n;
-    } else if (compression == XSG_COMPRESSION_ZSTD) {
-      packed.resize(codecs().ZSTD_compressBound(raw.size()));
-      const size_t n = codecs().ZSTD_compress(packed.data(), packed.size(), raw.data(), raw.size(), 3);
-      if (codecs().ZSTD_isError(n)) {
-        r = fail(XSG_EIO, "ZSTD compression failed");
-        break;
-      }
-      actual_size = n;
-    }
-    if (df && actual_size && fwrite(packed.data(), 1, actual_size, df) != actual_size) {
-      r = fail(XSG_EIO, "short write to '%s'", data_out_path);
-      break;
-    }
-    const uint64_t rec[5] = {pc.original_offset, compression == XSG_COMPRESSION_NONE ? pc.original_offset : actual_off,
-                             pc.original_size, actual_size, maps.size() / 2};
-    fwrite(rec, 8, 5, mf);
-    fwrite(maps.data(), 8, maps.size(), mf);
-    actual_off += actual_size;
-  }
-  if (fclose(mf) != 0 && r == XSG_OK) r = fail(XSG_EIO, "cannot write '%s'", meta_out_path);
-  if (df && fclose(df) != 0 && r == XSG_OK) r = fail(XSG_EIO, "cannot write '%s'", data_out_path);
-  close(fd);
-  return r;
-}
-
-// ---------------------------------------------------------------------------
-// the job
-// ---------------------------------------------------------------------------
+// what one chunk adds to the job's result
 struct Partial {
   uint64_t count = 0;     // count tags
   uint64_t newlines = 0;  // line indices without metafile bases
@@ -435,30 +45,8 @@ struct Partial {
   std::vector<xsg_context::Extra<std::string>> head_lines, tail_lines;
 };
 
-// The device side of XSG_FLAG_CONTEXT, reached through a weak reference: this file is also linked without the device
-// library (tests/cpp: the sanitizer binaries, against a stand-in that knows nothing of context), and a context job is
-// then refused at its start.
-extern "C" int xsg_result_context_edges(xsg_shard* shard, xsg_context_edge* out, uint64_t cap_chunks) __attribute__((weak));
-// ... and of a literal list (xsg_job_opts.pattern_is_list, xsg_host_searcher_create_list), the same way
-extern "C" int xsg_set_literals_opts(xsg_ctx* ctx, const void* list, size_t n, uint32_t flags, uint32_t list_flags) __attribute__((weak));
-extern "C" int xsg_literals_info(const void* list, size_t n, uint32_t flags, xsg_literal_list* info, uint8_t* filter) __attribute__((weak));
-static const char kNoListMsg[] = "this build holds no device side for literal lists";
-// the pattern of a worker or a slot: a literal list where the caller said so, with its list flags (XSG_LIST_WHOLE_WORDS)
-static int set_job_pattern(xsg_ctx* ctx, const std::vector<uint8_t>& pattern, uint32_t flags, bool is_list, uint32_t list_flags) {
-  if (!is_list) return xsg_set_pattern(ctx, pattern.data(), pattern.size(), flags);
-  if (!xsg_set_literals_opts) return xsg::fail(XSG_ENOTSUP, "%s", kNoListMsg);
-  return xsg_set_literals_opts(ctx, pattern.data(), pattern.size(), flags, list_flags);
-}
-static int check_list_flags(uint32_t list_flags) {
-  return (list_flags & ~(XSG_LIST_WHOLE_WORDS | XSG_LIST_ALL_OF)) ? xsg::fail(XSG_EINVAL, "unknown list flags 0x%x", list_flags) : XSG_OK;
-}
-static bool context_flags(uint32_t flags) { return XSG_CONTEXT_BEFORE(flags) != 0 || XSG_CONTEXT_AFTER(flags) != 0; }
-// the tags whose list context widens (every other tag ignores the bits)
-static bool context_mode(uint32_t mode) { return mode == XSG_LINE_BYTE_OFFSETS || mode == XSG_LINE_INDICES || mode == XSG_LINES; }
-
 static std::atomic<uint64_t> g_job_serial{0};
 
-static bool is_string_mode(uint32_t mode) { return mode == XSG_LINES || mode == XSG_MATCHES; }  // results are strings
 struct xsg_job {
   const uint64_t serial = ++g_job_serial;
   xsg_job_opts opts{};
@@ -556,7 +144,7 @@ static int publish(xsg_job* j, uint64_t index, Partial&& p) {
     Partial& q = it->second;
     if (q.context) {
       int r = XSG_OK;
-      if (is_string_mode(mode)) {
+      if (string_mode(mode)) {
         r = publish_context(j, j->stitch_lines, it->first, q.edge, std::move(q.lines), std::move(q.head_lines), std::move(q.tail_lines), &j->lines);
         j->total = j->lines.size();
       } else {
@@ -569,10 +157,10 @@ static int publish(xsg_job* j, uint64_t index, Partial&& p) {
         j->total = j->values.size();
       }
       if (rc == XSG_OK) rc = r;
-    } else if (mode == XSG_COUNT_MATCHES || mode == XSG_COUNT_LINES) {
+    } else if (count_mode(mode)) {
       j->total += q.count;
       j->values.push_back(j->total);
-    } else if (is_string_mode(mode)) {
+    } else if (string_mode(mode)) {
       for (std::string& s : q.lines) j->lines.push_back(std::move(s));
       j->total = j->lines.size();
     } else {
@@ -663,15 +251,13 @@ static void slot_give_back(Slot* s) {
   delete s;
 }
 
-static bool is_count_mode(uint32_t mode) { return mode == XSG_COUNT_MATCHES || mode == XSG_COUNT_LINES; }
-
 // One lane of a slot, ready for this job: its context and shard (created on first use), the job's pattern, a device
 // buffer that holds the job's largest chunk.  `serial` = the job the lane was last prepared for.
 static int lane_prepare(xsg_job* j, Slot& s, int k) {
   Lane& l = s.lane[k];
   if (l.job_serial == j->serial) return XSG_OK;
   HIP_TRY(hipSetDevice(j->opts.device));
-  const uint64_t need = ((j->max_orig + 15u) & ~(uint64_t)15u) + 256u;
+  const uint64_t need = staged_bytes(j->max_orig);
   if (!l.ctx) {
     XSG_TRY(xsg_ctx_create(j->opts.device, &l.ctx));
     XSG_TRY(xsg_shard_create(l.ctx, nullptr, 0, nullptr, 0, &l.shard));
@@ -714,7 +300,7 @@ static int buf_prepare(xsg_job* j, HostBuf** out) {
   }
   std::unique_ptr<HostBuf> own(b ? b : new (std::nothrow) HostBuf());
   if (!own) return fail(XSG_ENOMEM, "host allocation failed");
-  const uint64_t need = ((j->max_orig + 15u) & ~(uint64_t)15u) + 256u;
+  const uint64_t need = staged_bytes(j->max_orig);
   if (need > own->cap) {
     if (own->pinned) (void)hipHostFree(own->pinned);
     own->pinned = nullptr;
@@ -937,19 +523,25 @@ static void reader_loop(xsg_job* j, double& t_read, double& t_dec, uint64_t& rby
   }
 }
 
+// nothing may leave a thread body (or the extern "C" boundary) as an exception: it fails the job
+template <typename F>
+static void thread_body(xsg_job* j, const char* who, F&& f) {
+  try {
+    f();
+  } catch (const std::bad_alloc&) {
+    (void)fail(XSG_ENOMEM, "host allocation failed in a %s", who);
+    job_fail(j, XSG_ENOMEM);
+  } catch (const std::exception& e) {
+    (void)fail(XSG_EIO, "%s: %s", who, e.what());
+    job_fail(j, XSG_EIO);
+  }
+}
+
 static void reader_main(xsg_job* j) {
   double t_read = 0, t_dec = 0;
   uint64_t rbytes = 0;
   bind_thread_to_device(j->opts.device);
-  try {
-    reader_loop(j, t_read, t_dec, rbytes);
-  } catch (const std::bad_alloc&) {
-    (void)fail(XSG_ENOMEM, "host allocation failed in a reader");
-    job_fail(j, XSG_ENOMEM);
-  } catch (const std::exception& e) {
-    (void)fail(XSG_EIO, "reader: %s", e.what());
-    job_fail(j, XSG_EIO);
-  }
+  thread_body(j, "reader", [&] { reader_loop(j, t_read, t_dec, rbytes); });
   {
     std::lock_guard<std::mutex> lk(j->q_mu);
     --j->readers_running;
@@ -1006,7 +598,7 @@ static int list_collect(xsg_job* j, Lane& l, const HostBuf& hb) {
   const xsg_file_chunk& fc = j->plan[hb.index];
   const uint32_t mode = j->opts.mode;
   Partial p;
-  if (is_string_mode(mode)) {
+  if (string_mode(mode)) {
     uint64_t n = 0, nl = 0, nb = 0;
     const uint64_t* lens = nullptr;
     const char* bytes = nullptr;
@@ -1065,7 +657,7 @@ static void worker_body(xsg_job* j, double& t_dev, uint64_t& bytes, uint64_t& ch
     job_fail(j, r);
     return;
   }
-  const bool counting = is_count_mode(j->opts.mode);
+  const bool counting = count_mode(j->opts.mode);
   HostBuf* inflight = nullptr;  // the chunk whose copy (count tags: and pass) is in lane (k ^ 1)'s queue
   int k = 0;
   // The second lane costs a fresh process 10-20 ms (a stream, a device buffer: profiles/r04_cli_start.txt) and buys
@@ -1143,15 +735,7 @@ static void worker_main(xsg_job* j) {
   double t_dev = 0;
   uint64_t bytes = 0, chunks = 0;
   bind_thread_to_device(j->opts.device);
-  try {
-    worker_body(j, t_dev, bytes, chunks);
-  } catch (const std::bad_alloc&) {  // nothing may leave a thread body (or the extern "C" boundary) as an exception
-    (void)fail(XSG_ENOMEM, "host allocation failed in a device worker");
-    job_fail(j, XSG_ENOMEM);
-  } catch (const std::exception& e) {
-    (void)fail(XSG_EIO, "device worker: %s", e.what());
-    job_fail(j, XSG_EIO);
-  }
+  thread_body(j, "device worker", [&] { worker_body(j, t_dev, bytes, chunks); });
   if (j->stop.load()) {  // wake everybody that may still be waiting on a queue
     { std::lock_guard<std::mutex> lk(j->q_mu); }
     j->q_cv_free.notify_all();
@@ -1182,30 +766,6 @@ extern "C" void xsg_job_opts_init(xsg_job_opts* o) {
 
 // force_list: xsg_job_start_list -- the pattern is a list whatever pattern_is_list says, with `list_flags`
 static int job_start_impl(const void* pattern, size_t plen, const char* file_path, const char* meta_file_path,
-                          const xsg_job_opts* opts, bool force_list, uint32_t list_flags, xsg_job** out);
-
-static int job_start_guarded(const void* pattern, size_t plen, const char* file_path, const char* meta_file_path,
-                             const xsg_job_opts* opts, bool force_list, uint32_t list_flags, xsg_job** out) {
-  try {
-    return job_start_impl(pattern, plen, file_path, meta_file_path, opts, force_list, list_flags, out);
-  } catch (const std::bad_alloc&) {  // e.g. a plan with millions of records
-    return fail(XSG_ENOMEM, "host allocation failed while setting up the job");
-  } catch (const std::exception& e) {
-    return fail(XSG_EIO, "xsg_job_start: %s", e.what());
-  }
-}
-
-extern "C" int xsg_job_start(const void* pattern, size_t plen, const char* file_path, const char* meta_file_path,
-                             const xsg_job_opts* opts, xsg_job** out) {
-  return job_start_guarded(pattern, plen, file_path, meta_file_path, opts, false, 0u, out);
-}
-
-extern "C" int xsg_job_start_list(const void* list, size_t n, uint32_t list_flags, const char* file_path,
-                                  const char* meta_file_path, const xsg_job_opts* opts, xsg_job** out) {
-  return job_start_guarded(list, n, file_path, meta_file_path, opts, true, list_flags, out);
-}
-
-static int job_start_impl(const void* pattern, size_t plen, const char* file_path, const char* meta_file_path,
                           const xsg_job_opts* opts, bool force_list, uint32_t list_flags, xsg_job** out) {
   XSG_TRACE("job: start");
   if (!out) return fail(XSG_EINVAL, "out is null");
@@ -1229,7 +789,7 @@ static int job_start_impl(const void* pattern, size_t plen, const char* file_pat
     if (list_flags & XSG_LIST_ALL_OF) {  // (xsg.h: XSG_LIST_ALL_OF -- what the set call and the searches would refuse, here)
       if (info.count > XSG_MAX_ALL_OF_LITERALS)
         return fail(XSG_EINVAL, "XSG_LIST_ALL_OF: %u literals, at most %u are served", info.count, XSG_MAX_ALL_OF_LITERALS);
-      if (opts->mode == XSG_COUNT_MATCHES || opts->mode == XSG_MATCH_BYTE_OFFSETS || opts->mode == XSG_MATCHES)
+      if (match_mode(opts->mode))
         return fail(XSG_ENOTSUP, "XSG_LIST_ALL_OF: a conjunction selects lines; it has no single match, and the match tags are not served for it");
     }
   }
@@ -1238,7 +798,7 @@ static int job_start_impl(const void* pattern, size_t plen, const char* file_pat
   if ((opts->pattern_flags & XSG_FLAG_REGEX) && plen > XSG_MAX_REGEX) return fail(XSG_EINVAL, "expression longer than %u bytes", XSG_MAX_REGEX);
   if (opts->mode > XSG_MATCHES) return fail(XSG_EINVAL, "bad mode %u", opts->mode);
   if (opts->num_threads < 1 || opts->num_max_readers < 1) return fail(XSG_EINVAL, "num_threads/num_max_readers < 1");
-  const bool line_mode = opts->mode != XSG_COUNT_MATCHES && opts->mode != XSG_MATCH_BYTE_OFFSETS && opts->mode != XSG_MATCHES;
+  const bool line_mode = !match_mode(opts->mode);
   if (opts->pattern_flags & XSG_FLAG_INVERT) {  // (xsg.h: the line tags only, and no pattern that can match '\n')
     if (!line_mode) return fail(XSG_ENOTSUP, "XSG_FLAG_INVERT: an inverted search reports lines without a match; the match tags have no inverted form");
     if (!is_list && !(opts->pattern_flags & XSG_FLAG_REGEX) && memchr(pattern, '\n', plen))
@@ -1357,6 +917,27 @@ static int job_start_impl(const void* pattern, size_t plen, const char* file_pat
   return XSG_OK;
 }
 
+static int job_start_guarded(const void* pattern, size_t plen, const char* file_path, const char* meta_file_path,
+                             const xsg_job_opts* opts, bool force_list, uint32_t list_flags, xsg_job** out) {
+  try {
+    return job_start_impl(pattern, plen, file_path, meta_file_path, opts, force_list, list_flags, out);
+  } catch (const std::bad_alloc&) {  // e.g. a plan with millions of records
+    return fail(XSG_ENOMEM, "host allocation failed while setting up the job");
+  } catch (const std::exception& e) {
+    return fail(XSG_EIO, "xsg_job_start: %s", e.what());
+  }
+}
+
+extern "C" int xsg_job_start(const void* pattern, size_t plen, const char* file_path, const char* meta_file_path,
+                             const xsg_job_opts* opts, xsg_job** out) {
+  return job_start_guarded(pattern, plen, file_path, meta_file_path, opts, false, 0u, out);
+}
+
+extern "C" int xsg_job_start_list(const void* list, size_t n, uint32_t list_flags, const char* file_path,
+                                  const char* meta_file_path, const xsg_job_opts* opts, xsg_job** out) {
+  return job_start_guarded(list, n, file_path, meta_file_path, opts, true, list_flags, out);
+}
+
 extern "C" int xsg_job_join(xsg_job* j) {
   if (!j) return fail(XSG_EINVAL, "job is null");
   for (std::thread& t : j->threads)
@@ -1390,7 +971,7 @@ extern "C" int xsg_job_total(xsg_job* j, uint64_t* total) {
 extern "C" int xsg_job_wait(xsg_job* j, uint64_t index, uint64_t* available, int* finished) {
   if (!j) return fail(XSG_EINVAL, "job is null");
   std::unique_lock<std::mutex> lk(j->mu);
-  const bool is_lines = is_string_mode(j->opts.mode);
+  const bool is_lines = string_mode(j->opts.mode);
   auto avail = [&] { return is_lines ? (uint64_t)j->lines.size() : (uint64_t)j->values.size(); };
   j->cv.wait(lk, [&] { return avail() > index || j->finished; });
   if (available) *available = avail();
@@ -1402,14 +983,14 @@ extern "C" int xsg_job_wait(xsg_job* j, uint64_t index, uint64_t* available, int
 extern "C" int xsg_job_poll(xsg_job* j, uint64_t* available, int* finished) {
   if (!j) return fail(XSG_EINVAL, "job is null");
   std::lock_guard<std::mutex> g(j->mu);
-  if (available) *available = is_string_mode(j->opts.mode) ? (uint64_t)j->lines.size() : (uint64_t)j->values.size();
+  if (available) *available = string_mode(j->opts.mode) ? (uint64_t)j->lines.size() : (uint64_t)j->values.size();
   if (finished) *finished = j->finished ? 1 : 0;
   return XSG_OK;
 }
 
 extern "C" int xsg_job_get_u64(xsg_job* j, uint64_t first, uint64_t n, uint64_t* out) {
   if (!j || (!out && n)) return fail(XSG_EINVAL, "null argument");
-  if (is_string_mode(j->opts.mode)) return fail(XSG_ESTATE, "XSG_LINES / XSG_MATCHES results are strings: use xsg_job_get_line");
+  if (string_mode(j->opts.mode)) return fail(XSG_ESTATE, "XSG_LINES / XSG_MATCHES results are strings: use xsg_job_get_line");
   std::lock_guard<std::mutex> g(j->mu);
   if (first + n > j->values.size()) return fail(XSG_EINVAL, "range beyond the available results");
   if (n) memcpy(out, j->values.data() + first, 8 * n);
@@ -1418,7 +999,7 @@ extern "C" int xsg_job_get_u64(xsg_job* j, uint64_t first, uint64_t n, uint64_t*
 
 extern "C" int xsg_job_get_line(xsg_job* j, uint64_t index, const char** data, uint64_t* len) {
   if (!j || !data || !len) return fail(XSG_EINVAL, "null argument");
-  if (!is_string_mode(j->opts.mode)) return fail(XSG_ESTATE, "not an XSG_LINES or XSG_MATCHES job");
+  if (!string_mode(j->opts.mode)) return fail(XSG_ESTATE, "not an XSG_LINES or XSG_MATCHES job");
   std::lock_guard<std::mutex> g(j->mu);
   if (index >= j->lines.size()) return fail(XSG_EINVAL, "index beyond the available results");
   const std::string& s = j->lines[index];  // deque: references stay valid while the job lives
@@ -1435,7 +1016,6 @@ extern "C" int xsg_job_stats_get(xsg_job* j, xsg_job_stats* stats) {
   if (!j->finished) stats->seconds_total = seconds_since(j->t_start);
   return XSG_OK;
 }
-
 
 // ---------------------------------------------------------------------------
 // several jobs of one search (one per device): the count is the sum of their totals.  That sum is the search's one
@@ -1529,235 +1109,4 @@ extern "C" int xsg_jobs_reduce_total(xsg_job* const* jobs, int n, uint64_t* tota
     if (via_rccl) *via_rccl = 1;
     return XSG_OK;
   });
-}
-
-// ---------------------------------------------------------------------------
-// the lower seam: chunks in host memory (reference-style searcher functors)
-// ---------------------------------------------------------------------------
-struct HostSlot {
-  xsg_ctx* ctx = nullptr;
-  xsg_shard* shard = nullptr;
-  void* pinned = nullptr;
-  void* dev = nullptr;
-  uint64_t cap = 0;
-  ~HostSlot() {
-    if (shard) xsg_shard_destroy(shard);
-    if (pinned) (void)hipHostFree(pinned);
-    if (dev) (void)hipFree(dev);
-    if (ctx) xsg_ctx_destroy(ctx);
-  }
-};
-
-struct xsg_host_searcher {
-  int device = 0;
-  std::vector<uint8_t> pattern;
-  uint32_t flags = 0;
-  bool is_list = false;  // xsg_host_searcher_create_list
-  uint32_t list_flags = 0;  // xsg_host_searcher_create_list_opts
-  int max_slots = 1;
-  std::mutex mu;
-  std::condition_variable cv;
-  std::vector<std::unique_ptr<HostSlot>> all;
-  std::vector<HostSlot*> free_slots;
-};
-
-static int host_slot_acquire(xsg_host_searcher* hs, HostSlot** out) {
-  std::unique_lock<std::mutex> lk(hs->mu);
-  for (;;) {
-    if (!hs->free_slots.empty()) {
-      *out = hs->free_slots.back();
-      hs->free_slots.pop_back();
-      return XSG_OK;
-    }
-    if ((int)hs->all.size() < hs->max_slots) {
-      hs->all.emplace_back(new HostSlot());
-      HostSlot* s = hs->all.back().get();
-      lk.unlock();
-      int r = xsg_ctx_create(hs->device, &s->ctx);
-      if (r == XSG_OK) r = set_job_pattern(s->ctx, hs->pattern, hs->flags, hs->is_list, hs->list_flags);
-      if (r == XSG_OK) r = xsg_shard_create(s->ctx, nullptr, 0, nullptr, 0, &s->shard);
-      if (r != XSG_OK) {
-        // give the place back, or later callers would wait for a slot that never comes
-        lk.lock();
-        for (size_t i = 0; i < hs->all.size(); ++i)
-          if (hs->all[i].get() == s) {
-            hs->all.erase(hs->all.begin() + (ptrdiff_t)i);
-            break;
-          }
-        lk.unlock();
-        hs->cv.notify_one();
-        return r;
-      }
-      *out = s;
-      return XSG_OK;
-    }
-    hs->cv.wait(lk);
-  }
-}
-
-static void host_slot_release(xsg_host_searcher* hs, HostSlot* s) {
-  {
-    std::lock_guard<std::mutex> g(hs->mu);
-    hs->free_slots.push_back(s);
-  }
-  hs->cv.notify_one();
-}
-
-// stage the chunk: host -> pinned -> device, bind it as a 1-chunk shard (local offsets, line base 0)
-static int host_stage(HostSlot* s, const void* data, uint64_t len) {
-  const uint64_t need = ((len + 15u) & ~(uint64_t)15u) + 256u;
-  if (need > s->cap) {
-    if (s->pinned) (void)hipHostFree(s->pinned);
-    if (s->dev) (void)hipFree(s->dev);
-    s->pinned = s->dev = nullptr;
-    s->cap = 0;
-    const uint64_t cap = std::max<uint64_t>(need, 1u << 20);
-    HIP_TRY(hipSetDevice(s->ctx->device));
-    HIP_TRY(hipHostMalloc(&s->pinned, cap, hipHostMallocDefault));
-    HIP_TRY(hipMalloc(&s->dev, cap));
-    s->cap = cap;
-  }
-  if (len) {
-    memcpy(s->pinned, data, len);
-    HIP_TRY(hipMemcpyAsync(s->dev, s->pinned, len, hipMemcpyHostToDevice, s->ctx->stream));
-  }
-  xsg_chunk ch{};
-  ch.offset = 0;
-  ch.length = len;
-  ch.global_offset = 0;
-  ch.line_base = 0;
-  return xsg_shard_rebind(s->shard, s->dev, s->cap, &ch, 1);
-}
-
-static int host_searcher_create(int device, const void* pattern, size_t plen, uint32_t flags, bool is_list, uint32_t list_flags,
-                                int max_slots, xsg_host_searcher** out) {
-  if (!out) return fail(XSG_EINVAL, "out is null");
-  *out = nullptr;
-  XSG_TRY(check_list_flags(list_flags));
-  if (!pattern || plen == 0 || plen > XSG_MAX_PATTERN) return fail(XSG_EINVAL, "pattern must be 1..%u bytes",
-                                                                  XSG_MAX_PATTERN);
-  if (is_list) {
-    if (!xsg_literals_info) return fail(XSG_ENOTSUP, "%s", kNoListMsg);
-    xsg_literal_list info;
-    XSG_TRY(xsg_literals_info(pattern, plen, flags, &info, nullptr));
-    if ((list_flags & XSG_LIST_ALL_OF) && info.count > XSG_MAX_ALL_OF_LITERALS)
-      return fail(XSG_EINVAL, "XSG_LIST_ALL_OF: %u literals, at most %u are served", info.count, XSG_MAX_ALL_OF_LITERALS);
-  } else if (flags & XSG_FLAG_REGEX) {
-    XSG_TRY(xsg_regex_check(pattern, plen, flags & XSG_FLAG_IGNORE_CASE, nullptr, nullptr));
-  }
-  int ndev = 0;
-  XSG_TRY(xsg_device_count(&ndev));
-  if (device < 0 || device >= ndev) return fail(XSG_ENODEV, "device %d out of range", device);
-  std::unique_ptr<xsg_host_searcher> hs(new (std::nothrow) xsg_host_searcher());
-  if (!hs) return fail(XSG_ENOMEM, "host allocation failed");
-  hs->device = device;
-  hs->pattern.assign((const uint8_t*)pattern, (const uint8_t*)pattern + plen);
-  hs->flags = flags;
-  hs->is_list = is_list;
-  hs->list_flags = list_flags;
-  hs->max_slots = max_slots < 1 ? 1 : max_slots;
-  // build the first slot now so that a bad pattern / missing GPU fails here, not in the first search
-  HostSlot* s = nullptr;
-  XSG_TRY(host_slot_acquire(hs.get(), &s));
-  host_slot_release(hs.get(), s);
-  *out = hs.release();
-  return XSG_OK;
-}
-
-extern "C" int xsg_host_searcher_create(int device, const void* pattern, size_t plen, uint32_t flags, int max_slots,
-                                        xsg_host_searcher** out) {
-  return host_searcher_create(device, pattern, plen, flags, false, 0u, max_slots, out);
-}
-
-extern "C" int xsg_host_searcher_create_list(int device, const void* list, size_t n, uint32_t flags, int max_slots,
-                                             xsg_host_searcher** out) {
-  return xsg_host_searcher_create_list_opts(device, list, n, flags, 0u, max_slots, out);
-}
-
-extern "C" int xsg_host_searcher_create_list_opts(int device, const void* list, size_t n, uint32_t flags, uint32_t list_flags,
-                                                  int max_slots, xsg_host_searcher** out) {
-  return host_searcher_create(device, list, n, flags, true, list_flags, max_slots, out);
-}
-
-extern "C" void xsg_host_searcher_destroy(xsg_host_searcher* hs) { delete hs; }
-
-struct SlotLease {
-  xsg_host_searcher* hs;
-  HostSlot* s = nullptr;
-  explicit SlotLease(xsg_host_searcher* h) : hs(h) {}
-  ~SlotLease() {
-    if (s) host_slot_release(hs, s);
-  }
-};
-
-extern "C" int xsg_host_count(xsg_host_searcher* hs, const void* data, uint64_t len, int skip_to_nl,
-                              uint64_t* count) {
-  if (!hs || !count || (!data && len)) return fail(XSG_EINVAL, "null argument");
-  SlotLease l(hs);
-  XSG_TRY(host_slot_acquire(hs, &l.s));
-  XSG_TRY(host_stage(l.s, data, len));
-  uint64_t ctr[XSG_NUM_COUNTERS];
-  XSG_TRY(xsg_count(l.s->shard, skip_to_nl ? XSG_COUNT_LINES : XSG_COUNT_MATCHES, ctr));
-  *count = ctr[skip_to_nl ? XSG_CTR_LINES : XSG_CTR_MATCHES];
-  return XSG_OK;
-}
-
-extern "C" int xsg_host_offsets(xsg_host_searcher* hs, uint32_t mode, const void* data, uint64_t len, uint64_t** out,
-                                uint64_t* n) {
-  if (!hs || !out || !n || (!data && len)) return fail(XSG_EINVAL, "null argument");
-  if (mode != XSG_MATCH_BYTE_OFFSETS && mode != XSG_LINE_BYTE_OFFSETS && mode != XSG_LINE_INDICES)
-    return fail(XSG_EINVAL, "mode %u has no uint64 list result", mode);
-  SlotLease l(hs);
-  XSG_TRY(host_slot_acquire(hs, &l.s));
-  XSG_TRY(host_stage(l.s, data, len));
-  uint64_t cnt = 0;
-  XSG_TRY(xsg_search(l.s->shard, mode, &cnt));
-  uint64_t* buf = static_cast<uint64_t*>(malloc(8 * std::max<uint64_t>(cnt, 1)));
-  if (!buf) return fail(XSG_ENOMEM, "host allocation failed");
-  const int r = xsg_result_u64(l.s->shard, buf, cnt);
-  if (r != XSG_OK) {
-    free(buf);
-    return r;
-  }
-  *out = buf;
-  *n = cnt;
-  return XSG_OK;
-}
-
-static int host_strings(xsg_host_searcher* hs, uint32_t mode, const void* data, uint64_t len, uint64_t** lengths, char** bytes,
-                        uint64_t* n, uint64_t* nbytes) {
-  if (!hs || !lengths || !bytes || !n || !nbytes || (!data && len)) return fail(XSG_EINVAL, "null argument");
-  SlotLease l(hs);
-  XSG_TRY(host_slot_acquire(hs, &l.s));
-  XSG_TRY(host_stage(l.s, data, len));
-  uint64_t cnt = 0, nl = 0, nb = 0;
-  const uint64_t* vlens = nullptr;
-  const char* vbytes = nullptr;
-  XSG_TRY(xsg_search(l.s->shard, mode, &cnt));
-  // out of the shard's pinned buffers (a large result arrives there by pinned copies, not by a pageable D2H)
-  XSG_TRY(xsg_result_lines_view(l.s->shard, &vlens, &vbytes, nullptr, &nl, &nb));
-  uint64_t* lens = static_cast<uint64_t*>(malloc(8 * std::max<uint64_t>(nl, 1)));
-  char* buf = static_cast<char*>(malloc(std::max<uint64_t>(nb, 1)));
-  if (!lens || !buf) {
-    free(lens);
-    free(buf);
-    return fail(XSG_ENOMEM, "host allocation failed");
-  }
-  if (nl) memcpy(lens, vlens, 8 * nl);
-  if (nb) memcpy(buf, vbytes, nb);
-  *lengths = lens;
-  *bytes = buf;
-  *n = nl;
-  *nbytes = nb;
-  return XSG_OK;
-}
-
-extern "C" int xsg_host_lines(xsg_host_searcher* hs, const void* data, uint64_t len, uint64_t** lengths, char** bytes,
-                              uint64_t* n, uint64_t* nbytes) {
-  return host_strings(hs, XSG_LINES, data, len, lengths, bytes, n, nbytes);
-}
-
-extern "C" int xsg_host_matches(xsg_host_searcher* hs, const void* data, uint64_t len, uint64_t** lengths, char** bytes,
-                                uint64_t* n, uint64_t* nbytes) {
-  return host_strings(hs, XSG_MATCHES, data, len, lengths, bytes, n, nbytes);
 }

@@ -1,15 +1,16 @@
 // xsg_litcount.cpp -- the C ABI of include/xsg.h: xsg_literal_counter_*, the host-memory seam of xsg_count_literals.  A
 // reader loop hands in chunk after chunk of a file; the counter stages each through one of two pinned slots, runs the pass
 // of xsg_count_literals over it on the slot's stream and keeps the running sums on the device.  The copy of chunk i + 1
-// overlaps the pass over chunk i.  (Its own file: xsg_file.cpp links against tests/cpp/device_double.cpp alone and must
-// not reference a chunk-level entry point that double does not have.)  Beside it xsg_literal_finder_*, the same seam of
-// xsg_find_literals: one chunk per call, its occurrences handed back in malloc'ed arrays.
+// overlaps the pass over chunk i.  (Its own file: xsg_hostsearch.cpp links against tests/cpp/device_double.cpp alone and
+// must not reference a chunk-level entry point that double does not have.)  Beside it xsg_literal_finder_*, the same seam
+// of xsg_find_literals: one chunk per call, its occurrences handed back in malloc'ed arrays.  Both stage through xsg_stage.h.
 #include <cstdlib>
 #include <cstring>
 #include <memory>
 #include <new>
 
 #include "xsg_host.h"
+#include "xsg_stage.h"
 
 using namespace xsg;
 
@@ -17,9 +18,7 @@ namespace {
 struct LitSlot {
   xsg_shard* shard = nullptr;
   hipStream_t stream = nullptr;
-  void* pinned = nullptr;
-  void* dev = nullptr;
-  uint64_t cap = 0;
+  StagedChunk buf;
 };
 }  // namespace
 
@@ -36,8 +35,7 @@ struct xsg_literal_counter {
       if (s.stream) (void)hipStreamSynchronize(s.stream);
       if (s.shard) xsg_shard_destroy(s.shard);
       if (s.stream) (void)hipStreamDestroy(s.stream);
-      if (s.pinned) (void)hipHostFree(s.pinned);
-      if (s.dev) (void)hipFree(s.dev);
+      s.buf.release();  // (here, ahead of the context: a member's own destructor runs after this body)
     }
     d_sums.release();
     h_sums.release();
@@ -83,22 +81,7 @@ extern "C" int xsg_literal_counter_add(xsg_literal_counter* lc, const void* data
   LitSlot& s = lc->slot[lc->next];
   lc->next ^= 1;
   HIP_TRY(hipStreamSynchronize(s.stream));  // the slot's last pass has read its buffer and its chunk table
-  const uint64_t need = ((len + 15u) & ~(uint64_t)15u) + 256u;
-  if (need > s.cap) {
-    if (s.pinned) (void)hipHostFree(s.pinned);
-    if (s.dev) (void)hipFree(s.dev);
-    s.pinned = s.dev = nullptr;
-    s.cap = 0;
-    const uint64_t cap = std::max<uint64_t>(need, 1u << 20);
-    HIP_TRY(hipHostMalloc(&s.pinned, cap, hipHostMallocDefault));
-    HIP_TRY(hipMalloc(&s.dev, cap));
-    s.cap = cap;
-  }
-  memcpy(s.pinned, data, len);
-  HIP_TRY(hipMemcpyAsync(s.dev, s.pinned, len, hipMemcpyHostToDevice, s.stream));
-  xsg_chunk ch{};
-  ch.length = len;
-  XSG_TRY(xsg_shard_rebind(s.shard, s.dev, s.cap, &ch, 1));  // (the table goes up on the context's stream, behind an event)
+  XSG_TRY(stage(s.buf, c->device, s.stream, s.shard, data, len, 0));  // (the table goes up on the context's stream, behind an event)
   XSG_TRY(enqueue_count_literals(s.shard, s.stream, lc->d_sums.as<uint64_t>(), false));
   lc->bytes += len;
   return XSG_OK;
@@ -127,15 +110,12 @@ extern "C" void xsg_literal_counter_destroy(xsg_literal_counter* lc) { delete lc
 struct xsg_literal_finder {
   xsg_ctx* ctx = nullptr;
   xsg_shard* shard = nullptr;
-  void* pinned = nullptr;
-  void* dev = nullptr;
-  uint64_t cap = 0;
+  StagedChunk buf;
   ~xsg_literal_finder() {
     if (ctx) (void)hipSetDevice(ctx->device);
     if (ctx && ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     if (shard) xsg_shard_destroy(shard);
-    if (pinned) (void)hipHostFree(pinned);
-    if (dev) (void)hipFree(dev);
+    buf.release();  // (behind the shard, ahead of the context)
     if (ctx) xsg_ctx_destroy(ctx);
   }
 };
@@ -167,23 +147,7 @@ extern "C" int xsg_literal_finder_find(xsg_literal_finder* lf, const void* data,
   HIP_TRY(hipSetDevice(c->device));
   uint64_t total = 0;
   if (len) {
-    const uint64_t need = ((len + 15u) & ~(uint64_t)15u) + 256u;
-    if (need > lf->cap) {
-      if (lf->pinned) (void)hipHostFree(lf->pinned);
-      if (lf->dev) (void)hipFree(lf->dev);
-      lf->pinned = lf->dev = nullptr;
-      lf->cap = 0;
-      const uint64_t cap = std::max<uint64_t>(need, 1u << 20);
-      HIP_TRY(hipHostMalloc(&lf->pinned, cap, hipHostMallocDefault));
-      HIP_TRY(hipMalloc(&lf->dev, cap));
-      lf->cap = cap;
-    }
-    memcpy(lf->pinned, data, len);
-    HIP_TRY(hipMemcpyAsync(lf->dev, lf->pinned, len, hipMemcpyHostToDevice, c->stream));
-    xsg_chunk ch{};
-    ch.length = len;
-    ch.global_offset = base;
-    XSG_TRY(xsg_shard_rebind(lf->shard, lf->dev, lf->cap, &ch, 1));
+    XSG_TRY(stage(lf->buf, c->device, c->stream, lf->shard, data, len, base));
     XSG_TRY(xsg_find_literals(lf->shard, &total));  // (waits on the context's stream, behind the copy)
   }
   uint64_t* p = static_cast<uint64_t*>(malloc(8 * std::max<uint64_t>(total, 1)));

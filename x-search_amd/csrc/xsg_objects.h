@@ -1,10 +1,12 @@
 // xsg_objects.h -- private object definitions shared by the host files of the C ABI (device-resident searches:
-// xsg_ctx / xsg_pattern / xsg_shard / xsg_count / xsg_list.cpp, through xsg_host.h) and xsg_file.cpp (the file
-// pipeline; tests/cpp/device_double.cpp stands in for the former under it).  Not installed.
+// xsg_ctx / xsg_pattern / xsg_shard / xsg_count / xsg_list.cpp, through xsg_host.h) and the host pipelines above them
+// (xsg_job.cpp, xsg_hostsearch.cpp, xsg_fileset.cpp; tests/cpp/device_double.cpp stands in for the former under the first
+// two).  Not installed.
 #pragma once
 #include <algorithm>
 #include <cstdarg>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -25,9 +27,12 @@ void trace(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
 // toggles between searches.
 namespace xsg {
 bool test_hooks();
+// a toggle that forces a kernel's grid (tests: a few workgroups on a dozen tiles): its workgroups, 0 where it is unset
+inline uint32_t forced_grid(const char* g) { return g && atoll(g) > 0 ? (uint32_t)std::min<long long>(atoll(g), 1 << 30) : 0u; }
 }
 #define XSG_TOGGLE(name) \
   ([]() -> const char* { static const char* const v = getenv(name); return xsg::test_hooks() ? getenv(name) : v; }())
+#define XSG_TOGGLE_GRID(name) xsg::forced_grid(XSG_TOGGLE(name))
 
 #define XSG_TRACE(...)                      \
   do {                                      \
@@ -115,6 +120,14 @@ struct PinBuf {
   T* as() const {
     return static_cast<T*>(p);
   }
+};
+
+// A ragged result kept on the shard for its read-out call, until the next call of its kind, rebind or invalidate.  The
+// pinned mirror holds rows + 1 pointer words, then `total` 8-byte words, then `total` 4-byte words.
+struct KeptRagged {
+  PinBuf h;
+  bool valid = false;
+  uint64_t rows = 0, total = 0;  // n and ptr[n] of the kept result
 };
 
 // ---------------------------------------------------------------------------
@@ -277,17 +290,13 @@ struct xsg_shard {
   // row_ptr[n]; the status word behind row_ptr) and its pinned mirror (row_ptr, vals, cols in this order), kept until the
   // next xsg_count_literals_csr, rebind or invalidate: xsg_result_literals_csr copies from the mirror.
   DevBuf d_csr_row_nnz, d_csr_tmp, d_csr_seam, d_csr_row_ptr, d_csr_cols, d_csr_vals;
-  PinBuf h_csr;
-  bool csr_valid = false;
-  uint64_t csr_rows = 0, csr_nnz = 0;  // ... n and row_ptr[n] of the kept result
+  KeptRagged kept_csr;
   // xsg_find_literals: the scratch of both forms -- a word per 4 KiB wave span (its occurrences), their prefix sum (uint64)
   // and its tmp: 12 bytes per span, 0.3 % of the text.  Then the synchronous form's result (chunk_ptr and the status word
   // behind it; pos and lit, sized exactly from chunk_ptr[n]) and its pinned mirror (chunk_ptr, pos, lit in this order), kept
   // until the next xsg_find_literals, rebind or invalidate: xsg_result_literal_hits copies from the mirror.
   DevBuf d_find_occ, d_find_off, d_find_tmp, d_find_ptr, d_find_pos, d_find_lit;
-  PinBuf h_find;
-  bool find_valid = false;
-  uint64_t find_rows = 0, find_total = 0;  // ... n and chunk_ptr[n] of the kept result
+  KeptRagged kept_find;
   uint64_t list_entries = 0;  // raw entries (ListArgs::M) the last exact list pass left in d_m_chunk / d_keep_pre
   // xsg_result_chunk_ptr: where the pending list result (last_mode) left its chunk bookkeeping -- noted by the search on
   // the host, nothing is launched or fetched for it until the accessor is called.  rows_chunk: the chunk column of the
@@ -341,7 +350,7 @@ struct xsg_shard {
     if (h_counters) (void)hipHostFree(h_counters);
     if (h_tot) (void)hipHostFree(h_tot);
     h_tot = nullptr;
-    for (PinBuf* b : {&h_result, &hp_line_len, &hp_line_bytes, &h_chunk_counts, &h_lit_counts, &h_lit_matrix, &h_csr, &h_find, &h_rows}) b->release();
+    for (PinBuf* b : {&h_result, &hp_line_len, &hp_line_bytes, &h_chunk_counts, &h_lit_counts, &h_lit_matrix, &kept_csr.h, &kept_find.h, &h_rows}) b->release();
     if (table_ev) (void)hipEventDestroy(table_ev);
     h_stage = nullptr;
     h_counters = nullptr;

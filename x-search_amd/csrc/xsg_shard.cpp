@@ -23,8 +23,8 @@ static void forget_derived(xsg_shard* s) {
   s->sketch_passes = 0;
   s->sketch_refused = false;
   s->gate_serial = 0;
-  s->csr_valid = false;                      // the kept result of xsg_count_literals_csr
-  s->find_valid = false;                     // the kept result of xsg_find_literals
+  s->kept_csr.valid = false;                 // the kept result of xsg_count_literals_csr
+  s->kept_find.valid = false;                // the kept result of xsg_find_literals
 }
 
 static int bind_shard(xsg_shard* s, const void* d_base, uint64_t capacity, const xsg_chunk* chunks, uint64_t nchunks) {
