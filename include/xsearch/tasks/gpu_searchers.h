@@ -47,6 +47,12 @@ struct Handle {
       throw std::runtime_error(std::string("xs::Gpu*Searcher: ") + xsg_strerror(r) + " (" + xsg_last_error() + ")");
   }
   ~Handle() { xsg_host_searcher_destroy(hs); }
+  // xsg_host_searcher_set_max_count: every later call reports the chunk's first n entries (a count: min(count, n)); 0: all
+  void set_max_count(uint64_t n) const {
+    const int r = xsg_host_searcher_set_max_count(hs, n);
+    if (r != XSG_OK)
+      throw std::runtime_error(std::string("xs::Gpu*Searcher: ") + xsg_strerror(r) + " (" + xsg_last_error() + ")");
+  }
   Handle(const Handle&) = delete;
   Handle& operator=(const Handle&) = delete;
 };
@@ -104,6 +110,9 @@ class GpuIndexSearcher {
     return gpu_detail::offsets(*_h, XSG_MATCH_BYTE_OFFSETS, data);
   }
 
+  // optional: a limit for the calls that follow (a loop over the chunks of a stream hands in what is left of its budget)
+  void set_max_count(uint64_t n) const { _h->set_max_count(n); }
+
  private:
   std::shared_ptr<gpu_detail::Handle> _h;
 };
@@ -118,6 +127,9 @@ class GpuLineIndexSearcher {
   std::optional<std::vector<uint64_t>> operator()(const T& data) const {
     return gpu_detail::offsets(*_h, XSG_LINE_BYTE_OFFSETS, data);
   }
+
+  // optional: a limit for the calls that follow (a loop over the chunks of a stream hands in what is left of its budget)
+  void set_max_count(uint64_t n) const { _h->set_max_count(n); }
 
  private:
   std::shared_ptr<gpu_detail::Handle> _h;
@@ -134,6 +146,9 @@ class GpuLineSearcher {
     return gpu_detail::strings(*_h, xsg_host_lines, data);
   }
 
+  // optional: a limit for the calls that follow (a loop over the chunks of a stream hands in what is left of its budget)
+  void set_max_count(uint64_t n) const { _h->set_max_count(n); }
+
  private:
   std::shared_ptr<gpu_detail::Handle> _h;
 };
@@ -148,6 +163,9 @@ class GpuMatchSearcher {
   std::optional<std::vector<std::string>> operator()(const T& data) const {
     return gpu_detail::strings(*_h, xsg_host_matches, data);
   }
+
+  // optional: a limit for the calls that follow (a loop over the chunks of a stream hands in what is left of its budget)
+  void set_max_count(uint64_t n) const { _h->set_max_count(n); }
 
  private:
   std::shared_ptr<gpu_detail::Handle> _h;
@@ -167,6 +185,9 @@ class GpuCountSearcher {
     if (c == 0) return {};
     return c;
   }
+
+  // optional: a limit for the calls that follow (a loop over the chunks of a stream hands in what is left of its budget)
+  void set_max_count(uint64_t n) const { _h->set_max_count(n); }
 
  private:
   std::shared_ptr<gpu_detail::Handle> _h;

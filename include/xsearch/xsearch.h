@@ -43,7 +43,9 @@
 // a single word being a list of one; without a list extern_search throws std::invalid_argument), XS_ALL_OF (1: the lines
 // that hold EVERY literal of the list, grep -F a | grep -F b -- xsg.h: XSG_LIST_ALL_OF; honoured only together with
 // XS_PATTERN_LIST=1 like XS_WHOLE_WORDS, at most 64 literals, the line tags only: count_matches, match_byte_offsets and
-// matches throw std::invalid_argument).
+// matches throw std::invalid_argument), XS_MAX_COUNT (N: the first N entries of the result are enough, grep --max-count --
+// xsg.h: xsg_job_start_max_count; the search stops reading there; default 0, no limit; with several XS_DEVICES or non-zero
+// XS_CONTEXT_* extern_search throws std::invalid_argument).
 #pragma once
 
 #include <xsg.h>
@@ -475,6 +477,13 @@ class ExternSearcher {
     _set.is_count = detail::traits<Tag>::is_count;
     _set.add_newline_base = o.mode == XSG_LINE_INDICES && meta == nullptr;
     const std::vector<int> devices = detail::device_list();
+    _max_count = detail::env_u64("XS_MAX_COUNT", 0);
+    if (_max_count != 0 && devices.size() > 1)  // the budget is spent in file order: the devices' ranges run side by side
+      throw std::invalid_argument("xs::extern_search: XS_MAX_COUNT (a limit) is served on one device only: the ranges of XS_DEVICES "
+                                  "are searched side by side");
+    if (_max_count != 0 && (detail::env_u64("XS_CONTEXT_BEFORE", 0) != 0 || detail::env_u64("XS_CONTEXT_AFTER", 0) != 0))
+      throw std::invalid_argument("xs::extern_search: XS_MAX_COUNT (a limit) is not served together with XS_CONTEXT_BEFORE / "
+                                  "XS_CONTEXT_AFTER (context lines) on a file");
     if (context != 0 && devices.size() > 1)  // the seams between the devices' chunk ranges are not stitched
       throw std::invalid_argument("xs::extern_search: XS_CONTEXT_BEFORE / XS_CONTEXT_AFTER (context lines) are served on one "
                                   "device only: the ranges of XS_DEVICES are searched on their own");
@@ -559,13 +568,15 @@ class ExternSearcher {
  private:
   void start(const std::string& pattern, const std::string& file_path, const char* meta, const xsg_job_opts& o) {
     xsg_job* j = nullptr;
-    const int r = _list_flags ? xsg_job_start_list(pattern.data(), pattern.size(), _list_flags, file_path.c_str(), meta, &o, &j)
+    const int r = _max_count ? xsg_job_start_max_count(pattern.data(), pattern.size(), _list_flags, _max_count, file_path.c_str(), meta, &o, &j)
+                  : _list_flags ? xsg_job_start_list(pattern.data(), pattern.size(), _list_flags, file_path.c_str(), meta, &o, &j)
                               : xsg_job_start(pattern.data(), pattern.size(), file_path.c_str(), meta, &o, &j);
     if (r != XSG_OK) detail::throw_last("xs::extern_search", r);
     _set.jobs.push_back(j);
   }
   detail::JobSet _set;
   uint32_t _list_flags = 0;  // XS_WHOLE_WORDS, XS_ALL_OF: through xsg_job_start_list
+  uint64_t _max_count = 0;   // XS_MAX_COUNT: through xsg_job_start_max_count
   std::unique_ptr<ResultT> _result;
 };
 

@@ -46,7 +46,8 @@ extern "C" {
  * xsg_set_literals_opts, xsg_host_searcher_create_list_opts, xsg_literal_counter_create_opts and xsg_job_start_list joined;
  * xsg_find_literals, xsg_result_literal_hits, xsg_find_literals_async and xsg_literal_finder_* joined;
  * XSG_LIST_ALL_OF joined the list_flags of xsg_set_literals_opts, xsg_host_searcher_create_list_opts and xsg_job_start_list;
- * xsg_result_chunk_ptr and xsg_fileset_* joined;
+ * xsg_result_chunk_ptr and xsg_fileset_* joined; xsg_set_max_count, xsg_job_start_max_count, xsg_fileset_start_max_count and
+ * xsg_host_searcher_set_max_count joined;
  * no entry point was removed or changed in meaning */
 #define XSG_ABI_VERSION 4
 
@@ -336,6 +337,37 @@ int xsg_set_literals(xsg_ctx* ctx, const void* list, size_t n, uint32_t flags);
                                 * unknown flag by every build so far, and callers that probe with it keep their answer */
 #define XSG_MAX_ALL_OF_LITERALS 64u
 int xsg_set_literals_opts(xsg_ctx* ctx, const void* list, size_t n, uint32_t flags, uint32_t list_flags);
+/* A ROW LIMIT PER CHUNK (grep --max-count on every chunk of a binding): "the first max_count are enough".  The limit is a
+ * property of the PATTERN, like the list options: it is set after xsg_set_pattern, xsg_set_literals or
+ * xsg_set_literals_opts, any later set call clears it whether that call succeeds or fails, and without a pattern the call
+ * returns XSG_ESTATE.  max_count == 0 means no limit: every entry point is then, result for result, what it is without
+ * this call.  Any other value N is accepted, up to UINT64_MAX.
+ *
+ * For one chunk let R be the list the tag reports for that chunk under the pattern and its flags: XSG_FLAG_INVERT is
+ * already applied (R is then the complement I) and the default lossy end-of-chunk behaviour is included -- all this before
+ * XSG_FLAG_CONTEXT widens anything and before XSG_LINES drops an unterminated last line.  With the limit R is replaced by
+ * its first N entries in file order, per chunk, and everything downstream sees that list.
+ *   line list tags   XSG_LINE_BYTE_OFFSETS, XSG_LINE_INDICES, XSG_LINES: the first N selected lines of every chunk; context,
+ *                    if set, is taken around those N lines and xsg_result_context_edges describes the limited list;
+ *                    XSG_LINES then drops an unterminated last line as always, so a chunk may hand out N - 1 lines.
+ *   match list tags  XSG_MATCH_BYTE_OFFSETS, XSG_MATCHES: the first N MATCHES of every chunk -- entries, not lines (grep -o
+ *                    --max-count counts lines); lengths and bytes follow their entries.
+ *   rows             xsg_result_chunk_ptr and its byte_ptr: the rows of the limited result.
+ *   counts           xsg_count, xsg_count_begin / _end: XSG_CTR_MATCHES or XSG_CTR_LINES is the sum over the chunks of
+ *                    min(count of chunk c, N); XSG_CTR_NEWLINES, XSG_CTR_BYTES and the non-ASCII refusal are unchanged;
+ *                    xsg_count_begin does its work synchronously, as it does for a count that is a list.
+ *                    xsg_count_chunks: counts[c] = min(counts[c] without the limit, N), totals as xsg_count gives them
+ *                    under the limit, newlines[] unchanged; sum(counts) == totals[...] keeps holding.
+ *   refused          XSG_ENOTSUP, never approximated: the stream-ordered counts under a limit (xsg_count_async,
+ *                    xsg_count_async_status, xsg_count_chunks_async) and every per-literal entry point under a limit
+ *                    (xsg_count_literals*, xsg_find_literals*: a clamp per literal is a different feature).  Every other
+ *                    refusal keeps its precedence and its message.
+ * xsg_scan_kernel_name names the stage, " + xsg::k_limit_copy (max count)" for a list tag and " + xsg::k_limit_counts (max
+ * count)" for a count, behind "(inverted)" and in front of "(context)"; xsg_time_scan_kernel and xsg_shard_tune ignore the
+ * limit.  A limited search takes the exact list route, as an inverted one does.
+ * Unlike GNU grep: the after-context of the Nth line includes later lines even if they would have been selected themselves
+ * (grep ends trailing context at the next selected line once the count is reached). */
+int xsg_set_max_count(xsg_ctx* ctx, uint64_t max_count);
 /* Would xsg_set_literals accept this list, and what does it compile to?  Host only, needs no device (like
  * xsg_regex_check).  XSG_OK or XSG_EINVAL with the reason in xsg_last_error().  `info` (optional) receives the numbers,
  * `filter` (optional, XSG_LITERAL_FILTER_BYTES) the filter image: bit h of the little-endian uint32 words is set <=> some
@@ -798,6 +830,23 @@ int xsg_job_start(const void* pattern, size_t plen, const char* file_path, const
  * as for any list; an unknown bit of list_flags too.  list_flags == 0: xsg_job_start with pattern_is_list = 1. */
 int xsg_job_start_list(const void* list, size_t n, uint32_t list_flags, const char* file_path,
                        const char* meta_file_path, const xsg_job_opts* opts, xsg_job** out);
+/* xsg_job_start with a LIMIT PER FILE (grep --max-count): the result is the first max_count entries of what the same job
+ * reports without a limit, over the searched range [chunk_begin, chunk_end); for the count tags it is min(total, max_count).
+ * An entry point of its own because xsg_job_opts does not grow.  `opts` is read exactly as xsg_job_start reads it,
+ * pattern_is_list included; list_flags are those of xsg_job_start_list and belong to a list: list_flags != 0 without
+ * pattern_is_list is XSG_EINVAL.  max_count == 0 is xsg_job_start / xsg_job_start_list.
+ *   The publisher is ordered: it keeps the remaining budget and appends min(remaining, entries of the chunk) of every chunk's
+ * result -- for XSG_LINES the entries after an unterminated last line was dropped.  When the budget reaches 0 the job
+ * stops reading and finishes normally: xsg_job_join returns XSG_OK, finished = 1; chunks behind that point are neither
+ * reported nor, beyond the buffers already in circulation (2 x num_threads + 3 chunks), read.  For the count tags the running
+ * totals are clamped to max_count, and the sequence of elements ends with the chunk that reached it.  xsg_job_stats counts
+ * what was actually read and searched.  The workers' contexts carry the limit too (xsg_set_max_count): a chunk alone never
+ * moves more than max_count rows.
+ *   A limit together with non-zero XSG_FLAG_CONTEXT counts is XSG_ENOTSUP from this call (and from
+ * xsg_fileset_start_max_count): the budget is only known in file order, and the seam stitcher joins lists that are already
+ * widened.  xsg_set_max_count on a binding serves the combination. */
+int xsg_job_start_max_count(const void* pattern, size_t plen, uint32_t list_flags, uint64_t max_count, const char* file_path,
+                            const char* meta_file_path, const xsg_job_opts* opts, xsg_job** out);
 /* Blocks until every worker has finished; returns the first worker error. */
 int xsg_job_join(xsg_job* job);
 /* Joins, then frees the job and everything it returned pointers into. */
@@ -856,6 +905,13 @@ typedef struct xsg_fileset_opts {
 void xsg_fileset_opts_init(xsg_fileset_opts* opts);  /* clears, stamps struct_size, mode = XSG_COUNT_LINES */
 int xsg_fileset_start(const void* pattern, size_t plen, const char* const* paths, uint64_t npaths,
                       const xsg_fileset_opts* opts, xsg_fileset** out);
+/* ... with a limit per FILE: every file's result is the first max_count entries of what xsg_fileset_start reports for it
+ * (count tags: min(count, max_count)), identical for every batch_bytes, chunk_bytes and reader count.  Small files are
+ * chunks of a binding under xsg_set_max_count, large ones go through xsg_job_start_max_count; the per-file search behind
+ * a non-ASCII refusal carries the limit too.  max_count == 0 is xsg_fileset_start; with non-zero XSG_FLAG_CONTEXT counts
+ * the call is XSG_ENOTSUP (see xsg_job_start_max_count). */
+int xsg_fileset_start_max_count(const void* pattern, size_t plen, const char* const* paths, uint64_t npaths,
+                                const xsg_fileset_opts* opts, uint64_t max_count, xsg_fileset** out);
 /* Blocks until file `file_index` is published or the set has finished; *files_done = files published so far (they publish
  * in path order, so the files [0, *files_done) have their results), *finished = 1 once no more will come. */
 int xsg_fileset_wait(xsg_fileset* set, uint64_t file_index, uint64_t* files_done, int* finished);
@@ -897,6 +953,10 @@ int xsg_host_searcher_create_list(int device, const void* list, size_t n, uint32
 int xsg_host_searcher_create_list_opts(int device, const void* list, size_t n, uint32_t flags, uint32_t list_flags,
                                        int max_slots, xsg_host_searcher** out);
 void xsg_host_searcher_destroy(xsg_host_searcher* hs);
+/* xsg_set_max_count on every slot's context, from the next call on: xsg_host_count returns min(count, max_count),
+ * xsg_host_offsets, xsg_host_lines and xsg_host_matches the chunk's limited lists.  It may be changed between calls (a loop
+ * over the chunks of a stream sets what is left of its budget); 0 clears it. */
+int xsg_host_searcher_set_max_count(xsg_host_searcher* hs, uint64_t max_count);
 /* search::count(data, pattern, skip_to_nl)  (search_wrappers.h:163-185) */
 int xsg_host_count(xsg_host_searcher* hs, const void* data, uint64_t len, int skip_to_nl, uint64_t* count);
 /* mode = XSG_MATCH_BYTE_OFFSETS / XSG_LINE_BYTE_OFFSETS / XSG_LINE_INDICES; *out is malloc'ed (xsg_free).

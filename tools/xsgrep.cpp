@@ -65,7 +65,19 @@
 //     selected (under -L: listed), 1 if nothing was, 2 if a file failed -- `xsgrep: PATH: reason` on stderr, the other files
 //     are still printed.  Output comes per published file, in operand / walk order.  A single FILE without any of -r -l -L
 //     -H --no-filename takes the single-file path above, output and exit status unchanged.
-// The one-letter options without an argument may be bundled (-vc, -ci, -oi, -wc, -rl).
+// --max-count=N, --max-count N  stop after N selected lines PER FILE (grep --max-count; -m stays the METAFILE): under -v
+//     after N lines without a match, under -c the count is min(count, N).  N takes digits only.  Served for one FILE, for
+//     several (each file has its own N) and for `-`, where the loop over the pipe's chunks hands what is left of the budget
+//     to the searchers and stops reading at 0; a large FILE is read no further than its Nth line and the buffers in flight.
+//     Combines with -c -i -v -w -x -E -F -e -f --all-of -l -L -r -H.  --max-count=0 prints nothing and exits 1 without
+//     touching a device.  Refused (exit 2, before a device is touched): with -o (grep counts LINES there, the engine's match
+//     tags count matches), with -A -B -C (the budget of a file is spent in file order, its context is widened per chunk),
+//     with --count-each and --find-each.
+// -q / --quiet / --silent  print nothing; exit 0 if a line was selected, 1 if none, 2 on error.  Runs as --max-count=1 with a
+//     count of lines, in every form but --count-each / --find-each (exit 2).  Without -q the single-file form's exit status
+//     stays what it was.
+// -l and -L pass a limit of 1 to the file set: a large file is read up to its first selected line.
+// The one-letter options without an argument may be bundled (-vc, -ci, -oi, -wc, -rl, -qi).
 // otherwise print the matching lines, live, as they are found (grep.cpp:74-79).
 #include <xsearch/tasks/gpu_searchers.h>
 #include <xsearch/xsearch.h>
@@ -90,6 +102,9 @@ static const char kUsage[] =
     "       %s -F [-i] [-w] --count-each (-e PATTERN)... [-f FILE]... FILE|-\n"
     "       %s -F [-i] [-w] --find-each (-e PATTERN)... [-f FILE]... FILE|-\n"
     "       %s [options of the first three forms but -m] [-r] [-l|-L] [-H|--no-filename] PATTERN FILE FILE...\n"
+    "  --max-count=N stop after N selected lines per file (-m is the METAFILE); N in digits; 0 prints nothing, exit 1; combines\n"
+    "     with -c -i -v -w -x -E -F -e -f --all-of -l -L -r -H, on FILE, FILEs and -; not with -o -A -B -C --count-each --find-each\n"
+    "  -q, --quiet print nothing: exit 0 if a line was selected, 1 if none, 2 on error (runs as --max-count=1 with -c)\n"
     "  FILE FILE..., -r / --recursive search several files in one run (directories depth-first, sorted byte-wise, regular files\n"
     "     only, links met on the walk not followed); -l / -L print only the names of files with / without a selected line;\n"
     "     -c prints PATH:COUNT; -H / --no-filename force the PATH: prefix on / off (default: on with several FILEs or -r;\n"
@@ -144,8 +159,9 @@ static bool context_number(const std::string& text, long* out) {
 // The input in newline-aligned chunks of about 16 MiB: each is cut behind its last newline and the rest opens the next
 // one; a line longer than the target grows the chunk; the last chunk ends where the input does.  XSGREP_CHUNK_BYTES sets
 // another target (the tests cut a small input into many chunks with it).
+// `stop` (optional): set by f when it has seen enough; nothing more is read then.
 template <typename F>
-static void for_each_aligned_chunk(std::FILE* in, F&& f) {
+static void for_each_aligned_chunk(std::FILE* in, F&& f, const bool* stop = nullptr) {
   size_t target = 16u << 20;
   if (const char* e = std::getenv("XSGREP_CHUNK_BYTES"))
     if (std::atoll(e) > 0) target = (size_t)std::atoll(e);
@@ -154,6 +170,7 @@ static void for_each_aligned_chunk(std::FILE* in, F&& f) {
   size_t want = target;
   bool eof = false;
   for (;;) {
+    if (stop && *stop) break;
     while (!eof && buf.size() < want) {
       const size_t at = buf.size();
       buf.resize(at + step);
@@ -266,6 +283,8 @@ struct FileSetRun {
   bool count = false, only = false, list_with = false, list_without = false, prefix = false, is_list = false;
   uint32_t list_flags = 0;
   int threads = 2;
+  uint64_t max_count = 0;  // per file (0: no limit)
+  bool quiet = false;      // -q: nothing is printed
 };
 
 // several files (xsg_fileset_*): prints per published file; -> grep's exit status
@@ -284,7 +303,7 @@ static int search_files(const std::string& pattern, bool icase, const std::vecto
   std::vector<const char*> paths;
   for (const std::string& f : files) paths.push_back(f.c_str());
   xsg_fileset* set = nullptr;
-  if (xsg_fileset_start(pattern.data(), pattern.size(), paths.data(), paths.size(), &o, &set) != XSG_OK) {
+  if (xsg_fileset_start_max_count(pattern.data(), pattern.size(), paths.data(), paths.size(), &o, run.max_count, &set) != XSG_OK) {
     std::fprintf(stderr, "xsgrep: %s\n", xsg_last_error());
     return 2;
   }
@@ -311,7 +330,9 @@ static int search_files(const std::string& pattern, bool icase, const std::vecto
         failed = true;
         continue;
       }
-      if (run.list_with || run.list_without) {
+      if (run.quiet) {
+        selected |= run.list_without ? counts[f] == 0 : counts[f] != 0;
+      } else if (run.list_with || run.list_without) {
         if ((counts[f] != 0) == run.list_with) {
           std::cout << path << '\n';
           selected = true;
@@ -347,6 +368,8 @@ int main(int argc, char** argv) {
   bool count = false, icase = false, fixed = false, extended = false, whole_lines = false, invert = false, only = false;
   bool each = false, find = false, context_given = false, words = false, all_of = false;
   bool recursive = false, list_with = false, list_without = false, with_filename = false, no_filename = false;
+  bool quiet = false, max_given = false;
+  std::string max_text;
   std::vector<std::string> files;  // every FILE operand (`file` is the first)
   int threads = 2;  // grep.cpp:21
   long before = 0, after = 0;
@@ -357,7 +380,7 @@ int main(int argc, char** argv) {
   std::vector<std::string> args;
   for (int i = 1; i < argc; ++i) {  // -vc -> -v -c (only letters that take no argument; anything else stays one word)
     const std::string a = argv[i];
-    if (a.size() > 2 && a[0] == '-' && a[1] != '-' && a.find_first_not_of("ciEFxvowlLrH", 1) == std::string::npos) {
+    if (a.size() > 2 && a[0] == '-' && a[1] != '-' && a.find_first_not_of("ciEFxvowlLrHq", 1) == std::string::npos) {
       for (size_t k = 1; k < a.size(); ++k) args.push_back(std::string("-") + a[k]);
     } else {
       args.push_back(a);
@@ -384,6 +407,14 @@ int main(int argc, char** argv) {
       with_filename = true;
     } else if (a == "--no-filename") {
       no_filename = true;
+    } else if (a == "-q" || a == "--quiet" || a == "--silent") {
+      quiet = true;
+    } else if (a.rfind("--max-count=", 0) == 0) {
+      max_text = a.substr(12);
+      max_given = true;
+    } else if (a == "--max-count" && i + 1 < nargs) {
+      max_text = args[++i];
+      max_given = true;
     } else if (a == "--count-each") {
       each = true;
     } else if (a == "--find-each") {
@@ -457,6 +488,27 @@ int main(int argc, char** argv) {
     return 2;
   }
   file = files[0];
+  uint64_t max_count = 0;
+  if (max_given) {  // digits only; refused where grep's lines and the engine's entries part ways
+    if (max_text.empty() || max_text.size() > 19 || max_text.find_first_not_of("0123456789") != std::string::npos) {
+      std::fprintf(stderr, "xsgrep: --max-count takes a number of lines in digits, not '%s'\n", max_text.c_str());
+      return 2;
+    }
+    max_count = std::strtoull(max_text.c_str(), nullptr, 10);
+    const char* clash = only && !quiet ? "excludes -o (grep counts lines there, the match tags count matches)"
+                        : context_given ? "excludes -A, -B and -C (a file's budget is spent in file order, its context is widened per chunk)"
+                        : each ? "excludes --count-each (that counts per literal, it selects no lines)"
+                        : find ? "excludes --find-each (that prints occurrences, it selects no lines)" : nullptr;
+    if (clash) {
+      std::fprintf(stderr, "xsgrep: --max-count %s\n", clash);
+      return 2;
+    }
+  }
+  if (quiet && (each || find)) {
+    std::fprintf(stderr, "xsgrep: -q excludes --count-each and --find-each (they select no lines)\n");
+    return 2;
+  }
+  if (quiet) count = true, only = false;  // -q: a count of lines under a limit of 1, nothing printed
   // several files, or an option that only the file-set mode knows; a single FILE without them goes the way it always went
   const bool multi = files.size() > 1 || recursive || list_with || list_without || with_filename || no_filename;
   if (multi) {
@@ -595,6 +647,9 @@ int main(int argc, char** argv) {
     }
     extended = true, fixed = false;
   }
+  if (max_given && max_count == 0) return 1;  // nothing can be selected: no device is touched
+  const uint64_t limit = quiet ? 1 : max_count;
+  if (limit) setenv("XS_MAX_COUNT", std::to_string(limit).c_str(), 1);
   if (list) setenv("XS_PATTERN_LIST", "1", 1);
   if (words) setenv("XS_WHOLE_WORDS", "1", 1);
   if (all_of) setenv("XS_ALL_OF", "1", 1);
@@ -617,6 +672,8 @@ int main(int argc, char** argv) {
       run.count = count, run.only = only, run.list_with = list_with, run.list_without = list_without;
       run.prefix = with_filename || (!no_filename && (files.size() > 1 || recursive));
       run.is_list = list, run.list_flags = list_flags, run.threads = threads;
+      run.quiet = quiet;
+      run.max_count = list_with || list_without ? 1 : limit;  // (a name is decided by the file's first selected line)
       const int rc = search_files(pattern, icase, paths, run);
       std::cout.flush();
       std::fflush(stdout);
@@ -630,17 +687,28 @@ int main(int argc, char** argv) {
       xs::GpuLineSearcher<std::vector<char>> lines(pattern, 0, 1, flags, list, list_flags);
       xs::GpuMatchSearcher<std::vector<char>> matches(pattern, 0, 1, flags, list, list_flags);
       xs::GpuCountSearcher<std::vector<char>> counter(pattern, true, 0, 1, flags, list, list_flags);
-      uint64_t total = 0;
+      uint64_t total = 0, left = limit;  // left: what remains of the budget (limit != 0)
+      bool enough = false;
       for_each_aligned_chunk(stdin, [&](const std::vector<char>& chunk) {
         if (count) {
-          if (auto c = counter(chunk)) total += *c;
+          if (limit) counter.set_max_count(left);
+          if (auto c = counter(chunk)) total += *c, left -= limit ? *c : 0;
         } else if (only) {
           if (auto ms = matches(chunk))
             for (const auto& m : *ms) std::cout << m << '\n';
-        } else if (auto ls = lines(chunk)) {
-          for (const auto& l : *ls) std::cout << l << '\n';
+        } else {
+          if (limit) lines.set_max_count(left);
+          if (auto ls = lines(chunk)) {
+            for (const auto& l : *ls) std::cout << l << '\n';
+            left -= limit ? ls->size() : 0;
+          }
         }
-      });
+        enough = limit != 0 && left == 0;
+      }, &enough);
+      if (quiet) {
+        std::fflush(stdout);
+        std::_Exit(total ? 0 : 1);
+      }
       if (count) std::cout << total << std::endl;
       return 0;
     }
@@ -648,6 +716,10 @@ int main(int argc, char** argv) {
       auto searcher = meta.empty() ? xs::extern_search<xs::count_lines>(pattern, file, icase, threads)
                                    : xs::extern_search<xs::count_lines>(pattern, file, meta, icase, threads, threads);
       searcher->join();
+      if (quiet) {
+        std::fflush(stdout);
+        std::_Exit(searcher->getResult()->size() ? 0 : 1);
+      }
       std::cout << searcher->getResult()->size() << std::endl;
     } else if (only) {
       auto searcher = meta.empty() ? xs::extern_search<xs::matches>(pattern, file, icase, threads)
@@ -664,7 +736,7 @@ int main(int argc, char** argv) {
     }
   } catch (const std::exception& e) {
     std::fprintf(stderr, "xsgrep: %s\n", e.what());
-    return 1;
+    return quiet ? 2 : 1;
   }
   // Everything is printed; what is left is tearing the HIP runtime down (streams, pinned memory, the device context):
   // 40-90 ms of a process that lives 0.2 s on a small file (profiles/r04_cli_start.txt).  A command-line tool leaves that

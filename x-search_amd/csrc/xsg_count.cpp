@@ -630,6 +630,13 @@ static int parse_count_mode(uint32_t mode, uint32_t* m, bool* want_nl) {
   return XSG_OK;
 }
 
+// xsg_set_max_count: a limit clamps every chunk's count, and the clamped sum needs the per-chunk words and a kernel behind
+// them that the stream-ordered entry points do not have: refused behind every refusal they already make
+static int refuse_limited(const xsg_ctx* c, const char* who) {
+  if (!c->max_count) return XSG_OK;
+  return fail(XSG_ENOTSUP, "%s does not serve a limit (xsg_set_max_count): xsg_count(), xsg_count_begin() and xsg_count_chunks() do", who);
+}
+
 static int count_async_impl(xsg_shard* s, uint32_t mode, void* stream, uint64_t* d_counters, uint64_t* d_status) {
   XSG_TRY(check_ready(s));
   if (!d_counters) return fail(XSG_EINVAL, "d_counters is null");
@@ -647,14 +654,17 @@ static int count_async_impl(xsg_shard* s, uint32_t mode, void* stream, uint64_t*
     if (c->bordered && !overlap_free_known(s)) {  // (known from an earlier synchronous call: this entry point may not wait)
       if (want_nl)
         return fail(XSG_ENOTSUP, "pattern can overlap itself: XSG_WITH_NEWLINES next to its match count needs xsg_count()");
+      XSG_TRY(refuse_limited(c, "xsg_count_async"));
       return enqueue_count_bordered(s, st, d_counters, d_status);
     }
+    XSG_TRY(refuse_limited(c, "xsg_count_async"));
     return enqueue_count(s, true, false, want_nl, st, d_counters, nullptr, nullptr, d_status, false);
   }
   if (m == XSG_COUNT_LINES) {
     if (c->pat.has_newline)
       return fail(XSG_ENOTSUP, "count_lines of a pattern that contains '\\n' walks a chain of occurrences: the stream-ordered entry "
                                "point does not serve it, xsg_count() does");
+    XSG_TRY(refuse_limited(c, "xsg_count_async"));
     if (!inverted(c)) return enqueue_count(s, false, true, want_nl, st, d_counters, nullptr, nullptr, d_status, false);
     XSG_TRY(enqueue_count(s, false, true, true, st, d_counters, nullptr, nullptr, d_status, false));
     return enqueue_invert_lines(s, st, d_counters, nullptr, d_status, want_nl);
@@ -685,6 +695,9 @@ static void note_density(xsg_shard* s, uint64_t results) {
   s->dense = results > s->total_bytes / 2048u ? 2u : results > s->total_bytes / per ? 1u : 0u;
 }
 
+static int count_chunks_impl(xsg_shard* s, uint32_t mode, uint32_t m, bool want_nl, uint64_t* counts, uint64_t* newlines,
+                             uint64_t totals[XSG_NUM_COUNTERS]);
+
 extern "C" int xsg_count(xsg_shard* s, uint32_t mode, uint64_t counters[XSG_NUM_COUNTERS]) {
   XSG_TRY(check_ready(s));
   if (!counters) return fail(XSG_EINVAL, "counters is null");
@@ -696,6 +709,9 @@ extern "C" int xsg_count(xsg_shard* s, uint32_t mode, uint64_t counters[XSG_NUM_
   XSG_TRY(parse_count_mode(mode, &m, &want_nl));
   if (m == XSG_COUNT_MATCHES && inverted(c)) return fail(XSG_ENOTSUP, "%s", kInvertMatchMsg);
   if (m == XSG_COUNT_MATCHES && all_of_list(c)) return fail(XSG_ENOTSUP, "%s", kAllOfMatchMsg);
+  // xsg_set_max_count: the sum of the chunks' clamped counts -- the per-chunk machinery into the shard's scratch, one
+  // kernel that clamps and sums (a binding without chunks counts nothing either way)
+  if (c->max_count && !s->chunks.empty()) return count_chunks_impl(s, mode, m, want_nl, nullptr, nullptr, counters);
   const bool inv = inverted(c);  // (XSG_COUNT_LINES from here on: the pass below also counts newlines)
   XSG_TRY(ensure_factor_mask(s));
   if (use_prefilter(s, false) && s->pre_dense_serial != c->pattern_serial) {  // (not again where the candidates were found dense)
@@ -809,6 +825,14 @@ extern "C" int xsg_count_chunks(xsg_shard* s, uint32_t mode, uint64_t* counts, u
   uint32_t m = 0;
   bool want_nl = false;
   XSG_TRY(count_chunks_args(s, mode, counts, newlines, cap_chunks, &m, &want_nl));
+  return count_chunks_impl(s, mode, m, want_nl, counts, newlines, totals);
+}
+
+// ... behind its argument checks.  counts == null: xsg_count under a limit (xsg_set_max_count), which wants the totals alone
+// -- the chunks' words stay in the shard's scratch.  Under a limit one more kernel clamps every chunk's word and sums them:
+// the sum replaces the pass's own total, and sum(counts) == totals[...] keeps holding.
+static int count_chunks_impl(xsg_shard* s, uint32_t mode, uint32_t m, bool want_nl, uint64_t* counts, uint64_t* newlines,
+                             uint64_t totals[XSG_NUM_COUNTERS]) {
   xsg_ctx* c = s->ctx;
   HIP_TRY(hipSetDevice(c->device));
   hipStream_t st = c->stream;
@@ -860,8 +884,15 @@ extern "C" int xsg_count_chunks(xsg_shard* s, uint32_t mode, uint64_t* counts, u
     XSG_TRY(enqueue_count_chunks(s, m, want_nl, st, d_counts, per_nl || inv ? d_nl : nullptr, s->d_counters.as<uint64_t>(),
                                  s->h_counters, nullptr, true));
   }
+  uint64_t limited_sum = 0;
+  if (c->max_count) {
+    XSG_TRY(s->d_lim_sum.ensure(8));
+    HIP_TRY(hipMemsetAsync(s->d_lim_sum.p, 0, 8, st));
+    HIP_TRY(launch_limit_counts(d_counts, nchunks, c->max_count, s->d_lim_sum.as<unsigned long long>(), st));
+    HIP_TRY(hipMemcpyAsync(&limited_sum, s->d_lim_sum.p, 8, hipMemcpyDeviceToHost, st));
+  }
   uint64_t* h = s->h_chunk_counts.as<uint64_t>();
-  HIP_TRY(hipMemcpyAsync(h, d_counts, 8 * nchunks * (per_nl ? 2 : 1), hipMemcpyDeviceToHost, st));
+  if (counts) HIP_TRY(hipMemcpyAsync(h, d_counts, 8 * nchunks * (per_nl ? 2 : 1), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   s->table_pending = false;
   if (!listed) {
@@ -869,7 +900,8 @@ extern "C" int xsg_count_chunks(xsg_shard* s, uint32_t mode, uint64_t* counts, u
     XSG_TRY(refuse_if_poisoned(tot));
     if (!inv) note_density(s, tot[m == XSG_COUNT_MATCHES ? XSG_CTR_MATCHES : XSG_CTR_LINES]);
   }
-  memcpy(counts, h, 8 * nchunks);
+  if (c->max_count) tot[m == XSG_COUNT_MATCHES ? XSG_CTR_MATCHES : XSG_CTR_LINES] = limited_sum;
+  if (counts) memcpy(counts, h, 8 * nchunks);
   if (per_nl) memcpy(newlines, h + nchunks, 8 * nchunks);
   if (totals) memcpy(totals, tot, sizeof tot);
   return XSG_OK;
@@ -894,6 +926,7 @@ extern "C" int xsg_count_chunks_async(xsg_shard* s, uint32_t mode, void* stream,
   if (m == XSG_COUNT_LINES && c->pat.has_newline)
     return fail(XSG_ENOTSUP, "count_lines of a pattern that contains '\\n' walks a chain of occurrences: xsg_count_chunks_async "
                              "does not serve it, xsg_count_chunks() does");
+  XSG_TRY(refuse_limited(c, "xsg_count_chunks_async"));
   uint64_t* d_nl = d_newlines;
   if (!d_nl && inverted(c) && !s->chunks.empty()) {  // an inverted count needs every chunk's newlines: the shard's scratch
     XSG_TRY(s->d_chunk_counts.ensure(16 * s->chunks.size()));
@@ -919,7 +952,8 @@ extern "C" int xsg_count_begin(xsg_shard* s, uint32_t mode) {
   XSG_TRY(ensure_factor_mask(s));
   if (m == XSG_COUNT_MATCHES && c->bordered) XSG_TRY(ensure_overlap_check(s));
   if ((m == XSG_COUNT_MATCHES && c->bordered && !overlap_free_known(s)) || (m == XSG_COUNT_LINES && newline_literal(c)) ||
-      (use_prefilter(s, false) && s->pre_dense_serial != c->pattern_serial)) {  // needs the ordered list: done synchronously, handed out by _end
+      (use_prefilter(s, false) && s->pre_dense_serial != c->pattern_serial) ||
+      c->max_count) {  // needs the ordered list, or the chunks' clamped words (xsg_set_max_count): done synchronously, handed out by _end
     XSG_TRY(xsg_count(s, mode, s->begin_counters));
     s->begin_sync_result = true;
     return XSG_OK;
@@ -1004,6 +1038,10 @@ extern "C" int xsg_scan_kernel_name(xsg_shard* s, uint32_t mode, char* out, size
   if (inverted(s->ctx)) {  // the inverted form: the same scan, then the complement (of the list, or of the line count)
     const size_t n = strlen(out);
     snprintf(out + n, cap - n, "%s", list ? " + xsg::k_invert_tile (inverted)" : " + xsg::k_invert_count_lines (inverted)");
+  }
+  if (s->ctx->max_count) {  // the limit stage: behind the complement, in front of the widening (of the list, or of the chunks' counts)
+    const size_t n = strlen(out);
+    snprintf(out + n, cap - n, "%s", list ? " + xsg::k_limit_copy (max count)" : " + xsg::k_limit_counts (max count)");
   }
   if (context) {  // the widening stage behind the assembled (or inverted) list
     const size_t n = strlen(out);

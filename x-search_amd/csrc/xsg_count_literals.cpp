@@ -21,6 +21,8 @@ static int count_literals_pattern(xsg_shard* s) {
   if (c->pat.kind != kSet)
     return fail(XSG_ENOTSUP, "counts per literal need a literal list as the pattern: xsg_set_literals (a single pattern: a list of one)");
   if (c->flags & XSG_FLAG_INVERT) return fail(XSG_ENOTSUP, "%s", kInvertMatchMsg);
+  if (c->max_count)  // (a clamp per literal would be a different feature: refused, never approximated)
+    return fail(XSG_ENOTSUP, "xsg_set_max_count limits a chunk's entries, not a literal's: the per-literal entry points do not serve a limit");
   return XSG_OK;
 }
 

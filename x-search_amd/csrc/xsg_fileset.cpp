@@ -26,6 +26,7 @@ struct xsg_fileset {
   xsg_fileset_opts opts{};
   std::vector<uint8_t> pattern;
   std::vector<std::string> paths;
+  uint64_t max_count = 0;  // xsg_fileset_start_max_count: per file (0: no limit)
   int nreaders = 1;
 
   std::thread driver;
@@ -274,9 +275,13 @@ static int run_large(xsg_fileset* fs, uint64_t f) {
   o.chunk_bytes = fs->opts.chunk_bytes;
   o.pattern_is_list = fs->opts.pattern_is_list;
   xsg_job* j = nullptr;
-  int r = fs->opts.pattern_is_list
-              ? xsg_job_start_list(fs->pattern.data(), fs->pattern.size(), fs->opts.list_flags, fs->paths[f].c_str(), nullptr, &o, &j)
-              : xsg_job_start(fs->pattern.data(), fs->pattern.size(), fs->paths[f].c_str(), nullptr, &o, &j);
+  int r;
+  if (fs->max_count)  // the file's own budget: the job stops reading where it is spent
+    r = xsg_job_start_max_count(fs->pattern.data(), fs->pattern.size(), fs->opts.list_flags, fs->max_count, fs->paths[f].c_str(), nullptr, &o, &j);
+  else if (fs->opts.pattern_is_list)
+    r = xsg_job_start_list(fs->pattern.data(), fs->pattern.size(), fs->opts.list_flags, fs->paths[f].c_str(), nullptr, &o, &j);
+  else
+    r = xsg_job_start(fs->pattern.data(), fs->pattern.size(), fs->paths[f].c_str(), nullptr, &o, &j);
   if (r == XSG_OK) r = xsg_job_join(j);
   if (r != XSG_OK) {
     if (j) xsg_job_destroy(j);
@@ -341,6 +346,9 @@ static int driver_body(xsg_fileset* fs) {
   if (!fs->plan.items.empty()) {  // (a set of large files only is its jobs: no context, no buffers of its own)
     XSG_TRY(xsg_ctx_create(fs->opts.device, &fs->ctx));
     XSG_TRY(set_job_pattern(fs->ctx, fs->pattern, fs->opts.pattern_flags, fs->opts.pattern_is_list != 0, fs->opts.list_flags));
+    // a small file is a chunk: the limit per chunk IS the limit per file, in the batch's one search and in the per-file
+    // searches behind a refusal alike (the limit stays with the context's pattern)
+    if (fs->max_count) XSG_TRY(xsg_set_max_count(fs->ctx, fs->max_count));
     // (a margin behind the last chunk: the scan reads whole 16-byte units, and an empty last file still needs an address)
     fs->d_cap = max_bytes + 256;
     if (hipMalloc(&fs->d_buf, fs->d_cap) != hipSuccess) return fail(XSG_ENOMEM, "hipMalloc(%llu) failed", (unsigned long long)fs->d_cap);
@@ -452,8 +460,8 @@ static int check_pattern(const void* pattern, size_t plen, const xsg_fileset_opt
   return XSG_OK;
 }
 
-extern "C" int xsg_fileset_start(const void* pattern, size_t plen, const char* const* paths, uint64_t npaths,
-                                 const xsg_fileset_opts* opts, xsg_fileset** out) {
+static int fileset_start(const void* pattern, size_t plen, const char* const* paths, uint64_t npaths,
+                         const xsg_fileset_opts* opts, uint64_t max_count, xsg_fileset** out) {
   if (!out) return fail(XSG_EINVAL, "out is null");
   *out = nullptr;
   if (npaths && !paths) return fail(XSG_EINVAL, "paths is null");
@@ -472,12 +480,17 @@ extern "C" int xsg_fileset_start(const void* pattern, size_t plen, const char* c
   XSG_TRY(check_list_flags(o.list_flags));
   if (o.list_flags && !o.pattern_is_list) return fail(XSG_EINVAL, "list_flags without pattern_is_list");
   XSG_TRY(check_pattern(pattern, plen, o));
+  if (max_count && context_flags(o.pattern_flags))
+    return fail(XSG_ENOTSUP, "a limit (max_count) with XSG_FLAG_CONTEXT is not served for files: a large file's budget is only known "
+                             "in file order, and the seams between its chunks join lists that are already widened; "
+                             "xsg_set_max_count on a binding serves the combination");
   int ndev = 0;
   XSG_TRY(xsg_device_count(&ndev));  // fail early and loudly without a device: there is no CPU search path
   if (o.device < 0 || o.device >= ndev) return fail(XSG_ENODEV, "device %d out of range", o.device);
   try {
     xsg_fileset* fs = new xsg_fileset();
     fs->opts = o;
+    fs->max_count = max_count;
     fs->pattern.assign((const uint8_t*)pattern, (const uint8_t*)pattern + plen);
     fs->paths.assign(paths, paths + npaths);
     fs->nreaders = o.num_readers ? std::min(o.num_readers, 16) : std::min(16, std::max(1, cpu_budget()));
@@ -494,6 +507,18 @@ extern "C" int xsg_fileset_start(const void* pattern, size_t plen, const char* c
     return fail(XSG_EIO, "xsg_fileset_start: %s", e.what());
   }
   return XSG_OK;
+}
+
+extern "C" int xsg_fileset_start(const void* pattern, size_t plen, const char* const* paths, uint64_t npaths,
+                                 const xsg_fileset_opts* opts, xsg_fileset** out) {
+  return fileset_start(pattern, plen, paths, npaths, opts, 0u, out);
+}
+
+// ... with a limit per FILE: every file's result is the first max_count entries of what it is without one (count tags:
+// min(count, max_count)), whatever batch_bytes, chunk_bytes and the reader count; 0 is the call above
+extern "C" int xsg_fileset_start_max_count(const void* pattern, size_t plen, const char* const* paths, uint64_t npaths,
+                                           const xsg_fileset_opts* opts, uint64_t max_count, xsg_fileset** out) {
+  return fileset_start(pattern, plen, paths, npaths, opts, max_count, out);
 }
 
 extern "C" int xsg_fileset_wait(xsg_fileset* fs, uint64_t file_index, uint64_t* files_done, int* finished) {

@@ -16,6 +16,7 @@ struct HostSlot {
   xsg_ctx* ctx = nullptr;
   xsg_shard* shard = nullptr;
   StagedChunk buf;
+  uint64_t max_count = 0;  // the limit its context carries now (xsg_host_searcher_set_max_count)
   ~HostSlot() {
     if (shard) xsg_shard_destroy(shard);
     buf.release();  // (behind the shard, ahead of the context: a member's own destructor would run after this body)
@@ -30,13 +31,14 @@ struct xsg_host_searcher {
   bool is_list = false;  // xsg_host_searcher_create_list
   uint32_t list_flags = 0;  // xsg_host_searcher_create_list_opts
   int max_slots = 1;
+  uint64_t max_count = 0;  // xsg_host_searcher_set_max_count: what every call from now on searches under; guarded by mu
   std::mutex mu;
   std::condition_variable cv;
   std::vector<std::unique_ptr<HostSlot>> all;
   std::vector<HostSlot*> free_slots;
 };
 
-static int host_slot_acquire(xsg_host_searcher* hs, HostSlot** out) {
+static int host_slot_take(xsg_host_searcher* hs, HostSlot** out) {
   std::unique_lock<std::mutex> lk(hs->mu);
   for (;;) {
     if (!hs->free_slots.empty()) {
@@ -76,6 +78,28 @@ static void host_slot_release(xsg_host_searcher* hs, HostSlot* s) {
     hs->free_slots.push_back(s);
   }
   hs->cv.notify_one();
+}
+
+// a slot for one call, its context under the searcher's limit of this moment (a slot that last served another limit is set
+// again: the limit is the context's, and the setter may be called between any two calls)
+static int host_slot_acquire(xsg_host_searcher* hs, HostSlot** out) {
+  HostSlot* s = nullptr;
+  XSG_TRY(host_slot_take(hs, &s));
+  uint64_t want = 0;
+  {
+    std::lock_guard<std::mutex> g(hs->mu);
+    want = hs->max_count;
+  }
+  if (s->max_count != want) {
+    const int r = xsg_set_max_count ? xsg_set_max_count(s->ctx, want) : fail(XSG_ENOTSUP, "this build holds no device side for a limit");
+    if (r != XSG_OK) {
+      host_slot_release(hs, s);
+      return r;
+    }
+    s->max_count = want;
+  }
+  *out = s;
+  return XSG_OK;
 }
 
 // stage the chunk: host -> pinned -> device, bind it as a 1-chunk shard (local offsets, line base 0)
@@ -134,6 +158,14 @@ extern "C" int xsg_host_searcher_create_list_opts(int device, const void* list, 
 }
 
 extern "C" void xsg_host_searcher_destroy(xsg_host_searcher* hs) { delete hs; }
+
+extern "C" int xsg_host_searcher_set_max_count(xsg_host_searcher* hs, uint64_t max_count) {
+  if (!hs) return fail(XSG_EINVAL, "host searcher is null");
+  if (max_count && !xsg_set_max_count) return fail(XSG_ENOTSUP, "this build holds no device side for a limit");
+  std::lock_guard<std::mutex> g(hs->mu);
+  hs->max_count = max_count;
+  return XSG_OK;
+}
 
 struct SlotLease {
   xsg_host_searcher* hs;

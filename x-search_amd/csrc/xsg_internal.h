@@ -313,6 +313,33 @@ struct ChunkRowsArgs {
   uint64_t* byte_rows;        // nchunks + 1, or null
 };
 hipError_t launch_chunk_rows(const ChunkRowsArgs& a, hipStream_t s);
+// xsg_set_max_count, the limit stage of the exact list route (xsg_list_kernels.hip: k_limit_rows, k_limit_copy): the final
+// list (behind launch_assemble or invert_list) is replaced by the first `limit` entries of every chunk.  Rows: one lane per
+// chunk, the two binary searches of k_chunk_rows in the chunk column; old_ptr[c] = the chunk's first entry, cnt[c] =
+// min(its entries, limit).  The caller takes the exclusive prefix of cnt (new_ptr, nchunks + 1 words) and fetches its last
+// word.  Copy: one lane per old entry i of chunk c; rank i - old_ptr[c] below limit -> slot new_ptr[c] + rank.  Ranks and
+// counts are 64-bit: a limit of 2^32 + 1 or UINT64_MAX cuts nothing.
+struct LimitArgs {
+  uint64_t nchunks;
+  uint64_t total;            // entries of the list that comes in
+  uint64_t limit;            // > 0
+  const uint64_t* f_pos;
+  const uint64_t* f_match;   // may be f_pos (an inverted list has no matches): then o_match is o_pos and is not written twice
+  const uint32_t* f_chunk;
+  const uint32_t* f_len;     // null: the tag has no length column
+  uint64_t* cnt;             // nchunks
+  uint64_t* old_ptr;         // nchunks
+  const uint64_t* new_ptr;   // nchunks + 1 (copy)
+  uint64_t* o_pos;
+  uint64_t* o_match;
+  uint32_t* o_chunk;
+  uint32_t* o_len;
+};
+hipError_t launch_limit_rows(const LimitArgs& a, hipStream_t s);
+hipError_t launch_limit_copy(const LimitArgs& a, hipStream_t s);
+// ... and its count-side twin (k_limit_counts): counts[c] = min(counts[c], limit) in place, their sum ADDED to *sum (zero
+// before the launch).  A refused pass left the words zero (launch_chunk_counts_post): the sum is then 0 as well.
+hipError_t launch_limit_counts(uint64_t* counts, uint64_t nchunks, uint64_t limit, unsigned long long* sum, hipStream_t s);
 
 // ---- launchers (xsg_kernels.hip) --------------------------------------------
 hipError_t launch_scan_count(const ScanArgs& a, bool want_nl, bool want_lines, hipStream_t s);

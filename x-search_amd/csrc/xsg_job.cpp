@@ -52,6 +52,13 @@ struct xsg_job {
   xsg_job_opts opts{};
   std::vector<uint8_t> pattern;
   uint32_t list_flags = 0;  // xsg_job_start_list
+  // xsg_job_start_max_count: the job reports the first max_count entries of the searched range (0: all of them).  The ordered
+  // publisher keeps what is left of that budget (guarded by mu); when it is spent the job stops reading and finishes.
+  uint64_t max_count = 0, budget = 0;
+  bool budget_spent = false;
+  // ... and the readers open no chunk further than bufs_max ahead of the publisher (next_piece): what a limited job reads
+  // beyond the chunk that spends the budget is bounded by the buffers in circulation, however the workers interleave
+  std::atomic<uint64_t> published_chunks{0};
   int fd = -1;
   int32_t compression = XSG_COMPRESSION_NONE;
   std::vector<xsg_file_chunk> plan;
@@ -135,13 +142,32 @@ static int publish_context(xsg_job* j, xsg_context::Stitcher<T>& st, uint64_t in
               (unsigned long long)(before ? index - 1 : index), (unsigned long long)j->opts.chunk_bytes);
 }
 
+// xsg_job_start_max_count: the chunk's part of the remaining budget -- its first entries, or its count clamped.  The
+// publisher is ordered, so this is the cut of the file's result at its first max_count entries.
+static void spend_budget(xsg_job* j, Partial& q) {
+  const uint32_t mode = j->opts.mode;
+  if (count_mode(mode)) {
+    q.count = std::min(q.count, j->budget);
+    j->budget -= q.count;
+  } else if (string_mode(mode)) {
+    if (q.lines.size() > j->budget) q.lines.resize((size_t)j->budget);
+    j->budget -= q.lines.size();
+  } else {
+    if (q.u64.size() > j->budget) q.u64.resize((size_t)j->budget);
+    j->budget -= q.u64.size();
+  }
+  j->budget_spent = j->budget == 0;
+}
+
 static int publish(xsg_job* j, uint64_t index, Partial&& p) {
   std::lock_guard<std::mutex> g(j->mu);
+  if (j->budget_spent) return XSG_OK;  // (a chunk behind the one that spent the budget: not reported)
   j->pending.emplace(index, std::move(p));
   const uint32_t mode = j->opts.mode;
   int rc = XSG_OK;
-  for (auto it = j->pending.find(j->next_publish); it != j->pending.end(); it = j->pending.find(j->next_publish)) {
+  for (auto it = j->pending.find(j->next_publish); it != j->pending.end() && !j->budget_spent; it = j->pending.find(j->next_publish)) {
     Partial& q = it->second;
+    if (j->max_count) spend_budget(j, q);
     if (q.context) {
       int r = XSG_OK;
       if (string_mode(mode)) {
@@ -172,6 +198,16 @@ static int publish(xsg_job* j, uint64_t index, Partial&& p) {
     j->nl_running += q.newlines;
     j->pending.erase(it);
     ++j->next_publish;
+  }
+  if (j->max_count) {
+    j->published_chunks.store(j->next_publish);
+    if (j->budget_spent) {  // enough: nothing behind this chunk is reported, so nothing more is read or searched
+      j->pending.clear();
+      j->stop.store(true);
+    }
+    { std::lock_guard<std::mutex> lk(j->q_mu); }  // a waiter is either before its predicate check or already blocked
+    j->q_cv_free.notify_all();  // (readers held back by the publisher's position, next_piece)
+    if (j->budget_spent) j->q_cv_ready.notify_all();
   }
   j->cv.notify_all();
   return rc;
@@ -264,6 +300,9 @@ static int lane_prepare(xsg_job* j, Slot& s, int k) {
     XSG_TRACE("slot: lane %d ctx + shard created", k);
   }
   XSG_TRY(set_job_pattern(l.ctx, j->pattern, j->opts.pattern_flags, j->opts.pattern_is_list != 0, j->list_flags));
+  // a chunk alone never contributes more than the job's limit: a dense needle then moves that many rows per chunk, not all
+  // (without the device side of the limit the publisher's cut alone is still the result)
+  if (j->max_count && xsg_set_max_count) XSG_TRY(xsg_set_max_count(l.ctx, j->max_count));
   if (need > l.cap) {
     if (l.dev) (void)hipFree(l.dev);
     l.dev = nullptr;
@@ -448,6 +487,10 @@ static bool next_piece(xsg_job* j, HostBuf** buf, uint64_t* piece) {
       return true;
     }
     if (j->next_chunk >= j->plan.size()) break;
+    if (j->max_count && j->next_chunk >= j->published_chunks.load() + (uint64_t)j->bufs_max) {
+      j->q_cv_free.wait(lk);  // a limited job reads no further ahead of its publisher than its ring is long
+      continue;
+    }
     if (!mine && !j->free_bufs.empty()) {
       mine = j->free_bufs.back();
       j->free_bufs.pop_back();
@@ -766,7 +809,7 @@ extern "C" void xsg_job_opts_init(xsg_job_opts* o) {
 
 // force_list: xsg_job_start_list -- the pattern is a list whatever pattern_is_list says, with `list_flags`
 static int job_start_impl(const void* pattern, size_t plen, const char* file_path, const char* meta_file_path,
-                          const xsg_job_opts* opts, bool force_list, uint32_t list_flags, xsg_job** out) {
+                          const xsg_job_opts* opts, bool force_list, uint32_t list_flags, uint64_t max_count, xsg_job** out) {
   XSG_TRACE("job: start");
   if (!out) return fail(XSG_EINVAL, "out is null");
   *out = nullptr;
@@ -782,6 +825,7 @@ static int job_start_impl(const void* pattern, size_t plen, const char* file_pat
   if (force_list) known.pattern_is_list = 1u;
   XSG_TRY(check_list_flags(list_flags));
   const bool is_list = known.pattern_is_list != 0;
+  if (list_flags && !is_list) return fail(XSG_EINVAL, "list_flags without pattern_is_list");
   if (is_list) {  // refuse a bad list here, not in a worker
     if (!xsg_literals_info) return fail(XSG_ENOTSUP, "%s", kNoListMsg);
     xsg_literal_list info;
@@ -810,6 +854,10 @@ static int job_start_impl(const void* pattern, size_t plen, const char* file_pat
     if (!is_list && !(opts->pattern_flags & XSG_FLAG_REGEX) && memchr(pattern, '\n', plen)) return fail(XSG_ENOTSUP, "%s", kContextNlMsg);
     if (context_mode(opts->mode) && !xsg_result_context_edges)
       return fail(XSG_ENOTSUP, "XSG_FLAG_CONTEXT: this build holds no device side for context lines");
+    if (max_count)
+      return fail(XSG_ENOTSUP, "a limit (max_count) with XSG_FLAG_CONTEXT is not served for a file: the budget is only known in file "
+                               "order, and the seams between chunks join lists that are already widened; xsg_set_max_count on a "
+                               "binding serves the combination");
   }
   if (opts->pattern_flags & XSG_FLAG_REGEX) {  // refuse an expression the kernel cannot decide here, not in a worker
     uint32_t npos = 0;
@@ -831,6 +879,7 @@ static int job_start_impl(const void* pattern, size_t plen, const char* file_pat
   if (!j->opts.chunk_bytes) j->opts.chunk_bytes = 16u << 20;
   j->pattern.assign((const uint8_t*)pattern, (const uint8_t*)pattern + plen);
   j->list_flags = list_flags;
+  j->max_count = j->budget = max_count;
   uint64_t fsize = 0;
   XSG_TRY(open_ro(file_path, &j->fd, &fsize));
   int r = XSG_OK;
@@ -918,9 +967,9 @@ static int job_start_impl(const void* pattern, size_t plen, const char* file_pat
 }
 
 static int job_start_guarded(const void* pattern, size_t plen, const char* file_path, const char* meta_file_path,
-                             const xsg_job_opts* opts, bool force_list, uint32_t list_flags, xsg_job** out) {
+                             const xsg_job_opts* opts, bool force_list, uint32_t list_flags, uint64_t max_count, xsg_job** out) {
   try {
-    return job_start_impl(pattern, plen, file_path, meta_file_path, opts, force_list, list_flags, out);
+    return job_start_impl(pattern, plen, file_path, meta_file_path, opts, force_list, list_flags, max_count, out);
   } catch (const std::bad_alloc&) {  // e.g. a plan with millions of records
     return fail(XSG_ENOMEM, "host allocation failed while setting up the job");
   } catch (const std::exception& e) {
@@ -930,12 +979,19 @@ static int job_start_guarded(const void* pattern, size_t plen, const char* file_
 
 extern "C" int xsg_job_start(const void* pattern, size_t plen, const char* file_path, const char* meta_file_path,
                              const xsg_job_opts* opts, xsg_job** out) {
-  return job_start_guarded(pattern, plen, file_path, meta_file_path, opts, false, 0u, out);
+  return job_start_guarded(pattern, plen, file_path, meta_file_path, opts, false, 0u, 0u, out);
+}
+
+// ... with a limit: the first max_count entries of what the same job reports without one (count tags: min(total, max_count)).
+// opts is read as xsg_job_start reads it, pattern_is_list included; list_flags belong to a list.
+extern "C" int xsg_job_start_max_count(const void* pattern, size_t plen, uint32_t list_flags, uint64_t max_count, const char* file_path,
+                                       const char* meta_file_path, const xsg_job_opts* opts, xsg_job** out) {
+  return job_start_guarded(pattern, plen, file_path, meta_file_path, opts, false, list_flags, max_count, out);
 }
 
 extern "C" int xsg_job_start_list(const void* list, size_t n, uint32_t list_flags, const char* file_path,
                                   const char* meta_file_path, const xsg_job_opts* opts, xsg_job** out) {
-  return job_start_guarded(list, n, file_path, meta_file_path, opts, true, list_flags, out);
+  return job_start_guarded(list, n, file_path, meta_file_path, opts, true, list_flags, 0u, out);
 }
 
 extern "C" int xsg_job_join(xsg_job* j) {

@@ -184,6 +184,7 @@ static bool fast_route_serves(const xsg_shard* s, uint32_t mode, bool outputs, b
   if ((e && *e == '0') || !outputs || s->ntiles == 0 || want_nl_total) return false;
   if (mode == XSG_MATCHES) return false;                                // the span and gather stages sit on the exact route
   if (c->flags & XSG_FLAG_INVERT) return false;                         // the complement stage sits on the exact route
+  if (c->max_count) return false;                                       // the limit stage sits on the exact route
   if (context_on(c) && mode != XSG_MATCH_BYTE_OFFSETS) return false;    // the widening stage sits on the exact route
   if (c->pat.kind == kDfa) return false;                                // k_rx_scan / the prefilter route: exact route
   if (c->pat.kind == kSet) return false;                                // a literal list: the candidate route sits on the exact route
@@ -781,6 +782,54 @@ static int invert_list(xsg_shard* s, const ScanArgs& a, ListArgs& l, uint64_t* t
   return XSG_OK;
 }
 
+// xsg_set_max_count: the assembled (or inverted) list is replaced by the first N entries of every chunk, l.f_* and *total
+// with it; the widening stage and every output kernel run on the new list unchanged.  Rows per chunk, one prefix sum, one
+// more size from the device, the copy (xsg_list_kernels.hip: k_limit_rows, k_limit_copy).  A list of N entries and fewer
+// cannot lose one: the stage is not run at all.
+static int limit_list(xsg_shard* s, ListArgs& l, uint64_t* total) {
+  xsg_ctx* c = s->ctx;
+  hipStream_t st = c->stream;
+  const uint64_t n_in = *total, nchunks = s->chunks.size();
+  if (n_in <= c->max_count) return XSG_OK;
+  XSG_TRY(s->d_lim_cnt.ensure(8 * std::max<uint64_t>(nchunks, 1)));
+  XSG_TRY(s->d_lim_old.ensure(8 * std::max<uint64_t>(nchunks, 1)));
+  XSG_TRY(s->d_lim_ptr.ensure(8 * (nchunks + 1)));
+  XSG_TRY(s->d_scan_tmp.ensure(8 * scan_tmp_elems(nchunks + 1)));
+  LimitArgs a{};
+  a.nchunks = nchunks;
+  a.total = n_in;
+  a.limit = c->max_count;
+  a.f_pos = l.f_pos;
+  a.f_match = l.f_match;
+  a.f_chunk = l.f_chunk;
+  a.f_len = l.f_len;
+  a.cnt = s->d_lim_cnt.as<uint64_t>();
+  a.old_ptr = s->d_lim_old.as<uint64_t>();
+  HIP_TRY(launch_limit_rows(a, st));
+  HIP_TRY(launch_exclusive_scan_u64(a.cnt, s->d_lim_ptr.as<uint64_t>(), nchunks, s->d_scan_tmp.as<uint64_t>(), st));
+  uint64_t n = 0;
+  XSG_TRY(d2h_u64(c, s->d_lim_ptr.as<uint64_t>() + nchunks, &n));
+  if (n > n_in) return fail(XSG_EHIP, "the limit stage counted %llu entries of %llu", (unsigned long long)n, (unsigned long long)n_in);
+  const bool own_match = l.f_match != l.f_pos;
+  XSG_TRY(s->d_lim_pos.ensure(8 * std::max<uint64_t>(n, 1)));
+  if (own_match) XSG_TRY(s->d_lim_match.ensure(8 * std::max<uint64_t>(n, 1)));
+  XSG_TRY(s->d_lim_chunk.ensure(4 * std::max<uint64_t>(n, 1)));
+  if (l.f_len) XSG_TRY(s->d_lim_len.ensure(4 * std::max<uint64_t>(n, 1)));
+  a.new_ptr = s->d_lim_ptr.as<uint64_t>();
+  a.o_pos = s->d_lim_pos.as<uint64_t>();
+  a.o_match = own_match ? s->d_lim_match.as<uint64_t>() : a.o_pos;
+  a.o_chunk = s->d_lim_chunk.as<uint32_t>();
+  a.o_len = l.f_len ? s->d_lim_len.as<uint32_t>() : nullptr;
+  HIP_TRY(launch_limit_copy(a, st));
+  l.f_pos = a.o_pos;
+  l.f_match = a.o_match;
+  l.f_chunk = a.o_chunk;
+  if (l.f_len) l.f_len = a.o_len;
+  l.total = n;
+  *total = s->total = n;
+  return XSG_OK;
+}
+
 // the exclusive prefix of the per-tile newline counts (a.tile_nl: the caller's count pass ran with them), once per binding
 static int ensure_tile_nl_off(xsg_shard* s, const ScanArgs& a) {
   hipStream_t st = s->ctx->stream;
@@ -883,6 +932,7 @@ static int list_outputs(xsg_shard* s, uint32_t mode, const ScanArgs& a, ListArgs
   HIP_TRY(launch_assemble(l, st));
   const bool invert = (s->ctx->flags & XSG_FLAG_INVERT) != 0;
   if (invert) XSG_TRY(invert_list(s, a, l, &total));
+  if (s->ctx->max_count) XSG_TRY(limit_list(s, l, &total));
   const bool context = context_on(s->ctx) && mode != XSG_MATCH_BYTE_OFFSETS && mode != XSG_MATCHES;
   if (context) XSG_TRY(context_list(s, a, l, &total));
   LineOutArgs o = line_out_args(s, a, l, total);

@@ -1483,6 +1483,66 @@ hipError_t launch_chunk_rows(const ChunkRowsArgs& a, hipStream_t s) {
   return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------
+// xsg_set_max_count: the first `limit` entries of every chunk (LimitArgs, xsg_internal.h)
+// ---------------------------------------------------------------------------
+// one lane per chunk: where its entries begin in the list that comes in, and how many of them stay
+__global__ __launch_bounds__(kBlock) void k_limit_rows(const LimitArgs A) {
+  const uint64_t c = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (c >= A.nchunks) return;
+  const uint64_t lo = first_entry_of_chunk(A.f_chunk, A.total, c);
+  const uint64_t n = first_entry_of_chunk(A.f_chunk, A.total, c + 1) - lo;
+  A.old_ptr[c] = lo;
+  A.cnt[c] = n < A.limit ? n : A.limit;
+}
+// one lane per entry that comes in: its rank in its chunk decides, its slot is the chunk's new first entry plus that rank
+__global__ __launch_bounds__(kBlock) void k_limit_copy(const LimitArgs A) {
+  const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= A.total) return;
+  const uint32_t c = A.f_chunk[i];
+  if ((uint64_t)c >= A.nchunks) return;  // (no entry names such a chunk: old_ptr and new_ptr end there)
+  const uint64_t rank = i - A.old_ptr[c];
+  if (rank >= A.limit) return;
+  const uint64_t j = A.new_ptr[c] + rank;
+  A.o_pos[j] = A.f_pos[i];
+  if (A.f_match != A.f_pos) A.o_match[j] = A.f_match[i];
+  A.o_chunk[j] = c;
+  if (A.f_len) A.o_len[j] = A.f_len[i];
+}
+hipError_t launch_limit_rows(const LimitArgs& a, hipStream_t s) {
+  if (a.nchunks == 0) return hipSuccess;
+  if (!a.limit || !a.f_chunk || !a.cnt || !a.old_ptr) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_limit_rows, grid_for(a.nchunks), dim3(kBlock), 0, s, a);
+  return hipGetLastError();
+}
+hipError_t launch_limit_copy(const LimitArgs& a, hipStream_t s) {
+  if (a.total == 0 || a.nchunks == 0) return hipSuccess;
+  if (!a.limit || !a.new_ptr || !a.o_pos || !a.o_chunk || (a.f_match != a.f_pos && !a.o_match) || (a.f_len && !a.o_len))
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_limit_copy, grid_for(a.total), dim3(kBlock), 0, s, a);
+  return hipGetLastError();
+}
+
+// the count side: every chunk's word clamped in place, the clamped words summed.  A bounded grid strides over the chunks;
+// a workgroup reduces its lanes' partial sums (wave shuffles, then the waves' words in LDS) and adds ONE word to *sum.
+__global__ __launch_bounds__(kBlock) void k_limit_counts(uint64_t* counts, uint64_t nchunks, uint64_t limit, unsigned long long* sum) {
+  __shared__ uint64_t sh[kWaves];
+  uint64_t v = 0;
+  for (uint64_t c = (uint64_t)blockIdx.x * kBlock + threadIdx.x; c < nchunks; c += (uint64_t)gridDim.x * kBlock) {
+    uint64_t n = counts[c];
+    if (n > limit) counts[c] = n = limit;
+    v += n;
+  }
+  v = block_sum_u64(v, sh);
+  if (threadIdx.x == 0 && v) atomicAdd(sum, (unsigned long long)v);
+}
+hipError_t launch_limit_counts(uint64_t* counts, uint64_t nchunks, uint64_t limit, unsigned long long* sum, hipStream_t s) {
+  if (nchunks == 0) return hipSuccess;
+  if (!counts || !sum || !limit) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_limit_counts, grid_capped(nchunks), dim3(kBlock), 0, s, counts, nchunks, limit, sum);
+  return hipGetLastError();
+}
+
 
 // ---------------------------------------------------------------------------
 // XSG_FLAG_CONTEXT: the lines around the reported ones (ContextArgs, xsg_internal.h)

@@ -138,6 +138,9 @@ struct xsg_ctx {
   hipStream_t stream = nullptr;
   std::vector<uint8_t> pattern;
   uint32_t flags = 0;
+  // xsg_set_max_count: every chunk's list is cut to its first max_count entries, every chunk's count clamped to it (0: no
+  // limit).  A property of the pattern, like the list bits of `flags`: every set call clears it.
+  uint64_t max_count = 0;
   bool bordered = false;  // the pattern can overlap itself
   // ... a literal one, in these ways: for every border b the word P[0 .. plen - b) + P, the text of two occurrences
   // plen - b apart.  No such word in the data <=> no two occurrences overlap <=> the greedy walk keeps every occurrence
@@ -233,6 +236,9 @@ struct xsg_shard {
   DevBuf d_inv_lo, d_inv_cnt, d_inv_off, d_inv_pos, d_inv_chunk;  // XSG_FLAG_INVERT: the complement stage (xsg_list.cpp: invert_list)
   // XSG_FLAG_CONTEXT: the widening stage (xsg_list.cpp: context_list)
   DevBuf d_cx_lo, d_cx_hi, d_cx_cnt, d_cx_slot, d_cx_pos, d_cx_chunk, d_cx_edge;
+  // xsg_set_max_count: the limit stage (xsg_list.cpp: limit_list) -- the chunks' kept counts, their old and new first
+  // entries, the columns of the cut list; d_lim_sum: the count side's sum (xsg_count.cpp)
+  DevBuf d_lim_cnt, d_lim_old, d_lim_ptr, d_lim_pos, d_lim_match, d_lim_chunk, d_lim_len, d_lim_sum;
   std::vector<xsg_context_edge> context_edges;  // ... the edges of the last search with context, one per chunk
   bool context_edges_valid = false;             // ... which was the last search on this shard (xsg_result_context_edges)
   DevBuf d_c_pos, d_c_chunk, d_c_len, d_c_keep, d_c_pre;  // prefilter route of kDfa: the candidates
@@ -344,7 +350,8 @@ struct xsg_shard {
                      &d_cx_slot, &d_cx_pos, &d_cx_chunk, &d_cx_edge, &d_sketch, &d_spans, &d_chunk_counts, &d_lit_counts,
                      &d_lit_matrix, &d_csr_row_nnz, &d_csr_tmp, &d_csr_seam, &d_csr_row_ptr, &d_csr_cols, &d_csr_vals,
                      &d_find_occ, &d_find_off, &d_find_tmp, &d_find_ptr, &d_find_pos, &d_find_lit, &d_c_mask, &d_m_mask,
-                     &d_line_mask, &d_rows};
+                     &d_line_mask, &d_rows, &d_lim_cnt, &d_lim_old, &d_lim_ptr, &d_lim_pos, &d_lim_match, &d_lim_chunk,
+                     &d_lim_len, &d_lim_sum};
     for (DevBuf* b : all) b->release();
     if (h_stage) (void)hipHostFree(h_stage);
     if (h_counters) (void)hipHostFree(h_counters);

@@ -497,6 +497,7 @@ extern "C" int xsg_test_class_fields(const void* expr, size_t n, uint32_t flags,
 // belongs to is not a line of the chunk), and the bits are kept on the context, where the list and count routes read them.
 constexpr uint32_t kContextBits = 0xffffff00u;  // XSG_FLAG_CONTEXT(before, after): bits 8-19 and 20-31
 extern "C" int xsg_set_pattern(xsg_ctx* c, const void* pattern, size_t plen, uint32_t flags) {
+  if (c) c->max_count = 0;  // xsg_set_max_count belongs to the pattern that was set before it: gone, whatever this call returns
   const uint32_t list_bits = flags & (XSG_FLAG_INVERT | kContextBits);
   if (!list_bits || !c) return set_pattern_plain(c, pattern, plen, flags);
   if (flags & ~(XSG_FLAG_EXACT_TAIL | XSG_FLAG_IGNORE_CASE | XSG_FLAG_REGEX | XSG_FLAG_INVERT | kContextBits))
@@ -509,6 +510,15 @@ extern "C" int xsg_set_pattern(xsg_ctx* c, const void* pattern, size_t plen, uin
     return fail(XSG_ENOTSUP, "XSG_FLAG_CONTEXT: a search with context lines does not accept a pattern that can match '\\n'");
   }
   c->flags |= list_bits;
+  return XSG_OK;
+}
+
+// The limit is a property of the pattern like the list bits above, and no more one of the compiled pattern than they are: it
+// is kept on the context, where the limit stage of the list route and the clamp of the count routes read it.
+extern "C" int xsg_set_max_count(xsg_ctx* c, uint64_t max_count) {
+  if (!c) return fail(XSG_EINVAL, "ctx is null");
+  if (c->pattern.empty()) return fail(XSG_ESTATE, "xsg_set_max_count: no pattern is set (the limit belongs to a pattern: set it after the pattern)");
+  c->max_count = max_count;
   return XSG_OK;
 }
 
@@ -545,6 +555,7 @@ extern "C" int xsg_set_literals(xsg_ctx* c, const void* list, size_t n, uint32_t
 // the pattern.  Under XSG_LIST_ALL_OF a line's literals are one 64-bit mask: a longer list is refused here.
 extern "C" int xsg_set_literals_opts(xsg_ctx* c, const void* list, size_t n, uint32_t flags, uint32_t list_flags) {
   if (c) c->pattern.clear();  // a failed call leaves the context without a pattern
+  if (c) c->max_count = 0;    // ... and without the limit of the pattern before it (xsg_set_max_count)
   if (list_flags & ~(XSG_LIST_WHOLE_WORDS | XSG_LIST_ALL_OF)) return fail(XSG_EINVAL, "unknown list flags 0x%x", list_flags);
   if (!c) return fail(XSG_EINVAL, "ctx is null");
   xsg::SetProgram prog;

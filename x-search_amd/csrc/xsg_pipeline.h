@@ -9,6 +9,7 @@
 // the device side of XSG_FLAG_CONTEXT, and of a literal list (xsg_job_opts.pattern_is_list, xsg_host_searcher_create_list)
 extern "C" int xsg_result_context_edges(xsg_shard* shard, xsg_context_edge* out, uint64_t cap_chunks) __attribute__((weak));
 extern "C" int xsg_set_literals_opts(xsg_ctx* ctx, const void* list, size_t n, uint32_t flags, uint32_t list_flags) __attribute__((weak));
+extern "C" int xsg_set_max_count(xsg_ctx* ctx, uint64_t max_count) __attribute__((weak));  // (absent: the publishers cut alone)
 extern "C" int xsg_literals_info(const void* list, size_t n, uint32_t flags, xsg_literal_list* info, uint8_t* filter) __attribute__((weak));
 
 namespace xsg {

@@ -136,6 +136,10 @@ def load():
         "xsg_literals_info": (ci, [C.c_char_p, sz, u32, C.POINTER(LiteralList), vp]),
         "xsg_host_searcher_create_list": (ci, [ci, C.c_char_p, sz, u32, ci, C.POINTER(vp)]),
         "xsg_set_literals_opts": (ci, [vp, C.c_char_p, sz, u32, u32]),
+        "xsg_set_max_count": (ci, [vp, u64]),
+        "xsg_job_start_max_count": (ci, [C.c_char_p, sz, u32, u64, C.c_char_p, C.c_char_p, C.POINTER(JobOpts), C.POINTER(vp)]),
+        "xsg_fileset_start_max_count": (ci, [C.c_char_p, sz, C.POINTER(C.c_char_p), u64, C.POINTER(FileSetOpts), u64, C.POINTER(vp)]),
+        "xsg_host_searcher_set_max_count": (ci, [vp, u64]),
         "xsg_host_searcher_create_list_opts": (ci, [ci, C.c_char_p, sz, u32, u32, ci, C.POINTER(vp)]),
         "xsg_literal_counter_create_opts": (ci, [ci, C.c_char_p, sz, u32, u32, C.POINTER(vp)]),
         "xsg_job_start_list": (ci, [C.c_char_p, sz, u32, C.c_char_p, C.c_char_p, C.POINTER(JobOpts), C.POINTER(vp)]),
@@ -260,7 +264,8 @@ EXPORTS = ["xsg_abi_version", "xsg_strerror", "xsg_last_error", "xsg_device_coun
            "xsg_find_literals_async", "xsg_literal_finder_create_opts", "xsg_literal_finder_find",
            "xsg_literal_finder_destroy", "xsg_result_chunk_ptr", "xsg_fileset_opts_init", "xsg_fileset_start",
            "xsg_fileset_wait", "xsg_fileset_join", "xsg_fileset_status", "xsg_fileset_counts", "xsg_fileset_file_ptr",
-           "xsg_fileset_get_u64", "xsg_fileset_get_line", "xsg_fileset_destroy"]
+           "xsg_fileset_get_u64", "xsg_fileset_get_line", "xsg_fileset_destroy", "xsg_set_max_count",
+           "xsg_job_start_max_count", "xsg_fileset_start_max_count", "xsg_host_searcher_set_max_count"]
 
 
 def _check(rc):
@@ -427,6 +432,12 @@ class Context:
         self.nliterals = 0
         _check(self._lib.xsg_set_literals_opts(self.h, lst, len(lst), flags, list_flags))
         self.nliterals = literals_info(lst, flags)["count"]  # what Shard.count_literals sizes its result by
+
+    def set_max_count(self, n: int):
+        """xsg_set_max_count: every chunk's list is cut to its first n entries and every chunk's count clamped to n, for the
+        pattern that is set now (any later set call clears it); 0: no limit.  The stream-ordered counts and the per-literal
+        calls are XSG_ENOTSUP under a limit."""
+        _check(self._lib.xsg_set_max_count(self.h, n))
 
     def info(self):
         arch = C.create_string_buffer(128)
@@ -681,6 +692,80 @@ class Shard:
         return ms.value
 
 
+class HostSearcher:
+    """One chunk in host memory per call (xsg_host_searcher_*): chunk-local results.  max_count: xsg_set_max_count on every
+    slot's context; set_max_count changes it between calls (0 clears it)."""
+
+    def __init__(self, device: int, pattern: bytes, flags: int = 0, max_slots: int = 1, pattern_is_list: bool = False,
+                 list_flags: int = 0, max_count: int = 0):
+        self._lib = load()
+        self.h = None
+        h = C.c_void_p()
+        if pattern_is_list or list_flags:
+            _check(self._lib.xsg_host_searcher_create_list_opts(device, pattern, len(pattern), flags, list_flags, max_slots, C.byref(h)))
+        else:
+            _check(self._lib.xsg_host_searcher_create(device, pattern, len(pattern), flags, max_slots, C.byref(h)))
+        self.h = h
+        if max_count:
+            self.set_max_count(max_count)
+
+    def set_max_count(self, n: int):
+        _check(self._lib.xsg_host_searcher_set_max_count(self.h, n))
+
+    @staticmethod
+    def _ptr(data):
+        buf = np.frombuffer(bytes(data), dtype=np.uint8) if isinstance(data, (bytes, bytearray)) else np.ascontiguousarray(data, dtype=np.uint8)
+        return buf, C.c_void_p(buf.ctypes.data if buf.size else None), int(buf.size)
+
+    def count(self, data, skip_to_nl: bool = False) -> int:
+        buf, p, n = self._ptr(data)
+        out = C.c_uint64(0)
+        _check(self._lib.xsg_host_count(self.h, p, n, 1 if skip_to_nl else 0, C.byref(out)))
+        return int(out.value)
+
+    def offsets(self, mode: int, data) -> np.ndarray:
+        buf, p, n = self._ptr(data)
+        out, cnt = C.c_void_p(), C.c_uint64(0)
+        _check(self._lib.xsg_host_offsets(self.h, mode, p, n, C.byref(out), C.byref(cnt)))
+        try:
+            return np.ctypeslib.as_array(C.cast(out, _u64p), shape=(cnt.value,)).copy() if cnt.value else np.zeros(0, dtype=np.uint64)
+        finally:
+            self._lib.xsg_free(out)
+
+    def _strings(self, fn, data):
+        buf, p, n = self._ptr(data)
+        lens, raw, cnt, nb = C.c_void_p(), C.c_void_p(), C.c_uint64(0), C.c_uint64(0)
+        _check(fn(self.h, p, n, C.byref(lens), C.byref(raw), C.byref(cnt), C.byref(nb)))
+        try:
+            ln = [int(C.cast(lens, _u64p)[i]) for i in range(cnt.value)]
+            data = C.string_at(raw, nb.value) if nb.value else b""
+            out, at = [], 0
+            for k in ln:
+                out.append(data[at:at + k])
+                at += k
+            return out
+        finally:
+            self._lib.xsg_free(lens)
+            self._lib.xsg_free(raw)
+
+    def lines(self, data):
+        return self._strings(self._lib.xsg_host_lines, data)
+
+    def matches(self, data):
+        return self._strings(self._lib.xsg_host_matches, data)
+
+    def close(self):
+        if self.h:
+            self._lib.xsg_host_searcher_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class LiteralCounter:
     """Counts per literal over chunks in host memory, accumulated (xsg_literal_counter_*): add() the newline-aligned
     chunks of a file, get() its table."""
@@ -892,7 +977,10 @@ class FileSet:
     (path, status, result) per file as it is published."""
 
     def __init__(self, pattern: bytes, paths, mode: int, flags: int = 0, device: int = 0, num_readers: int = 0,
-                 batch_bytes: int = 0, chunk_bytes: int = 0, pattern_is_list: bool = False, list_flags: int = 0):
+                 batch_bytes: int = 0, chunk_bytes: int = 0, pattern_is_list: bool = False, list_flags: int = 0,
+                 max_count: int = 0):
+        """max_count: a limit per file (xsg_fileset_start_max_count) -- every file's first max_count entries, its count
+        clamped to it; 0: none"""
         self._lib = load()
         self.h = None
         self.mode = mode
@@ -904,7 +992,10 @@ class FileSet:
         o.pattern_is_list, o.list_flags = (1 if pattern_is_list or list_flags else 0), list_flags
         arr = (C.c_char_p * max(len(self.paths), 1))(*self.paths)
         h = C.c_void_p()
-        _check(self._lib.xsg_fileset_start(pattern, len(pattern), arr, len(self.paths), C.byref(o), C.byref(h)))
+        if max_count:
+            _check(self._lib.xsg_fileset_start_max_count(pattern, len(pattern), arr, len(self.paths), C.byref(o), max_count, C.byref(h)))
+        else:
+            _check(self._lib.xsg_fileset_start(pattern, len(pattern), arr, len(self.paths), C.byref(o), C.byref(h)))
         self.h = h
 
     def __len__(self):
@@ -979,7 +1070,10 @@ class Job:
 
     def __init__(self, pattern: bytes, path: str, mode: int, meta_path: str | None = None, device: int = 0,
                  num_threads: int = 1, num_max_readers: int = 1, chunk_bytes: int = 16 << 20, flags: int = 0,
-                 chunk_range: tuple[int, int] | None = None, pattern_is_list: bool = False, list_flags: int = 0):
+                 chunk_range: tuple[int, int] | None = None, pattern_is_list: bool = False, list_flags: int = 0,
+                 max_count: int = 0):
+        """max_count: the job reports the first max_count entries of the searched range and stops reading there
+        (xsg_job_start_max_count; count tags: the total clamped); 0: no limit"""
         self._lib = load()
         o = JobOpts()
         self._lib.xsg_job_opts_init(C.byref(o))
@@ -990,7 +1084,10 @@ class Job:
         o.pattern_is_list = 1 if pattern_is_list else 0
         h = C.c_void_p()
         meta = os.fsencode(meta_path) if meta_path else None
-        if list_flags:  # (xsg_job_start_list: the pattern is a list whatever pattern_is_list says)
+        if max_count:  # (list_flags belong to a list here as well)
+            o.pattern_is_list = 1 if pattern_is_list or list_flags else 0
+            _check(self._lib.xsg_job_start_max_count(pattern, len(pattern), list_flags, max_count, os.fsencode(path), meta, C.byref(o), C.byref(h)))
+        elif list_flags:  # (xsg_job_start_list: the pattern is a list whatever pattern_is_list says)
             _check(self._lib.xsg_job_start_list(pattern, len(pattern), list_flags, os.fsencode(path), meta, C.byref(o), C.byref(h)))
         else:
             _check(self._lib.xsg_job_start(pattern, len(pattern), os.fsencode(path), meta, C.byref(o), C.byref(h)))
