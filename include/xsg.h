@@ -439,8 +439,10 @@ int xsg_regex_factor(const void* expr, size_t n, uint32_t flags, uint32_t* posit
  * The sketch is 512 bytes of device memory per 16 KiB tile (a
  * binding simply goes without if the allocation fails): one bit per hashed 4-gram that starts in the tile.  It does not
  * depend on the pattern.  A span locator of another 1 KiB per tile is built with it -- 2048 such bits for each of the
- * tile's four 4 KiB spans -- so the two together take 9.4 % of the text (3.1 % before the locator existed); a binding
- * without memory for the locator keeps the sketch alone.  The plain count pass of a case-sensitive literal of 4 bytes and more -- xsg_count,
+ * tile's four 4 KiB spans -- and, with the locator, the sketch's bit planes: the same 4096 bits per tile transposed, one
+ * 64-bit word per (bit, group of 64 tiles), another 512 bytes per tile.  The three together take 12.5 % of the text in
+ * device memory, 6.25 GiB beside a 50 GiB binding (9.4 % before the planes existed, 3.1 % before the locator); a binding
+ * without memory for the locator keeps the sketch alone, one without memory for the planes keeps sketch and locator.  The plain count pass of a case-sensitive literal of 4 bytes and more -- xsg_count,
  * xsg_count_begin, xsg_count_async, the count pass of xsg_search -- is then one launch of a bounded grid: its workgroups
  * test the sketches of 256 tiles at a time for the needle's first grams and scan the tiles that hold every one of them --
  * the candidate tiles -- and read no other text.  A needle whose grams are words of the text passes everywhere: the synchronous
@@ -462,6 +464,10 @@ int xsg_regex_factor(const void* expr, size_t n, uint32_t flags, uint32_t* posit
  * front of " by 4 KiB spans").  A wave takes its groups four at a time: the sketch words of all four are requested together,
  * the batch's candidates are looked up in one round trip and then scanned (50 GiB, `Sherlock`: 0.076 -> 0.062 ms per call;
  * the name says " in batches of 4" in front of " a wave per group"; XSG_GATE_BATCH=1 keeps one group at a time).
+ * Where the binding holds the bit planes the wave picks a group's candidates from them -- the AND of one 64-bit word per
+ * gram of the needle, 40 bytes a group for `Sherlock` where the sketch words are 1280 and a chunk number per tile (50 GiB,
+ * `Sherlock`: 0.062 -> 0.058 ms per call; the name says " from bit planes" in front of " in batches of 4";
+ * XSG_GATE_PLANES=0 keeps the select from sketch words).  Building them adds 2.3 ms to the sketch's 38 ms on 50 GiB.
  * XSG_GATE_WAVES=0 keeps the workgroup form; XSG_GATE_GRID=N sets the number of workgroups of either form (default 1536
  * for the wave form, 8192 for the workgroup form and the storing pass; never more than one per 256 tiles).  Bindings of
  * 64 MiB and more get the sketch from

@@ -101,11 +101,16 @@ static int build_sketch(xsg_shard* s) {
   const bool spans = s->d_spans.ensure((size_t)span_alloc_words(s->ntiles) * 4) == XSG_OK;
   b.spans = spans ? s->d_spans.as<uint32_t>() : nullptr;
   HIP_TRY(launch_sketch_build(b, c->stream));
+  // the bit planes, transposed from the finished sketch right behind it -- with the locator only: the wave form of the
+  // finishing pass is their one reader; without memory for them the binding keeps the select from sketch words
+  const bool planes = spans && s->d_planes.ensure((size_t)plane_alloc_words(s->ntiles) * 8) == XSG_OK;
+  if (planes) HIP_TRY(launch_sketch_planes(b.sketch, s->ntiles, s->d_planes.as<uint64_t>(), c->stream));
   // a pass on a caller's stream must find it complete: the event that orders the chunk table orders the sketch as well
   HIP_TRY(hipEventRecord(s->table_ev, c->stream));
   s->table_pending = true;
   s->sketch_tiles = s->ntiles;
   s->span_tiles = spans ? s->ntiles : 0;
+  s->plane_tiles = planes ? s->ntiles : 0;
   s->gate_serial = 0;
   return XSG_OK;
 }
@@ -425,6 +430,20 @@ static GateFinArgs fin_args(xsg_shard* s, const ScanArgs& a, uint64_t* d_counter
   // that keeps one group at a time in the same build
   const char* b = XSG_TOGGLE("XSG_GATE_BATCH");
   f.batch = b && *b == '1' && b[1] == 0 ? 1u : kGateBatch;
+  // the wave form selects from the sketch's bit planes where the binding holds them for its tiles: one word per gram
+  // sketch_fields folded into sk_word / sk_mask, all of them; XSG_GATE_PLANES=0 is the A/B switch that keeps the select
+  // from sketch words in the same build
+  const char* p = XSG_TOGGLE("XSG_GATE_PLANES");
+  if (f.waves && !(p && *p == '0') && s->plane_tiles != 0 && s->plane_tiles == s->ntiles && s->d_planes.p) {
+    const xsg_ctx* c = s->ctx;
+    const uint32_t first = a.sk_koff, n = sketch_pattern_grams(a.pat.plen, first);
+    if (n != 0 && n <= kSketchMaxGrams && first + n <= c->sketch_hashes.size()) {
+      for (uint32_t g = 0; g < n; ++g) f.pl_bit[g] = c->sketch_hashes[first + g];
+      f.pl_n = n;
+      f.pl_stride = plane_stride(s->ntiles);
+      f.planes = s->d_planes.as<uint64_t>();
+    }
+  }
   return f;
 }
 
@@ -1033,7 +1052,7 @@ extern "C" int xsg_scan_kernel_name(xsg_shard* s, uint32_t mode, char* out, size
     const GateFinArgs f = fin_args(s, a, nullptr, nullptr, nullptr);
     describe_scan(a, want_nl, !list && m == XSG_COUNT_LINES, false, out, cap,
                   !list && count_finishes(s, a, m, (mode & XSG_WITH_NEWLINES) != 0), s->total_bytes, spans_apply(s, a),
-                  f.waves != 0, f.batch);
+                  f.waves != 0, f.batch, f.planes != nullptr);
   }
   if (inverted(s->ctx)) {  // the inverted form: the same scan, then the complement (of the list, or of the line count)
     const size_t n = strlen(out);

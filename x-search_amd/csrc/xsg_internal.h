@@ -173,6 +173,9 @@ struct SketchArgs {
   uint32_t* spans;              // the span locator: span_alloc_words(ntiles), at span_index(tile, word, span); null: not built
 };
 hipError_t launch_sketch_build(const SketchArgs& a, hipStream_t s);
+// k_sketch_planes: the finished sketch transposed into its bit planes (xsg_sketch.h), plane_alloc_words(ntiles) words of
+// 64 bits; stream-ordered behind launch_sketch_build
+hipError_t launch_sketch_planes(const uint32_t* sketch, uint64_t ntiles, uint64_t* planes, hipStream_t s);
 // k_sketch_sample: *passed += the number of tiles among 0, stride, 2 * stride, ... (nsamp of them, all < ntiles) whose
 // sketch holds every bit of a.sk_word / a.sk_mask -- what share of the tiles the gate of this pattern would let through
 hipError_t launch_sketch_sample(const ScanArgs& a, uint64_t stride, uint32_t nsamp, uint32_t* passed, hipStream_t s);
@@ -207,6 +210,13 @@ struct GateFinArgs {
   // The wave form takes its groups in batches: a wave's next `batch` rounds (1 .. kGateBatch) are selected together,
   // their candidates located in one round trip and then scanned.  XSG_GATE_BATCH=1 keeps one group at a time.
   uint32_t batch;
+  // The wave form's select from the sketch's bit planes (xsg_sketch.h; null: from the sketch words, as the other forms
+  // do): a group's candidates are the AND of one 64-bit word per tested gram, pl_bit[k] = the gram's sketch_hash = its
+  // plane -- every gram sketch_fields folds into sk_word / sk_mask, pl_n of them.  XSG_GATE_PLANES=0 keeps the word select.
+  const uint64_t* planes;
+  uint64_t pl_stride;         // plane_stride(ntiles)
+  uint32_t pl_n;
+  uint16_t pl_bit[kSketchMaxGrams];
 };
 #ifndef XSG_GATE_BATCH_N
 #define XSG_GATE_BATCH_N 4
@@ -477,9 +487,10 @@ hipError_t launch_set_find_chunk_ptr(const ScanArgs& a, const uint64_t* wave_off
 // "xsg::k_scan<KIND, WANT_NL, WANT_LINES, EMIT, LOADS, ICASE>" + the stagger launch_scan would use, for reports
 // finishing: the caller's pass is a plain match count that takes the finishing form where scan_finishing says so;
 // spans: that form would run with the binding's span locator (GateFinArgs::spans); waves: and as the wave form, taking
-// `batch` groups at a time (GateFinArgs::batch)
+// `batch` groups at a time (GateFinArgs::batch); planes: selecting from the sketch's bit planes (GateFinArgs::planes)
 void describe_scan(const ScanArgs& a, bool want_nl, bool want_lines, bool emit, char* out, size_t cap,
-                   bool finishing = false, uint64_t total_bytes = 0, bool spans = false, bool waves = false, uint32_t batch = 1);
+                   bool finishing = false, uint64_t total_bytes = 0, bool spans = false, bool waves = false, uint32_t batch = 1,
+                   bool planes = false);
 
 // exclusive scan: out[i] = sum_{k<i} in[k] for i in [0, n]; out has n+1 entries.
 // tmp must hold scan_tmp_elems(n) uint64 values.

@@ -1427,12 +1427,20 @@ __device__ __forceinline__ void gated_pass(const ScanArgs& A, const GateFinArgs*
 // candidate tile is looked at by the wave that owns the tile, in its own row of s_zone; the rule is gated_pass's.
 // Used when the binding has a span locator (GateFinArgs::waves); without one, four spans read in turn by one wave are
 // not what whole-tile reads want, and gated_pass<..., FIN> serves.
+// Where the binding holds the sketch's bit planes (xsg_sketch.h, GateFinArgs::planes) phase 1 reads those instead: per
+// group one 64-bit word per gram, a lane per word, AND-ed into the group's ballot -- 40 bytes a group for an 8-byte needle
+// where the word select reads 5 x 256 and the chunk numbers -- and the candidate's chunk number moves to phase 2.
 // ---------------------------------------------------------------------------
+#ifndef XSG_PLANES_CHUNK_IN_SELECT
+#define XSG_PLANES_CHUNK_IN_SELECT 0  // 1: the plane select still reads tile_chunk for every tile (the A/B switch)
+#endif
 template <int KIND, int LOADS, bool ALIGNED>
 __device__ __forceinline__ void gated_pass_waves(const ScanArgs& A, const GateFinArgs& F) {
   __shared__ __attribute__((aligned(16))) uint8_t s_zone[kWaves][kZoneStage];  // the zone a candidate tile looks at, per wave
   __shared__ uint64_t s_fin[kWaves];
   __shared__ uint2 s_cand[kWaves][kSketchGroup];  // a batch's candidates, per wave: {place in the batch, chunk number}
+  __shared__ uint16_t s_plbit[kWaves][32];        // the planes of the needle's grams (GateFinArgs::pl_bit), per wave
+  static_assert(kSketchMaxGrams <= 32, "s_plbit: a row holds every tested gram");
   uint64_t fin_acc = 0;  // this wave's matches (wave-uniform)
   const uint32_t tid = threadIdx.x;
   const uint32_t lane = tid & 63u;
@@ -1452,6 +1460,24 @@ __device__ __forceinline__ void gated_pass_waves(const ScanArgs& A, const GateFi
   constexpr uint32_t B = kGateBatch;
   const uint32_t bn = F.batch - 1u < B ? F.batch : B;  // rounds per batch, 1 .. B (XSG_GATE_BATCH=1: one group at a time)
   const uint64_t stride = (uint64_t)gridDim.x * kWaves;
+  // the select reads the sketch's bit planes where the binding has them (GateFinArgs::planes), else the sketch words;
+  // have_wc: the select phase has read every lane's chunk number (the word select does, the plane select only when built
+  // with XSG_PLANES_CHUNK_IN_SELECT: the A/B switch for where that read belongs, DESIGN.md section 5 "Planes")
+  const uint64_t* const planes = F.pl_n ? F.planes : nullptr;
+  const uint32_t pn = F.pl_n;
+  const bool have_wc = planes == nullptr || XSG_PLANES_CHUNK_IN_SELECT != 0;
+  // pl_bit in the wave's own LDS row, so that a lane finds the plane of ITS gram: lane l brings entry l there by selects
+  // over constant indices (the argument block is never indexed in memory); written and read by this wave alone
+  if (planes) {
+    uint32_t bit = 0;
+#pragma unroll
+    for (uint32_t i = 0; i < kSketchMaxGrams; ++i)
+      if (lane == i) bit = F.pl_bit[i];
+    if (lane < kSketchMaxGrams) s_plbit[wave][lane] = (uint16_t)bit;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  }
 
 #pragma unroll 1
   for (uint64_t g0 = (uint64_t)blockIdx.x * kWaves + wave; g0 < ngroups; g0 += stride * bn) {
@@ -1459,8 +1485,53 @@ __device__ __forceinline__ void gated_pass_waves(const ScanArgs& A, const GateFi
     // to one ballot per group (scalar); the words are dead behind this block.  Group j of the batch is g0 + j * stride.
     unsigned long long bal[B];
     uint32_t total = 0;
-    {
-      uint32_t w[B][kGateRegs], wc[B], miss[B];
+    uint32_t wc[B];  // the lane's chunk numbers, where the select phase reads them (have_wc)
+#pragma unroll
+    for (uint32_t j = 0; j < B; ++j) wc[j] = 0;
+    if (planes) {
+      // from the bit planes: a group's candidates are the AND of one 64-bit word per gram, plane_index(pl_bit[k], g).
+      // One 8-byte load a lane: lane i asks for gram k0 + i % G of the batch's group i / G, so that every word of the batch
+      // -- 16 grams of four groups a round -- is one vector request in flight at once; the words come together by
+      // readlane.  (The same words at wave-uniform addresses through the scalar cache measured 3 % SLOWER than the word
+      // select with 28 % fewer bytes: DESIGN.md section 5 "Planes".)
+      constexpr uint32_t G = kSketchGroup / B;
+      const uint32_t pj = lane / G, pk = lane % G;
+      const uint64_t gm = g0 + pj * stride;
+      const bool mine = pj < bn && gm < ngroups;  // (bn <= B; lanes behind B * G idle)
+#pragma unroll
+      for (uint32_t j = 0; j < B; ++j) {
+        bal[j] = ~0ull;
+#if XSG_PLANES_CHUNK_IN_SELECT
+        const uint64_t g = g0 + j * stride, mytile = g * kSketchGroup + lane;
+        if (A.tile_chunk && j < bn && g < ngroups && mytile < A.ntiles) wc[j] = A.tile_chunk[mytile];
+#endif
+      }
+#pragma unroll 1
+      for (uint32_t k0 = 0; k0 < pn; k0 += G) {
+        unsigned long long x = ~0ull;  // a lane without a word leaves the AND alone
+        if (mine && k0 + pk < pn) x = planes[plane_index(s_plbit[wave][k0 + pk], gm, F.pl_stride)];
+        const uint32_t xl = (uint32_t)x, xh = (uint32_t)(x >> 32);
+        const uint32_t nk = pn - k0 < G ? pn - k0 : G;
+#pragma unroll 1
+        for (uint32_t k = 0; k < nk; ++k) {  // wave-uniform
+#pragma unroll
+          for (uint32_t j = 0; j < B; ++j) {
+            const uint32_t l = j * G + k;
+            bal[j] &= ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)xh, (int)l) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)xl, (int)l);
+          }
+        }
+      }
+#pragma unroll
+      for (uint32_t j = 0; j < B; ++j) {
+        const uint64_t g = g0 + j * stride;
+        if (!(j < bn && g < ngroups)) bal[j] = 0;
+        // (the planes hold no bit of a tile at or beyond ntiles: k_sketch_planes; the mask keeps the lanes of the last
+        // group inside the binding whatever the planes hold)
+        if (g == ngroups - 1u && (A.ntiles & (kSketchGroup - 1u)) != 0) bal[j] &= (1ull << (A.ntiles & (kSketchGroup - 1u))) - 1ull;
+        total += (uint32_t)__builtin_popcountll(bal[j]);
+      }
+    } else {
+      uint32_t w[B][kGateRegs], miss[B];
 #pragma unroll
       for (uint32_t j = 0; j < B; ++j) {
         const uint64_t g = g0 + j * stride, mytile = g * kSketchGroup + lane;
@@ -1492,24 +1563,28 @@ __device__ __forceinline__ void gated_pass_waves(const ScanArgs& A, const GateFi
         bal[j] = __ballot(miss[j] == 0);
         total += (uint32_t)__builtin_popcountll(bal[j]);
       }
-      if (total == 0) continue;
-      // ---- 2a. the batch's passing (group, lane) pairs, compacted in (round, lane) order into the wave's row: entry
-      // i = {j * 64 + lane, tile_chunk}.  64 entries; a batch with more takes its groups one at a time (below).
-      if (total <= kSketchGroup) {
-        uint32_t before = 0;
+    }
+    if (total == 0) continue;
+    // ---- 2a. the batch's passing (group, lane) pairs, compacted in (round, lane) order into the wave's row: entry
+    // i = {j * 64 + lane, tile_chunk} -- the place alone where the chunk number is read in the locate phase (!have_wc).
+    // 64 entries; a batch with more takes its groups one at a time (below).
+    if (total <= kSketchGroup) {
+      uint32_t before = 0;
 #pragma unroll
-        for (uint32_t j = 0; j < B; ++j) {
-          if ((bal[j] >> lane) & 1ull) {
-            const uint32_t at = before + __builtin_amdgcn_mbcnt_hi((uint32_t)(bal[j] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal[j], 0u));
+      for (uint32_t j = 0; j < B; ++j) {
+        if ((bal[j] >> lane) & 1ull) {
+          const uint32_t at = before + __builtin_amdgcn_mbcnt_hi((uint32_t)(bal[j] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal[j], 0u));
+          if (have_wc)
             s_cand[wave][at] = make_uint2(j * kSketchGroup + lane, wc[j]);
-          }
-          before += (uint32_t)__builtin_popcountll(bal[j]);
+          else
+            s_cand[wave][at].x = j * kSketchGroup + lane;
         }
-        // the row is written and read by this wave alone: LDS serves a wave's requests in order
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        before += (uint32_t)__builtin_popcountll(bal[j]);
       }
+      // the row is written and read by this wave alone: LDS serves a wave's requests in order
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     }
     // one pass over the whole batch, or -- more than 64 candidates -- one per group, the lane then keeping its own tile
     const bool packed = total <= kSketchGroup;
@@ -1529,6 +1604,7 @@ __device__ __forceinline__ void gated_pass_waves(const ScanArgs& A, const GateFi
       if ((cand >> lane) & 1ull) {
         uint32_t wc;
         if (packed) {
+          // (!have_wc: only .x of the entry was written for this batch; .y is stale and replaced below)
           const uint2 e = s_cand[wave][lane];
           g_at = e.x;
           wc = e.y;
@@ -1537,6 +1613,8 @@ __device__ __forceinline__ void gated_pass_waves(const ScanArgs& A, const GateFi
           wc = A.tile_chunk ? A.tile_chunk[(g0 + j0 * stride) * kSketchGroup + lane] : 0u;
         }
         const uint64_t mytile = (g0 + (g_at >> 6) * stride) * kSketchGroup + (g_at & 63u);
+        // (the select from bit planes reads no chunk number: the candidate's is requested here, with its locator words)
+        if (packed && !have_wc) wc = A.tile_chunk ? A.tile_chunk[mytile] : 0u;
         uint4 x[kSpanRegs];
         const uint4* sp = reinterpret_cast<const uint4*>(F.spans + span_index(mytile, 0, 0));
 #pragma unroll
@@ -1617,8 +1695,11 @@ template <int KIND, int LOADS, bool ALIGNED, bool WAVES>
 // past the 80 that six waves per SIMD allow; asked for six, the compiler fits all of them into 74 .. 78 without scratch
 // -- profiles/spans_registers.txt.  The wave form is bounded to six from above as well, so that the compiler does not
 // squeeze it towards seven: it came out at 69 .. 72, and with batches of four at 76 .. 79, without a spill of a vector
-// register -- profiles/waves_registers.txt, batch_registers.txt; batches of eight spill: 7 registers a round in the
-// select phase.)
+// register -- profiles/waves_registers.txt, batch_registers.txt.  With both selects in the kernel -- from bit planes and
+// from sketch words -- all six sit at exactly 80 VGPRs, no vector spill, no scratch instruction, a 20-byte private
+// segment reserved that nothing addresses: profiles/planes_registers.txt.  There is NO headroom left: a register more in
+// any phase spills.  Batches of eight spill as before: the select from sketch words, 7 registers a round, is still here
+// for bindings without planes.)
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(6, WAVES ? 6 : 8))) void k_scan_fin(const ScanArgs A, const GateFinArgs F) {
   if constexpr (WAVES)
     gated_pass_waves<KIND, LOADS, ALIGNED>(A, F);
@@ -1766,7 +1847,7 @@ static uint32_t pick_stagger(const ScanArgs& a, bool want_nl, bool want_lines, b
 }
 
 void describe_scan(const ScanArgs& a, bool want_nl, bool want_lines, bool emit, char* out, size_t cap, bool finishing,
-                   uint64_t total_bytes, bool spans, bool waves, uint32_t batch) {
+                   uint64_t total_bytes, bool spans, bool waves, uint32_t batch, bool planes) {
   if (!out || !cap) return;
   const char* b[2] = {"false", "true"};
   if (a.pat.kind == kSet) return describe_set_scan(a, emit, out, cap);
@@ -1798,9 +1879,11 @@ void describe_scan(const ScanArgs& a, bool want_nl, bool want_lines, bool emit, 
     const bool fin = finishing && scan_finishing(a, total_bytes);
     // and, in front of that, whether a wave owns a sketch group from its sketch words to its text (gated_pass_waves)
     // and, in front of that, how many of its groups the wave takes at a time (GateFinArgs::batch), if more than one
+    // and, in front of that, whether the wave form selects from the sketch's bit planes (GateFinArgs::planes)
     char bt[32] = "";
     if (fin && spans && waves && batch > 1) snprintf(bt, sizeof bt, " in batches of %u", batch);
-    snprintf(out + n, cap - n, "%s%s%s%s gated by xsg::k_sketch (512 B/tile)", bt, fin && spans && waves ? " a wave per group" : "",
+    snprintf(out + n, cap - n, "%s%s%s%s%s gated by xsg::k_sketch (512 B/tile)", fin && spans && waves && planes ? " from bit planes" : "", bt,
+             fin && spans && waves ? " a wave per group" : "",
              fin && spans ? " by 4 KiB spans" : "", fin ? " finishing (xsg::k_scan_fin)" : "");
   }
 }
@@ -2325,6 +2408,65 @@ hipError_t launch_sketch_build(const SketchArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(k_sketch_build<true>, grid, dim3(kBlock), 0, s, a);
   else
     hipLaunchKernelGGL(k_sketch_build<false>, grid, dim3(kBlock), 0, s, a);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// k_sketch_planes: the finished sketch transposed into its bit planes (xsg_sketch.h), right behind k_sketch_build on the
+// same stream.  A workgroup takes a BLOCK of 16 consecutive groups -- one 128-byte line of every plane -- and
+// kPlaneWordsPerWg of the 128 sketch words.  Per word w a wave loads the 64 dwords of each of its four groups (one
+// 256-byte load: sketch_index(g * 64 + lane, w)) and takes 32 ballots, one per bit: ballot b is plane w * 32 + b's word of
+// the group, kept by lane b and staged in LDS as [bit][group of the block]; the workgroup then writes the 32 staged
+// lines whole, 16 bytes a lane.  Groups of the last block behind the binding's last one are written as zero (the
+// plane stride is padded to whole lines), and so are the bits of tiles behind `ntiles`: their sketch words are zero.
+// ---------------------------------------------------------------------------
+constexpr uint32_t kPlaneWordsPerWg = 8;
+static_assert(kSketchWords % kPlaneWordsPerWg == 0 && kPlaneLineGroups == 4 * kWaves && kBlock == 32 * kPlaneLineGroups / 2,
+              "k_sketch_planes: four groups a wave, two staged words a thread");
+__global__ __launch_bounds__(kBlock) void k_sketch_planes(const uint32_t* __restrict__ sketch, const uint64_t ntiles,
+                                                          uint64_t* __restrict__ planes) {
+  __shared__ __attribute__((aligned(16))) uint64_t s_line[32][kPlaneLineGroups];
+  const uint64_t ngroups = (ntiles + kSketchGroup - 1) / kSketchGroup, stride = plane_stride(ntiles);
+  const uint64_t wg = (uint64_t)blockIdx.x + (uint64_t)blockIdx.y * gridDim.x;
+  const uint64_t block = wg / (kSketchWords / kPlaneWordsPerWg);
+  const uint32_t w0 = (uint32_t)(wg % (kSketchWords / kPlaneWordsPerWg)) * kPlaneWordsPerWg;
+  if (block * kPlaneLineGroups >= stride) return;  // (a folded grid's tail; workgroup-uniform)
+  const uint32_t tid = threadIdx.x;
+  const uint32_t lane = tid & 63u;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+#pragma unroll 1
+  for (uint32_t w = w0; w < w0 + kPlaneWordsPerWg; ++w) {
+    uint32_t v[4];
+#pragma unroll
+    for (uint32_t q = 0; q < 4u; ++q) {
+      const uint64_t g = block * kPlaneLineGroups + wave * 4u + q;
+      v[q] = g < ngroups ? sketch[sketch_index(g * kSketchGroup + lane, w)] : 0u;
+    }
+#pragma unroll
+    for (uint32_t q = 0; q < 4u; ++q) {
+      unsigned long long mine = 0;
+#pragma unroll
+      for (uint32_t b = 0; b < 32u; ++b) {
+        const unsigned long long bal = __ballot((v[q] >> b) & 1u);  // bit l = bit b of tile g * 64 + l
+        if (lane == b) mine = bal;
+      }
+      if (lane < 32u) s_line[lane][wave * 4u + q] = mine;
+    }
+    __syncthreads();
+    {  // line b of the staged 32: 8 lanes x 16 bytes
+      const uint32_t b = tid >> 3, c = (tid & 7u) * 2u;
+      const ulonglong2 two = *reinterpret_cast<const ulonglong2*>(&s_line[b][c]);
+      *reinterpret_cast<ulonglong2*>(planes + plane_index(w * 32u + b, block * kPlaneLineGroups + c, stride)) = two;
+    }
+    __syncthreads();  // the staged lines are rewritten for the next word
+  }
+}
+
+hipError_t launch_sketch_planes(const uint32_t* sketch, uint64_t ntiles, uint64_t* planes, hipStream_t s) {
+  if (ntiles == 0) return hipSuccess;
+  if (!sketch || !planes) return hipErrorInvalidValue;
+  const uint64_t blocks = plane_stride(ntiles) / kPlaneLineGroups;
+  hipLaunchKernelGGL(k_sketch_planes, tile_grid(blocks * (kSketchWords / kPlaneWordsPerWg)), dim3(kBlock), 0, s, sketch, ntiles, planes);
   return hipGetLastError();
 }
 

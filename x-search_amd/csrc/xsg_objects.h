@@ -255,6 +255,11 @@ struct xsg_shard {
   // for it keeps the tile sketch and whole-tile reads.
   DevBuf d_spans;
   uint64_t span_tiles = 0;        // != 0: d_spans holds the locator of this binding's `ntiles` tiles
+  // The sketch's bit planes (xsg_sketch.h): the sketch transposed, another 512 B per tile, built right behind it when the
+  // locator was (the wave form of the finishing pass is their only reader).  Valid with the sketch, void with it; a
+  // binding without memory for them keeps the sketch, the locator and the select from sketch words.
+  DevBuf d_planes;
+  uint64_t plane_tiles = 0;       // != 0: d_planes holds the planes of this binding's `ntiles` tiles
   uint64_t gate_serial = 0;       // ctx->pattern_serial the verdict below was taken for (0: none)
   uint32_t gate_koff = 0;         // ... with this filter window
   bool gate_on = false;           // ... fewer than a quarter of the sampled tiles pass: the gate pays
@@ -347,7 +352,7 @@ struct xsg_shard {
                      &d_f_chunk, &d_out_u64, &d_line_len, &d_line_off, &d_line_bytes, &d_dropped, &d_c_pos, &d_c_chunk, &d_c_len, &d_c_keep,
                      &d_c_pre, &d_tile_mask, &d_tot, &d_hit, &d_scan2, &d_wmask, &d_inv_lo, &d_inv_cnt,
                      &d_inv_off, &d_inv_pos, &d_inv_chunk, &d_m_len, &d_f_len, &d_cx_lo, &d_cx_hi, &d_cx_cnt,
-                     &d_cx_slot, &d_cx_pos, &d_cx_chunk, &d_cx_edge, &d_sketch, &d_spans, &d_chunk_counts, &d_lit_counts,
+                     &d_cx_slot, &d_cx_pos, &d_cx_chunk, &d_cx_edge, &d_sketch, &d_spans, &d_planes, &d_chunk_counts, &d_lit_counts,
                      &d_lit_matrix, &d_csr_row_nnz, &d_csr_tmp, &d_csr_seam, &d_csr_row_ptr, &d_csr_cols, &d_csr_vals,
                      &d_find_occ, &d_find_off, &d_find_tmp, &d_find_ptr, &d_find_pos, &d_find_lit, &d_c_mask, &d_m_mask,
                      &d_line_mask, &d_rows, &d_lim_cnt, &d_lim_old, &d_lim_ptr, &d_lim_pos, &d_lim_match, &d_lim_chunk,

@@ -19,7 +19,7 @@ static void forget_derived(xsg_shard* s) {
   s->line_len_on_device = false;
   s->density_serial = 0;                     // a pattern found dense in this data (scan_args: stagger)
   s->overlap_serial = 0;                     // a bordered pattern whose occurrences do not overlap in this data
-  s->sketch_tiles = s->span_tiles = 0;       // the 4-gram sketch of the tiles, its span locator and the gate's verdict on a pattern
+  s->sketch_tiles = s->span_tiles = s->plane_tiles = 0;  // the 4-gram sketch of the tiles, its span locator, its bit planes and the gate's verdict on a pattern
   s->sketch_passes = 0;
   s->sketch_refused = false;
   s->gate_serial = 0;

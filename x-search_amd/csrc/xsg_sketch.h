@@ -50,6 +50,23 @@ XSG_SKETCH_HD uint64_t sketch_index(uint64_t tile, uint32_t word) {
   return tile / kSketchGroup * ((uint64_t)kSketchGroup * kSketchWords) + (uint64_t)word * kSketchGroup + tile % kSketchGroup;
 }
 
+// ---- the bit planes: the same bits, transposed ---------------------------------------------------------------------------
+// A second array derived from the finished sketch (k_sketch_planes), for the one reader that asks "which of a group's 64
+// tiles hold bit b": plane b (0 .. kSketchBits - 1) holds one 64-bit word per sketch group, bit l of it = bit b of tile
+// group * 64 + l.  Plane-major: a plane is contiguous over the binding's groups, its stride padded to whole 128-byte lines
+// (16 groups), so a plane starts on a line, 16 consecutive groups share one and groups 16 apart share none.  The size is
+// the sketch's own: 512 B per tile.  A pattern's test of a group is the AND of one word per gram (its sketch_hash is the
+// plane); the reader fetches them one word a lane and brings them together by readlane (gated_pass_waves).  The bits of
+// tiles behind the last one are zero like their sketch words.  plane_index takes the stride (plane_stride(ntiles)), which
+// the host computes once and hands to the kernel (GateFinArgs::pl_stride).
+constexpr uint32_t kPlaneLineGroups = 16;  // 64-bit words in a 128-byte line
+XSG_SKETCH_HD uint64_t plane_stride(uint64_t ntiles) {  // words from one plane to the next
+  const uint64_t groups = (ntiles + kSketchGroup - 1) / kSketchGroup;
+  return (groups + kPlaneLineGroups - 1) / kPlaneLineGroups * kPlaneLineGroups;
+}
+XSG_SKETCH_HD uint64_t plane_alloc_words(uint64_t ntiles) { return plane_stride(ntiles) * kSketchBits; }  // of 64 bits
+XSG_SKETCH_HD uint64_t plane_index(uint32_t bit, uint64_t group, uint64_t stride) { return (uint64_t)bit * stride + group; }
+
 // the grams of a pattern that the gate tests: pattern offsets [first, first + n)
 XSG_SKETCH_HD uint32_t sketch_pattern_grams(uint32_t plen, uint32_t first) {
   if (plen < 4u || first + 4u > plen) return 0u;
